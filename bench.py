@@ -3,6 +3,7 @@
 
   python bench.py [--gpus 1 --steps K --warmup W]                 headline: C2 (BASELINE configs[1])
   python bench.py --config C3|C4|C5 [...]                         the other GPU configs, same JSON contract
+  python bench.py [...] --dump-outputs DIR                        also write what the last timed step returned, DIR/<name>.npy
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W [--config C4]
 
@@ -518,6 +519,43 @@ def write_detail(path, result):
         return None
 
 
+DUMP_LIMIT = 60_000_000      # bytes of --dump-outputs in all (below 64 MB with the .npy headers)
+DUMP_SAMPLE = 1 << 23        # float32 elements of a trajectory too large for the limit (32 MiB)
+DUMP_SEED = 20240229
+
+
+def snapshot_outputs(acc):
+    """What the last timed step handed its caller, as host arrays: the rollout trajectory (float32; a fixed seeded sample
+    of DUMP_SAMPLE flat positions, sorted, drawn with replacement, when the whole trajectory would pass DUMP_LIMIT) and the
+    evaluation scores of the timed region (float64).  Taken right after the timed region, before any other leg runs."""
+    arrays = {}
+    scores = acc.get("scores") or {}
+    for k in ("rmse", "acc"):
+        if scores.get(k) is not None:
+            arrays[k] = scores[k].detach().to("cpu", torch.float64).numpy()
+    out = acc["out"].detach()
+    room = DUMP_LIMIT - sum(a.nbytes for a in arrays.values())
+    if out.numel() * 4 <= room:
+        arrays["rollout"] = out.to("cpu", torch.float32).numpy()
+    else:
+        import numpy as np
+
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, out.numel(), size=DUMP_SAMPLE, dtype=np.int64))
+        flat = out.reshape(-1)[torch.from_numpy(idx).to(out.device)]
+        arrays["rollout_sample"] = flat.to("cpu", torch.float32).numpy()
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT
+    return arrays
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    print(f"bench: wrote {', '.join(f'{n}{list(a.shape)}' for n, a in arrays.items())} to {path}", file=sys.stderr)
+
+
 # ------------------------------------------------------------------------------------------------ distributed plumbing
 
 def init_dist(args):
@@ -656,6 +694,8 @@ def run_c2(args, world, rank, device, dist, backend):
     step, finish, acc = make_runner(model, world, rank, args, prog, H, W)
     dt = timed_region(step, finish, args.steps, args.warmup, dist, device, backend)
     out = acc["out"]
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, snapshot_outputs(acc))
     ms_per_step = dt / args.steps * 1e3
     form = model.precision_form
     result = {
@@ -811,6 +851,8 @@ def run_backbone(tag, args, world, rank, device, dist, backend):
     step = lambda: step0(constants=c, prescribed=p)
     dt = timed_region(step, finish, args.steps, args.warmup, dist, device, backend)
     out = acc["out"]
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, snapshot_outputs(acc))
     result = {
         "metric": "rollout cell-steps/s",
         "value": world * B * H * W * K_roll * args.steps / dt,
@@ -884,7 +926,13 @@ def main():
     ap.add_argument("--collect", choices=["metrics", "gather", "none"], default="metrics",
                     help="what leaves a rank per rollout: per-lead-time RMSE sums reduced on the device and all-reduced "
                          "(default; SURVEY.md 8e/8f-f1), the whole trajectory (one chunked RCCL all-gather), or nothing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy: the "
+                         "rollout trajectory in float32 (a fixed seeded sample when it is larger than the limit) and the "
+                         "evaluation scores in float64, < 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world, rank, device, dist, backend = init_dist(args)
     if args.config == "C2":

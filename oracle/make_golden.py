@@ -9,6 +9,7 @@ each fixture stores the SHA-256 of the weight blob it was made with so drift is 
 """
 import hashlib
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -22,6 +23,15 @@ from dlwp_benchmark_amd import weights as W  # noqa: E402
 from oracle import ref_import  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+# CPU arithmetic that does not depend on the host: MKL's COMPATIBLE code path (the same results on every x86 processor),
+# ATen's non-vectorised kernels, one thread.  The bit-exact fixtures (SpectralConv2d) are made -- and checked by
+# tests/test_oracle_golden.py -- in a child interpreter with this environment, which MKL and ATen read when they load.
+PORTABLE_CPU_ENV = {"MKL_CBWR": "COMPATIBLE", "ATEN_CPU_CAPABILITY": "default", "OMP_NUM_THREADS": "1", "MKL_NUM_THREADS": "1"}
+
+
+def portable_cpu_env():
+    return all(os.environ.get(k) == v for k, v in PORTABLE_CPU_ENV.items())
 
 
 def _save(name, **arrays):
@@ -421,6 +431,23 @@ def gen_diffusion():
               state_spec=np.array(json.dumps(full)))
 
 
+def gen_model_configs():
+    """configs/model/*.yaml of the reference, parsed (yaml.safe_load, interpolations left as written), as one JSON mapping
+    file name -> config: the input of tests/test_registry_cpu.py, which constructs every hot-path type through the shim."""
+    import glob
+    import json
+
+    import yaml
+
+    src = os.path.join(ref_import.REF_PKG, "configs", "model")
+    cfgs = {os.path.basename(p): yaml.safe_load(open(p).read()) for p in sorted(glob.glob(os.path.join(src, "*.yaml")))}
+    path = os.path.join(GOLDEN, "model_configs.json")
+    with open(path, "w") as f:
+        json.dump(cfgs, f, indent=1)
+        f.write("\n")
+    print(f"wrote {path} ({len(cfgs)} configs)")
+
+
 def main():
     if not ref_import.reference_available():
         raise SystemExit("reference tree not available: golden fixtures can only be regenerated in the build container")
@@ -428,12 +455,18 @@ def main():
     torch.manual_seed(1234)
     only = set(sys.argv[1:])
     if not only or "spectral" in only:
-        gen_spectral(ref)
+        if portable_cpu_env():
+            gen_spectral(ref)
+        else:
+            subprocess.run([sys.executable, "-m", "oracle.make_golden", "spectral"], cwd=ROOT, check=True,
+                           env=dict(os.environ, **PORTABLE_CPU_ENV))
     if not only or "hpx" in only:
         gen_hpx(ref)
     if not only or "diffusion" in only:
         gen_diffusion()
-    rest = only - {"spectral", "hpx", "grads", "horizons", "diffusion"} - set(HORIZON_CASES)
+    if not only or "configs" in only:
+        gen_model_configs()
+    rest = only - {"spectral", "hpx", "grads", "horizons", "diffusion", "configs"} - set(HORIZON_CASES)
     if not only or "grads" in only:
         gen_grads(ref, None)
     if not only or rest:

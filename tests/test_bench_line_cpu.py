@@ -88,3 +88,30 @@ def test_roofline_fractions_are_fractions():
     r = bench._linear_roofline(summ)
     assert r["peak"] == bench.MFMA_16BIT_PEAK_TF and 0 < r["frac"] < 1
     assert r["matrix_products_per_algorithmic_product"] == 6
+
+
+def test_dump_outputs_whole_trajectory_and_scores(tmp_path):
+    import numpy as np
+    import torch
+
+    out = torch.randn(2, 3, 1, 8, 8)
+    scores = {"rmse": torch.rand(3, 1, dtype=torch.float64), "acc": None}
+    bench.write_outputs(str(tmp_path), bench.snapshot_outputs({"out": out, "scores": scores}))
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["rmse.npy", "rollout.npy"]
+    r = np.load(tmp_path / "rollout.npy")
+    assert r.dtype == np.float32 and np.array_equal(r, out.numpy())
+    assert np.load(tmp_path / "rmse.npy").dtype == np.float64
+
+
+def test_dump_outputs_samples_a_large_trajectory_within_the_limit(monkeypatch):
+    import torch
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 4000)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 500)
+    out = torch.arange(5000, dtype=torch.float32).reshape(5, 1000)
+    a = bench.snapshot_outputs({"out": out, "scores": None})
+    b = bench.snapshot_outputs({"out": out.clone(), "scores": None})
+    assert list(a) == ["rollout_sample"] and a["rollout_sample"].shape == (500,)
+    assert (a["rollout_sample"] == b["rollout_sample"]).all()                 # same positions from run to run
+    assert (a["rollout_sample"][1:] >= a["rollout_sample"][:-1]).all()         # sorted flat positions of the trajectory
+    assert sum(x.nbytes for x in a.values()) <= bench.DUMP_LIMIT

@@ -1,14 +1,18 @@
 """Pins the oracle (CPU restatement) against fixtures made by the REAL reference
-(oracle/make_golden.py, reference imported from /root/reference).  CPU only."""
+(oracle/make_golden.py, run where the reference is available).  CPU only."""
 import hashlib
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
 import torch
 
 from helpers import load_golden, rel_l2
-from oracle.make_golden import spectral_conv2d_case, tensor_sha
-from oracle.restate.fno import spectral_conv2d_ref
+from oracle.make_golden import PORTABLE_CPU_ENV, spectral_conv2d_case, tensor_sha
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 SPECTRAL_CASES = {
     "c32_64x64_m12": (32, 32, 64, 64, 12, 12, 1),
@@ -17,14 +21,29 @@ SPECTRAL_CASES = {
 }
 
 
+@pytest.fixture(scope="module")
+def spectral_portable(tmp_path_factory):
+    """the restatement's output of every SPECTRAL_CASES entry, computed in a child interpreter with PORTABLE_CPU_ENV -- the
+    environment the fixtures were made in, so that the bits do not depend on the CPU the suite runs on"""
+    path = str(tmp_path_factory.mktemp("spectral") / "y.npz")
+    code = ("import numpy as np; from oracle.make_golden import spectral_conv2d_case; "
+            "from oracle.restate.fno import spectral_conv2d_ref; "
+            f"cases = {SPECTRAL_CASES!r}; "
+            f"np.savez({path!r}, **{{t: spectral_conv2d_ref(*spectral_conv2d_case(*c, t)).numpy() for t, c in cases.items()}})")
+    r = subprocess.run([sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", code], cwd=ROOT,
+                       env=dict(os.environ, **PORTABLE_CPU_ENV), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    return np.load(path)
+
+
 @pytest.mark.parametrize("tag", list(SPECTRAL_CASES))
-def test_spectral_conv2d_restatement_matches_reference(tag):
+def test_spectral_conv2d_restatement_matches_reference(tag, spectral_portable):
     ci, co, h, w, m1, m2, b = SPECTRAL_CASES[tag]
     g = load_golden(f"spectral_conv2d_{tag}")
     x, w1, w2 = spectral_conv2d_case(ci, co, h, w, m1, m2, b, tag)
     assert tensor_sha(x, w1, w2) == str(g["sha"]), "filler drifted: regenerate fixtures"
-    y = spectral_conv2d_ref(x, w1, w2)
-    # same torch build on both sides -> bit-identical
+    y = torch.from_numpy(spectral_portable[tag])
+    # same torch build, same portable CPU arithmetic on both sides -> bit-identical
     assert torch.equal(y, torch.from_numpy(g["y"]))
 
 

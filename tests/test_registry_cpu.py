@@ -2,19 +2,19 @@
 shipped shim package, then `eval(cfg.model.type)(**cfg.model)` for every configs/model/*.yaml of the reference whose
 `type` names a hot-path backbone.  Construction only (CPU): no compute call is made without a GPU.
 
-The YAML text is read from /root/reference in the build container; the test skips where the reference is absent
-(the GPU box).  OmegaConf interpolations are resolved with the values of configs/data/weatherbench.yaml."""
-import glob
+The configs are read from tests/golden/model_configs.json: the reference's YAML files parsed as they are, interpolations
+included (oracle/make_golden.py, `configs`).  OmegaConf interpolations are resolved with the values of
+configs/data/weatherbench.yaml."""
 import importlib
+import json
 import os
 import sys
 
 import pytest
 import torch
-import yaml
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_CFG = "/root/reference/src/dlwpbench/configs/model"
+REF_CFG = os.path.join(ROOT, "tests", "golden", "model_configs.json")   # file name -> parsed configs/model/*.yaml
 
 HOT_PATH_TYPES = {"FourCastNet", "PanguWeather", "SwinTransformer", "SwinTransformerHPX", "UNet", "UNetHPX", "ModernUNet",
                   "MUNetHPX", "FNO2DModule", "TFNO2DModule", "ConvLSTM", "ConvLSTMHPX",           # SURVEY.md 8b "Registry"
@@ -56,14 +56,24 @@ def _resolve(v):
     return v
 
 
-def _reference_yamls():
-    return sorted(glob.glob(os.path.join(REF_CFG, "*.yaml")))
+def _reference_configs():
+    with open(REF_CFG) as f:
+        return json.load(f)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference configs only exist in the build container")
-@pytest.mark.parametrize("path", _reference_yamls(), ids=lambda p: os.path.basename(p))
-def test_reference_model_yaml_constructs(path):
-    cfg = {k: _resolve(v) for k, v in yaml.safe_load(open(path).read()).items()}
+def test_reference_model_configs_cover_hot_path():
+    """The parametrisation below is built from this file: an empty or truncated one would collect a single placeholder
+    case and check nothing.  Every hot-path type the reference ships a config for must be in it."""
+    types = {c.get("type") for c in _reference_configs().values()}
+    shipped = {"ConvLSTM", "DiffModernUNet", "FourCastNet", "ModernUNet", "PanguWeather", "SwinTransformer", "TFNO2DModule",
+               "UNet"}
+    assert shipped <= HOT_PATH_TYPES
+    assert shipped <= types, f"missing configs of {sorted(shipped - types)}"
+
+
+@pytest.mark.parametrize("name", sorted(_reference_configs()))
+def test_reference_model_yaml_constructs(name):
+    cfg = {k: _resolve(v) for k, v in _reference_configs()[name].items()}
     if cfg.get("type") not in HOT_PATH_TYPES:
         pytest.skip(f"type {cfg.get('type')} is out of the hot-path scope (SURVEY.md section 2)")
     ns = _shim()

@@ -19,7 +19,9 @@
 //   i.e. one read and one write of the activation per layer; lifting and projection MLPs are one
 //   fused kernel each (hidden 256-wide activation never leaves registers).
 #include "common.hpp"
+#include "spectral_any.hpp"
 #include <atomic>
+#include <memory>
 
 // GELU form per phase of the fused step kernel (A/B switch: -DDLWP_GELU8_LIFT=gelu_erf8_fma etc.)
 #ifndef DLWP_GELU8_LIFT
@@ -2379,7 +2381,16 @@ struct dlwp_fno2d_plan {
   DevBuf proj_w1p, proj_b1, proj_w2p, proj_b2, proj_w2v, proj_w1b, proj_w1bp;   // w1bp: k order of the trunk's resident activation
   int proj_co = 0;  // outputs handled by pw_proj_small_kernel (1, 2 or 4), 0 = generic MFMA path
   std::vector<DevBuf> wt, wsp, sbias, wsb, wsbp;   // wsbp: bf16x3 skip weights in the trunk kernel's k order
+  sany::Fno* gen = nullptr;   // shapes outside the 32-channel kernels' domain: the width-generic plan (spectral_any.hip)
+  ~dlwp_fno2d_plan() { sany::fno_destroy(gen); }
 };
+
+// The 32-channel kernels' domain; every other shape gets a width-generic plan.
+static bool fno_specialised(const dlwp_fno2d_desc* d) {
+  return d->hidden_channels == kC && d->lifting_channels > 0 && d->lifting_channels % 16 == 0 &&
+         d->projection_channels > 0 && d->projection_channels % 16 == 0 && d->in_channels >= 1 && d->in_channels <= 32 &&
+         d->out_channels >= 1 && d->out_channels <= 16 && 2 * d->n_cols <= 32;
+}
 
 static void pack_w1(std::vector<float>& dst, const float* w1, int hid, int cin, int cin_steps) {
   dst.assign((size_t)(hid / 16) * cin_steps * 64, 0.f);
@@ -2455,6 +2466,15 @@ extern "C" int32_t dlwp_fno2d_plan_create(dlwp_fno2d_plan** out, const dlwp_fno2
   DLWP_REQUIRE(out && d, DLWP_ERR_INVALID_ARGUMENT, "null plan/desc");
   *out = nullptr;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (!fno_specialised(d)) {
+    sany::Fno* gen = nullptr;
+    const int32_t rc = sany::fno_create(&gen, d, s);
+    if (rc != DLWP_OK) return rc;
+    auto* p = new dlwp_fno2d_plan();
+    p->gen = gen;
+    *out = p;
+    return DLWP_OK;
+  }
   DLWP_REQUIRE(d->hidden_channels == kC, DLWP_ERR_UNSUPPORTED, "hidden_channels %d: kernels are specialised for %d",
                d->hidden_channels, kC);
   DLWP_REQUIRE(d->lifting_channels > 0 && d->lifting_channels % 16 == 0 && d->projection_channels > 0 &&
@@ -3134,12 +3154,15 @@ int32_t fno_step(const dlwp_fno2d_plan* p, const ChanTable& xt, int B, const Fno
 
 extern "C" size_t dlwp_fno2d_workspace_bytes(const dlwp_fno2d_plan* plan, int32_t batch) {
   if (!plan || batch <= 0) return 0;
+  if (plan->gen) return sany::fno_workspace_bytes(plan->gen, batch);
   return carve(plan, batch, nullptr).total;
 }
 
 extern "C" int32_t dlwp_fno2d_forward_f32(const dlwp_fno2d_plan* plan, const float* x, float* y, int32_t batch,
                                           void* workspace, size_t workspace_bytes, void* stream) {
   DLWP_REQUIRE(plan && x && y && workspace, DLWP_ERR_INVALID_ARGUMENT, "null argument");
+  if (plan->gen)
+    return sany::fno_forward(plan->gen, x, y, batch, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
   DLWP_REQUIRE(batch > 0, DLWP_ERR_INVALID_ARGUMENT, "batch must be positive");
   const FnoWorkspace ws = carve(plan, batch, workspace);
   DLWP_REQUIRE(workspace_bytes >= ws.total, DLWP_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, ws.total);
@@ -3173,6 +3196,7 @@ extern "C" int32_t dlwp_fno2d_forward_f32(const dlwp_fno2d_plan* plan, const flo
 
 extern "C" int32_t dlwp_fno2d_status(const dlwp_fno2d_plan* plan, void* stream) {
   DLWP_REQUIRE(plan, DLWP_ERR_INVALID_ARGUMENT, "null argument");
+  if (plan->gen) return DLWP_OK;   // the generic path has no hand-offs and no f16 range
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   thread_local unsigned* h_word = nullptr;   // pinned, one per host thread; never freed
   if (!h_word) DLWP_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_word), 64, hipHostMallocDefault));
@@ -3207,6 +3231,10 @@ static int32_t fno_rollout_impl(const dlwp_fno2d_plan* plan, const float* consta
                                 int32_t n_prog, int32_t batch, int32_t n_time, int32_t context, float* out,
                                 void* workspace, size_t workspace_bytes, void* stream, KernelTimer* timer,
                                 int32_t step_begin = 0, int32_t step_end = -1) {
+  if (plan && plan->gen)
+    return sany::fno_rollout(plan->gen, constants, n_const, prescribed, n_presc, prognostic, n_prog, batch, n_time,
+                             context, out, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), step_begin,
+                             step_end, nullptr, nullptr);
   bool fused = false;
   int32_t rc = fno_rollout_once(plan, constants, n_const, prescribed, n_presc, prognostic, n_prog, batch, n_time, context,
                                 out, workspace, workspace_bytes, stream, timer, step_begin, step_end, false, &fused);
@@ -3329,6 +3357,10 @@ extern "C" int32_t dlwp_fno2d_rollout_profiled_f32(const dlwp_fno2d_plan* plan, 
                                                    size_t workspace_bytes, void* stream, double* class_ms,
                                                    int32_t* class_launches) {
   DLWP_REQUIRE(class_ms && class_launches, DLWP_ERR_INVALID_ARGUMENT, "null profile output");
+  if (plan && plan->gen)
+    return sany::fno_rollout(plan->gen, constants, n_const, prescribed, n_presc, prognostic, n_prog, batch, n_time,
+                             context, out, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), 0, -1,
+                             class_ms, class_launches);
   KernelTimer timer;
   timer.s = reinterpret_cast<hipStream_t>(stream);
   int32_t rc = fno_rollout_impl(plan, constants, n_const, prescribed, n_presc, prognostic, n_prog, batch, n_time,
@@ -3358,13 +3390,51 @@ struct dlwp_spectral_plan {
   int ci = 0, co = 0;
   SpectralCore sc;
   DevBuf wt, zero_bias;
+  std::unique_ptr<sany::Geom> gen;   // shapes outside the 32-channel kernels' domain (spectral_any.hip); wt is its image
 };
+
+// The 32-channel kernels' domain; every other shape gets a width-generic plan.
+static bool spectral_specialised(int ci, int co, int H, int W, int n_cols) {
+  return ci == kC && co == kC && W > 0 && W % 64 == 0 && H > 0 && 2 * n_cols <= 32;
+}
+
+static int32_t spectral_generic_create(dlwp_spectral_plan** out, int ci, int co, int H, int W, int n_rows, int n_cols,
+                                       const int32_t* rows_in, const int32_t* rows_out, float fwd_scale, float inv_scale,
+                                       const float* w1, const float* w2, hipStream_t s) {
+  auto* p = new dlwp_spectral_plan();
+  p->ci = ci; p->co = co;
+  p->gen.reset(new sany::Geom());
+  int32_t rc = sany::geom_build(*p->gen, ci, co, H, W, n_rows, n_cols, rows_in, rows_out, fwd_scale, inv_scale, s);
+  if (rc != DLWP_OK) { delete p; return rc; }
+  hipError_t e;
+  if (w1) {   // host weights: rows [0, n_rows / 2) from w1, the rest from w2 (unet.py:60-65)
+    std::vector<float> w;
+    sany::pack_host(w, *p->gen, w1, n_rows / 2, 0);
+    sany::pack_host(w, *p->gen, w2, n_rows / 2, n_rows / 2);
+    e = p->wt.upload(w.data(), w.size() * 4, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+  } else {
+    e = p->wt.alloc((size_t)n_cols * n_rows * ci * co * 2 * sizeof(float));
+    if (e == hipSuccess) e = hipMemsetAsync(p->wt.p, 0, p->wt.bytes, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+  }
+  if (e != hipSuccess) { delete p; return fail(DLWP_ERR_HIP, "plan upload failed: %s", hipGetErrorString(e)); }
+  *out = p;
+  return DLWP_OK;
+}
 
 extern "C" int32_t dlwp_spectral_conv2d_plan_create(dlwp_spectral_plan** out, int32_t ci, int32_t co, int32_t H,
                                                     int32_t W, int32_t m1, int32_t m2, const float* w1, const float* w2,
                                                     void* stream) {
   DLWP_REQUIRE(out && w1 && w2, DLWP_ERR_INVALID_ARGUMENT, "null argument");
   *out = nullptr;
+  if (!spectral_specialised(ci, co, H, W, m2)) {
+    DLWP_REQUIRE(m1 >= 1 && 2 * m1 <= H && m2 >= 1 && m2 <= W / 2 + 1, DLWP_ERR_INVALID_ARGUMENT, "bad mode counts");
+    std::vector<int32_t> rows(2 * m1);
+    for (int r = 0; r < m1; ++r) { rows[r] = r; rows[m1 + r] = H - m1 + r; }
+    return spectral_generic_create(out, ci, co, H, W, 2 * m1, m2, rows.data(), rows.data(), 1.0f,
+                                   1.0f / ((float)H * (float)W), w1, w2, reinterpret_cast<hipStream_t>(stream));
+  }
   DLWP_REQUIRE(ci == kC && co == kC, DLWP_ERR_UNSUPPORTED, "SpectralConv2d kernels are specialised for %d channels", kC);
   DLWP_REQUIRE(W > 0 && W % 64 == 0 && H > 0, DLWP_ERR_UNSUPPORTED, "width %d must be a positive multiple of 64", W);
   DLWP_REQUIRE(m1 >= 1 && 2 * m1 <= H && m2 >= 1 && m2 <= W / 2 + 1, DLWP_ERR_INVALID_ARGUMENT, "bad mode counts");
@@ -3398,6 +3468,9 @@ extern "C" int32_t dlwp_spectral_conv2d_plan_create_ex(dlwp_spectral_plan** out,
                                                        void* stream) {
   DLWP_REQUIRE(out && rows_in && rows_out, DLWP_ERR_INVALID_ARGUMENT, "null argument");
   *out = nullptr;
+  if (!spectral_specialised(ci, co, H, W, n_cols))
+    return spectral_generic_create(out, ci, co, H, W, n_rows, n_cols, rows_in, rows_out, fwd_scale, inv_scale, nullptr,
+                                   nullptr, reinterpret_cast<hipStream_t>(stream));
   DLWP_REQUIRE(ci == kC && co == kC, DLWP_ERR_UNSUPPORTED, "SpectralConv2d kernels are specialised for %d channels", kC);
   DLWP_REQUIRE(W > 0 && W % 64 == 0 && H > 0, DLWP_ERR_UNSUPPORTED, "width %d must be a positive multiple of 64", W);
   DLWP_REQUIRE(n_rows >= 1 && n_rows <= H && n_cols >= 1 && n_cols <= W / 2 + 1, DLWP_ERR_INVALID_ARGUMENT, "bad mode counts");
@@ -3419,6 +3492,8 @@ extern "C" int32_t dlwp_spectral_conv2d_plan_create_ex(dlwp_spectral_plan** out,
 extern "C" int32_t dlwp_spectral_conv2d_set_weights_dev(dlwp_spectral_plan* plan, const float* weights_dev,
                                                         int32_t adjoint, void* stream) {
   DLWP_REQUIRE(plan && weights_dev, DLWP_ERR_INVALID_ARGUMENT, "null argument");
+  if (plan->gen)
+    return sany::pack_dev(*plan->gen, weights_dev, adjoint, plan->wt.as<float2>(), reinterpret_cast<hipStream_t>(stream));
   const int R = plan->sc.M1, K = plan->sc.M2;
   const long long total = (long long)plan->ci * plan->co * R * K;
   long long blocks = (total + 255) / 256;
@@ -3438,6 +3513,7 @@ extern "C" int32_t dlwp_spectral_conv2d_plan_destroy(dlwp_spectral_plan* plan) {
 
 extern "C" size_t dlwp_spectral_conv2d_workspace_bytes(const dlwp_spectral_plan* plan, int32_t batch) {
   if (!plan || batch <= 0) return 0;
+  if (plan->gen) return sany::workspace_bytes(*plan->gen, batch);
   return 2 * align_up((size_t)batch * plan->sc.H * kC * plan->sc.KP * 4, 256);
 }
 
@@ -3451,6 +3527,10 @@ extern "C" int32_t dlwp_spectral_conv2d_f32(const dlwp_spectral_plan* plan, cons
                    (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
                DLWP_ERR_INVALID_ARGUMENT, "pointers must be 16-byte (workspace 256-byte) aligned");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (plan->gen) {
+    const int32_t rc = sany::run_fwd_mix(*plan->gen, plan->wt.as<float2>(), x, batch, workspace, s);
+    return rc != DLWP_OK ? rc : sany::run_inv(*plan->gen, y, batch, workspace, s);
+  }
   const SpectralCore& sc = plan->sc;
   float* ybuf = reinterpret_cast<float*>(workspace);
   float* zbuf = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + need / 2);

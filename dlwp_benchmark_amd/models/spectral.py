@@ -1,7 +1,8 @@
 """SpectralConv2d -- drop-in for reference models/unet/unet.py:19-69 (the only in-tree spectral
 convolution; PDE-Arena style) on MI355X.  Same constructor, parameter names (`weights1`,
 `weights2` of shape [Ci, Co, m1, m2, 2]) and forward(x) as the reference class; the forward runs
-`dlwp_spectral_conv2d_f32` (pruned-DFT fp32 MFMA kernels) instead of rfft2 / einsum / irfft2.
+`dlwp_spectral_conv2d_f32` (pruned-DFT fp32 MFMA kernels) instead of rfft2 / einsum / irfft2: the 32-channel kernels
+where they apply, the width-generic ones (any Ci, Co <= 512, width a multiple of 4) otherwise.
 """
 import ctypes
 
@@ -79,7 +80,7 @@ class SpectralConv2d(nn.Module):
         _lib.require_cuda_tensor(x, "x")
         if torch.is_grad_enabled() and (x.requires_grad or self.weights1.requires_grad and self.training):
             if self.in_channels != self.out_channels:
-                raise _lib.DlwpError("training path needs in_channels == out_channels (== 32)")
+                raise _lib.DlwpError("training path needs in_channels == out_channels")
             return self._forward_train(x)
         with torch.no_grad():
             return self._forward_infer(x)

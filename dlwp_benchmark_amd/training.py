@@ -41,8 +41,9 @@ def spectral_weight_grad(x, grad_y, rows_in, rows_out, n_cols: int, fwd_scale: f
 
 
 class SpectralOperator:
-    """Forward + adjoint plans of one mode-truncated spectral convolution geometry (32 -> 32 channels,
-    width a multiple of 64: what the HIP kernels are specialised for)."""
+    """Forward + adjoint plans of one mode-truncated spectral convolution geometry, C -> C channels.  32 channels on a
+    width that is a multiple of 64 with at most 16 kept columns run the specialised kernels; every other shape up to
+    C = 512 (width a multiple of 4) the width-generic ones (csrc/spectral_any.hip)."""
 
     def __init__(self, channels: int, height: int, width: int, rows_in: Sequence[int], rows_out: Sequence[int],
                  n_cols: int, fwd_scale: float, inv_scale: float, device):

@@ -50,16 +50,25 @@ int32_t dlwp_device_count(void);
  * ------------------------------------------------------------------------------------------ */
 typedef struct dlwp_fno2d_plan dlwp_fno2d_plan;
 
+/* Two kernel sets behind one plan type, chosen at creation from the shape alone:
+ *   specialised (csrc/fno2d.hip): hidden == 32, lifting and projection multiples of 16, in_channels <= 32,
+ *     out_channels <= 16, n_cols <= 16 -- fused persistent kernels, the execution-form fields below apply;
+ *   width-generic (csrc/spectral_any.hip): every other shape with every channel count in [1, 512] -- one fp32
+ *     arithmetic (MFMA / FMA chains) and a fixed launch sequence per step (lifting 1x1 GELU 1x1, per layer the spectral
+ *     convolution in three launches + the skip 1x1 with bias, GELU and the spectral output fused, projection 1x1 GELU
+ *     1x1 + residual).  precision_form / launch_form / on_timeout / unchecked / debug_spin_limit are validated and
+ *     otherwise ignored; it has no hand-offs and no f16 range: dlwp_fno2d_status returns DLWP_OK, the statistics 0.
+ * Either way the width must be a multiple of 64; other shapes return DLWP_ERR_UNSUPPORTED naming the limit. */
 typedef struct dlwp_fno2d_desc {
-  int32_t in_channels;         /* constant + (prescribed + prognostic) * context            */
-  int32_t hidden_channels;     /* fno.py:24  (kernel support: 32)                           */
-  int32_t lifting_channels;    /* fno.py:25  (multiple of 16)                               */
-  int32_t projection_channels; /* fno.py:26  (multiple of 16)                               */
-  int32_t out_channels;        /* = prognostic_channels, fno.py:45 (<= 16)                  */
+  int32_t in_channels;         /* constant + (prescribed + prognostic) * context  (1..512)  */
+  int32_t hidden_channels;     /* fno.py:24  (1..512; 32 runs the specialised kernels)      */
+  int32_t lifting_channels;    /* fno.py:25  (1..512)                                       */
+  int32_t projection_channels; /* fno.py:26  (1..512)                                       */
+  int32_t out_channels;        /* = prognostic_channels, fno.py:45 (1..512)                 */
   int32_t n_layers;            /* fno.py:27                                                 */
   int32_t height, width;       /* grid; width must be a multiple of 64                      */
   int32_t n_rows;              /* kept spectral rows   (neuralop: min(H, n_modes[0]))       */
-  int32_t n_cols;              /* kept rfft columns    (neuralop: n_modes[1]/2+1), <= 16    */
+  int32_t n_cols;              /* kept rfft columns    (neuralop: n_modes[1]/2+1)           */
   const int32_t* rows_in;      /* host [n_rows]: un-shifted rfft row read by weight row r   */
   const int32_t* rows_out;     /* host [n_rows]: un-shifted row of out_fft it lands in      */
   float fwd_scale;             /* rfftn normalisation  (norm="forward": 1/(H*W))            */
@@ -156,6 +165,10 @@ int32_t dlwp_fno2d_rollout_profiled_f32(const dlwp_fno2d_plan* plan, const float
  * SpectralConv2d  (reference models/unet/unet.py:19-69 + batchmul2d :15-17; PDE-Arena style:
  * un-normalised rfft2, rows [:m1] with weights1 and rows [-m1:] with weights2, cols [:m2],
  * irfft2).  x_dev [B, Ci, H, W] -> y_dev [B, Co, H, W], contiguous fp32.
+ * Ci == Co == 32 on a width that is a multiple of 64 with at most 16 kept columns runs the specialised kernels
+ * (csrc/fno2d.hip); every other shape with Ci, Co in [1, 512], any H, a width that is a multiple of 4 and
+ * H x 2 n_cols within the transform kernels' LDS image (128 KB) runs the width-generic ones (csrc/spectral_any.hip,
+ * fp32 throughout).  Shapes outside both return DLWP_ERR_UNSUPPORTED naming the limit.
  * ------------------------------------------------------------------------------------------ */
 typedef struct dlwp_spectral_plan dlwp_spectral_plan;
 

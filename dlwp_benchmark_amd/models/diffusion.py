@@ -14,8 +14,14 @@ caller supplies (the reference scripts pass diffusers' DDPMScheduler, scripts/ev
 and `.step(pred, k, sample).prev_sample` works).  The reference draws the start noise with `th.randn(shape)` on the host and
 moves it to the device (:186); so does this mirror, so a seeded run sees the same noise.
 
-Not mirrored: the optional `AttentionBlock` (`attention=True`; both reference configs run without it and the encoder / decoder
-never receive the flag's blocks in a usable form) -- constructing with attention=True raises."""
+`attention=True` (modern_unet.py:54, the PDE-Refiner paper's attention experiment; both reference configs run without it) adds
+an `AttentionBlock` after the residual block of every ENCODER level: global multi-head self-attention over the whole feature map
+(per HEALPix face, faces being folded into the batch), its core one dlwp_global_attn_f32 launch pair that never forms the N x N
+score tensor, its two Linears on dlwp_linear_f32.  `DiffModernUNet` / `DiffMUNetHPX` pass the flag to the encoder only, as the
+reference does (:94-121): the middle block and the decoder keep their Identity slots.  `MiddleBlock` and `ModernUNetDecoder`
+constructed directly with attention=True build blocks too.  The encoder and decoder reassign `self.attn` per level, so
+`attn` is the LAST level's block under a second name, registered before `layers` -- the state dict lists it twice
+(`encoder.attn.*`, `encoder.layers.{L-1}.{i}.*`), named_parameters() once."""
 import math
 from typing import Optional
 
@@ -24,6 +30,7 @@ from torch import nn
 
 from .. import lib as _lib
 from .. import ops
+from .. import training as _T
 from .unet import CylinderPad, HEALPixPadding, _resolve_activation
 
 
@@ -42,6 +49,36 @@ def _zero_module(m: nn.Module) -> nn.Module:
     for p in m.parameters():
         p.detach().zero_()
     return m
+
+
+class AttentionBlock(nn.Module):
+    """modern_unet.py:520-585: multi-head self-attention over all H W tokens of a [B, C, H, W] map, `projection` Linear
+    C -> heads * 3 d_k (per head q | k | v contiguous), softmax over the QUERY axis (dim=1 of attn[b, i, j, h]: every key's
+    weights over all queries sum to one), `output` Linear heads d_k -> C, skip `+ x`.  d_k defaults to C, not C / heads.
+    Forward: ops.attention_block (HIP); with gradients wanted the same arithmetic composed from torch operators
+    (training.py's convention)."""
+
+    def __init__(self, in_channels: int, n_heads: int = 4, d_k: Optional[int] = None):
+        super().__init__()
+        self.in_channels = in_channels
+        self.n_heads = n_heads
+        self.d_k = d_k if d_k is not None else in_channels
+        self.projection = nn.Linear(in_channels, n_heads * self.d_k * 3)
+        self.output = nn.Linear(n_heads * self.d_k, in_channels)
+        self.scale = self.d_k ** -0.5
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if _T.wants_grad(x, *self.parameters()):
+            return self._torch_forward(x)
+        return ops.attention_block(x, self.projection, self.output, self.n_heads, self.d_k, self.scale)
+
+    def _torch_forward(self, x: torch.Tensor) -> torch.Tensor:
+        b, c, h, w = x.shape
+        t = x.reshape(b, c, h * w).transpose(1, 2)
+        q, k, v = self.projection(t).view(b, h * w, self.n_heads, 3, self.d_k).unbind(3)
+        p = torch.softmax(torch.einsum("bihd,bjhd->bhij", q, k) * self.scale, dim=2)     # over the queries i
+        res = torch.einsum("bhij,bjhd->bihd", p, v).reshape(b, h * w, self.n_heads * self.d_k)
+        return (self.output(res) + t).transpose(1, 2).reshape(b, c, h, w)
 
 
 class ResidualBlock(nn.Module):
@@ -108,20 +145,22 @@ class ConditionalHEALPixLayer(nn.Module):
 
 
 class MiddleBlock(nn.Module):
-    """modern_unet.py:653-706 (the attention slot is an Identity)."""
+    """modern_unet.py:679-733 (res1, attn, res2; attn an AttentionBlock only when constructed with attention=True --
+    DiffModernUNet never asks for one)."""
 
     def __init__(self, in_channels: int, time_embed_dim: int, attention: bool = False, activation=None, norm: bool = False,
                  use_scale_shift_norm: bool = True, mesh=None):
         super().__init__()
-        if attention:
-            raise NotImplementedError("MiddleBlock: attention=True is not built (unused by the reference configs)")
         kw = dict(cond_channels=time_embed_dim, activation=activation, norm=norm, use_scale_shift_norm=use_scale_shift_norm, mesh=mesh)
         self.res1 = ResidualBlock(in_channels, in_channels, **kw)
-        self.attn = nn.Identity()
+        self.attn = AttentionBlock(in_channels) if attention else nn.Identity()
         self.res2 = ResidualBlock(in_channels, in_channels, **kw)
 
     def forward(self, x, emb):
-        return self.res2(self.res1(x, emb), emb)
+        x = self.res1(x, emb)
+        if isinstance(self.attn, AttentionBlock):
+            x = self.attn(x)
+        return self.res2(x, emb)
 
 
 def _cond_layer(c_in, c_out, time_embed_dim, mesh, use_scale_shift_norm):
@@ -133,23 +172,22 @@ def _cond_layer(c_in, c_out, time_embed_dim, mesh, use_scale_shift_norm):
 
 
 class ModernUNetEncoder(nn.Module):
-    """modern_unet.py:325-406: per level [Conv2d(3x3, stride 2) below the top], conditioned ResidualBlock, Identity."""
+    """modern_unet.py:325-406: per level [Conv2d(3x3, stride 2) below the top], conditioned ResidualBlock, then the
+    level's AttentionBlock (attention=True) or Identity; `attn` is the last level's."""
 
     def __init__(self, in_channels=2, hidden_channels=(64, 128, 256, 1024), time_embed_dim=1024, activation=None,
                  attention: bool = False, mesh: str = "equirectangular", use_scale_shift_norm=True):
         super().__init__()
-        if attention:
-            raise NotImplementedError("attention=True is not built (unused by the reference configs)")
         channels = [in_channels] + list(hidden_channels)
         layers = []
         for i in range(len(channels) - 1):
+            self.attn = AttentionBlock(channels[i + 1]) if attention else nn.Identity()   # reassigned per level, as :352-355
             layer = []
             if i > 0:
                 layer.append(nn.Conv2d(channels[i], channels[i], (3, 3), (2, 2), (1, 1)))
             layer.append(_cond_layer(channels[i], channels[i + 1], time_embed_dim, mesh, use_scale_shift_norm))
-            layer.append(nn.Identity())
+            layer.append(self.attn)
             layers.append(nn.Sequential(*layer))
-        self.attn = nn.Identity()
         self.layers = nn.ModuleList(layers)
 
     def forward(self, x, emb):
@@ -158,6 +196,8 @@ class ModernUNetEncoder(nn.Module):
             for m in layer:
                 if isinstance(m, nn.Conv2d):
                     x = ops.small_module(m, x)
+                elif isinstance(m, AttentionBlock):
+                    x = m(x)
                 elif not isinstance(m, nn.Identity):
                     x = m(x, emb)
             outs.append(x)
@@ -166,22 +206,21 @@ class ModernUNetEncoder(nn.Module):
 
 class ModernUNetDecoder(nn.Module):
     """modern_unet.py:408-497: per level conditioned ResidualBlock (on cat([skip, x]) below the bottom), Identity,
-    [ConvTranspose2d(4, 2, 1) above the top]; then GroupNorm(4) -> activation -> 1x1 output convolution."""
+    [ConvTranspose2d(4, 2, 1) above the top]; then GroupNorm(4) -> activation -> 1x1 output convolution.  With attention=True
+    the Identity of every level is that level's AttentionBlock, `attn` the last level's (DiffModernUNet never asks for it)."""
 
     def __init__(self, hidden_channels=(64, 128, 256, 1024), out_channels=2, time_embed_dim=1024, activation=None,
                  attention: bool = False, mesh: str = "equirectangular", use_scale_shift_norm=True):
         super().__init__()
-        if attention:
-            raise NotImplementedError("attention=True is not built (unused by the reference configs)")
         hidden = list(hidden_channels)[::-1]
         self.activation = _resolve_activation(activation) if activation is not None else nn.GELU()
         layers = []
         for i, c in enumerate(hidden):
-            layer = [_cond_layer(c if i == 0 else 2 * c, c, time_embed_dim, mesh, use_scale_shift_norm), nn.Identity()]
+            self.attn = AttentionBlock(c) if attention else nn.Identity()                 # reassigned per level, as :438-441
+            layer = [_cond_layer(c if i == 0 else 2 * c, c, time_embed_dim, mesh, use_scale_shift_norm), self.attn]
             if i < len(hidden) - 1:
                 layer.append(nn.ConvTranspose2d(c, hidden[i + 1], (4, 4), (2, 2), (1, 1)))
             layers.append(nn.Sequential(*layer))
-        self.attn = nn.Identity()
         self.layers = nn.ModuleList(layers)
         self.output_layer = _zero_module(nn.Conv2d(hidden[-1], out_channels, kernel_size=1))
         self.final_norm = nn.GroupNorm(4, hidden[-1])
@@ -193,6 +232,8 @@ class ModernUNetDecoder(nn.Module):
             for m in layer:
                 if isinstance(m, nn.ConvTranspose2d):
                     x = ops.small_module(m, x)
+                elif isinstance(m, AttentionBlock):
+                    x = m(x)
                 elif not isinstance(m, nn.Identity):
                     x = m(x, emb)
         fn = self.final_norm
@@ -208,8 +249,6 @@ class DiffModernUNet(nn.Module):
                  attention: bool = False, norm: bool = False, use_scale_shift_norm=True, predict_diff=True,
                  num_refinement_step=5, **kwargs):
         super().__init__()
-        if attention:
-            raise NotImplementedError("attention=True is not built (unused by the reference configs)")
         activation = _resolve_activation(activation) if activation is not None else nn.GELU()
         self.context_size = context_size
         self.mesh = mesh
@@ -224,6 +263,7 @@ class DiffModernUNet(nn.Module):
         self.encoder = ModernUNetEncoder(in_channels=in_channels, hidden_channels=self.hidden_channels,
                                          time_embed_dim=time_embed_dim, activation=activation, attention=attention, mesh=mesh,
                                          use_scale_shift_norm=use_scale_shift_norm)
+        # the flag reaches the encoder only (:94-121): middle block and decoder keep their Identity slots
         self.middle = MiddleBlock(in_channels=self.hidden_channels[-1], time_embed_dim=time_embed_dim, norm=norm,
                                   activation=activation, use_scale_shift_norm=use_scale_shift_norm, mesh=mesh)
         self.decoder = ModernUNetDecoder(hidden_channels=self.hidden_channels, out_channels=prognostic_channels,

@@ -1115,3 +1115,55 @@ class HipLayerNorm(torch.nn.LayerNorm):
         if len(self.normalized_shape) != 1 or self.weight is None or self.bias is None or x.shape[-1] % 4:
             raise _lib.DlwpError("HipLayerNorm needs a 1-D affine normalized_shape with channels % 4 == 0")
         return layer_norm(x, self.weight, self.bias, self.eps)
+
+
+def global_attention(qkv: torch.Tensor, heads: int, d_k: int, scale: Optional[float] = None) -> torch.Tensor:
+    """Global multi-head self-attention over all tokens of a sample (reference modern_unet.py:565-571, the core of the
+    diffusion U-Net's AttentionBlock) on dlwp_global_attn_f32: qkv [Bt, N, heads * 3 * d_k] (or [Bt, N, heads, 3, d_k]),
+    per head q | k | v contiguous, as the projection Linear writes it; returns [Bt, N, heads * d_k].  The softmax runs
+    over the QUERY axis (the reference's dim=1); scale defaults to d_k ** -0.5.  Runs on the current stream with no host
+    synchronisation; there is no other path -- a shape the kernel cannot take raises."""
+    _lib.require_cuda_tensor(qkv, "qkv")
+    heads, d_k = int(heads), int(d_k)
+    if heads <= 0 or d_k <= 0:
+        raise _lib.DlwpError(f"global_attention: heads {heads} and d_k {d_k} must be positive")
+    if qkv.dim() == 5:
+        if tuple(qkv.shape[2:]) != (heads, 3, d_k):
+            raise _lib.DlwpError(f"global_attention: qkv {tuple(qkv.shape)} is not [Bt, N, {heads}, 3, {d_k}]")
+        qkv = qkv.reshape(qkv.shape[0], qkv.shape[1], -1)
+    if qkv.dim() != 3 or qkv.shape[-1] != heads * 3 * d_k:
+        raise _lib.DlwpError(f"global_attention: qkv {tuple(qkv.shape)} is not [Bt, N, {heads * 3 * d_k}]")
+    bt, n = int(qkv.shape[0]), int(qkv.shape[1])
+    if bt <= 0 or n <= 0 or bt > 2 ** 31 - 1 or n > 2 ** 31 - 1:
+        raise _lib.DlwpError(f"global_attention: batch {bt} and tokens {n} must be in [1, 2^31)")
+    scale = d_k ** -0.5 if scale is None else float(scale)
+    qkv = qkv.contiguous()
+    lib = _lib.load()
+    ws = torch.empty(int(lib.dlwp_global_attn_workspace_bytes(bt, heads, n)) // 4, device=qkv.device, dtype=torch.float32)
+    out = torch.empty((bt, n, heads * d_k), device=qkv.device, dtype=torch.float32)
+    with torch.cuda.device(qkv.device):
+        _lib.check(lib.dlwp_global_attn_f32(qkv.data_ptr(), out.data_ptr(), bt, n, heads, d_k, scale, ws.data_ptr(),
+                                            ws.numel() * 4, _lib.stream_ptr()), "dlwp_global_attn_f32")
+    return out
+
+
+def attention_block(x: torch.Tensor, projection: torch.nn.Linear, output: torch.nn.Linear, heads: int, d_k: int,
+                    scale: Optional[float] = None) -> torch.Tensor:
+    """AttentionBlock.forward of the diffusion U-Net (reference modern_unet.py:551-585) on [B, C, H, W]: tokens
+    [B, H W, C] (a copy), the projection Linear (linear_any), global_attention, the output Linear with the skip `+ x`
+    in its epilogue (linear(resid=), in place on the token copy; the module itself where dlwp_linear_f32 does not take
+    the shape), back to [B, C, H, W] (a copy)."""
+    _lib.require_cuda_tensor(x, "x")
+    if x.dim() != 4:
+        raise _lib.DlwpError(f"attention_block: x must be [B, C, H, W] (got {tuple(x.shape)})")
+    b, c, h, w = x.shape
+    if projection.in_features != c or projection.out_features != heads * 3 * d_k or \
+            output.in_features != heads * d_k or output.out_features != c:
+        raise _lib.DlwpError(f"attention_block: Linears {projection} / {output} do not match C {c}, heads {heads}, d_k {d_k}")
+    t = x.reshape(b, c, h * w).transpose(1, 2).contiguous()
+    res = global_attention(linear_any(t, projection), heads, d_k, scale)
+    if linear_supported(output.in_features, output.out_features):
+        y = linear(res, output, resid=t, out=t)
+    else:
+        y = output(res).add_(t)
+    return y.transpose(1, 2).reshape(b, c, h, w).contiguous()

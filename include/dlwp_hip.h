@@ -577,6 +577,18 @@ int32_t dlwp_weighted_error_sums_acc_f32(const float* out_dev, const float* targ
                                          int32_t batch, int32_t steps, int32_t channels, int32_t height, int32_t width,
                                          void* stream);
 
+/* Global multi-head self-attention of the diffusion U-Net's AttentionBlock (reference
+ * models/diffusion_models/modern_unet/modern_unet.py:565-571: einsum -> softmax(dim=1) -> einsum, between the `projection`
+ * and `output` Linears), fp32-accurate (v_mfma_f32_16x16x4_f32), with no N x N tensor anywhere.
+ * qkv_dev [batch, tokens, heads, 3, head_dim] (the projection output viewed [B, N, heads, 3 d_k] and chunked in three);
+ * out_dev [batch, tokens, heads * head_dim].  The softmax runs over the QUERY axis, as the reference's dim=1: every key's
+ * weights over all queries sum to one.  Two launches on `stream`: per-key log-sum-exp statistics into the workspace, then
+ * the output.  Any shape with positive sizes runs; head_dim % 4 == 0 with 16-byte aligned pointers takes 16-byte loads.
+ *   dlwp_global_attn_workspace_bytes: batch * heads * tokens floats (0 for a non-positive size) */
+size_t dlwp_global_attn_workspace_bytes(int32_t batch, int32_t heads, int32_t tokens);
+int32_t dlwp_global_attn_f32(const float* qkv_dev, float* out_dev, int32_t batch, int32_t tokens, int32_t heads,
+                             int32_t head_dim, float scale, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -156,6 +156,9 @@ SIGNATURES = {
     "dlwp_global_attn_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "dlwp_global_attn_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_size_t,
                                        c_void_p]),
+    "dlwp_global_attn_bwd_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "dlwp_global_attn_bwd_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float,
+                                           c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

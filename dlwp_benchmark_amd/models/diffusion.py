@@ -55,8 +55,11 @@ class AttentionBlock(nn.Module):
     """modern_unet.py:520-585: multi-head self-attention over all H W tokens of a [B, C, H, W] map, `projection` Linear
     C -> heads * 3 d_k (per head q | k | v contiguous), softmax over the QUERY axis (dim=1 of attn[b, i, j, h]: every key's
     weights over all queries sum to one), `output` Linear heads d_k -> C, skip `+ x`.  d_k defaults to C, not C / heads.
-    Forward: ops.attention_block (HIP); with gradients wanted the same arithmetic composed from torch operators
-    (training.py's convention)."""
+    Forward: ops.attention_block (HIP).  With gradients wanted: tokens by a torch transpose, the attention through
+    training.global_attention (HIP forward and backward, no N x N tensor), the two Linears as the modules themselves: the
+    HIP GEMM's weight gradient reduces over all Bt N tokens, which it does slower than torch here and refuses at nside 64
+    with batch 32 (its 32-bit tile offsets), DESIGN.md section 12.  _torch_forward is the same block composed from torch
+    operators, kept as the cross-check."""
 
     def __init__(self, in_channels: int, n_heads: int = 4, d_k: Optional[int] = None):
         super().__init__()
@@ -69,8 +72,18 @@ class AttentionBlock(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if _T.wants_grad(x, *self.parameters()):
-            return self._torch_forward(x)
+            # a CPU tensor keeps the torch composition it always had with gradients; on the device the HIP kernels run
+            return self._train_forward(x) if x.is_cuda else self._torch_forward(x)
         return ops.attention_block(x, self.projection, self.output, self.n_heads, self.d_k, self.scale)
+
+    def _train_forward(self, x: torch.Tensor) -> torch.Tensor:
+        b, c, h, w = x.shape
+        if c != self.in_channels:
+            raise _lib.DlwpError(f"AttentionBlock: x has {c} channels, the block {self.in_channels}")
+        t = x.reshape(b, c, h * w).transpose(1, 2)
+        qkv = self.projection(t)
+        res = _T.global_attention(qkv, self.n_heads, self.d_k, self.scale)
+        return (self.output(res) + t).transpose(1, 2).reshape(b, c, h, w)
 
     def _torch_forward(self, x: torch.Tensor) -> torch.Tensor:
         b, c, h, w = x.shape

@@ -1117,12 +1117,14 @@ class HipLayerNorm(torch.nn.LayerNorm):
         return layer_norm(x, self.weight, self.bias, self.eps)
 
 
-def global_attention(qkv: torch.Tensor, heads: int, d_k: int, scale: Optional[float] = None) -> torch.Tensor:
+def global_attention(qkv: torch.Tensor, heads: int, d_k: int, scale: Optional[float] = None, return_stats: bool = False):
     """Global multi-head self-attention over all tokens of a sample (reference modern_unet.py:565-571, the core of the
     diffusion U-Net's AttentionBlock) on dlwp_global_attn_f32: qkv [Bt, N, heads * 3 * d_k] (or [Bt, N, heads, 3, d_k]),
     per head q | k | v contiguous, as the projection Linear writes it; returns [Bt, N, heads * d_k].  The softmax runs
     over the QUERY axis (the reference's dim=1); scale defaults to d_k ** -0.5.  Runs on the current stream with no host
-    synchronisation; there is no other path -- a shape the kernel cannot take raises."""
+    synchronisation; there is no other path -- a shape the kernel cannot take raises.  return_stats=True returns
+    (out, stats): stats [Bt, heads, N] is the kernel's workspace, the per-key log-sum-exp in base 2 that
+    global_attention_backward takes."""
     _lib.require_cuda_tensor(qkv, "qkv")
     heads, d_k = int(heads), int(d_k)
     if heads <= 0 or d_k <= 0:
@@ -1144,7 +1146,47 @@ def global_attention(qkv: torch.Tensor, heads: int, d_k: int, scale: Optional[fl
     with torch.cuda.device(qkv.device):
         _lib.check(lib.dlwp_global_attn_f32(qkv.data_ptr(), out.data_ptr(), bt, n, heads, d_k, scale, ws.data_ptr(),
                                             ws.numel() * 4, _lib.stream_ptr()), "dlwp_global_attn_f32")
-    return out
+    return (out, ws.view(bt, heads, n)) if return_stats else out
+
+
+def global_attention_backward(qkv: torch.Tensor, stats: torch.Tensor, grad_out: torch.Tensor, heads: int, d_k: int,
+                              scale: Optional[float] = None) -> torch.Tensor:
+    """Gradient of global_attention with respect to qkv on dlwp_global_attn_bwd_f32: qkv as given to the forward, stats its
+    return_stats workspace [Bt, heads, N], grad_out [Bt, N, heads * d_k]; returns dqkv in the shape of qkv (per head
+    dq | dk | dv, the layout the projection Linear's backward takes).  Runs on the current stream with no host
+    synchronisation; a shape the kernel does not take raises DlwpError (status -2 for DLWP_ERR_UNSUPPORTED)."""
+    _lib.require_cuda_tensor(qkv, "qkv")
+    _lib.require_cuda_tensor(stats, "stats")
+    _lib.require_cuda_tensor(grad_out, "grad_out")
+    heads, d_k = int(heads), int(d_k)
+    if heads <= 0 or d_k <= 0:
+        raise _lib.DlwpError(f"global_attention_backward: heads {heads} and d_k {d_k} must be positive")
+    shape = qkv.shape
+    if qkv.dim() == 5:
+        if tuple(qkv.shape[2:]) != (heads, 3, d_k):
+            raise _lib.DlwpError(f"global_attention_backward: qkv {tuple(qkv.shape)} is not [Bt, N, {heads}, 3, {d_k}]")
+        qkv = qkv.reshape(qkv.shape[0], qkv.shape[1], -1)
+    if qkv.dim() != 3 or qkv.shape[-1] != heads * 3 * d_k:
+        raise _lib.DlwpError(f"global_attention_backward: qkv {tuple(qkv.shape)} is not [Bt, N, {heads * 3 * d_k}]")
+    bt, n = int(qkv.shape[0]), int(qkv.shape[1])
+    if bt <= 0 or n <= 0 or bt > 2 ** 31 - 1 or n > 2 ** 31 - 1:
+        raise _lib.DlwpError(f"global_attention_backward: batch {bt} and tokens {n} must be in [1, 2^31)")
+    if tuple(grad_out.shape) != (bt, n, heads * d_k):
+        raise _lib.DlwpError(f"global_attention_backward: grad_out {tuple(grad_out.shape)} is not [{bt}, {n}, {heads * d_k}]")
+    if stats.numel() != bt * heads * n:
+        raise _lib.DlwpError(f"global_attention_backward: stats of {stats.numel()} values, {bt * heads * n} needed")
+    if qkv.device != grad_out.device or qkv.device != stats.device:
+        raise _lib.DlwpError("global_attention_backward: qkv, stats and grad_out must be on one device")
+    scale = d_k ** -0.5 if scale is None else float(scale)
+    qkv, grad_out, stats = qkv.contiguous(), grad_out.contiguous(), stats.contiguous()
+    lib = _lib.load()
+    ws = torch.empty(int(lib.dlwp_global_attn_bwd_workspace_bytes(bt, heads, n)) // 4, device=qkv.device, dtype=torch.float32)
+    dqkv = torch.empty_like(qkv)
+    with torch.cuda.device(qkv.device):
+        _lib.check(lib.dlwp_global_attn_bwd_f32(qkv.data_ptr(), grad_out.data_ptr(), stats.data_ptr(), dqkv.data_ptr(), bt, n,
+                                                heads, d_k, scale, ws.data_ptr(), ws.numel() * 4, _lib.stream_ptr()),
+                   "dlwp_global_attn_bwd_f32")
+    return dqkv.view(shape)
 
 
 def attention_block(x: torch.Tensor, projection: torch.nn.Linear, output: torch.nn.Linear, heads: int, d_k: int,

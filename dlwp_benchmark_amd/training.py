@@ -284,6 +284,55 @@ def window_attention(qkv, qkv_bias, table, spec, precision="fp32"):
     return _WindowAttentionFn.apply(qkv, qkv_bias, table, spec, precision)
 
 
+def global_attention_torch(qkv: torch.Tensor, heads: int, d_k: int, scale: float) -> torch.Tensor:
+    """What dlwp_global_attn_f32 computes, with torch operators (differentiable in qkv): modern_unet.py:558-571 between the
+    two Linears, qkv [Bt, N, heads 3 d_k] -> [Bt, N, heads d_k], softmax over the queries.  Forms the N x N scores."""
+    bt, n = qkv.shape[:2]
+    q, k, v = qkv.reshape(bt, n, heads, 3, d_k).unbind(3)
+    p = torch.softmax(torch.einsum("bihd,bjhd->bhij", q, k) * scale, dim=2)
+    return torch.einsum("bhij,bjhd->bihd", p, v).reshape(bt, n, heads * d_k)
+
+
+class _GlobalAttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, heads, d_k, scale):
+        from . import ops
+
+        with torch.no_grad():
+            out, stats = ops.global_attention(qkv.detach(), heads, d_k, scale, return_stats=True)
+        ctx.cfg = (heads, d_k, scale)
+        ctx.save_for_backward(qkv, stats)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        """HIP backward (dlwp_global_attn_bwd_f32) from the forward's per-key statistics: no N x N tensor.  DLWP_ERR_UNSUPPORTED
+        (head_dim above 1024) and DLWP_TRAIN_TORCH_BACKWARD=1 (the cross-check the tests use) take the torch recomputation
+        below; any other error raises."""
+        from . import ops
+
+        qkv, stats = ctx.saved_tensors
+        heads, d_k, scale = ctx.cfg
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        if not _TORCH_BACKWARD():
+            try:
+                return ops.global_attention_backward(qkv, stats, grad_out, heads, d_k, scale), None, None, None
+            except _lib.DlwpError as e:
+                if "status -2:" not in str(e):       # DLWP_ERR_UNSUPPORTED only
+                    raise
+        with torch.enable_grad():
+            q_ = qkv.detach().requires_grad_(True)
+            out = global_attention_torch(q_, heads, d_k, scale)
+            g, = torch.autograd.grad(out, q_, grad_out.contiguous())
+        return g, None, None, None
+
+
+def global_attention(qkv, heads: int, d_k: int, scale: float):
+    """differentiable global attention of the diffusion AttentionBlock: HIP forward and HIP backward"""
+    return _GlobalAttentionFn.apply(qkv, heads, d_k, scale)
+
+
 def afno_filter_torch(x_cf, w1, b1, w2, b2, num_blocks: int, sparsity_threshold: float, hard_thresholding_fraction: float):
     """fourcastnet.py:85-124 on a CHANNELS-FIRST field (without the `+ bias` of :127), torch operators."""
     b, c, h, w = x_cf.shape

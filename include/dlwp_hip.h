@@ -584,10 +584,24 @@ int32_t dlwp_weighted_error_sums_acc_f32(const float* out_dev, const float* targ
  * out_dev [batch, tokens, heads * head_dim].  The softmax runs over the QUERY axis, as the reference's dim=1: every key's
  * weights over all queries sum to one.  Two launches on `stream`: per-key log-sum-exp statistics into the workspace, then
  * the output.  Any shape with positive sizes runs; head_dim % 4 == 0 with 16-byte aligned pointers takes 16-byte loads.
- *   dlwp_global_attn_workspace_bytes: batch * heads * tokens floats (0 for a non-positive size) */
+ *   dlwp_global_attn_workspace_bytes: batch * heads * tokens floats (0 for a non-positive size)
+ * After the call the workspace holds the per-key statistics [batch, heads, tokens] in base 2, L_j log2(e) with
+ * L_j = m_j + ln sum_i exp(s_ij - m_j): the `stats_dev` of dlwp_global_attn_bwd_f32. */
 size_t dlwp_global_attn_workspace_bytes(int32_t batch, int32_t heads, int32_t tokens);
 int32_t dlwp_global_attn_f32(const float* qkv_dev, float* out_dev, int32_t batch, int32_t tokens, int32_t heads,
                              int32_t head_dim, float scale, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Backward of dlwp_global_attn_f32: from grad_out_dev [batch, tokens, heads * head_dim] (the gradient of out_dev) and the
+ * forward's workspace as it stands (stats_dev, L_j log2(e)), writes dqkv_dev in the layout of qkv_dev
+ * [batch, tokens, heads, 3, head_dim] -- every element, so it needs no zeroing -- with the same scale.  fp32-accurate
+ * (v_mfma_f32_16x16x4_f32), no N x N tensor, no atomics: bitwise reproducible.  Three launches on `stream` (dV; the per-key
+ * delta D_j = v_j . dV_j into the workspace and dK; dQ), no host synchronisation.  head_dim 1 .. 1024 and any positive
+ * batch / tokens / heads; head_dim above 1024 returns DLWP_ERR_UNSUPPORTED.  dqkv_dev may not alias an input.
+ *   dlwp_global_attn_bwd_workspace_bytes: batch * heads * tokens floats (0 for a non-positive size) */
+size_t dlwp_global_attn_bwd_workspace_bytes(int32_t batch, int32_t heads, int32_t tokens);
+int32_t dlwp_global_attn_bwd_f32(const float* qkv_dev, const float* grad_out_dev, const float* stats_dev, float* dqkv_dev,
+                                 int32_t batch, int32_t tokens, int32_t heads, int32_t head_dim, float scale,
+                                 void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

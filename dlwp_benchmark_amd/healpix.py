@@ -11,6 +11,7 @@ Face order and orientation follow the reference (healpix.py:209-226): faces 0-3 
 quarter-turns that border crossing applies.
 """
 import functools
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -94,3 +95,39 @@ def device_table(h: int, w: int, p: int, device) -> torch.Tensor:
     if key not in _device_tables:
         _device_tables[key] = pad_table(h, w, p).to(device).contiguous()
     return _device_tables[key]
+
+
+class AdjointTable(NamedTuple):
+    """CSR of the transpose of `pad_table`: for source cell s = face*h*w + pixel of one sample, entries
+    indptr[s] .. indptr[s+1] list the padded positions q = face*(h+2p)*(w+2p) + padded pixel that read s, in increasing q,
+    with their weight (1, or 0.5 for a synthesised corner, which is the mean of two cells)."""
+    indptr: torch.Tensor     # int32 [12*h*w + 1]
+    index: torch.Tensor      # int32 [nnz]
+    weight: torch.Tensor     # float32 [nnz]
+
+
+@functools.lru_cache(maxsize=32)
+def pad_adjoint_table(h: int, w: int, p: int) -> AdjointTable:
+    """The adjoint of HEALPixPadding(p) as a gather: dx[s] = sum over the entries of s of weight * dy[q] (CPU tensors)."""
+    table = pad_table(h, w, p).reshape(-1, 2).numpy().astype(np.int64)
+    q = np.arange(table.shape[0], dtype=np.int64)
+    single = table[:, 1] < 0
+    src = np.concatenate([table[:, 0], table[~single, 1]])
+    pos = np.concatenate([q, q[~single]])
+    wt = np.concatenate([np.where(single, 1.0, 0.5), np.full(int((~single).sum()), 0.5)])
+    order = np.lexsort((pos, src))                  # by source cell, then by padded position
+    src, pos, wt = src[order], pos[order], wt[order]
+    indptr = np.zeros(12 * h * w + 1, dtype=np.int64)
+    np.add.at(indptr, src + 1, 1)
+    return AdjointTable(torch.from_numpy(np.cumsum(indptr).astype(np.int32)), torch.from_numpy(pos.astype(np.int32)),
+                        torch.from_numpy(wt.astype(np.float32)))
+
+
+_device_adjoints = {}
+
+
+def device_adjoint_table(h: int, w: int, p: int, device) -> AdjointTable:
+    key = (h, w, p, str(device))
+    if key not in _device_adjoints:
+        _device_adjoints[key] = AdjointTable(*(t.to(device).contiguous() for t in pad_adjoint_table(h, w, p)))
+    return _device_adjoints[key]

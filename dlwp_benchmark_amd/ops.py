@@ -405,18 +405,67 @@ def healpix_pad(x: torch.Tensor, padding: int) -> torch.Tensor:
     n, c, h, w = x.shape
     if n % 12:
         raise _lib.DlwpError(f"leading dimension {n} is not (batch * 12 faces)")
-    table = _hpx.device_table(h, w, int(padding), x.device)
     if torch.is_grad_enabled() and x.requires_grad:
-        if int(padding) != 1:
-            raise _lib.DlwpError("differentiable HEALPix padding is built for padding 1")
         from . import training as _T
-        return _T._hpx_pad_torch(x, table)
+        return _T.healpix_pad(x, int(padding))          # HIP forward, backward through the adjoint kernel
+    table = _hpx.device_table(h, w, int(padding), x.device)
     y = torch.empty(n, c, h + 2 * padding, w + 2 * padding, device=x.device, dtype=torch.float32)
     lib = _lib.load()
     with torch.cuda.device(x.device):
         _lib.check(lib.dlwp_healpix_pad_f32(x.data_ptr(), y.data_ptr(), table.data_ptr(), n, c, h, w, int(padding),
                                             _lib.stream_ptr()), "dlwp_healpix_pad_f32")
     return y
+
+
+def healpix_pad_backward(dy: torch.Tensor, padding: int) -> torch.Tensor:
+    """Adjoint of healpix_pad: [(B*12), C, H+2p, W+2p] -> [(B*12), C, H, W] through the transposed table
+    (dlwp_healpix_pad_bwd_f32)."""
+    from . import healpix as _hpx
+
+    _lib.require_cuda_tensor(dy, "dy")
+    dy = dy.contiguous()
+    p = int(padding)
+    n, c, ph, pw = dy.shape
+    h, w = ph - 2 * p, pw - 2 * p
+    if n % 12:
+        raise _lib.DlwpError(f"leading dimension {n} is not (batch * 12 faces)")
+    if h <= 0 or h != w:
+        raise _lib.DlwpError(f"padded face {ph}x{pw} does not hold a square face with padding {p}")
+    adj = _hpx.device_adjoint_table(h, w, p, dy.device)
+    dx = torch.empty(n, c, h, w, device=dy.device, dtype=torch.float32)
+    lib = _lib.load()
+    with torch.cuda.device(dy.device):
+        _lib.check(lib.dlwp_healpix_pad_bwd_f32(dy.data_ptr(), dx.data_ptr(), adj.indptr.data_ptr(), adj.index.data_ptr(),
+                                                adj.weight.data_ptr(), n, c, h, w, p, _lib.stream_ptr()),
+                   "dlwp_healpix_pad_bwd_f32")
+    return dx
+
+
+def conv3x3_hpx_backward_data(dy: torch.Tensor, weight: torch.Tensor, cin: int) -> torch.Tensor:
+    """Gradient of HEALPixPadding(1) + Conv2d(3x3, padding 0) with respect to its (activated, concatenated) input:
+    dy [(B*12), Cout, H, W], weight [Cout, cin, 3, 3] in the forward layout -> [(B*12), cin, H, W]
+    (dlwp_conv3x3_hpx_bwd_data_f32)."""
+    from . import healpix as _hpx
+
+    _lib.require_cuda_tensor(dy, "dy")
+    _lib.require_cuda_tensor(weight, "weight")
+    dy = dy.contiguous()
+    weight = weight.contiguous()
+    n, cout, h, w = dy.shape
+    if n % 12:
+        raise _lib.DlwpError(f"leading dimension {n} is not (batch * 12 faces)")
+    if tuple(weight.shape) != (cout, int(cin), 3, 3):
+        raise _lib.DlwpError(f"weight {tuple(weight.shape)} does not match {cout} output, {cin} input channels, 3x3")
+    adj = _hpx.device_adjoint_table(h, w, 1, dy.device)
+    dx = torch.empty(n, int(cin), h, w, device=dy.device, dtype=torch.float32)
+    lib = _lib.load()
+    nbytes = lib.dlwp_conv3x3_hpx_bwd_data_workspace_bytes(n, h, w, int(cin))
+    ring = torch.empty(max(nbytes, 4) // 4, device=dy.device, dtype=torch.float32)
+    with torch.cuda.device(dy.device):
+        _lib.check(lib.dlwp_conv3x3_hpx_bwd_data_f32(dy.data_ptr(), weight.data_ptr(), dx.data_ptr(), n, h, w, int(cin), cout,
+                                                     adj.indptr.data_ptr(), adj.index.data_ptr(), adj.weight.data_ptr(),
+                                                     ring.data_ptr(), nbytes, _lib.stream_ptr()), "dlwp_conv3x3_hpx_bwd_data_f32")
+    return dx
 
 
 def convlstm_gates(gates: torch.Tensor, c_prev: torch.Tensor):

@@ -396,8 +396,9 @@ def afno_filter(x_cf, w1, b1, w2, b2, num_blocks, lam, frac):
 
 
 def _hpx_pad_torch(x, table):
-    """HEALPixPadding(1) as a differentiable gather: x [(B*12), C, H, W], table int32 [12, (H+2)(W+2), 2]."""
+    """HEALPixPadding(p) as a differentiable gather: x [(B*12), C, H, W], table int32 [12, (H+2p)(W+2p), 2]."""
     n, c, h, w = x.shape
+    p = (int(round(table.shape[1] ** 0.5)) - h) // 2
     bsz = n // 12
     flat = x.view(bsz, 12, c, h * w).permute(0, 2, 1, 3).reshape(bsz, c, 12 * h * w)
     a = table[:, :, 0].long().reshape(-1)
@@ -405,7 +406,41 @@ def _hpx_pad_torch(x, table):
     va = flat[:, :, a]
     vb = flat[:, :, b_.clamp(min=0)]
     v = torch.where((b_ >= 0).view(1, 1, -1), 0.5 * va + 0.5 * vb, va)
-    return v.view(bsz, c, 12, h + 2, w + 2).permute(0, 2, 1, 3, 4).reshape(n, c, h + 2, w + 2)
+    return v.view(bsz, c, 12, h + 2 * p, w + 2 * p).permute(0, 2, 1, 3, 4).reshape(n, c, h + 2 * p, w + 2 * p)
+
+
+class _HpxPadFn(torch.autograd.Function):
+    """HEALPixPadding(p) (reference utils/healpix.py:165-368) for any p: dlwp_healpix_pad_f32 forward, its adjoint
+    dlwp_healpix_pad_bwd_f32 (the gather through healpix.pad_adjoint_table) backward; DLWP_TRAIN_TORCH_BACKWARD=1
+    differentiates the torch gather _hpx_pad_torch instead."""
+
+    @staticmethod
+    def forward(ctx, x, padding):
+        from . import ops
+
+        ctx.padding = padding
+        ctx.save_for_backward(x)
+        with torch.no_grad():
+            return ops.healpix_pad(x.detach(), padding)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from . import healpix as _hpx
+        from . import ops
+
+        if not _TORCH_BACKWARD():
+            with torch.no_grad():
+                return ops.healpix_pad_backward(grad_out, ctx.padding), None
+        x, = ctx.saved_tensors
+        with torch.enable_grad():
+            x_ = x.detach().requires_grad_(True)
+            table = _hpx.device_table(x.shape[2], x.shape[3], ctx.padding, x.device)
+            gx, = torch.autograd.grad(_hpx_pad_torch(x_, table), x_, grad_out.contiguous())
+        return gx, None
+
+
+def healpix_pad(x, padding: int):
+    return _HpxPadFn.apply(x, int(padding))
 
 
 def conv3x3_torch(x0, x1, weight, bias, resid, pre_act: int, act: int, hpx_table=None):
@@ -420,6 +455,11 @@ def conv3x3_torch(x0, x1, weight, bias, resid, pre_act: int, act: int, hpx_table
     if resid is not None:
         y = y + resid
     return _ACT_FNS[act](y)
+
+
+# output channels up to which the HEALPix input gradient runs dlwp_conv3x3_hpx_bwd_data_f32; wider layers take the two-step
+# form (MIOpen transposed conv + dlwp_healpix_pad_bwd_f32), which measured faster there
+HPX_DX_DIRECT_MAX_COUT = 48
 
 
 class _Conv3x3Fn(torch.autograd.Function):
@@ -440,25 +480,34 @@ class _Conv3x3Fn(torch.autograd.Function):
 
         pre_act, act, hpx = ctx.cfg
         saved = ctx.saved_tensors
-        if not hpx and not _TORCH_BACKWARD():
+        if not _TORCH_BACKWARD():
             # CylinderPad (circular in longitude, zeros in latitude) + 3x3: the input gradient is the SAME operator with the weights
             # transposed and flipped -- dlwp_conv3x3_ex_f32 again (reference backward: train.py:271 through unet.py:429-555,
             # convlstm.py:82-111); pre- / post-activation derivatives are pointwise torch operators, the weight gradient is one
-            # correlation of the padded input with the output gradient (MIOpen through torch, like the other weight gradients)
+            # correlation of the padded input with the output gradient (MIOpen through torch, like the other weight gradients).
+            # HEALPixPadding(1) + 3x3 (healpix.py:69-114): the input gradient is dlwp_conv3x3_hpx_bwd_data_f32 (the transposed
+            # 3x3 folded through the adjoint of the padding table) and the padded input of the weight gradient is
+            # dlwp_healpix_pad_f32; everything else is the cylinder path's
             x0, x1, weight, bias, resid = saved
             with torch.no_grad():
                 xcat = x0 if x1 is None else torch.cat([x0, x1], dim=1)
                 gz = grad_out.contiguous()
                 if act != 0:
-                    z = ops.conv3x3(x0, weight, bias, act=0, x1=x1, pre_act=pre_act, resid=resid)
+                    z = ops.conv3x3(x0, weight, bias, act=0, x1=x1, pre_act=pre_act, resid=resid, hpx=hpx)
                     with torch.enable_grad():
                         z_ = z.detach().requires_grad_(True)
                         gz, = torch.autograd.grad(_ACT_FNS[act](z_), z_, gz)
                     gz = gz.contiguous()
                 res = [None] * 5
                 if ctx.needs_input_grad[0] or (x1 is not None and ctx.needs_input_grad[1]):
-                    wt = weight.flip(2, 3).transpose(0, 1).contiguous()
-                    dxa = ops.conv3x3(gz, wt, None)
+                    if hpx and weight.shape[0] <= HPX_DX_DIRECT_MAX_COUT:
+                        dxa = ops.conv3x3_hpx_backward_data(gz, weight, xcat.shape[1])
+                    elif hpx:
+                        # wide layers: the full transposed 3x3 (MIOpen) onto the padded face, folded by the padding's adjoint
+                        dxa = ops.healpix_pad_backward(F.conv_transpose2d(gz, weight), 1)
+                    else:
+                        wt = weight.flip(2, 3).transpose(0, 1).contiguous()
+                        dxa = ops.conv3x3(gz, wt, None)
                     if pre_act != 0:
                         with torch.enable_grad():
                             xc_ = xcat.detach().requires_grad_(True)
@@ -468,7 +517,10 @@ class _Conv3x3Fn(torch.autograd.Function):
                     res[1] = dxa[:, c0:].contiguous() if (x1 is not None and ctx.needs_input_grad[1]) else None
                 if ctx.needs_input_grad[2]:
                     xa = _ACT_FNS[pre_act](xcat)
-                    xp = F.pad(F.pad(xa, (1, 1, 0, 0), mode="circular"), (0, 0, 1, 1))
+                    if hpx:
+                        xp = ops.healpix_pad(xa, 1)
+                    else:
+                        xp = F.pad(F.pad(xa, (1, 1, 0, 0), mode="circular"), (0, 0, 1, 1))
                     res[2] = torch.nn.grad.conv2d_weight(xp, weight.shape, gz)
                 if bias is not None and ctx.needs_input_grad[3]:
                     res[3] = gz.sum(dim=(0, 2, 3))

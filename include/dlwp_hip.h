@@ -434,6 +434,32 @@ int32_t dlwp_conv3x3_hpx_f32(const float* x0_dev, int32_t c0, const float* x1_de
                              int32_t height, int32_t width, int32_t cout, int32_t act,
                              const int32_t* ring_table_dev, void* stream);
 
+/* Backward of the HEALPix padding and of HEALPixLayer(Conv2d 3x3) (the reference lines differentiated: utils/healpix.py:69-114
+ * and :165-368).  The adjoint of the padding table is handed over as a CSR over the 12*H*W source cells of one sample
+ * (healpix.pad_adjoint_table): adj_indptr_dev [12*H*W + 1], adj_index_dev [nnz] padded positions face*(H+2p)*(W+2p) + pixel
+ * of the padded face, adj_weight_dev [nnz] 1 or 0.5 (a synthesised corner is the mean of two cells).  Both kernels gather
+ * through it: every element of dx_dev is written once, no atomics, bitwise reproducible; dx_dev may not alias dy_dev.
+ * Faces are square; n_faces a multiple of 12 and at most 65535 (DLWP_ERR_UNSUPPORTED above).
+ *   dlwp_healpix_pad_bwd_f32: the adjoint of dlwp_healpix_pad_f32 for every pad it takes (1 <= pad <= H):
+ *   dy_dev [n_faces, C, H+2p, W+2p] -> dx_dev [n_faces, C, H, W], dx[s] = sum over the entries of s of weight * dy[q].
+ *   dlwp_conv3x3_hpx_bwd_data_f32: the gradient of HEALPixPadding(1) + Conv2d(3x3, padding 0) with respect to its input:
+ *   dy_dev [n_faces, cout, H, W] (the gradient of the convolution's output), weight_dev [cout, cin, 3, 3] in the forward
+ *   layout (flipped and transposed as it is loaded) -> dx_dev [n_faces, cin, H, W]; the adjoint table of pad 1.  Any channel
+ *   counts (cin up to 65535).  Two launches on `stream`: the transposed 3x3 at the halo positions of every face into the
+ *   workspace (a ring of 2 (W+2) + 2 H cells per face and channel), then the interior transposed 3x3 plus, on face borders,
+ *   the ring values of the neighbouring faces through the adjoint table.
+ *   dlwp_conv3x3_hpx_bwd_data_workspace_bytes: n_faces * cin * (2 (W+2) + 2 H) floats (0 for a non-positive size); a
+ *   smaller workspace returns DLWP_ERR_WORKSPACE. */
+size_t dlwp_conv3x3_hpx_bwd_data_workspace_bytes(int32_t n_faces, int32_t height, int32_t width, int32_t cin);
+int32_t dlwp_healpix_pad_bwd_f32(const float* dy_dev, float* dx_dev, const int32_t* adj_indptr_dev,
+                                 const int32_t* adj_index_dev, const float* adj_weight_dev, int32_t n_faces,
+                                 int32_t channels, int32_t height, int32_t width, int32_t pad, void* stream);
+int32_t dlwp_conv3x3_hpx_bwd_data_f32(const float* dy_dev, const float* weight_dev, float* dx_dev, int32_t n_faces,
+                                      int32_t height, int32_t width, int32_t cin, int32_t cout,
+                                      const int32_t* adj_indptr_dev, const int32_t* adj_index_dev,
+                                      const float* adj_weight_dev, void* workspace, size_t workspace_bytes,
+                                      void* stream);
+
 /* ConvLSTM cell gate math (models/convlstm/convlstm.py:96-109): gates_dev [B, 4*hidden, H, W] in the
  * order (netin, igate, fgate, ogate), c_prev_dev [B, hidden, H, W] -> h_out_dev, c_out_dev. */
 int32_t dlwp_convlstm_gates_f32(const float* gates_dev, const float* c_prev_dev, float* h_out_dev,

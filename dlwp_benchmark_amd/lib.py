@@ -41,6 +41,14 @@ class WAttnDesc(ctypes.Structure):
     ]
 
 
+class MgnMlpDesc(ctypes.Structure):
+    """mirror of struct dlwp_mgn_mlp_desc (include/dlwp_hip.h)"""
+    _fields_ = [
+        ("n_linear", c_int32), ("dims", c_int32 * 6), ("wt", c_void_p * 5), ("bias", c_void_p * 5),
+        ("ln_gamma", c_void_p), ("ln_beta", c_void_p), ("ln_eps", c_float),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/dlwp_hip.h declares
 SIGNATURES = {
     "dlwp_version": (c_int32, []),
@@ -164,6 +172,11 @@ SIGNATURES = {
     "dlwp_global_attn_bwd_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "dlwp_global_attn_bwd_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float,
                                            c_void_p, c_size_t, c_void_p]),
+    "dlwp_mgn_mlp_f32": (c_int32, [POINTER(MgnMlpDesc), c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "dlwp_mgn_processor_layer_f32": (c_int32, [POINTER(MgnMlpDesc), POINTER(MgnMlpDesc), c_int32, c_void_p, c_void_p, c_void_p,
+                                               c_int32,
+                                               c_int32, c_int32, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p,
+                                               c_void_p]),
 }
 
 _lib = None

@@ -1258,3 +1258,112 @@ def attention_block(x: torch.Tensor, projection: torch.nn.Linear, output: torch.
     else:
         y = output(res).add_(t)
     return y.transpose(1, 2).reshape(b, c, h, w).contiguous()
+
+
+# ---- MeshGraphNet (models/mgn.py; csrc/mgn.hip) --------------------------------------------------------------------------
+MGN_MAX_WIDTH = 512         # hidden / output widths the HIP kernels take (include/dlwp_hip.h)
+MGN_MAX_IN_WIDTH = 2048     # input width of dlwp_mgn_mlp_f32
+
+
+def mgn_parts(seq: torch.nn.Sequential):
+    """(Linears, LayerNorm or None) of a MeshGraphMLP's `model` (mesh_graph_mlp.py: Linear, act, ..., Linear[, norm])"""
+    lins = [m for m in seq if isinstance(m, torch.nn.Linear)]
+    ln = seq[-1] if isinstance(seq[-1], torch.nn.LayerNorm) else None
+    return lins, ln
+
+
+def mgn_mlp_supported(seq: torch.nn.Sequential, max_in: int = MGN_MAX_IN_WIDTH) -> bool:
+    lins, _ = mgn_parts(seq)
+    return 2 <= len(lins) <= 5 and lins[0].in_features <= max_in and all(l.out_features <= MGN_MAX_WIDTH for l in lins)
+
+
+def mgn_layer_supported(edge_seq: torch.nn.Sequential, node_seq: torch.nn.Sequential, aggregation: str) -> bool:
+    el, eln = mgn_parts(edge_seq)
+    nl, nln = mgn_parts(node_seq)
+    d = el[-1].out_features
+    return (aggregation in ("sum", "mean") and eln is not None and nln is not None and d <= MGN_MAX_WIDTH
+            and mgn_mlp_supported(edge_seq, 3 * d) and mgn_mlp_supported(node_seq, 2 * d)
+            and all(l.out_features <= d for l in el + nl))
+
+
+class MgnMlpWeights:
+    """Derived operand of one MeshGraphMLP: its Linear weights transposed to [in][out] and the descriptor pointing at them,
+    re-derived when a parameter's (pointer, version) or the pack epoch changes."""
+
+    def __init__(self):
+        self._key = None
+        self._keep = None
+        self._desc = None
+
+    def get(self, seq: torch.nn.Sequential) -> "_lib.MgnMlpDesc":
+        lins, ln = mgn_parts(seq)
+        params = [t for l in lins for t in (l.weight, l.bias)] + ([ln.weight, ln.bias] if ln is not None else [])
+        key = tuple((t.data_ptr(), t._version) for t in params) + (pack_epoch(),)
+        if key != self._key:
+            wts = [l.weight.detach().t().contiguous() for l in lins]
+            d = _lib.MgnMlpDesc()
+            d.n_linear = len(lins)
+            d.dims[0] = lins[0].in_features
+            for i, l in enumerate(lins):
+                d.dims[i + 1] = l.out_features
+                d.wt[i] = wts[i].data_ptr()
+                d.bias[i] = l.bias.data_ptr()
+            d.ln_gamma = ln.weight.data_ptr() if ln is not None else None
+            d.ln_beta = ln.bias.data_ptr() if ln is not None else None
+            d.ln_eps = float(ln.eps) if ln is not None else 0.0
+            self._keep, self._desc, self._key = wts, d, key
+        return self._desc
+
+
+def mgn_mlp(packed: MgnMlpWeights, seq: torch.nn.Sequential, x: torch.Tensor, batch: int, rows: int,
+            channels_first_in: bool = False, channels_first_out: bool = False) -> torch.Tensor:
+    """dlwp_mgn_mlp_f32 over batch * rows rows; x [batch * rows, C] or channels-first [batch, C, rows] (any trailing shape
+    of `rows` elements); returns [batch * rows, C_out] or [batch, C_out, rows]"""
+    _lib.require_cuda_tensor(x, "x")
+    lins, _ = mgn_parts(seq)
+    cin, cout = lins[0].in_features, lins[-1].out_features
+    if x.numel() != batch * rows * cin or (channels_first_in and (x.shape[0] != batch or x.shape[1] != cin)) or \
+            (not channels_first_in and x.shape[-1] != cin):
+        raise _lib.DlwpError(f"mgn mlp: input of shape {tuple(x.shape)} for {batch} x {rows} rows of width {cin}")
+    x = x.contiguous()                  # the kernel indexes a dense [B, C, rows] / [rows, C] block
+    out = torch.empty((batch, cout, rows) if channels_first_out else (batch * rows, cout), device=x.device, dtype=torch.float32)
+    d = packed.get(seq)
+    _lib.check(_lib.load().dlwp_mgn_mlp_f32(ctypes.byref(d), x.data_ptr(), out.data_ptr(), batch, rows,
+                                            int(channels_first_in), int(channels_first_out), _lib.stream_ptr()), "mgn mlp")
+    return out
+
+
+def mgn_processor_layer(edge_packed: MgnMlpWeights, edge_seq, node_packed: MgnMlpWeights, node_seq, aggregation: str,
+                        row_ptr: torch.Tensor, src: torch.Tensor, dst: torch.Tensor, batch: int, x_in: torch.Tensor, x_out: torch.Tensor,
+                        e_in: torch.Tensor, e_shared: bool, e_out: torch.Tensor) -> None:
+    """dlwp_mgn_processor_layer_f32: x_out <- node block(edge block(x_in, e_in)); e_out <- the edge block's output.
+    e_shared: e_in is one [E, D] table for the whole batch (stride 0), else [batch, E, D]."""
+    n_nodes, n_edges = row_ptr.numel() - 1, src.numel()
+    d = edge_seq[-1].normalized_shape[0]
+    _lib.check(_lib.load().dlwp_mgn_processor_layer_f32(
+        ctypes.byref(edge_packed.get(edge_seq)), ctypes.byref(node_packed.get(node_seq)), 0 if aggregation == "sum" else 1,
+        row_ptr.data_ptr(), src.data_ptr(), dst.data_ptr(), n_nodes, n_edges, batch, x_in.data_ptr(), x_out.data_ptr(), e_in.data_ptr(),
+        0 if e_shared else n_edges * d, e_out.data_ptr(), _lib.stream_ptr()), "mgn processor layer")
+
+
+def mgn_mlp_torch(seq: torch.nn.Sequential, x: torch.Tensor) -> torch.Tensor:
+    """torch composition of a MeshGraphMLP (training with gradients, widths outside the HIP envelope)"""
+    return seq(x)
+
+
+def mgn_layer_torch(edge_seq, node_seq, aggregation: str, src: torch.Tensor, dst: torch.Tensor, deg: torch.Tensor,
+                    batch: int, x: torch.Tensor, e: torch.Tensor):
+    """torch composition of one processor layer on [batch * N, D] nodes and [batch * E, D] (or shared [E, D]) edges,
+    one graph shared by the batch: returns (x', e')"""
+    n, ne = deg.numel(), src.numel()
+    off = (torch.arange(batch, device=x.device) * n).repeat_interleave(ne)
+    s, t = src.long().repeat(batch) + off, dst.long().repeat(batch) + off
+    if e.shape[0] != batch * ne:
+        e = e.repeat(batch, 1)
+    e_new = mgn_mlp_torch(edge_seq, torch.cat((e, x[s], x[t]), dim=1)) + e
+    agg = torch.zeros_like(x).index_add_(0, t, e_new)
+    if aggregation == "mean":
+        agg = agg / deg.clamp(min=1).to(x.dtype).repeat(batch).unsqueeze(1)
+    elif aggregation != "sum":
+        raise _lib.DlwpError(f"aggregation {aggregation!r}: sum or mean")
+    return mgn_mlp_torch(node_seq, torch.cat((agg, x), dim=1)) + x, e_new

@@ -629,6 +629,52 @@ int32_t dlwp_global_attn_bwd_f32(const float* qkv_dev, const float* grad_out_dev
                                  int32_t batch, int32_t tokens, int32_t heads, int32_t head_dim, float scale,
                                  void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * MeshGraphNet message passing (reference models/mgn/meshgraphnet.py:412-423 `update_nodes_and_edges`, built from
+ * models/graphcast/gnn_layers/mesh_graph_mlp.py MeshGraphMLP / MeshGraphEdgeMLPConcat, mesh_edge_block.py,
+ * mesh_node_block.py and utils.py concat_message_function :96-111, agg_concat_dgl :340-380)
+ * ------------------------------------------------------------------------------------------ */
+/* One MeshGraphMLP: n_linear Linears (hidden_layers + 1, 2..5) with ReLU between them, then an optional LayerNorm.
+ * dims[0] is the input width, dims[i + 1] the output width of Linear i.  wt[i] is Linear i's weight TRANSPOSED,
+ * [dims[i]][dims[i + 1]] row-major (nn.Linear keeps [out][in]); bias[i] has dims[i + 1] values.  ln_gamma / ln_beta:
+ * both NULL (no LayerNorm) or both of width dims[n_linear]. */
+typedef struct dlwp_mgn_mlp_desc {
+  int32_t n_linear;
+  int32_t dims[6];
+  const float* wt[5];
+  const float* bias[5];
+  const float* ln_gamma;
+  const float* ln_beta;
+  float ln_eps;
+} dlwp_mgn_mlp_desc;
+
+/* The MLP row by row over batch * rows rows (mesh_graph_mlp.py MeshGraphMLP.default_forward; meshgraphnet.py:418-419 and
+ * :422 -- the node / edge encoders and the node decoder).  layout 0: [batch * rows, C] row-major; layout 1: channels-first
+ * [batch, C, rows] (the node encoder reads x_t [B, C, H, W] and the decoder writes [B, C, H, W]: the reference's
+ * "b d h w -> (b h w) d" rearranges of :480 and :486 without a copy).  Envelope: input width <= 2048, hidden and output
+ * widths <= 512; otherwise DLWP_ERR_UNSUPPORTED.  One launch, no atomics (bitwise reproducible). */
+int32_t dlwp_mgn_mlp_f32(const dlwp_mgn_mlp_desc* mlp, const float* in_dev, float* out_dev, int32_t batch, int32_t rows,
+                         int32_t in_layout, int32_t out_layout, void* stream);
+
+/* One processor layer, MeshEdgeBlock then MeshNodeBlock (meshgraphnet.py:541 pairs them), in ONE launch.  The graph is
+ * one graph shared by the batch, in CSC order by destination: row_ptr_dev [n_nodes + 1], src_dev / dst_dev [n_edges];
+ * edge i of the CSC order runs src_dev[i] -> dst_dev[i], and dst_dev[i] = n for row_ptr[n] <= i < row_ptr[n + 1].
+ *   e'  = LN(edge_mlp([e, x[src], x[dst]])) + e                        (mesh_edge_block.py, concat order utils.py:110)
+ *   x'  = LN(node_mlp([agg_{edges into n} e', x])) + x                 (mesh_node_block.py, concat order utils.py:379)
+ * aggregation 0 = sum, 1 = mean (a node without incoming edges aggregates to 0).  edge_mlp: 3D -> D, node_mlp: 2D -> D,
+ * hidden widths <= D <= 512, both with a LayerNorm; otherwise DLWP_ERR_UNSUPPORTED.  D >= 64 runs the products on
+ * v_mfma_f32_16x16x4_f32, narrower layers as fp32 FMA chains; both are fp32-exact products.
+ * x_in_dev / x_out_dev: [batch, n_nodes, D] (distinct buffers).  e_in_dev: sample b's edges at e_in_dev + b *
+ * e_in_batch_stride (0: one table shared by the batch, the encoded edge features; else n_edges * D); e_out_dev
+ * [batch, n_edges, D] may equal e_in_dev when the stride is n_edges * D (each edge is read and written by one workgroup),
+ * never when it is 0 (DLWP_ERR_INVALID_ARGUMENT).  Sums run in CSC order,
+ * every output has one writer: bitwise reproducible. */
+int32_t dlwp_mgn_processor_layer_f32(const dlwp_mgn_mlp_desc* edge_mlp, const dlwp_mgn_mlp_desc* node_mlp,
+                                     int32_t aggregation, const int32_t* row_ptr_dev, const int32_t* src_dev,
+                                     const int32_t* dst_dev, int32_t n_nodes, int32_t n_edges, int32_t batch, const float* x_in_dev,
+                                     float* x_out_dev, const float* e_in_dev, int64_t e_in_batch_stride,
+                                     float* e_out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,19 @@ class MgnMlpDesc(ctypes.Structure):
     ]
 
 
+class GcLinearArgs(ctypes.Structure):
+    """mirror of struct dlwp_gc_linear_args (include/dlwp_hip.h)"""
+    _fields_ = [
+        ("a_mode", c_int32), ("a", c_void_p), ("a_batch_stride", ctypes.c_int64), ("lda", c_int32),
+        ("agg_e", c_void_p), ("agg_batch_stride", ctypes.c_int64), ("agg_width", c_int32), ("row_ptr", c_void_p),
+        ("agg_mean", c_int32), ("wt", c_void_p), ("bias", c_void_p), ("k", c_int32), ("n", c_int32), ("batch", c_int32),
+        ("rows", c_int32), ("src_products", c_void_p), ("src_index", c_void_p), ("src_products_batch_stride", ctypes.c_int64),
+        ("ld_src_products", c_int32), ("dst_products", c_void_p), ("dst_index", c_void_p),
+        ("dst_products_batch_stride", ctypes.c_int64), ("ld_dst_products", c_int32), ("act", c_int32), ("out", c_void_p),
+        ("out_layout", c_int32), ("ldo", c_int32), ("res", c_void_p), ("res_batch_stride", ctypes.c_int64),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/dlwp_hip.h declares
 SIGNATURES = {
     "dlwp_version": (c_int32, []),
@@ -173,6 +186,9 @@ SIGNATURES = {
     "dlwp_global_attn_bwd_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float,
                                            c_void_p, c_size_t, c_void_p]),
     "dlwp_mgn_mlp_f32": (c_int32, [POINTER(MgnMlpDesc), c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "dlwp_gc_linear_f32": (c_int32, [POINTER(GcLinearArgs), c_void_p]),
+    "dlwp_gc_layernorm_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p,
+                                        ctypes.c_int64, c_void_p]),
     "dlwp_mgn_processor_layer_f32": (c_int32, [POINTER(MgnMlpDesc), POINTER(MgnMlpDesc), c_int32, c_void_p, c_void_p, c_void_p,
                                                c_int32,
                                                c_int32, c_int32, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p,

@@ -12,8 +12,9 @@ from .pangu import PanguWeather
 from .spectral import SpectralConv2d
 from .swin import SwinTransformer, SwinTransformerHPX
 from .diffusion import DiffModernUNet, DiffMUNetHPX
+from .graphcast import GraphCastNet
 from .mgn import MeshGraphNet
 from .unet import ConvLSTM, ConvLSTMHPX, HEALPixLayer, HEALPixPadding, ModernUNet, MUNetHPX, UNet, UNetHPX
 
-__all__ = ["DiffModernUNet", "DiffMUNetHPX", "FNO2DModule", "TFNO2DModule", "ConvLSTMHPX", "ModernUNet", "FourCastNet", "AFNONet", "MeshGraphNet", "PanguWeather", "SpectralConv2d", "SwinTransformer", "SwinTransformerHPX", "UNet",
+__all__ = ["DiffModernUNet", "DiffMUNetHPX", "FNO2DModule", "TFNO2DModule", "ConvLSTMHPX", "ModernUNet", "FourCastNet", "AFNONet", "GraphCastNet", "MeshGraphNet", "PanguWeather", "SpectralConv2d", "SwinTransformer", "SwinTransformerHPX", "UNet",
            "UNetHPX", "MUNetHPX", "ConvLSTM", "HEALPixPadding", "HEALPixLayer"]

@@ -1,0 +1,372 @@
+"""GraphCastNet -- drop-in for reference models/graphcast/graph_cast_net.py (commented out of the reference registry,
+config configs/model/graphcast.yaml).  Same constructor kwargs, state-dict names, order and shapes (`device_buffer` of the
+modulus `Module` base, `encoder_embedder.*`, `decoder_embedder.*`, `encoder.*`, `processor_encoder.*`, `processor.*`,
+`processor_decoder.*`, `decoder.*`, `finale.*`) and forward signature.
+
+The mesh is read from `meshgraph_path` when it exists; otherwise it is generated in memory (dlwp_benchmark_amd.icosphere)
+at the level of an `_l<k>` suffix of the path, else 6.  The three graphs are built on the host as the reference builds
+them and kept in non-persistent buffers in CSC order by destination, one graph shared by the batch.
+
+A step runs every MLP on the gather-GEMM of csrc/graphcast.hip (ops.gc_mlp): the first Linear of an edge MLP is split into
+W_e e + (W_s x_src)[src] + (W_d x_dst)[dst] with the node products computed once per node, and the node MLPs read
+[aggregate, x] in the A-operand load.  The four static embeddings (mesh nodes, mesh / g2m / m2g edges) depend on the
+weights only and are computed once per weight version.  Batches B >= 1 share the graph (the reference raises for B != 1).
+
+Training with gradients runs the torch composition of the same math under autograd; so do MLPs outside the kernels'
+envelope (ops.gc_mlp_supported) and `set_hip_step(False)` (A/B timing).
+"""
+import os
+import re
+from typing import Optional
+
+import numpy as np
+import torch
+from torch import nn
+
+from .. import icosphere
+from .. import lib as _lib
+from .. import ops
+from ..rollout import rollout_into
+from ._base import HipBackbone
+
+_ACTIVATIONS = {"relu": nn.ReLU, "leaky_relu": (nn.LeakyReLU, {"negative_slope": 0.1}), "relu6": nn.ReLU6, "elu": nn.ELU,
+                "selu": nn.SELU, "silu": nn.SiLU, "gelu": nn.GELU, "sigmoid": nn.Sigmoid, "logsigmoid": nn.LogSigmoid,
+                "softplus": nn.Softplus, "softshrink": nn.Softshrink, "softsign": nn.Softsign, "tanh": nn.Tanh,
+                "tanhshrink": nn.Tanhshrink, "threshold": (nn.Threshold, {"threshold": 1.0, "value": 1.0}),
+                "hardtanh": nn.Hardtanh}
+
+
+def get_activation(name: str) -> nn.Module:
+    """utils/activations.py get_activation for its parameter-free torch entries"""
+    m = _ACTIVATIONS.get(name.lower())
+    if m is None:
+        raise NotImplementedError(f"activation {name!r}: one of {sorted(_ACTIVATIONS)}")
+    return m[0](**m[1]) if isinstance(m, tuple) else m()
+
+
+class MeshGraphMLP(nn.Module):
+    """mesh_graph_mlp.py MeshGraphMLP: Linear, act, (Linear, act) x (hidden_layers - 1), Linear[, LayerNorm]"""
+
+    def __init__(self, input_dim, output_dim, hidden_dim, hidden_layers, activation_fn, norm_type="LayerNorm"):
+        super().__init__()
+        layers = [nn.Linear(input_dim, hidden_dim), activation_fn]
+        for _ in range(hidden_layers - 1):
+            layers += [nn.Linear(hidden_dim, hidden_dim), activation_fn]
+        layers.append(nn.Linear(hidden_dim, output_dim))
+        if norm_type is not None:
+            if norm_type != "LayerNorm":
+                raise NotImplementedError(f"norm_type {norm_type!r}: LayerNorm or None (the only ones nn can build)")
+            layers.append(nn.LayerNorm(output_dim))
+        self.model = nn.Sequential(*layers)
+
+    def forward(self, x):
+        return self.model(x)
+
+
+class _Embedder(nn.Module):
+    def __init__(self, names_dims, d, hl, act, norm):
+        super().__init__()
+        for name, din in names_dims:
+            setattr(self, name, MeshGraphMLP(din, d, d, hl, act, norm))
+
+
+class _EdgeBlock(nn.Module):
+    """mesh_edge_block.py with MeshGraphEdgeMLPConcat"""
+
+    def __init__(self, d, hl, act, norm):
+        super().__init__()
+        self.edge_mlp = MeshGraphMLP(3 * d, d, d, hl, act, norm)
+
+
+class _NodeBlock(nn.Module):
+    def __init__(self, d, hl, act, norm):
+        super().__init__()
+        self.node_mlp = MeshGraphMLP(2 * d, d, d, hl, act, norm)
+
+
+class GraphCastProcessor(nn.Module):
+    def __init__(self, n, d, hl, act, norm):
+        super().__init__()
+        layers = []
+        for _ in range(n):
+            layers += [_EdgeBlock(d, hl, act, norm), _NodeBlock(d, hl, act, norm)]
+        self.processor_layers = nn.ModuleList(layers)
+
+    def pairs(self):
+        ls = self.processor_layers
+        return [(ls[2 * i].edge_mlp.model, ls[2 * i + 1].node_mlp.model) for i in range(len(ls) // 2)]
+
+
+class MeshGraphEncoder(nn.Module):
+    def __init__(self, d, hl, act, norm):
+        super().__init__()
+        self.edge_mlp = MeshGraphMLP(3 * d, d, d, hl, act, norm)
+        self.src_node_mlp = MeshGraphMLP(d, d, d, hl, act, norm)
+        self.dst_node_mlp = MeshGraphMLP(2 * d, d, d, hl, act, norm)
+
+
+class MeshGraphDecoder(nn.Module):
+    def __init__(self, d, hl, act, norm):
+        super().__init__()
+        self.edge_mlp = MeshGraphMLP(3 * d, d, d, hl, act, norm)
+        self.node_mlp = MeshGraphMLP(2 * d, d, d, hl, act, norm)
+
+
+def _mesh_level(path: str) -> int:
+    m = re.search(r"_l(\d+)", os.path.basename(str(path)))
+    return int(m.group(1)) if m else 6
+
+
+def _csc(src, dst, n_dst):
+    """edge permutation into CSC order by destination (source order within), row_ptr [n_dst + 1]"""
+    order = np.lexsort((src, dst))
+    deg = np.bincount(dst[order], minlength=n_dst)
+    return order, np.concatenate([[0], np.cumsum(deg)]).astype(np.int32), deg
+
+
+class GraphCastNet(HipBackbone):
+    def __init__(self, meshgraph_path: str, input_height: int = 721, input_width: int = 1440, constant_channels: int = 4,
+                 prescribed_channels: int = 1, prognostic_channels: int = 8, input_dim_mesh_nodes: int = 3,
+                 input_dim_edges: int = 4, processor_layers: int = 16, hidden_layers: int = 1, hidden_dim: int = 512,
+                 aggregation: str = "sum", activation_fn: str = "silu", norm_type: str = "LayerNorm",
+                 use_cugraphops_encoder: bool = False, use_cugraphops_processor: bool = False,
+                 use_cugraphops_decoder: bool = False, do_concat_trick: bool = False, recompute_activation: bool = False,
+                 partition_size: int = 1, partition_group_name: Optional[str] = None, expect_partitioned_input: bool = False,
+                 produce_aggregated_output: bool = True, context_size: int = 1, **kwargs):
+        super().__init__()
+        if do_concat_trick:
+            raise NotImplementedError("do_concat_trick=True (MeshGraphEdgeMLPSum) has another parameter layout")
+        if use_cugraphops_encoder or use_cugraphops_processor or use_cugraphops_decoder:
+            raise NotImplementedError("use_cugraphops_*: cugraph-ops is a CUDA library; the graphs here are HIP CSC tables")
+        if partition_size > 1:
+            raise NotImplementedError("partition_size > 1: distributed graph partitioning is not implemented")
+        if processor_layers <= 2:
+            raise ValueError("Expected at least 3 processor layers")
+        if aggregation not in ("sum", "mean"):
+            raise ValueError(f"aggregation {aggregation!r}: sum or mean")
+        self.register_buffer("device_buffer", torch.empty(0))        # modulus Module (utils/module.py)
+        self.context_size = int(context_size)
+        self.aggregation = aggregation
+        self.height, self.width = int(input_height), int(input_width)
+        self.prognostic_channels = int(prognostic_channels)
+        self.constant_channels, self.prescribed_channels = int(constant_channels), int(prescribed_channels)
+        self.input_dim_grid_nodes = constant_channels + (prescribed_channels + prognostic_channels) * context_size
+        d, hl = int(hidden_dim), int(hidden_layers)
+        act = get_activation(activation_fn)                          # one instance shared by every MLP, as the reference
+
+        if meshgraph_path is not None and os.path.exists(str(meshgraph_path)):
+            ico = icosphere.load(str(meshgraph_path))
+        else:
+            ico = icosphere.icospheres(_mesh_level(meshgraph_path))
+        g = icosphere.graphcast_graphs(ico, self.height, self.width)
+
+        self.encoder_embedder = _Embedder([("grid_node_mlp", self.input_dim_grid_nodes), ("mesh_node_mlp", input_dim_mesh_nodes),
+                                           ("mesh_edge_mlp", input_dim_edges), ("grid2mesh_edge_mlp", input_dim_edges)],
+                                          d, hl, act, norm_type)
+        self.decoder_embedder = _Embedder([("mesh2grid_edge_mlp", input_dim_edges)], d, hl, act, norm_type)
+        self.encoder = MeshGraphEncoder(d, hl, act, norm_type)
+        self.processor_encoder = GraphCastProcessor(1, d, hl, act, norm_type)
+        self.processor = GraphCastProcessor(processor_layers - 2, d, hl, act, norm_type)
+        self.processor_decoder = GraphCastProcessor(1, d, hl, act, norm_type)
+        self.decoder = MeshGraphDecoder(d, hl, act, norm_type)
+        self.finale = MeshGraphMLP(d, self.prognostic_channels, d, hl, act, None)
+
+        self.n_mesh, self.n_grid = int(g["n_mesh"]), self.height * self.width
+        self.register_buffer("mesh_ndata", g["mesh_nodes"].float().contiguous(), persistent=False)
+        for name, n_dst in (("mesh", self.n_mesh), ("g2m", self.n_mesh), ("m2g", self.n_grid)):
+            src, dst, feat = g[name]
+            order, row_ptr, deg = _csc(np.asarray(src), np.asarray(dst), n_dst)
+            self.register_buffer(f"{name}_src", torch.from_numpy(np.asarray(src)[order].astype(np.int32)), persistent=False)
+            self.register_buffer(f"{name}_dst", torch.from_numpy(np.asarray(dst)[order].astype(np.int32)), persistent=False)
+            self.register_buffer(f"{name}_row_ptr", torch.from_numpy(row_ptr), persistent=False)
+            self.register_buffer(f"{name}_deg", torch.from_numpy(deg.astype(np.int32)), persistent=False)
+            self.register_buffer(f"{name}_edata", feat[torch.from_numpy(order)].float().contiguous(), persistent=False)
+        # channel order of the rollout's x_t ([constants, prescribed window, prognostic window]) -> the reference's
+        # prepare_inputs order ([prescribed window, prognostic window, constants], graph_cast_net.py:691-694)
+        cc, pw = self.constant_channels, (self.prescribed_channels + self.prognostic_channels) * self.context_size
+        ref_order = torch.cat([torch.arange(cc, cc + pw), torch.arange(cc)])
+        self.register_buffer("_to_ref_order", ref_order, persistent=False)
+        self.register_buffer("_from_ref_order", torch.argsort(ref_order), persistent=False)   # rows of the grid embedder
+        self._pk = {}
+        self._static = None
+        self.hip_step = True
+
+    # ---- bookkeeping ---------------------------------------------------------------------------------------------------
+    def _mlps(self):
+        ee, de = self.encoder_embedder, self.decoder_embedder
+        yield from (ee.grid_node_mlp.model, ee.mesh_node_mlp.model, ee.mesh_edge_mlp.model, ee.grid2mesh_edge_mlp.model,
+                    de.mesh2grid_edge_mlp.model, self.encoder.edge_mlp.model, self.encoder.src_node_mlp.model,
+                    self.encoder.dst_node_mlp.model, self.decoder.edge_mlp.model, self.decoder.node_mlp.model,
+                    self.finale.model)
+        for p in (self.processor_encoder, self.processor, self.processor_decoder):
+            for e, n in p.pairs():
+                yield e
+                yield n
+
+    def hip_supported(self) -> bool:
+        return all(ops.gc_mlp_supported(m) for m in self._mlps())
+
+    def set_hip_step(self, on: bool = True):
+        """True (default): the step on csrc/graphcast.hip wherever hip_supported(); False: the torch composition"""
+        self.hip_step = bool(on)
+        self._graphed = None
+        return self
+
+    def uses_hip_step(self) -> bool:
+        return self.hip_step and self.hip_supported()
+
+    def _packed(self, seq, split=None, perm=None) -> ops.GcMlpWeights:
+        p = self._pk.get(id(seq))
+        if p is None:
+            p = self._pk[id(seq)] = ops.GcMlpWeights(split, perm)
+        return p.get(seq)
+
+    def _edge_packed(self, seq):
+        d = seq[0].in_features // 3
+        return self._packed(seq, split=(d, d, d))
+
+    # ---- HIP step --------------------------------------------------------------------------------------------------------
+    def _static_embeddings(self):
+        key = self._param_key()
+        if self._static is None or self._static[0] != key:
+            ee = self.encoder_embedder
+
+            def emb(seq, x):
+                return ops.gc_mlp(self._packed(seq), seq, 1, x.shape[0],
+                                  dict(a_mode=0, a=x, a_batch_stride=0, lda=x.shape[1]))
+
+            self._static = (key, dict(mesh_n=emb(ee.mesh_node_mlp.model, self.mesh_ndata),
+                                      mesh_e=emb(ee.mesh_edge_mlp.model, self.mesh_edata),
+                                      g2m_e=emb(ee.grid2mesh_edge_mlp.model, self.g2m_edata),
+                                      m2g_e=emb(self.decoder_embedder.mesh2grid_edge_mlp.model, self.m2g_edata)))
+        return self._static[1]
+
+    def _edge_mlp(self, seq, b, name, e, e_bs, xs, xs_bs, n_src, xd, xd_bs, n_dst, residual):
+        """e' = LN(mlp([e, x_src[src], x_dst[dst]])) (+ e): node products once per node, gathered in the epilogue"""
+        pk = self._edge_packed(seq)
+        d = seq[0].out_features
+        ps = ops.gc_node_products(pk, 1, xs, b if xs_bs else 1, n_src, xs_bs)
+        pd = ops.gc_node_products(pk, 2, xd, b if xd_bs else 1, n_dst, xd_bs)
+        src, dst = getattr(self, f"{name}_src"), getattr(self, f"{name}_dst")
+        n_e = src.numel()
+        first = dict(a_mode=0, a=e, a_batch_stride=e_bs, lda=e.shape[-1], wt=pk.first[0],
+                     src_products=ps, src_index=src, src_products_batch_stride=n_src * d if xs_bs else 0, ld_src_products=d,
+                     dst_products=pd, dst_index=dst, dst_products_batch_stride=n_dst * d if xd_bs else 0, ld_dst_products=d)
+        return ops.gc_mlp(pk, seq, b, n_e, first, res=e if residual else None, res_bs=e_bs)
+
+    def _node_mlp(self, seq, b, name, e_new, x, x_bs, n):
+        """x' = LN(mlp([agg e', x])) + x, the aggregate and the concat read in the A-operand load"""
+        d = x.shape[-1]
+        n_e = getattr(self, f"{name}_src").numel()
+        first = dict(a_mode=2, a=x, a_batch_stride=x_bs, lda=d, agg_e=e_new, agg_batch_stride=n_e * e_new.shape[-1],
+                     agg_width=e_new.shape[-1], row_ptr=getattr(self, f"{name}_row_ptr"),
+                     agg_mean=int(self.aggregation == "mean"))
+        return ops.gc_mlp(self._packed(seq), seq, b, n, first, res=x, res_bs=x_bs)
+
+    def _step_hip(self, x_t: torch.Tensor) -> torch.Tensor:
+        b = x_t.shape[0]
+        G, N = self.n_grid, self.n_mesh
+        st = self._static_embeddings()
+        gm = self.encoder_embedder.grid_node_mlp.model
+        x_t = x_t.contiguous()
+        grid = ops.gc_mlp(self._packed(gm, perm=self._from_ref_order), gm, b, G,
+                          dict(a_mode=1, a=x_t, a_batch_stride=gm[0].in_features * G))
+        d = grid.shape[-1]
+        enc = self.encoder
+        # grid -> mesh (mesh_graph_encoder.py): edge MLP without residual, dst node MLP + mesh_n, src node MLP + grid
+        e = self._edge_mlp(enc.edge_mlp.model, b, "g2m", st["g2m_e"], 0, grid, G * d, G, st["mesh_n"], 0, N, False)
+        mesh = self._node_mlp(enc.dst_node_mlp.model, b, "g2m", e, st["mesh_n"], 0, N)
+        grid = ops.gc_mlp(self._packed(enc.src_node_mlp.model), enc.src_node_mlp.model, b, G,
+                          dict(a_mode=0, a=grid, a_batch_stride=G * d, lda=d), res=grid, res_bs=G * d)
+        # processor: processor_encoder, processor, processor_decoder (its edge output is discarded)
+        e, e_bs = st["mesh_e"], 0
+        n_e = self.mesh_src.numel()
+        for p in (self.processor_encoder, self.processor, self.processor_decoder):
+            for em, nm in p.pairs():
+                e = self._edge_mlp(em, b, "mesh", e, e_bs, mesh, N * d, N, mesh, N * d, N, True)
+                e_bs = n_e * d
+                mesh = self._node_mlp(nm, b, "mesh", e, mesh, N * d, N)
+        # mesh -> grid (mesh_graph_decoder.py), then the norm-free finale, channels-first
+        dec = self.decoder
+        e = self._edge_mlp(dec.edge_mlp.model, b, "m2g", st["m2g_e"], 0, mesh, N * d, N, grid, G * d, G, False)
+        grid = self._node_mlp(dec.node_mlp.model, b, "m2g", e, grid, G * d, G)
+        y = ops.gc_mlp(self._packed(self.finale.model), self.finale.model, b, G,
+                       dict(a_mode=0, a=grid, a_batch_stride=G * d, lda=d), out_cf=True)
+        return y.view(b, self.prognostic_channels, self.height, self.width)
+
+    # ---- torch composition -----------------------------------------------------------------------------------------------
+    def _edge_torch(self, seq, b, name, e, xs, n_src, xd, n_dst):
+        src, dst = getattr(self, f"{name}_src").long(), getattr(self, f"{name}_dst").long()
+        ne = src.numel()
+        if e.shape[0] != b * ne:
+            e = e.repeat(b, 1)
+        off_s = (torch.arange(b, device=e.device) * n_src).repeat_interleave(ne) if xs.shape[0] == b * n_src else 0
+        off_d = (torch.arange(b, device=e.device) * n_dst).repeat_interleave(ne) if xd.shape[0] == b * n_dst else 0
+        return seq(torch.cat((e, xs[src.repeat(b) + off_s], xd[dst.repeat(b) + off_d]), dim=1))
+
+    def _node_torch(self, seq, b, name, e, x, n):
+        dst = getattr(self, f"{name}_dst").long()
+        ne = dst.numel()
+        t = dst.repeat(b) + (torch.arange(b, device=e.device) * n).repeat_interleave(ne)
+        agg = torch.zeros(b * n, e.shape[1], device=e.device, dtype=e.dtype).index_add(0, t, e)
+        if self.aggregation == "mean":
+            deg = getattr(self, f"{name}_deg").clamp(min=1).to(e.dtype).repeat(b).unsqueeze(1)
+            agg = agg / deg
+        if x.shape[0] != b * n:
+            x = x.repeat(b, 1)
+        return seq(torch.cat((agg, x), dim=1)) + x
+
+    def _step_torch(self, x_t: torch.Tensor) -> torch.Tensor:
+        """the same step as a torch composition, concat-materialising like the reference (autograd; outside the envelope)"""
+        b = x_t.shape[0]
+        G, N = self.n_grid, self.n_mesh
+        ee = self.encoder_embedder
+        x = x_t[:, self._to_ref_order].reshape(b, -1, G).permute(0, 2, 1).reshape(b * G, -1)
+        grid = ee.grid_node_mlp(x)
+        mesh_n = ee.mesh_node_mlp(self.mesh_ndata)
+        g2m_e = ee.grid2mesh_edge_mlp(self.g2m_edata)
+        mesh_e = ee.mesh_edge_mlp(self.mesh_edata)
+        enc = self.encoder
+        e = self._edge_torch(enc.edge_mlp.model, b, "g2m", g2m_e, grid, G, mesh_n, N)
+        mesh = self._node_torch(enc.dst_node_mlp.model, b, "g2m", e, mesh_n, N)
+        grid = grid + enc.src_node_mlp(grid)
+        e = mesh_e
+        for p in (self.processor_encoder, self.processor, self.processor_decoder):
+            for em, nm in p.pairs():
+                e_new = self._edge_torch(em, b, "mesh", e, mesh, N, mesh, N)
+                e = e_new + (e if e.shape[0] == e_new.shape[0] else e.repeat(b, 1))
+                mesh = self._node_torch(nm, b, "mesh", e, mesh, N)
+        m2g_e = self.decoder_embedder.mesh2grid_edge_mlp(self.m2g_edata)
+        e = self._edge_torch(self.decoder.edge_mlp.model, b, "m2g", m2g_e, mesh, N, grid, G)
+        grid = self._node_torch(self.decoder.node_mlp.model, b, "m2g", e, grid, G)
+        y = self.finale(grid)
+        return y.view(b, self.height, self.width, -1).permute(0, 3, 1, 2)
+
+    # ---- rollout ---------------------------------------------------------------------------------------------------------
+    def one_step(self, x_t: torch.Tensor) -> torch.Tensor:
+        """x_t [B, C_in, H, W] (rollout channel order) -> increment [B, C_out, H, W] (forward_one_step)"""
+        b, c, h, w = x_t.shape
+        if (h, w) != (self.height, self.width) or c != self.input_dim_grid_nodes:
+            raise _lib.DlwpError(f"input {c}x{h}x{w} does not match the model's {self.input_dim_grid_nodes}x{self.height}x"
+                                 f"{self.width}")
+        if (self.training and torch.is_grad_enabled()) or not self.uses_hip_step():
+            return self._step_torch(x_t)
+        return self._step_hip(x_t)
+
+    def rollout_into(self, out, constants, prescribed, prognostic, step_begin=0, step_end=-1):
+        return rollout_into(self._step_fn(), self.context_size, out, constants, prescribed, prognostic, step_begin, step_end)
+
+    def forward(self, constants: Optional[torch.Tensor] = None, prescribed: Optional[torch.Tensor] = None,
+                prognostic: torch.Tensor = None) -> torch.Tensor:
+        constants, prescribed, prognostic = self._check_inputs(constants, prescribed, prognostic)
+        if self.constant_channels == 0:
+            constants = None
+        if self._grad_mode():
+            return self._forward_train(constants, prescribed, prognostic)
+        with torch.no_grad():
+            b, t, cg, h, w = prognostic.shape
+            if t <= self.context_size:
+                raise _lib.DlwpError(f"need more than context_size={self.context_size} frames, got {t}")
+            out = torch.empty(b, t - self.context_size, cg, h, w, device=prognostic.device, dtype=torch.float32)
+            self.rollout_into(out, constants, prescribed, prognostic)
+        return out

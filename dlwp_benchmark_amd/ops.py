@@ -1367,3 +1367,110 @@ def mgn_layer_torch(edge_seq, node_seq, aggregation: str, src: torch.Tensor, dst
     elif aggregation != "sum":
         raise _lib.DlwpError(f"aggregation {aggregation!r}: sum or mean")
     return mgn_mlp_torch(node_seq, torch.cat((agg, x), dim=1)) + x, e_new
+
+
+# ---- GraphCastNet (models/graphcast.py; csrc/graphcast.hip) --------------------------------------------------------------
+GC_MAX_WIDTH = 512          # hidden / output widths of dlwp_gc_linear_f32 (include/dlwp_hip.h)
+GC_MAX_IN = 4096            # input width of one Linear
+GC_ACT = {torch.nn.ReLU: 1, torch.nn.SiLU: 2}
+
+
+def gc_mlp_supported(seq: torch.nn.Sequential) -> bool:
+    """a MeshGraphMLP `model` inside the HIP envelope: 2..5 Linears, ReLU or SiLU between them, LayerNorm or no norm"""
+    lins, ln = mgn_parts(seq)
+    acts = [m for m in seq if not isinstance(m, (torch.nn.Linear, torch.nn.LayerNorm))]
+    return (2 <= len(lins) <= 5 and lins[0].in_features <= GC_MAX_IN and all(l.out_features <= GC_MAX_WIDTH for l in lins)
+            and all(type(a) in GC_ACT for a in acts) and len(seq) == 2 * len(lins) - 1 + (ln is not None))
+
+
+class GcMlpWeights:
+    """Derived operands of one MeshGraphMLP for dlwp_gc_linear_f32: Linear weights transposed to [in][out]; the first
+    Linear's input rows optionally split into column blocks (the edge MLP's e / x_src / x_dst parts) or permuted (the grid
+    embedder reads the rollout's channel order).  Re-derived when a parameter's (pointer, version) or the pack epoch
+    changes."""
+
+    def __init__(self, split=None, perm=None):
+        self.split, self.perm = split, perm
+        self._key = None
+        self.wt = self.first = self.zero = None
+
+    def get(self, seq: torch.nn.Sequential):
+        lins, ln = mgn_parts(seq)
+        params = [t for l in lins for t in (l.weight, l.bias)] + ([ln.weight, ln.bias] if ln is not None else [])
+        key = tuple((t.data_ptr(), t._version) for t in params) + (pack_epoch(),)
+        if key != self._key:
+            self.wt = [l.weight.detach().t().contiguous() for l in lins]
+            w0 = self.wt[0]
+            if self.perm is not None:
+                w0 = w0[self.perm].contiguous()
+                self.wt[0] = w0
+            if self.split is not None:
+                self.first = [p.contiguous() for p in torch.split(w0, list(self.split), dim=0)]
+            self.zero = torch.zeros(lins[0].out_features, device=w0.device, dtype=torch.float32)
+            self._key = key
+        return self
+
+
+def _gc_args(**kw) -> "_lib.GcLinearArgs":
+    a = _lib.GcLinearArgs()
+    for k, v in kw.items():
+        setattr(a, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
+    return a
+
+
+def gc_linear(args: "_lib.GcLinearArgs") -> None:
+    _lib.check(_lib.load().dlwp_gc_linear_f32(ctypes.byref(args), _lib.stream_ptr()), "gc linear")
+
+
+def gc_layernorm(x: torch.Tensor, batch: int, rows: int, ln: torch.nn.LayerNorm, res: Optional[torch.Tensor] = None,
+                 res_bs: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    out = x if out is None else out
+    d = ln.normalized_shape[0]
+    _lib.check(_lib.load().dlwp_gc_layernorm_f32(x.data_ptr(), out.data_ptr(), batch, rows, d, ln.weight.data_ptr(),
+                                                 ln.bias.data_ptr(), float(ln.eps), res.data_ptr() if res is not None else None,
+                                                 res_bs, _lib.stream_ptr()), "gc layernorm")
+    return out
+
+
+def gc_mlp(pk: GcMlpWeights, seq: torch.nn.Sequential, batch: int, rows: int, first: dict, res: Optional[torch.Tensor] = None,
+           res_bs: int = 0, out_cf: bool = False) -> torch.Tensor:
+    """One MeshGraphMLP over batch * rows rows on dlwp_gc_linear_f32 / dlwp_gc_layernorm_f32.  `first`: the A operand (and
+    gathered products) of the first Linear as dlwp_gc_linear_args fields; its weight is `first["wt"]` if given, else the
+    whole transposed first weight.  Then act -> Linears -> [LayerNorm] [+ res].  Returns [batch * rows, D_out], or
+    channels-first [batch, D_out, rows] when out_cf (no norm)."""
+    w = pk.get(seq)
+    lins, ln = mgn_parts(seq)
+    act = GC_ACT[type(seq[1])]
+    dev = w.wt[0].device
+    cur = None
+    for i, l in enumerate(lins):
+        last = i + 1 == len(lins)
+        n = l.out_features
+        if last and out_cf:
+            out = torch.empty(batch, n, rows, device=dev, dtype=torch.float32)
+        else:
+            out = torch.empty(batch * rows, n, device=dev, dtype=torch.float32)
+        kw = dict(wt=w.wt[i], bias=l.bias, k=l.in_features, n=n, batch=batch, rows=rows, act=0 if last else act, out=out,
+                  out_layout=int(last and out_cf), ldo=n)
+        if i == 0:
+            kw.update(first)
+            kw["k"] = kw["wt"].shape[0]     # the e-part of a split edge Linear
+        else:
+            kw.update(a_mode=0, a=cur, a_batch_stride=rows * l.in_features, lda=l.in_features)
+        if last and ln is None and res is not None:
+            kw.update(res=res, res_batch_stride=res_bs)
+        gc_linear(_gc_args(**kw))
+        cur = out
+    if ln is not None:
+        gc_layernorm(cur, batch, rows, ln, res, res_bs)
+    return cur
+
+
+def gc_node_products(pk: GcMlpWeights, part: int, x: torch.Tensor, batch: int, rows: int, x_bs: int) -> torch.Tensor:
+    """x @ W_part (no bias): one per-node term of an edge MLP's first Linear, [batch * rows, H] (batch 1 when x_bs is 0)"""
+    w = pk.first[part]
+    k, h = w.shape
+    out = torch.empty(batch * rows, h, device=x.device, dtype=torch.float32)
+    gc_linear(_gc_args(a_mode=0, a=x, a_batch_stride=x_bs, lda=k, wt=w, bias=pk.zero, k=k, n=h, batch=batch, rows=rows,
+                       act=0, out=out, out_layout=0, ldo=h))
+    return out

@@ -675,6 +675,62 @@ int32_t dlwp_mgn_processor_layer_f32(const dlwp_mgn_mlp_desc* edge_mlp, const dl
                                      float* x_out_dev, const float* e_in_dev, int64_t e_in_batch_stride,
                                      float* e_out_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * GraphCastNet (reference models/graphcast/graph_cast_net.py; MeshGraphMLP / MeshGraphEdgeMLPConcat of
+ * gnn_layers/mesh_graph_mlp.py, aggregate_and_concat of gnn_layers/utils.py): a wide gather-GEMM (csrc/graphcast.hip)
+ * ------------------------------------------------------------------------------------------ */
+/* One Linear over batch * rows rows:  out[m][j] = act(sum_k A[m][k] wt[k][j] + bias[j] + src_products[src[p]][j]
+ * + dst_products[dst[p]][j]) + res[m][j], row m = b * rows + p.  wt is the weight TRANSPOSED, [k][n] row-major.
+ * A operand (a_mode):
+ *   0  A[m][k] = a[b * a_batch_stride + p * lda + k]            (a_batch_stride 0: one table shared by the batch)
+ *   1  A[m][k] = a[b * a_batch_stride + k * rows + p]           (channels-first [B, K, rows])
+ *   2  A[m][k] = agg_{row_ptr[p] <= i < row_ptr[p + 1]} agg_e[b * agg_batch_stride + i * agg_width + k]  for k < agg_width
+ *               (sum in CSC order; agg_mean 1 divides by the count; an empty row is 0),
+ *      A[m][k] = a[b * a_batch_stride + p * lda + k - agg_width]  above: the node MLP's [agg, x] without the concat.
+ * The gathered products (each optional, with its index array of `rows` entries) are the first edge Linear's node terms.
+ * act: 0 none, 1 ReLU, 2 SiLU.  out_layout 0: out[m * ldo + j]; 1: channels-first out[(b * n + j) * rows + p].
+ * res (optional) in the output's layout, sample b at res + b * res_batch_stride.  Envelope: k <= 4096, n <= 512, batch <=
+ * 65535, otherwise DLWP_ERR_UNSUPPORTED.  out may not alias a or agg_e.  No atomics: bitwise reproducible. */
+typedef struct dlwp_gc_linear_args {
+  int32_t a_mode;
+  const float* a;
+  int64_t a_batch_stride;
+  int32_t lda;
+  const float* agg_e;
+  int64_t agg_batch_stride;
+  int32_t agg_width;
+  const int32_t* row_ptr;
+  int32_t agg_mean;
+  const float* wt;
+  const float* bias;
+  int32_t k;
+  int32_t n;
+  int32_t batch;
+  int32_t rows;
+  const float* src_products;
+  const int32_t* src_index;
+  int64_t src_products_batch_stride;
+  int32_t ld_src_products;
+  const float* dst_products;
+  const int32_t* dst_index;
+  int64_t dst_products_batch_stride;
+  int32_t ld_dst_products;
+  int32_t act;
+  float* out;
+  int32_t out_layout;
+  int32_t ldo;
+  const float* res;
+  int64_t res_batch_stride;
+} dlwp_gc_linear_args;
+
+int32_t dlwp_gc_linear_f32(const dlwp_gc_linear_args* args, void* stream);
+
+/* out[m] = LayerNorm(in[m]) (two-pass mean / biased variance, like torch) [+ res], rows of `width` <= 512 over batch * rows
+ * rows; res (optional) [rows, width] per sample at res_dev + b * res_batch_stride (0: shared).  out may equal in. */
+int32_t dlwp_gc_layernorm_f32(const float* in_dev, float* out_dev, int32_t batch, int32_t rows, int32_t width,
+                              const float* gamma, const float* beta, float eps, const float* res_dev,
+                              int64_t res_batch_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

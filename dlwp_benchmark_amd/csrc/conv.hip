@@ -202,6 +202,8 @@ static void launch_conv3x3_co(const conv::Params& p, hipStream_t s) {
   else
     hipLaunchKernelGGL((conv::conv3x3_cyl_kernel<8, 8, CO>), dim3(tiles(8, 8), p.B, zc), dim3(64), 0, s, p);
 }
+// CO_CHUNK grows with the batch: the goldens run CO_CHUNK = 1, C1 at the benchmark's batch runs 4.  The rule is restated in
+// tests/test_conv3x3_variants_gpu.py (conv3x3_variant), whose cases reach all 9 instances in both padding forms.
 static void launch_conv3x3(const conv::Params& p, hipStream_t s) {
   const int th = p.W >= 32 ? 8 : (p.W >= 16 ? 16 : 8), tw = p.W >= 32 ? 32 : (p.W >= 16 ? 16 : 8);
   const long long wgs16 = (long long)((p.W + tw - 1) / tw) * ((p.H + th - 1) / th) * p.B * ((p.Cout + 15) / 16);

@@ -193,6 +193,15 @@ SIGNATURES = {
                                                c_int32,
                                                c_int32, c_int32, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p,
                                                c_void_p]),
+    "dlwp_mgn_mlp_bwd_workspace_bytes": (c_size_t, [POINTER(MgnMlpDesc), c_int32, c_int32]),
+    "dlwp_mgn_mlp_bwd_f32": (c_int32, [POINTER(MgnMlpDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                       c_int32, c_void_p, c_size_t, c_void_p]),
+    "dlwp_mgn_processor_layer_bwd_workspace_bytes": (c_size_t, [POINTER(MgnMlpDesc), POINTER(MgnMlpDesc), c_int32, c_int32,
+                                                                c_int32, c_int32]),
+    "dlwp_mgn_processor_layer_bwd_f32": (c_int32, [POINTER(MgnMlpDesc), POINTER(MgnMlpDesc), c_int32, c_void_p, c_void_p,
+                                                   c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                                   ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                   c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

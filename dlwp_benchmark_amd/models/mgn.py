@@ -12,9 +12,17 @@ and shared by the batch.  Like the reference (:412-423) every message-passing st
 processor passes only its node features on.  The rollout is device resident and does NOT reproduce the reference's crash
 on the second step (`.to()` on a list, :469-472) nor its per-step `.cpu()` (:487).
 
-Training with gradients runs the torch composition of the same math (ops.mgn_mlp_torch / ops.mgn_layer_torch) under
-autograd; so do widths outside the kernels' envelope (ops.mgn_layer_supported) and, by default, processors wider than
-FUSED_MAX_WIDTH, where the measured fused step is slower than the composition (`set_fused_layers`).
+Training with gradients (`.train()` and autograd recording) runs the same kernels inside autograd Functions
+(training.mgn_mlp / training.mgn_layer) whose backward is csrc/mgn_bwd.hip: each saves only its inputs and recomputes
+the forward in LDS, and every gradient is bitwise reproducible.  In training each layer writes fresh x' / e' tensors (the
+next layer's saved inputs) instead of the eval path's ping-pong and in-place buffers, and the edge encoder runs once per
+`forward` through the differentiable MLP (not the eval-time cache), so its gradients from every step and message-passing
+step accumulate.  This holds, by default, for processors up to TRAIN_FUSED_MAX_WIDTH (the measured crossover), and under
+`set_fused_layers("always")` wherever the backward envelope (widths up to 64, ops.mgn_layer_backward_supported) holds
+(`uses_hip_training`).  Elsewhere -- wider default processors, widths outside the envelope such as "always" at D > 64 --
+training runs the torch composition of the same math (ops.mgn_mlp_torch / ops.mgn_layer_torch) under autograd, as eval
+does for processors wider than FUSED_MAX_WIDTH.
+DLWP_TRAIN_TORCH_BACKWARD=1 keeps the HIP forward and differentiates the torch composition instead (a cross-check).
 """
 import functools
 from typing import Optional
@@ -25,6 +33,7 @@ from torch import nn
 
 from .. import lib as _lib
 from .. import ops
+from .. import training
 from ..rollout import rollout_into
 from ._base import HipBackbone
 
@@ -34,6 +43,11 @@ GRAPH_TYPES = ("grid_2d", "grid_2d_8stencil", "delaunay")
 # (per 16-edge chunk the fused layer re-reads every weight of the edge MLP; the composition's GEMMs read them once).
 # Wider layers take the composition unless `set_fused_layers("always")`; the kernels themselves run up to D = 512.
 FUSED_MAX_WIDTH = 64
+# Widest processor that TRAINS on the HIP kernels by default.  Measured at B = 32, sequence_length 3 (DESIGN.md section 16,
+# profiles/meshgraphnet_train.jsonl): the yaml D = 34 step is 1.24x faster than the composition (1.12x on grid_2d 128x256),
+# D = 48 / 64 with 15 layers are 0.75x / 0.52x.  Wider processors train on the composition unless
+# `set_fused_layers("always")`; the backward kernels themselves run up to D = 64.
+TRAIN_FUSED_MAX_WIDTH = 34
 
 
 class MeshGraphMLP(nn.Module):
@@ -244,10 +258,16 @@ class MeshGraphNet(HipBackbone):
         self.register_buffer("graph_dst", torch.from_numpy(dst_c.astype(np.int32)), persistent=False)
         self.register_buffer("graph_deg", torch.from_numpy(deg.astype(np.int32)), persistent=False)
         self.register_buffer("graph_edge_features", torch.from_numpy(np.ascontiguousarray(feats[order])), persistent=False)
+        # the same edges sorted by source (a CSR by source over the CSC indices): the backward's source-side gather
+        src_perm = np.argsort(src_c, kind="stable")
+        src_row_ptr = np.concatenate([[0], np.cumsum(np.bincount(src_c, minlength=n_nodes))])
+        self.register_buffer("graph_src_row_ptr", torch.from_numpy(src_row_ptr.astype(np.int32)), persistent=False)
+        self.register_buffer("graph_src_perm", torch.from_numpy(src_perm.astype(np.int32)), persistent=False)
         self._pk = {}               # MeshGraphMLP -> ops.MgnMlpWeights (transposed weights)
         self._enc_edges = None      # (key, [E, D] encoded edge table)
         self.fused_layers = "auto"  # "auto": fused kernels up to FUSED_MAX_WIDTH; "always": everywhere they run
         self._bufs = None
+        self._enc_train = None      # the edge encoder's output of the current training forward
 
     @property
     def n_edges(self) -> int:
@@ -266,8 +286,9 @@ class MeshGraphNet(HipBackbone):
                 and all(ops.mgn_layer_supported(e, n, self.aggregation) for e, n in self.processor.pairs()))
 
     def set_fused_layers(self, mode: str):
-        """"auto" (default): the fused kernels for processor widths up to FUSED_MAX_WIDTH, the torch composition above;
-        "always": the fused kernels wherever hip_supported()"""
+        """"auto" (default): the fused kernels for processor widths up to FUSED_MAX_WIDTH (training: TRAIN_FUSED_MAX_WIDTH),
+        the torch composition above; "always": the fused kernels wherever hip_supported() (training: wherever the backward
+        envelope holds too)"""
         if mode not in ("auto", "always"):
             raise _lib.DlwpError(f"fused_layers {mode!r}: 'auto' or 'always'")
         self.fused_layers = mode
@@ -277,6 +298,22 @@ class MeshGraphNet(HipBackbone):
     def uses_fused_layers(self) -> bool:
         dim = self.processor.processor_layers[0].edge_mlp.model[-1].normalized_shape[0]
         return self.hip_supported() and (self.fused_layers == "always" or dim <= FUSED_MAX_WIDTH)
+
+    def backward_supported(self) -> bool:
+        """every MLP of the step inside the backward kernels' envelope (ops.mgn_layer_backward_supported /
+        mgn_mlp_backward_supported: widths up to 64)"""
+        return (ops.mgn_mlp_backward_supported(self.node_encoder.model)
+                and ops.mgn_mlp_backward_supported(self.edge_encoder.model)
+                and ops.mgn_mlp_backward_supported(self.node_decoder.model)
+                and all(ops.mgn_layer_backward_supported(e, n, self.aggregation) for e, n in self.processor.pairs()))
+
+    def uses_hip_training(self) -> bool:
+        """training with gradients runs the HIP forward and backward kernels (else the torch composition under autograd):
+        processors up to TRAIN_FUSED_MAX_WIDTH by default, wherever the backward envelope holds under "always".
+        """
+        dim = self.processor.processor_layers[0].edge_mlp.model[-1].normalized_shape[0]
+        return (self.uses_fused_layers() and self.backward_supported()
+                and (self.fused_layers == "always" or dim <= TRAIN_FUSED_MAX_WIDTH))
 
     def _encoded_edges(self) -> torch.Tensor:
         key = self._param_key()
@@ -298,7 +335,9 @@ class MeshGraphNet(HipBackbone):
         b, _, h, w = x_t.shape
         if (h, w) != (self.height, self.width):
             raise _lib.DlwpError(f"input grid {h}x{w} does not match the graph's {self.height}x{self.width}")
-        if (self.training and torch.is_grad_enabled()) or not self.uses_fused_layers():
+        if self.training and torch.is_grad_enabled():
+            return self._step_train(x_t) if self.uses_hip_training() else self._step_torch(x_t)
+        if not self.uses_fused_layers():
             return self._step_torch(x_t)
         n = self.n_nodes
         dim = self.processor.processor_layers[0].edge_mlp.model[-1].normalized_shape[0]
@@ -315,6 +354,44 @@ class MeshGraphNet(HipBackbone):
                 cur = nxt
         y = ops.mgn_mlp(self._packed(self.node_decoder.model), self.node_decoder.model, cur, b, n, channels_first_out=True)
         return y.view(b, self.prognostic_channels, h, w)
+
+    def _graph_tuple(self):
+        return (self.graph_row_ptr, self.graph_src, self.graph_dst, self.graph_deg, self.graph_src_row_ptr,
+                self.graph_src_perm)
+
+    def _encode_edges_train(self) -> torch.Tensor:
+        """the edge encoder through the differentiable MLP (not the eval cache: its parameters take gradients)"""
+        ef = self.graph_edge_features
+        return training.mgn_mlp(self.edge_encoder.model, self._packed(self.edge_encoder.model), ef, 1, ef.shape[0])
+
+    def _step_train(self, x_t: torch.Tensor) -> torch.Tensor:
+        """one step with autograd on the HIP kernels: every MLP and processor layer is an autograd Function whose backward
+        runs csrc/mgn_bwd.hip; each layer writes fresh x' / e' (the next layer's saved inputs)"""
+        b, _, h, w = x_t.shape
+        n = self.n_nodes
+        enc = self._enc_train if self._enc_train is not None else self._encode_edges_train()
+        x = training.mgn_mlp(self.node_encoder.model, self._packed(self.node_encoder.model), x_t, b, n,
+                             channels_first_in=True)
+        graph = self._graph_tuple()
+        for _ in range(self.message_passing_steps):
+            e, shared = enc, True
+            for em, nm in self.processor.pairs():
+                x, e = training.mgn_layer(em, self._packed(em), nm, self._packed(nm), self.aggregation, graph, b, x, e,
+                                          shared)
+                shared = False
+        y = training.mgn_mlp(self.node_decoder.model, self._packed(self.node_decoder.model), x, b, n,
+                             channels_first_out=True)
+        return y.view(b, self.prognostic_channels, h, w)
+
+    def _forward_train(self, constants, prescribed, prognostic):
+        """the edge encoder runs once per forward; its gradients from every step and message-passing step accumulate"""
+        if not self.uses_hip_training():
+            return super()._forward_train(constants, prescribed, prognostic)
+        self._enc_train = self._encode_edges_train()
+        try:
+            return super()._forward_train(constants, prescribed, prognostic)
+        finally:
+            self._enc_train = None
 
     def _step_torch(self, x_t: torch.Tensor) -> torch.Tensor:
         """the same step as a torch composition (autograd; widths outside the HIP envelope)"""

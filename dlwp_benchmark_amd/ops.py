@@ -1346,6 +1346,107 @@ def mgn_processor_layer(edge_packed: MgnMlpWeights, edge_seq, node_packed: MgnMl
         0 if e_shared else n_edges * d, e_out.data_ptr(), _lib.stream_ptr()), "mgn processor layer")
 
 
+MGN_BWD_MAX_WIDTH = 64      # hidden / output widths of the backward kernels (csrc/mgn_bwd.hip)
+MGN_BWD_MAX_IN_WIDTH = 256  # input width of dlwp_mgn_mlp_bwd_f32
+
+
+def mgn_mlp_backward_supported(seq: torch.nn.Sequential, max_in: int = MGN_BWD_MAX_IN_WIDTH) -> bool:
+    lins, _ = mgn_parts(seq)
+    return (2 <= len(lins) <= 5 and lins[0].in_features <= max_in
+            and all(l.out_features <= MGN_BWD_MAX_WIDTH for l in lins))
+
+
+def mgn_layer_backward_supported(edge_seq: torch.nn.Sequential, node_seq: torch.nn.Sequential, aggregation: str) -> bool:
+    d = mgn_parts(edge_seq)[0][-1].out_features
+    return (mgn_layer_supported(edge_seq, node_seq, aggregation) and d <= MGN_BWD_MAX_WIDTH
+            and mgn_mlp_backward_supported(edge_seq, 3 * d) and mgn_mlp_backward_supported(node_seq, 2 * d))
+
+
+def _mgn_param_grads(seq: torch.nn.Sequential, flat: torch.Tensor):
+    """the kernels' flat parameter gradient (include/dlwp_hip.h: per Linear the weight [in][out] then the bias, then gamma,
+    beta) as a list in the order of seq.parameters()"""
+    lins, ln = mgn_parts(seq)
+    out, o = [], 0
+    for l in lins:
+        k, n = l.in_features, l.out_features
+        out.append(flat[o:o + k * n].view(k, n).t().contiguous())
+        o += k * n
+        out.append(flat[o:o + n])
+        o += n
+    if ln is not None:
+        d = ln.normalized_shape[0]
+        out += [flat[o:o + d], flat[o + d:o + 2 * d]]
+        o += 2 * d
+    assert o == flat.numel()
+    return out
+
+
+def _mgn_param_count(seq: torch.nn.Sequential) -> int:
+    lins, ln = mgn_parts(seq)
+    return sum(l.in_features * l.out_features + l.out_features for l in lins) + (2 * ln.normalized_shape[0] if ln else 0)
+
+
+def mgn_mlp_backward(packed: MgnMlpWeights, seq: torch.nn.Sequential, x: torch.Tensor, grad_out: torch.Tensor, batch: int,
+                     rows: int, channels_first_in: bool = False, channels_first_out: bool = False, need_input_grad: bool = True):
+    """dlwp_mgn_mlp_bwd_f32: the backward of mgn_mlp (same layouts).  Returns (grad_x in x's layout or None, [gradients in
+    the order of seq.parameters()])."""
+    _lib.require_cuda_tensor(x, "x")
+    _lib.require_cuda_tensor(grad_out, "grad_out")
+    x, grad_out = x.contiguous(), grad_out.contiguous()
+    d = packed.get(seq)
+    lib = _lib.load()
+    ws_bytes = lib.dlwp_mgn_mlp_bwd_workspace_bytes(ctypes.byref(d), batch, rows)
+    if ws_bytes == 0:
+        raise _lib.DlwpError("mgn mlp backward: shape outside the backward envelope (ops.mgn_mlp_backward_supported)")
+    ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8)
+    gx = torch.empty_like(x) if need_input_grad else None
+    flat = torch.empty(_mgn_param_count(seq), device=x.device, dtype=torch.float32)
+    _lib.check(lib.dlwp_mgn_mlp_bwd_f32(ctypes.byref(d), x.data_ptr(), grad_out.data_ptr(),
+                                        gx.data_ptr() if gx is not None else None, flat.data_ptr(), batch, rows,
+                                        int(channels_first_in), int(channels_first_out), ws.data_ptr(), ws_bytes,
+                                        _lib.stream_ptr()), "mgn mlp backward")
+    return gx, _mgn_param_grads(seq, flat)
+
+
+def mgn_source_csr(src: torch.Tensor, n_nodes: int):
+    """(src_row_ptr [n_nodes + 1], src_perm [E]) int32: the CSC edges sorted by source (stable), for the source-side gather
+    of dlwp_mgn_processor_layer_bwd_f32"""
+    s = src.long().cpu()
+    perm = torch.sort(s, stable=True).indices
+    row_ptr = torch.cat([torch.zeros(1, dtype=torch.long), torch.bincount(s, minlength=n_nodes).cumsum(0)])
+    return row_ptr.int().to(src.device), perm.int().to(src.device)
+
+
+def mgn_processor_layer_backward(edge_packed: MgnMlpWeights, edge_seq, node_packed: MgnMlpWeights, node_seq,
+                                 aggregation: str, row_ptr, src, dst, src_row_ptr, src_perm, batch: int, x_in: torch.Tensor,
+                                 e_in: torch.Tensor, e_shared: bool, dx_out: torch.Tensor, de_out: Optional[torch.Tensor]):
+    """dlwp_mgn_processor_layer_bwd_f32: the backward of mgn_processor_layer from its inputs.  Returns (dx_in [B N, D],
+    de_in (e_in's shape), [edge MLP parameter gradients], [node MLP parameter gradients])."""
+    n_nodes, n_edges = row_ptr.numel() - 1, src.numel()
+    d = edge_seq[-1].normalized_shape[0]
+    dx_out = dx_out.contiguous()
+    de_out = de_out.contiguous() if de_out is not None else None
+    ed, nd = edge_packed.get(edge_seq), node_packed.get(node_seq)
+    lib = _lib.load()
+    ws_bytes = lib.dlwp_mgn_processor_layer_bwd_workspace_bytes(ctypes.byref(ed), ctypes.byref(nd), n_nodes, n_edges, batch,
+                                                                int(e_shared))
+    if ws_bytes == 0:
+        raise _lib.DlwpError("mgn processor layer backward: shape outside the backward envelope "
+                             "(ops.mgn_layer_backward_supported)")
+    ws = torch.empty(ws_bytes, device=x_in.device, dtype=torch.uint8)
+    dx_in = torch.empty_like(x_in)
+    de_in = torch.empty(e_in.shape, device=e_in.device, dtype=torch.float32)
+    ge = torch.empty(_mgn_param_count(edge_seq), device=x_in.device, dtype=torch.float32)
+    gn = torch.empty(_mgn_param_count(node_seq), device=x_in.device, dtype=torch.float32)
+    _lib.check(lib.dlwp_mgn_processor_layer_bwd_f32(
+        ctypes.byref(ed), ctypes.byref(nd), 0 if aggregation == "sum" else 1, row_ptr.data_ptr(), src.data_ptr(),
+        dst.data_ptr(), src_row_ptr.data_ptr(), src_perm.data_ptr(), n_nodes, n_edges, batch, x_in.data_ptr(),
+        e_in.data_ptr(), 0 if e_shared else n_edges * d, dx_out.data_ptr(), de_out.data_ptr() if de_out is not None else None,
+        dx_in.data_ptr(), de_in.data_ptr(), ge.data_ptr(), gn.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr()),
+        "mgn processor layer backward")
+    return dx_in, de_in, _mgn_param_grads(edge_seq, ge), _mgn_param_grads(node_seq, gn)
+
+
 def mgn_mlp_torch(seq: torch.nn.Sequential, x: torch.Tensor) -> torch.Tensor:
     """torch composition of a MeshGraphMLP (training with gradients, widths outside the HIP envelope)"""
     return seq(x)

@@ -591,3 +591,129 @@ def linear_fn(x, weight, bias):
 def wants_grad(*tensors) -> bool:
     """True when autograd is recording and one of the tensors takes part: the ops then run their differentiable form."""
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+# ---- MeshGraphNet (models/mgn.py; csrc/mgn.hip forward, csrc/mgn_bwd.hip backward) -------------------------------------
+def _mgn_rows(x: torch.Tensor, batch: int, rows: int, channels_first: bool) -> torch.Tensor:
+    """[batch, C, rows...] channels-first or [batch * rows, C] -> [batch * rows, C] (the torch composition's row view)"""
+    if not channels_first:
+        return x.reshape(batch * rows, -1)
+    return x.reshape(batch, -1, rows).permute(0, 2, 1).reshape(batch * rows, -1)
+
+
+def mgn_mlp_backward_torch(seq, x, grad_out, batch: int, rows: int, channels_first_in: bool, channels_first_out: bool,
+                           need_input_grad: bool):
+    """the backward of one MeshGraphMLP by autograd of the torch composition (DLWP_TRAIN_TORCH_BACKWARD=1): (grad_x or None,
+    [gradients in the order of seq.parameters()])"""
+    from . import ops
+
+    params = list(seq.parameters())
+    with torch.enable_grad():
+        x_ = x.detach().requires_grad_(need_input_grad)
+        y = ops.mgn_mlp_torch(seq, _mgn_rows(x_, batch, rows, channels_first_in))
+        if channels_first_out:
+            y = y.view(batch, rows, -1).permute(0, 2, 1)
+        grads = torch.autograd.grad(y, ([x_] if need_input_grad else []) + params, grad_out.reshape(y.shape))
+    return (grads[0] if need_input_grad else None), list(grads[int(need_input_grad):])
+
+
+class _MgnMlpFn(torch.autograd.Function):
+    """One MeshGraphMLP: dlwp_mgn_mlp_f32 forward, dlwp_mgn_mlp_bwd_f32 backward (recomputes the forward from x; only x is
+    saved).  DLWP_TRAIN_TORCH_BACKWARD=1 differentiates the torch composition instead."""
+
+    @staticmethod
+    def forward(ctx, x, seq, packed, batch, rows, channels_first_in, channels_first_out, *params):
+        from . import ops
+
+        with torch.no_grad():
+            y = ops.mgn_mlp(packed, seq, x.detach(), batch, rows, channels_first_in, channels_first_out)
+        ctx.save_for_backward(x, *params)         # the parameters too: autograd's version check sees in-place edits
+        ctx.cfg = (seq, packed, batch, rows, channels_first_in, channels_first_out)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from . import ops
+
+        x = ctx.saved_tensors[0]
+        seq, packed, batch, rows, cf_in, cf_out = ctx.cfg
+        need_x = ctx.needs_input_grad[0]
+        if _TORCH_BACKWARD():
+            gx, gp = mgn_mlp_backward_torch(seq, x, grad_out, batch, rows, cf_in, cf_out, need_x)
+        else:
+            gx, gp = ops.mgn_mlp_backward(packed, seq, x, grad_out, batch, rows, cf_in, cf_out, need_x)
+        if gx is not None:
+            gx = gx.view(x.shape)
+        return (gx, None, None, None, None, None, None, *gp)
+
+
+def mgn_mlp(seq, packed, x, batch: int, rows: int, channels_first_in: bool = False, channels_first_out: bool = False):
+    """differentiable MeshGraphMLP (ops.mgn_mlp layouts): HIP forward and HIP backward"""
+    return _MgnMlpFn.apply(x, seq, packed, batch, rows, channels_first_in, channels_first_out, *seq.parameters())
+
+
+def mgn_layer_backward_torch(edge_seq, node_seq, aggregation, graph, batch: int, x, e, dx_out, de_out):
+    """the backward of one processor layer by autograd of ops.mgn_layer_torch (DLWP_TRAIN_TORCH_BACKWARD=1): (dx, de,
+    [edge MLP gradients], [node MLP gradients])"""
+    from . import ops
+
+    _, src, dst, deg = graph[:4]
+    pe, pn = list(edge_seq.parameters()), list(node_seq.parameters())
+    with torch.enable_grad():
+        x_, e_ = x.detach().requires_grad_(True), e.detach().requires_grad_(True)
+        xo, eo = ops.mgn_layer_torch(edge_seq, node_seq, aggregation, src, dst, deg, batch, x_, e_)
+        outs, gouts = [xo], [dx_out if dx_out is not None else torch.zeros_like(xo)]
+        if de_out is not None:
+            outs.append(eo)
+            gouts.append(de_out)
+        grads = torch.autograd.grad(outs, [x_, e_] + pe + pn, gouts, allow_unused=True)
+    grads = [g if g is not None else torch.zeros_like(t) for g, t in zip(grads, [x_, e_] + pe + pn)]
+    return grads[0], grads[1], grads[2:2 + len(pe)], grads[2 + len(pe):]
+
+
+class _MgnLayerFn(torch.autograd.Function):
+    """One processor layer: dlwp_mgn_processor_layer_f32 forward into FRESH x' / e' (they are the next layer's saved
+    inputs), dlwp_mgn_processor_layer_bwd_f32 backward from the saved inputs x, e.  de' is None for a layer whose e'
+    nothing reads (the last of a message-passing step).  DLWP_TRAIN_TORCH_BACKWARD=1 differentiates ops.mgn_layer_torch."""
+
+    @staticmethod
+    def forward(ctx, x, e, e_shared, cfg, *params):
+        from . import ops
+
+        edge_seq, edge_packed, node_seq, node_packed, aggregation, graph, batch = cfg
+        row_ptr, src, dst = graph[0], graph[1], graph[2]
+        d = x.shape[1]
+        with torch.no_grad():
+            x_out = torch.empty_like(x)
+            e_out = torch.empty(batch * src.numel(), d, device=x.device, dtype=torch.float32)
+            ops.mgn_processor_layer(edge_packed, edge_seq, node_packed, node_seq, aggregation, row_ptr, src, dst, batch,
+                                    x.detach(), x_out, e.detach(), e_shared, e_out)
+        ctx.save_for_backward(x, e, *params)      # the parameters too: autograd's version check sees in-place edits
+        ctx.cfg, ctx.e_shared = cfg, e_shared
+        ctx.set_materialize_grads(False)
+        return x_out, e_out
+
+    @staticmethod
+    def backward(ctx, dx_out, de_out):
+        from . import ops
+
+        x, e = ctx.saved_tensors[:2]
+        edge_seq, edge_packed, node_seq, node_packed, aggregation, graph, batch = ctx.cfg
+        if _TORCH_BACKWARD():
+            dx, de, ge, gn = mgn_layer_backward_torch(edge_seq, node_seq, aggregation, graph, batch, x, e, dx_out, de_out)
+        else:
+            if dx_out is None:
+                dx_out = torch.zeros_like(x)
+            row_ptr, src, dst, _, src_row_ptr, src_perm = graph
+            dx, de, ge, gn = ops.mgn_processor_layer_backward(edge_packed, edge_seq, node_packed, node_seq, aggregation,
+                                                              row_ptr, src, dst, src_row_ptr, src_perm, batch, x, e,
+                                                              ctx.e_shared, dx_out, de_out)
+        return (dx if ctx.needs_input_grad[0] else None, de if ctx.needs_input_grad[1] else None, None, None, *ge, *gn)
+
+
+def mgn_layer(edge_seq, edge_packed, node_seq, node_packed, aggregation: str, graph, batch: int, x, e, e_shared: bool):
+    """differentiable processor layer on [batch * N, D] nodes and [batch * E, D] (or shared [E, D]) edges: (x', e').
+    graph = (row_ptr, src, dst, deg, src_row_ptr, src_perm): the CSC graph, its in-degrees and the CSR by source
+    (ops.mgn_source_csr)"""
+    cfg = (edge_seq, edge_packed, node_seq, node_packed, aggregation, graph, batch)
+    return _MgnLayerFn.apply(x, e, e_shared, cfg, *edge_seq.parameters(), *node_seq.parameters())

@@ -675,6 +675,48 @@ int32_t dlwp_mgn_processor_layer_f32(const dlwp_mgn_mlp_desc* edge_mlp, const dl
                                      float* x_out_dev, const float* e_in_dev, int64_t e_in_batch_stride,
                                      float* e_out_dev, void* stream);
 
+/* MeshGraphNet training (csrc/mgn_bwd.hip): the backward of the two entry points above, which reference
+ * scripts/train.py:271 `loss.backward()` reaches through mesh_graph_mlp.py MeshGraphMLP.default_forward, mesh_edge_block.py,
+ * mesh_node_block.py and utils.py concat_message_function :96-111 / agg_concat_dgl :340-380.  Nothing of the forward is
+ * stored: each launch recomputes the forward of the rows it owns from the saved INPUTS.
+ * Parameter gradients are written as one flat fp32 array per MLP, in this order: for each Linear i, its weight gradient
+ * TRANSPOSED like wt[i] ([dims[i]][dims[i + 1]]) then its bias gradient (dims[i + 1]); then, with a LayerNorm, the
+ * gamma and beta gradients (dims[n_linear] each).
+ * Backward envelope: 2..5 Linears, hidden and output widths <= 64, input width <= 256 (the MLP) or 3D / 2D (the layer);
+ * otherwise DLWP_ERR_UNSUPPORTED (and the workspace queries return 0).  fp32 FMA chains (exact fp32 products).
+ * Parameter gradients: a capped grid of 512 workgroups (two per CU) each sums its tiles into its own partial -- in LDS
+ * when it fits beside the tile, else in its row of the workspace -- and a second launch adds the rows in workgroup order.  Every output
+ * element has one writer, every sum runs in a fixed order, no atomics: bitwise reproducible, and a sample's input
+ * gradients do not depend on its batch neighbours.
+ *
+ *   dlwp_mgn_mlp_bwd_f32: in_dev / grad_out_dev in the layouts of dlwp_mgn_mlp_f32 (in_layout / out_layout).  grad_in_dev
+ *   (optional, NULL: not computed -- the edge encoder's constant input) in in_layout.  param_grad_dev: the flat array above.
+ *   dlwp_mgn_mlp_bwd_workspace_bytes: the partial rows (0 outside the envelope). */
+size_t dlwp_mgn_mlp_bwd_workspace_bytes(const dlwp_mgn_mlp_desc* mlp, int32_t batch, int32_t rows);
+int32_t dlwp_mgn_mlp_bwd_f32(const dlwp_mgn_mlp_desc* mlp, const float* in_dev, const float* grad_out_dev,
+                             float* grad_in_dev, float* param_grad_dev, int32_t batch, int32_t rows, int32_t in_layout,
+                             int32_t out_layout, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The backward of dlwp_mgn_processor_layer_f32 (same graph, MLPs, aggregation, x_in_dev and e_in_dev / stride).
+ * src_row_ptr_dev [n_nodes + 1] / src_perm_dev [n_edges]: the CSC edges sorted by source (stable), a CSR by source:
+ * src_perm_dev[j] for src_row_ptr[n] <= j < src_row_ptr[n + 1] are the CSC indices of the edges leaving n.
+ * dx_out_dev [batch, n_nodes, D]; de_out_dev [batch, n_edges, D] or NULL (the last layer of a message-passing step, whose
+ * e' nothing reads).  Outputs: dx_in_dev [batch, n_nodes, D]; de_in_dev [batch, n_edges, D], or [n_edges, D] summed over
+ * the batch in sample order when the stride is 0 (the shared encoded edge table); edge_grad_dev / node_grad_dev the flat
+ * parameter gradients.  Outputs may not alias inputs.  Launches: the destination-owner pass (edge MLP and node MLP
+ * recomputed and backpropagated in LDS; x_src parts of the edge-input gradient to a [batch, n_edges, D] scratch), the
+ * source-side gather into dx_in, and the fixed-order sums of the parameter partials (and of a shared table's de_in).
+ *   dlwp_mgn_processor_layer_bwd_workspace_bytes: partial rows + the x_src scratch (+ the per-sample de_in when e_shared). */
+size_t dlwp_mgn_processor_layer_bwd_workspace_bytes(const dlwp_mgn_mlp_desc* edge_mlp, const dlwp_mgn_mlp_desc* node_mlp,
+                                                    int32_t n_nodes, int32_t n_edges, int32_t batch, int32_t e_shared);
+int32_t dlwp_mgn_processor_layer_bwd_f32(const dlwp_mgn_mlp_desc* edge_mlp, const dlwp_mgn_mlp_desc* node_mlp,
+                                         int32_t aggregation, const int32_t* row_ptr_dev, const int32_t* src_dev,
+                                         const int32_t* dst_dev, const int32_t* src_row_ptr_dev, const int32_t* src_perm_dev,
+                                         int32_t n_nodes, int32_t n_edges, int32_t batch, const float* x_in_dev,
+                                         const float* e_in_dev, int64_t e_in_batch_stride, const float* dx_out_dev,
+                                         const float* de_out_dev, float* dx_in_dev, float* de_in_dev, float* edge_grad_dev,
+                                         float* node_grad_dev, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * GraphCastNet (reference models/graphcast/graph_cast_net.py; MeshGraphMLP / MeshGraphEdgeMLPConcat of
  * gnn_layers/mesh_graph_mlp.py, aggregate_and_concat of gnn_layers/utils.py): a wide gather-GEMM (csrc/graphcast.hip)

@@ -1,4 +1,5 @@
-"""Writes tests/golden/mgn_*.npz: MeshGraphNet rollouts, a gradient case, graphs and the state-dict layout, all from the REAL
+"""Writes tests/golden/mgn_*.npz: MeshGraphNet rollouts, gradient cases (one step, and multi-step training
+rollouts: mgn_train_*), graphs and the state-dict layout, all from the REAL
 reference class (models/mgn/meshgraphnet.py) on the CPU, imported through oracle.ref_import, with the filler weights of
 dlwp_benchmark_amd.weights (`fill`, below).  Only outputs are stored; each file carries the weight SHA and the case, and a
 test regenerates weights and inputs by name.
@@ -64,6 +65,18 @@ ROLLOUT_CASES = {
     "grid_nonperiodic_8x16": (_small(graph_type="grid_2d"), (8, 16, False), 2, 3),
 }
 GRAD_CASE = ("grad_yaml_8x16", dict(YAML), (8, 16, True), 2, 2)
+# training gradients through multi-step rollouts (stepwise_rollout), tag -> (ctor kwargs, graph, batch, frames):
+# `mgn_train_<tag>.npz`, the HIP backward's fixtures (tests/test_meshgraphnet_train_gpu.py)
+TRAIN_GRAD_CASES = {
+    "mean_mp2_grid_8x16": (_small(graph_type="grid_2d", aggregation="mean", message_passing_steps=2), (8, 16, True), 2, 3),
+    "stencil8_8x16": (_small(graph_type="grid_2d_8stencil", input_dim_edges=3), (8, 16, True), 2, 3),
+    "ctx2_prescribed_grid_8x16": (_small(graph_type="grid_2d", context_size=2, prescribed_channels=2), (8, 16, True), 2, 4),
+    "grid_nonperiodic_8x16": (_small(graph_type="grid_2d"), (8, 16, False), 2, 3),
+    "d48_delaunay_8x16": (_small(graph_type="delaunay", hidden_dim_processor=48, hidden_dim_node_encoder=48,
+                                 hidden_dim_edge_encoder=48, hidden_dim_node_decoder=48), (8, 16, True), 2, 3),
+    "d64_delaunay_8x16": (_small(graph_type="delaunay", hidden_dim_processor=64, hidden_dim_node_encoder=64,
+                                 hidden_dim_edge_encoder=64, hidden_dim_node_decoder=64), (8, 16, True), 2, 3),
+}
 GRAPH_CASES = [(t, h, w) for t in ("grid_2d", "grid_2d_8stencil", "delaunay") for h, w in ((32, 64), (16, 32))]
 
 
@@ -221,8 +234,8 @@ def gen_rollouts(mod):
               state_spec=np.array(json.dumps([[k, list(v.shape)] for k, v in m.state_dict().items()])))
 
 
-def gen_grad(mod):
-    tag, kw, hwp, batch, frames = GRAD_CASE
+def gen_grad(mod, case=GRAD_CASE, prefix="mgn_"):
+    tag, kw, hwp, batch, frames = case
     torch.set_num_threads(1)         # threaded CPU reductions of the backward differ run to run in the last bits
     m = build(mod, kw, hwp)
     sha = fill(m)
@@ -238,7 +251,7 @@ def gen_grad(mod):
         norms.append(float(g.norm()))
         projs.append(float((g * W.normal(f"golden/mgn/{tag}/probe/{name}", tuple(g.shape), 1.0).double()).sum()))
     case = dict(kwargs=kw, graph=list(hwp), batch=batch, frames=frames)
-    _save(f"mgn_{tag}", names=np.array(json.dumps(names)), norms=np.array(norms), projs=np.array(projs),
+    _save(f"{prefix}{tag}", names=np.array(json.dumps(names)), norms=np.array(norms), projs=np.array(projs),
           loss=np.array(float(loss.detach())), sha=np.array(sha), case=np.array(json.dumps(case)))
 
 
@@ -265,6 +278,9 @@ def main():
         gen_rollouts(mod)
     if not only or "grad" in only:
         gen_grad(mod)
+    if not only or "train" in only:
+        for tag, (kw, hwp, batch, frames) in TRAIN_GRAD_CASES.items():
+            gen_grad(mod, (tag, kw, hwp, batch, frames), prefix="mgn_train_")
 
 
 if __name__ == "__main__":

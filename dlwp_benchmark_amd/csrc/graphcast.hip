@@ -19,6 +19,9 @@
 //                           no [E, 3D] concat is built and the 2D-deep part of the product runs once per node, not per edge.
 //                           The output is row-major or channels-first [B, N, rows] (the final MLP writes [B, C, H, W]) and
 //                           may take a residual in its own layout (the rollout's prognostic_t[:, -1] + step).
+//                           Training adds two flags (both off by default): act on the A load (a hidden Linear reads
+//                           act(z) of the saved pre-activation z, so act(z) never exists in memory) and an epilogue factor
+//                           act'(z) (the data gradient (dZ W) * act'(z) of a hidden Linear; csrc/graphcast_bwd.hip).
 //   dlwp_gc_layernorm_f32   LayerNorm over rows (two-pass, biased variance, like torch) plus an optional residual, one
 //                           wave per row; may run in place.
 //
@@ -70,12 +73,26 @@ struct Args {
   long long out_bs;
   const float* res;
   long long res_bs;
+  int a_act;                           // act applied to A as it is loaded (modes 0 / 1)
+  const float* gz;                     // epilogue v *= act'(gz[m * ld_gz + j]) (the data gradient of a hidden Linear)
+  int gz_act;
+  int ld_gz;
 };
 
 __device__ __forceinline__ float activate(float v, int act) {
   if (act == 1) return fmaxf(v, 0.f);
   if (act == 2) return v / (1.0f + expf(-v));
   return v;
+}
+
+// d act / d z at the pre-activation z, as torch's relu / silu backward: ReLU z > 0; SiLU s (1 + z (1 - s)), s = sigmoid z
+__device__ __forceinline__ float activate_grad(float z, int act) {
+  if (act == 1) return z > 0.f ? 1.f : 0.f;
+  if (act == 2) {
+    const float s = 1.0f / (1.0f + expf(-z));
+    return s * (1.0f + z * (1.0f - s));
+  }
+  return 1.f;
 }
 
 // One staging row of the A tile, decomposed once per thread before the K loop: the row's base offset in `a` (mode 1: its
@@ -173,6 +190,10 @@ __global__ void __launch_bounds__(kThreads) linear_kernel(const Args p) {
     } else {
 #pragma unroll
       for (int i = 0; i < 8; ++i) ra[i] = load_a(p, arow[i], k0 + a_k + i * a_kstep);
+      if (p.a_act) {                  // act(0) = 0: the zero padding stays zero
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ra[i] = activate(ra[i], p.a_act);
+      }
     }
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -232,6 +253,7 @@ __global__ void __launch_bounds__(kThreads) linear_kernel(const Args p) {
         if (p.ps) v += p.ps[b * p.ps_bs + (long long)p.src[q] * p.ld_ps + j];
         if (p.pd) v += p.pd[b * p.pd_bs + (long long)p.dst[q] * p.ld_pd + j];
         v = activate(v, p.act);
+        if (p.gz) v *= activate_grad(p.gz[m * p.ld_gz + j], p.gz_act);
         const long long o = p.out_layout == 1 ? b * p.out_bs + (long long)j * p.rows + q : m * p.ldo + j;
         if (p.res) v += p.res[(p.out_layout == 1 ? b * p.res_bs + (long long)j * p.rows + q : b * p.res_bs + q * p.ldo + j)];
         p.out[o] = v;
@@ -313,6 +335,11 @@ extern "C" int32_t dlwp_gc_linear_f32(const dlwp_gc_linear_args* a, void* stream
   DLWP_REQUIRE(a->out_layout == 1 || a->ldo >= a->n, DLWP_ERR_INVALID_ARGUMENT, "gc linear: ldo %d < n %d", a->ldo, a->n);
   DLWP_REQUIRE((const float*)a->out != a->a && (const float*)a->out != a->agg_e, DLWP_ERR_INVALID_ARGUMENT,
                "gc linear: the output may not alias the A operand");
+  DLWP_REQUIRE(a->a_act >= 0 && a->a_act <= 2 && (a->a_act == 0 || a->a_mode != 2), DLWP_ERR_UNSUPPORTED,
+               "gc linear: A activation %d in mode %d", a->a_act, a->a_mode);
+  DLWP_REQUIRE(!a->act_grad_z || (a->act_grad >= 1 && a->act_grad <= 2 && a->out_layout == 0 && a->ld_act_grad_z >= a->n),
+               DLWP_ERR_INVALID_ARGUMENT, "gc linear: act' epilogue %d (ld %d, out layout %d)", a->act_grad,
+               a->ld_act_grad_z, a->out_layout);
   gc::Args p;
   p.mode = a->a_mode;
   p.a = a->a;
@@ -344,6 +371,10 @@ extern "C" int32_t dlwp_gc_linear_f32(const dlwp_gc_linear_args* a, void* stream
   p.out_bs = a->out_layout == 1 ? (long long)a->n * a->rows : 0;
   p.res = a->res;
   p.res_bs = a->res_batch_stride;
+  p.a_act = a->a_act;
+  p.gz = a->act_grad_z;
+  p.gz_act = a->act_grad;
+  p.ld_gz = a->ld_act_grad_z;
   const long long mt = (p.M + gc::BM - 1) / gc::BM;
   DLWP_REQUIRE(mt <= INT32_MAX, DLWP_ERR_UNSUPPORTED, "gc linear: %lld rows", p.M);
   const dim3 grid((unsigned)mt, (unsigned)((a->n + gc::BN - 1) / gc::BN));

@@ -59,6 +59,7 @@ class GcLinearArgs(ctypes.Structure):
         ("ld_src_products", c_int32), ("dst_products", c_void_p), ("dst_index", c_void_p),
         ("dst_products_batch_stride", ctypes.c_int64), ("ld_dst_products", c_int32), ("act", c_int32), ("out", c_void_p),
         ("out_layout", c_int32), ("ldo", c_int32), ("res", c_void_p), ("res_batch_stride", ctypes.c_int64),
+        ("a_act", c_int32), ("act_grad_z", c_void_p), ("act_grad", c_int32), ("ld_act_grad_z", c_int32),
     ]
 
 
@@ -189,6 +190,15 @@ SIGNATURES = {
     "dlwp_gc_linear_f32": (c_int32, [POINTER(GcLinearArgs), c_void_p]),
     "dlwp_gc_layernorm_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p,
                                         ctypes.c_int64, c_void_p]),
+    "dlwp_gc_weight_grad_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "dlwp_gc_weight_grad_f32": (c_int32, [POINTER(GcLinearArgs), c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p,
+                                          c_void_p, c_size_t, c_void_p]),
+    "dlwp_gc_layernorm_bwd_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "dlwp_gc_layernorm_bwd_f32": (c_int32, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, ctypes.c_int64, c_void_p,
+                                            c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_size_t, c_void_p]),
+    "dlwp_gc_segment_sum_f32": (c_int32, [c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                          c_void_p, c_void_p]),
     "dlwp_mgn_processor_layer_f32": (c_int32, [POINTER(MgnMlpDesc), POINTER(MgnMlpDesc), c_int32, c_void_p, c_void_p, c_void_p,
                                                c_int32,
                                                c_int32, c_int32, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p,

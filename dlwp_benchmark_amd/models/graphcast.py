@@ -12,8 +12,16 @@ W_e e + (W_s x_src)[src] + (W_d x_dst)[dst] with the node products computed once
 [aggregate, x] in the A-operand load.  The four static embeddings (mesh nodes, mesh / g2m / m2g edges) depend on the
 weights only and are computed once per weight version.  Batches B >= 1 share the graph (the reference raises for B != 1).
 
-Training with gradients runs the torch composition of the same math under autograd; so do MLPs outside the kernels'
-envelope (ops.gc_mlp_supported) and `set_hip_step(False)` (A/B timing).
+Training with gradients (`.train()` and autograd recording) can run the same kernels inside autograd Functions
+(training.gc_mlp / training.gc_layer) whose backward is csrc/graphcast_bwd.hip: each saves its inputs, every hidden
+pre-activation and the LayerNorm input (the LayerNorm writes a fresh tensor), about half of what autograd of the
+composition keeps, and every gradient is bitwise reproducible.  The static embeddings then run once per `forward`
+through the Functions, so their gradients accumulate over the rollout steps.  The HIP backward is slower than the
+composition at the benchmarked shapes, so training keeps the composition by default and
+`set_hip_training(True)` opts in for the memory (`uses_hip_training`).  The composition (`_step_torch`) also trains MLPs
+outside the envelope (ops.gc_mlp_supported, or no LayerNorm), `set_hip_step(False)` models and CPU tensors; eval MLPs
+outside the envelope and `set_hip_step(False)` (A/B timing) run it too.  DLWP_TRAIN_TORCH_BACKWARD=1 keeps the HIP
+forward and differentiates the composition instead (a cross-check).
 """
 import os
 import re
@@ -26,6 +34,7 @@ from torch import nn
 from .. import icosphere
 from .. import lib as _lib
 from .. import ops
+from .. import training
 from ..rollout import rollout_into
 from ._base import HipBackbone
 
@@ -112,6 +121,12 @@ class MeshGraphDecoder(nn.Module):
         self.node_mlp = MeshGraphMLP(2 * d, d, d, hl, act, norm)
 
 
+# Training with gradients runs the HIP kernels only when opted in (set_hip_training): at the benchmarked shapes the HIP
+# step is slower than the composition; it keeps about half the activation memory (DESIGN.md section 17,
+# profiles/graphcast_train.jsonl).
+HIP_TRAINING_DEFAULT = False
+
+
 def _mesh_level(path: str) -> int:
     m = re.search(r"_l(\d+)", os.path.basename(str(path)))
     return int(m.group(1)) if m else 6
@@ -189,7 +204,10 @@ class GraphCastNet(HipBackbone):
         self.register_buffer("_from_ref_order", torch.argsort(ref_order), persistent=False)   # rows of the grid embedder
         self._pk = {}
         self._static = None
+        self._static_train = None   # the static embeddings of the current training forward
+        self._train_graphs = {}
         self.hip_step = True
+        self.hip_training = HIP_TRAINING_DEFAULT
 
     # ---- bookkeeping ---------------------------------------------------------------------------------------------------
     def _mlps(self):
@@ -214,6 +232,23 @@ class GraphCastNet(HipBackbone):
 
     def uses_hip_step(self) -> bool:
         return self.hip_step and self.hip_supported()
+
+    def set_hip_training(self, on: bool = True):
+        """True: training with gradients runs the HIP forward and backward kernels wherever uses_hip_training() holds;
+        False (default, the faster path at the measured shapes): the torch composition under autograd"""
+        self.hip_training = bool(on)
+        return self
+
+    def uses_hip_training(self) -> bool:
+        """training with gradients runs on csrc/graphcast.hip + csrc/graphcast_bwd.hip: opted in, the HIP step on, every
+        MLP inside the envelope (ops.gc_mlp_supported) and every message-passing MLP ending in its LayerNorm"""
+        layers = [self.encoder.edge_mlp.model, self.encoder.dst_node_mlp.model, self.decoder.edge_mlp.model,
+                  self.decoder.node_mlp.model]
+        for p in (self.processor_encoder, self.processor, self.processor_decoder):
+            for e, n in p.pairs():
+                layers += [e, n]
+        return (self.hip_training and self.uses_hip_step()
+                and all(ops.mgn_parts(m)[1] is not None for m in layers))
 
     def _packed(self, seq, split=None, perm=None) -> ops.GcMlpWeights:
         p = self._pk.get(id(seq))
@@ -294,6 +329,65 @@ class GraphCastNet(HipBackbone):
                        dict(a_mode=0, a=grid, a_batch_stride=G * d, lda=d), out_cf=True)
         return y.view(b, self.prognostic_channels, self.height, self.width)
 
+    # ---- HIP training step ----------------------------------------------------------------------------------------------
+    def _graph_train(self, name: str, n_src: int, n_dst: int) -> dict:
+        src = getattr(self, f"{name}_src")
+        g = self._train_graphs.get(name)
+        if g is None or g["src"] is not src:
+            src_row_ptr, src_perm = ops.mgn_source_csr(src, n_src)
+            g = self._train_graphs[name] = dict(row_ptr=getattr(self, f"{name}_row_ptr"), src=src,
+                                                dst=getattr(self, f"{name}_dst"), deg=getattr(self, f"{name}_deg"),
+                                                src_row_ptr=src_row_ptr, src_perm=src_perm, n_src=n_src, n_dst=n_dst)
+        return g
+
+    def _static_embeddings_train(self):
+        """the four static embeddings through training.gc_mlp: one [rows, D] table each, shared by the batch"""
+        ee = self.encoder_embedder
+
+        def emb(seq, x):
+            return training.gc_mlp(seq, self._packed(seq), x, 1, x.shape[0], x_bs=0)
+
+        return dict(mesh_n=emb(ee.mesh_node_mlp.model, self.mesh_ndata), mesh_e=emb(ee.mesh_edge_mlp.model, self.mesh_edata),
+                    g2m_e=emb(ee.grid2mesh_edge_mlp.model, self.g2m_edata),
+                    m2g_e=emb(self.decoder_embedder.mesh2grid_edge_mlp.model, self.m2g_edata))
+
+    def _layer_train(self, edge, node, name, b, e, xs, xd, n_src, n_dst, residual):
+        return training.gc_layer(edge, self._edge_packed(edge), node, self._packed(node), self.aggregation,
+                                 self._graph_train(name, n_src, n_dst), b, e, xs, xd, residual)
+
+    def _step_train(self, x_t: torch.Tensor) -> torch.Tensor:
+        """_step_hip with autograd: every MLP through training.gc_mlp / training.gc_layer"""
+        b = x_t.shape[0]
+        G, N = self.n_grid, self.n_mesh
+        st = self._static_train if self._static_train is not None else self._static_embeddings_train()
+        gm = self.encoder_embedder.grid_node_mlp.model
+        grid = training.gc_mlp(gm, self._packed(gm, perm=self._from_ref_order), x_t.contiguous(), b, G, mode=1,
+                               col_order=self._to_ref_order)
+        enc = self.encoder
+        mesh, _ = self._layer_train(enc.edge_mlp.model, enc.dst_node_mlp.model, "g2m", b, st["g2m_e"], grid, st["mesh_n"],
+                                    G, N, False)
+        sm = enc.src_node_mlp.model
+        grid = training.gc_mlp(sm, self._packed(sm), grid, b, G, residual=True)
+        e = st["mesh_e"]
+        for p in (self.processor_encoder, self.processor, self.processor_decoder):
+            for em, nm in p.pairs():
+                mesh, e = self._layer_train(em, nm, "mesh", b, e, mesh, mesh, N, N, True)
+        dec = self.decoder
+        grid, _ = self._layer_train(dec.edge_mlp.model, dec.node_mlp.model, "m2g", b, st["m2g_e"], mesh, grid, N, G, False)
+        fm = self.finale.model
+        y = training.gc_mlp(fm, self._packed(fm), grid, b, G, out_cf=True)
+        return y.view(b, self.prognostic_channels, self.height, self.width)
+
+    def _forward_train(self, constants, prescribed, prognostic):
+        """the static embeddings once per forward (their gradients accumulate over the rollout steps), then the rollout"""
+        if not (prognostic.is_cuda and self.uses_hip_training()):
+            return super()._forward_train(constants, prescribed, prognostic)
+        self._static_train = self._static_embeddings_train()
+        try:
+            return super()._forward_train(constants, prescribed, prognostic)
+        finally:
+            self._static_train = None
+
     # ---- torch composition -----------------------------------------------------------------------------------------------
     def _edge_torch(self, seq, b, name, e, xs, n_src, xd, n_dst):
         src, dst = getattr(self, f"{name}_src").long(), getattr(self, f"{name}_dst").long()
@@ -349,7 +443,11 @@ class GraphCastNet(HipBackbone):
         if (h, w) != (self.height, self.width) or c != self.input_dim_grid_nodes:
             raise _lib.DlwpError(f"input {c}x{h}x{w} does not match the model's {self.input_dim_grid_nodes}x{self.height}x"
                                  f"{self.width}")
-        if (self.training and torch.is_grad_enabled()) or not self.uses_hip_step():
+        if self.training and torch.is_grad_enabled():
+            if x_t.is_cuda and self.uses_hip_training():
+                return self._step_train(x_t)
+            return self._step_torch(x_t)
+        if not self.uses_hip_step():
             return self._step_torch(x_t)
         return self._step_hip(x_t)
 

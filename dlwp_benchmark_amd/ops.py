@@ -1508,8 +1508,22 @@ class GcMlpWeights:
             if self.split is not None:
                 self.first = [p.contiguous() for p in torch.split(w0, list(self.split), dim=0)]
             self.zero = torch.zeros(lins[0].out_features, device=w0.device, dtype=torch.float32)
+            self.bwd_first = None
             self._key = key
         return self
+
+    def backward_first(self, seq: torch.nn.Sequential, split=None):
+        """the first Linear's weight in torch's [out][in] layout (the data gradient's [k][n] operand), its input columns
+        permuted like the forward (`perm`) and split into contiguous column blocks (`split`, else this object's split; the
+        node MLP's agg / x halves): cached per weight version with the forward operands"""
+        self.get(seq)
+        if self.bwd_first is None:
+            w = mgn_parts(seq)[0][0].weight.detach()
+            if self.perm is not None:
+                w = w[:, self.perm]
+            split = split if split is not None else self.split
+            self.bwd_first = [c.contiguous() for c in torch.split(w, list(split), dim=1)] if split else [w.contiguous()]
+        return self.bwd_first
 
 
 def _gc_args(**kw) -> "_lib.GcLinearArgs":
@@ -1574,4 +1588,118 @@ def gc_node_products(pk: GcMlpWeights, part: int, x: torch.Tensor, batch: int, r
     out = torch.empty(batch * rows, h, device=x.device, dtype=torch.float32)
     gc_linear(_gc_args(a_mode=0, a=x, a_batch_stride=x_bs, lda=k, wt=w, bias=pk.zero, k=k, n=h, batch=batch, rows=rows,
                        act=0, out=out, out_layout=0, ldo=h))
+    return out
+
+
+# ---- GraphCastNet backward (training.gc_mlp / training.gc_layer; csrc/graphcast_bwd.hip) ----------------------------------
+def gc_mlp_train(pk: GcMlpWeights, seq: torch.nn.Sequential, batch: int, rows: int, first: dict,
+                 res: Optional[torch.Tensor] = None, res_bs: int = 0, out_cf: bool = False):
+    """gc_mlp for training: every Linear writes its pre-activation z_i (the next one applies act on its A load, so act(z_i)
+    never exists) and the LayerNorm writes a fresh tensor, so its input survives.  Returns (output, [z_0 .. z_last])."""
+    w = pk.get(seq)
+    lins, ln = mgn_parts(seq)
+    act = GC_ACT[type(seq[1])]
+    dev = w.wt[0].device
+    zs = []
+    for i, l in enumerate(lins):
+        last = i + 1 == len(lins)
+        n = l.out_features
+        cf = last and out_cf
+        out = torch.empty((batch, n, rows) if cf else (batch * rows, n), device=dev, dtype=torch.float32)
+        kw = dict(wt=w.wt[i], bias=l.bias, k=l.in_features, n=n, batch=batch, rows=rows, act=0, out=out,
+                  out_layout=int(cf), ldo=n)
+        if i == 0:
+            kw.update(first)
+            kw["k"] = kw["wt"].shape[0]
+        else:
+            kw.update(a_mode=0, a=zs[-1], a_batch_stride=rows * l.in_features, lda=l.in_features, a_act=act)
+        if last and ln is None and res is not None:
+            kw.update(res=res, res_batch_stride=res_bs)
+        gc_linear(_gc_args(**kw))
+        zs.append(out)
+    if ln is None:
+        return zs[-1], zs
+    y = torch.empty_like(zs[-1])
+    gc_layernorm(zs[-1], batch, rows, ln, res, res_bs, out=y)
+    return y, zs
+
+
+def gc_weight_grad(a_fields: dict, k: int, n: int, batch: int, rows: int, dz: torch.Tensor, dz_cf: bool = False,
+                   dw: Optional[torch.Tensor] = None, db: Optional[torch.Tensor] = None, bias: bool = True):
+    """dlwp_gc_weight_grad_f32: (dW [n, k] = A^T dZ in torch's layout, db = column sums of dZ or None).  a_fields: the A
+    operand as dlwp_gc_linear_args fields (a_mode, a, a_batch_stride, lda, agg_*, row_ptr, a_act).  dw may be a column
+    block of a wider weight gradient (a view with unit column stride)."""
+    lib = _lib.load()
+    ws_bytes = lib.dlwp_gc_weight_grad_workspace_bytes(k, n, batch, rows)
+    if ws_bytes == 0:
+        raise _lib.DlwpError(f"gc weight grad: {k} -> {n} is outside the envelope")
+    dev = dz.device
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    if dw is None:
+        dw = torch.empty(n, k, device=dev, dtype=torch.float32)
+    if dw.stride(1) != 1 or dw.shape != (n, k):
+        raise _lib.DlwpError(f"gc weight grad: dW view {tuple(dw.shape)} / {dw.stride()} for {n} x {k}")
+    if db is None and bias:
+        db = torch.empty(n, device=dev, dtype=torch.float32)
+    args = _gc_args(k=k, n=n, batch=batch, rows=rows, **a_fields)
+    _lib.check(lib.dlwp_gc_weight_grad_f32(ctypes.byref(args), dz.data_ptr(), int(dz_cf), 0 if dz_cf else dz.stride(0),
+                                           dw.data_ptr(), dw.stride(0), db.data_ptr() if db is not None else None,
+                                           ws.data_ptr(), ws_bytes, _lib.stream_ptr()), "gc weight grad")
+    return dw, db
+
+
+def gc_data_grad(dz: torch.Tensor, w: torch.Tensor, batch: int, rows: int, dz_cf: bool = False,
+                 z: Optional[torch.Tensor] = None, act: int = 0, res: Optional[torch.Tensor] = None, res_bs: int = 0,
+                 out_cf: bool = False) -> torch.Tensor:
+    """dA = dZ w on dlwp_gc_linear_f32 (torch's [out][in] weight w as its [k][n] operand) [* act'(z)] [+ res]: [batch * rows,
+    in] or channels-first [batch, in, rows]; dZ [batch * rows, out] or channels-first [batch, out, rows]"""
+    k, n = w.shape
+    zero = torch.zeros(n, device=dz.device, dtype=torch.float32)
+    out = torch.empty((batch, n, rows) if out_cf else (batch * rows, n), device=dz.device, dtype=torch.float32)
+    kw = dict(a_mode=1 if dz_cf else 0, a=dz, a_batch_stride=k * rows, lda=k, wt=w, bias=zero, k=k, n=n, batch=batch,
+              rows=rows, act=0, out=out, out_layout=int(out_cf), ldo=n)
+    if z is not None:
+        kw.update(act_grad_z=z, act_grad=act, ld_act_grad_z=z.stride(0))
+    if res is not None:
+        kw.update(res=res, res_batch_stride=res_bs)
+    gc_linear(_gc_args(**kw))
+    return out
+
+
+def gc_layernorm_backward(z: torch.Tensor, ln: torch.nn.LayerNorm, batch: int, rows: int, gy: Optional[torch.Tensor],
+                          g_agg: Optional[torch.Tensor] = None, g_agg_bs: int = 0, idx: Optional[torch.Tensor] = None,
+                          deg: Optional[torch.Tensor] = None, want_total: bool = False):
+    """dlwp_gc_layernorm_bwd_f32: (g_total or None, dz, dgamma, dbeta) with g = gy + g_agg[idx] (/ deg[idx])"""
+    lib = _lib.load()
+    d = ln.normalized_shape[0]
+    ws_bytes = lib.dlwp_gc_layernorm_bwd_workspace_bytes(batch, rows, d)
+    if ws_bytes == 0:
+        raise _lib.DlwpError(f"gc layernorm backward: width {d} is outside the envelope")
+    dev = z.device
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    gx = torch.empty(batch * rows, d, device=dev, dtype=torch.float32)
+    gt = torch.empty(batch * rows, d, device=dev, dtype=torch.float32) if want_total else None
+    dg = torch.empty(d, device=dev, dtype=torch.float32)
+    dbeta = torch.empty(d, device=dev, dtype=torch.float32)
+
+    def ptr(t):
+        return t.data_ptr() if t is not None else None
+
+    _lib.check(lib.dlwp_gc_layernorm_bwd_f32(z.data_ptr(), ln.weight.data_ptr(), float(ln.eps), ptr(gy), ptr(g_agg), g_agg_bs,
+                                             ptr(idx), ptr(deg), batch, rows, d, ptr(gt), gx.data_ptr(), dg.data_ptr(),
+                                             dbeta.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr()),
+               "gc layernorm backward")
+    return gt, gx, dg, dbeta
+
+
+def gc_segment_sum(x: torch.Tensor, batch: int, row_ptr: Optional[torch.Tensor], perm: Optional[torch.Tensor],
+                   n_segments: int, batch_sum: bool = False) -> torch.Tensor:
+    """dlwp_gc_segment_sum_f32 over x [batch * rows, D]: [batch (1 when batch_sum) * n_segments, D]; row_ptr None: the
+    segment of n is row n (a plain fixed-order batch sum)"""
+    d = x.shape[-1]
+    x = x.contiguous()
+    out = torch.empty((1 if batch_sum else batch) * n_segments, d, device=x.device, dtype=torch.float32)
+    _lib.check(_lib.load().dlwp_gc_segment_sum_f32(x.data_ptr(), x.numel() // batch, row_ptr.data_ptr() if row_ptr is not None
+                                                   else None, perm.data_ptr() if perm is not None else None, n_segments, d,
+                                                   batch, int(batch_sum), out.data_ptr(), _lib.stream_ptr()), "gc segment sum")
     return out

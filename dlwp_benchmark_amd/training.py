@@ -18,7 +18,7 @@ Everything pointwise around the spectral operator (1x1 convolutions, GELU, resid
 the GPU in training mode; window-attention backward is not built yet.
 """
 import ctypes
-from typing import List, Sequence
+from typing import List, Optional, Sequence
 
 import torch
 
@@ -717,3 +717,258 @@ def mgn_layer(edge_seq, edge_packed, node_seq, node_packed, aggregation: str, gr
     (ops.mgn_source_csr)"""
     cfg = (edge_seq, edge_packed, node_seq, node_packed, aggregation, graph, batch)
     return _MgnLayerFn.apply(x, e, e_shared, cfg, *edge_seq.parameters(), *node_seq.parameters())
+
+
+# ---- GraphCastNet (models/graphcast.py; csrc/graphcast.hip forward, csrc/graphcast_bwd.hip backward) --------------------
+def _gc_first(mode: int, x: torch.Tensor, x_bs: int) -> dict:
+    """the A fields of a first Linear reading x: mode 0 rows [rows, D] per sample (x_bs 0: one table for the batch),
+    mode 1 channels-first [B, C, rows...]"""
+    return dict(a_mode=mode, a=x, a_batch_stride=x_bs, lda=x.shape[-1] if mode == 0 else 0)
+
+
+def _gc_tail_backward(seq, batch: int, rows: int, zs, gy, out_cf: bool, ln_gather: Optional[dict] = None,
+                      want_total: bool = False):
+    """the backward of a MeshGraphMLP above its first Linear from the saved pre-activations zs: (dZ_0 [batch * rows, H],
+    the LayerNorm's total output gradient or None, [gradients in the order of seq.parameters(), the first Linear's None])"""
+    from . import ops
+
+    lins, ln = ops.mgn_parts(seq)
+    act = ops.GC_ACT[type(seq[1])]
+    n = len(lins)
+    grads = [None] * (2 * n + (2 if ln is not None else 0))
+    g_total = None
+    g, cf = gy, out_cf
+    if ln is not None:
+        g_total, g, grads[2 * n], grads[2 * n + 1] = ops.gc_layernorm_backward(zs[-1], ln, batch, rows, gy,
+                                                                              want_total=want_total, **(ln_gather or {}))
+        cf = False
+    for i in range(n - 1, 0, -1):
+        l = lins[i]
+        grads[2 * i], grads[2 * i + 1] = ops.gc_weight_grad(
+            dict(a_mode=0, a=zs[i - 1], a_batch_stride=rows * l.in_features, lda=l.in_features, a_act=act),
+            l.in_features, l.out_features, batch, rows, g, dz_cf=cf)
+        g = ops.gc_data_grad(g, l.weight.detach(), batch, rows, dz_cf=cf, z=zs[i - 1], act=act)
+        cf = False
+    return g, g_total, grads
+
+
+def _gc_batch_sum(t: torch.Tensor, batch: int) -> torch.Tensor:
+    """the fixed-order sum over the batch of [batch * rows, D] (the gradient of a table the batch shares)"""
+    from . import ops
+
+    if batch == 1:
+        return t
+    return ops.gc_segment_sum(t, batch, None, None, t.shape[0] // batch, batch_sum=True)
+
+
+def gc_mlp_torch(seq, x, batch: int, rows: int, mode: int, x_bs: int, residual: bool, out_cf: bool, col_order=None):
+    """torch composition of one GraphCast MLP in the layouts of gc_mlp (DLWP_TRAIN_TORCH_BACKWARD=1, tests)"""
+    if mode == 1:
+        a = x.reshape(batch, -1, rows)
+        if col_order is not None:
+            a = a[:, col_order]
+        a = a.permute(0, 2, 1).reshape(batch * rows, -1)
+    else:
+        a = x if x_bs else x.repeat(batch, 1)
+    y = seq(a)
+    if residual:
+        y = y + a
+    if out_cf:
+        y = y.view(batch, rows, -1).permute(0, 2, 1)
+    return y
+
+
+class _GcMlpFn(torch.autograd.Function):
+    """One GraphCast MeshGraphMLP (A modes 0 / 1, optional LayerNorm, residual and channels-first output): forward on
+    dlwp_gc_linear_f32 saving the input (a reference), each pre-activation z_i and the LayerNorm input; backward on
+    csrc/graphcast_bwd.hip.  DLWP_TRAIN_TORCH_BACKWARD=1 differentiates gc_mlp_torch instead."""
+
+    @staticmethod
+    def forward(ctx, x, cfg, *params):
+        from . import ops
+
+        seq, pk, batch, rows, mode, x_bs, residual, out_cf, col_order = cfg
+        with torch.no_grad():
+            xd = x.detach()
+            y, zs = ops.gc_mlp_train(pk, seq, batch, rows, _gc_first(mode, xd, x_bs), res=xd if residual else None,
+                                     res_bs=x_bs, out_cf=out_cf)
+        ctx.save_for_backward(x, *zs, *params)    # the parameters too: autograd's version check sees in-place edits
+        ctx.cfg, ctx.n_z = cfg, len(zs)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        from . import ops
+
+        seq, pk, batch, rows, mode, x_bs, residual, out_cf, col_order = ctx.cfg
+        saved = ctx.saved_tensors
+        x, zs = saved[0], saved[1:1 + ctx.n_z]
+        params = list(seq.parameters())
+        need_x = ctx.needs_input_grad[0]
+        if _TORCH_BACKWARD():
+            with torch.enable_grad():
+                x_ = x.detach().requires_grad_(need_x)
+                y = gc_mlp_torch(seq, x_, batch, rows, mode, x_bs, residual, out_cf, col_order)
+                grads = torch.autograd.grad(y, ([x_] if need_x else []) + params, gy.reshape(y.shape))
+            return ((grads[0] if need_x else None), None, *grads[int(need_x):])
+        gy = gy.contiguous()
+        lins, _ = ops.mgn_parts(seq)
+        g0, _, grads = _gc_tail_backward(seq, batch, rows, zs, gy, out_cf)
+        l0 = lins[0]
+        dw, grads[1] = ops.gc_weight_grad(_gc_first(mode, x, x_bs), l0.in_features, l0.out_features, batch, rows, g0)
+        grads[0] = dw[:, col_order] if col_order is not None else dw
+        gx = None
+        if need_x:
+            w0 = pk.backward_first(seq)[0]
+            res = gy if residual else None
+            gx = ops.gc_data_grad(g0, w0, batch, rows, res=res, res_bs=rows * l0.in_features, out_cf=mode == 1)
+            if mode == 0 and not x_bs:
+                gx = _gc_batch_sum(gx, batch)
+            gx = gx.view(x.shape)
+        return (gx, None, *grads)
+
+
+def gc_mlp(seq, pk, x, batch: int, rows: int, mode: int = 0, x_bs: Optional[int] = None, residual: bool = False,
+           out_cf: bool = False, col_order=None):
+    """differentiable GraphCast MLP: x [batch * rows, D] rows (x_bs 0: one [rows, D] table shared by the batch) or, mode 1,
+    channels-first [batch, C, rows...] whose weight-gradient columns are put back in torch's order by col_order"""
+    if x_bs is None:
+        x_bs = rows * x.shape[-1] if mode == 0 else x.numel() // batch
+    cfg = (seq, pk, batch, rows, mode, x_bs, residual, out_cf, col_order)
+    return _GcMlpFn.apply(x, cfg, *seq.parameters())
+
+
+def gc_layer_torch(edge_seq, node_seq, aggregation: str, graph: dict, batch: int, e, xs, xd, residual: bool):
+    """torch composition of one GraphCast message-passing layer (edge MLP on [e, xs[src], xd[dst]] (+ e), node MLP on
+    [agg e', xd] + xd): (x', e') as [batch * n_dst, D], [batch * E, D].  Shared tables are [rows, D]."""
+    src, dst = graph["src"].long(), graph["dst"].long()
+    n_src, n_dst, ne = graph["n_src"], graph["n_dst"], src.numel()
+    ar = torch.arange(batch, device=e.device).repeat_interleave(ne)
+    e_b = e if e.shape[0] == batch * ne else e.repeat(batch, 1)
+    xs_b = xs if xs.shape[0] == batch * n_src else xs.repeat(batch, 1)
+    xd_b = xd if xd.shape[0] == batch * n_dst else xd.repeat(batch, 1)
+    e_new = edge_seq(torch.cat((e_b, xs_b[src.repeat(batch) + ar * n_src], xd_b[dst.repeat(batch) + ar * n_dst]), dim=1))
+    if residual:
+        e_new = e_new + e_b
+    t = dst.repeat(batch) + ar * n_dst
+    agg = torch.zeros(batch * n_dst, e_new.shape[1], device=e.device, dtype=e.dtype).index_add(0, t, e_new)
+    if aggregation == "mean":
+        agg = agg / graph["deg"].clamp(min=1).to(e.dtype).repeat(batch).unsqueeze(1)
+    return node_seq(torch.cat((agg, xd_b), dim=1)) + xd_b, e_new
+
+
+class _GcLayerFn(torch.autograd.Function):
+    """One GraphCast message-passing layer: the split edge MLP (node products W_s x_src, W_d x_dst computed once per node
+    and gathered) writing e' = LN(z) (+ e), then the node MLP on [agg e', x_dst] + x_dst.  Saves the inputs (references),
+    each MLP's pre-activations and LayerNorm input, and e'.  The backward runs the node MLP's first, so the edge
+    LayerNorm backward gathers its aggregate gradient by destination (dlwp_gc_layernorm_bwd_f32); the source /
+    destination products' gradients are per-node segment sums (N rows, not E).  DLWP_TRAIN_TORCH_BACKWARD=1
+    differentiates gc_layer_torch instead."""
+
+    @staticmethod
+    def forward(ctx, e, xs, xd, cfg, *params):
+        from . import ops
+
+        edge_seq, epk, node_seq, npk, aggregation, graph, batch, residual = cfg
+        n_src, n_dst, ne = graph["n_src"], graph["n_dst"], graph["src"].numel()
+        d = edge_seq[0].out_features
+        e_bs = ne * e.shape[-1] if e.shape[0] == batch * ne else 0
+        xs_bs = n_src * xs.shape[-1] if xs.shape[0] == batch * n_src else 0
+        xd_bs = n_dst * xd.shape[-1] if xd.shape[0] == batch * n_dst else 0
+        with torch.no_grad():
+            e_, xs_, xd_ = e.detach(), xs.detach(), xd.detach()
+            pk = epk.get(edge_seq)
+            ps = ops.gc_node_products(pk, 1, xs_, batch if xs_bs else 1, n_src, xs_bs)
+            pd = ops.gc_node_products(pk, 2, xd_, batch if xd_bs else 1, n_dst, xd_bs)
+            first = dict(a_mode=0, a=e_, a_batch_stride=e_bs, lda=e.shape[-1], wt=pk.first[0],
+                         src_products=ps, src_index=graph["src"], src_products_batch_stride=n_src * d if xs_bs else 0,
+                         ld_src_products=d, dst_products=pd, dst_index=graph["dst"],
+                         dst_products_batch_stride=n_dst * d if xd_bs else 0, ld_dst_products=d)
+            e_new, ze = ops.gc_mlp_train(epk, edge_seq, batch, ne, first, res=e_ if residual else None, res_bs=e_bs)
+            del ps, pd
+            nfirst = dict(a_mode=2, a=xd_, a_batch_stride=xd_bs, lda=xd.shape[-1], agg_e=e_new,
+                          agg_batch_stride=ne * e_new.shape[-1], agg_width=e_new.shape[-1], row_ptr=graph["row_ptr"],
+                          agg_mean=int(aggregation == "mean"))
+            x_new, zn = ops.gc_mlp_train(npk, node_seq, batch, n_dst, nfirst, res=xd_, res_bs=xd_bs)
+        ctx.save_for_backward(e, xs, xd, e_new, *ze, *zn, *params)   # the parameters: in-place edits raise
+        ctx.cfg, ctx.n_ze, ctx.n_zn = cfg, len(ze), len(zn)
+        ctx.bs = (e_bs, xs_bs, xd_bs)
+        ctx.set_materialize_grads(False)
+        return x_new, e_new
+
+    @staticmethod
+    def backward(ctx, gx_out, ge_out):
+        from . import ops
+
+        edge_seq, epk, node_seq, npk, aggregation, graph, batch, residual = ctx.cfg
+        sv = ctx.saved_tensors
+        e, xs, xd, e_new = sv[:4]
+        ze, zn = sv[4:4 + ctx.n_ze], sv[4 + ctx.n_ze:4 + ctx.n_ze + ctx.n_zn]
+        e_bs, xs_bs, xd_bs = ctx.bs
+        n_src, n_dst, ne = graph["n_src"], graph["n_dst"], graph["src"].numel()
+        pe, pn = list(edge_seq.parameters()), list(node_seq.parameters())
+        if gx_out is None:
+            gx_out = torch.zeros(batch * n_dst, xd.shape[-1], device=xd.device, dtype=torch.float32)
+        if _TORCH_BACKWARD():
+            with torch.enable_grad():
+                e_, xs_, xd_ = (t.detach().requires_grad_(True) for t in (e, xs, xd))
+                xo, eo = gc_layer_torch(edge_seq, node_seq, aggregation, graph, batch, e_, xs_, xd_, residual)
+                outs, gouts = [xo], [gx_out]
+                if ge_out is not None:
+                    outs.append(eo)
+                    gouts.append(ge_out)
+                grads = torch.autograd.grad(outs, [e_, xs_, xd_] + pe + pn, gouts, allow_unused=True)
+            grads = [g if g is not None else torch.zeros_like(t) for g, t in zip(grads, [e_, xs_, xd_] + pe + pn)]
+            return (*grads[:3], None, *grads[3:])
+        gx_out = gx_out.contiguous()
+        ge_out = ge_out.contiguous() if ge_out is not None else None
+        d = e_new.shape[-1]
+        # node MLP: x' = LN(mlp([agg e', x])) + x
+        gu, _, gn = _gc_tail_backward(node_seq, batch, n_dst, zn, gx_out, False)
+        nl0 = ops.mgn_parts(node_seq)[0][0]
+        gn[0], gn[1] = ops.gc_weight_grad(
+            dict(a_mode=2, a=xd, a_batch_stride=xd_bs, lda=xd.shape[-1], agg_e=e_new, agg_batch_stride=ne * d, agg_width=d,
+                 row_ptr=graph["row_ptr"], agg_mean=int(aggregation == "mean")),
+            nl0.in_features, nl0.out_features, batch, n_dst, gu)
+        v_agg, v_x = npk.backward_first(node_seq, (d, nl0.in_features - d))
+        g_agg = ops.gc_data_grad(gu, v_agg, batch, n_dst)
+        gxd = ops.gc_data_grad(gu, v_x, batch, n_dst, res=gx_out, res_bs=n_dst * xd.shape[-1])
+        # edge MLP: e' = LN(mlp([e, xs[src], xd[dst]])) (+ e); its output gradient ge' + g_agg[dst] (/ deg) is formed
+        # inside the LayerNorm backward
+        gather = dict(g_agg=g_agg, g_agg_bs=n_dst * d, idx=graph["dst"],
+                      deg=graph["deg"] if aggregation == "mean" else None)
+        gz, ge_tot, gedge = _gc_tail_backward(edge_seq, batch, ne, ze, ge_out, False, ln_gather=gather,
+                                              want_total=residual and ctx.needs_input_grad[0])
+        el0 = ops.mgn_parts(edge_seq)[0][0]
+        h, de = el0.out_features, e.shape[-1]
+        w_e, w_s, w_d = epk.backward_first(edge_seq)
+        dw0 = torch.empty(h, el0.in_features, device=e.device, dtype=torch.float32)
+        _, gedge[1] = ops.gc_weight_grad(_gc_first(0, e, e_bs), de, h, batch, ne, gz, dw=dw0[:, :de])
+        gps = ops.gc_segment_sum(gz, batch, graph["src_row_ptr"], graph["src_perm"], n_src, batch_sum=not xs_bs)
+        gpd = ops.gc_segment_sum(gz, batch, graph["row_ptr"], None, n_dst, batch_sum=not xd_bs)
+        bs_s, bs_d = (batch if xs_bs else 1), (batch if xd_bs else 1)
+        ds = xs.shape[-1]
+        ops.gc_weight_grad(_gc_first(0, xs, xs_bs), ds, h, bs_s, n_src, gps, dw=dw0[:, de:de + ds], bias=False)
+        ops.gc_weight_grad(_gc_first(0, xd, xd_bs), xd.shape[-1], h, bs_d, n_dst, gpd, dw=dw0[:, de + ds:], bias=False)
+        gedge[0] = dw0
+        gxs = ops.gc_data_grad(gps, w_s, bs_s, n_src) if ctx.needs_input_grad[1] else None
+        gxd_out = None
+        if ctx.needs_input_grad[2]:
+            if not xd_bs:
+                gxd = _gc_batch_sum(gxd, batch)
+            gxd_out = ops.gc_data_grad(gpd, w_d, bs_d, n_dst, res=gxd, res_bs=n_dst * xd.shape[-1])
+        ge = None
+        if ctx.needs_input_grad[0]:
+            ge = ops.gc_data_grad(gz, w_e, batch, ne, res=ge_tot, res_bs=ne * de)
+            if not e_bs:
+                ge = _gc_batch_sum(ge, batch)
+        return (ge, gxs, gxd_out, None, *gedge, *gn)
+
+
+def gc_layer(edge_seq, edge_packed, node_seq, node_packed, aggregation: str, graph: dict, batch: int, e, xs, xd,
+             residual: bool):
+    """differentiable GraphCast message-passing layer: (x' [batch * n_dst, D], e' [batch * E, D]).  e, xs, xd are per
+    sample ([batch * rows, D]) or one table the batch shares ([rows, D]).  graph: row_ptr, src, dst, deg (CSC by
+    destination), src_row_ptr, src_perm (ops.mgn_source_csr), n_src, n_dst."""
+    cfg = (edge_seq, edge_packed, node_seq, node_packed, aggregation, graph, batch, residual)
+    return _GcLayerFn.apply(e, xs, xd, cfg, *edge_seq.parameters(), *node_seq.parameters())

@@ -763,6 +763,11 @@ typedef struct dlwp_gc_linear_args {
   int32_t ldo;
   const float* res;
   int64_t res_batch_stride;
+  /* training (zero: off; every earlier field keeps its meaning) */
+  int32_t a_act;              /* A[m][k] <- act(A[m][k]) as it is loaded (a_mode 0 / 1; act codes as `act`) */
+  const float* act_grad_z;    /* optional: out[m][j] *= act'(act_grad_z[m * ld_act_grad_z + j]) before res (out_layout 0) */
+  int32_t act_grad;           /* 1 ReLU, 2 SiLU */
+  int32_t ld_act_grad_z;
 } dlwp_gc_linear_args;
 
 int32_t dlwp_gc_linear_f32(const dlwp_gc_linear_args* args, void* stream);
@@ -772,6 +777,42 @@ int32_t dlwp_gc_linear_f32(const dlwp_gc_linear_args* args, void* stream);
 int32_t dlwp_gc_layernorm_f32(const float* in_dev, float* out_dev, int32_t batch, int32_t rows, int32_t width,
                               const float* gamma, const float* beta, float eps, const float* res_dev,
                               int64_t res_batch_stride, void* stream);
+
+/* ---- GraphCastNet backward (csrc/graphcast_bwd.hip) -------------------------------------------------------------------
+ * The data gradients dA = dZ W of every Linear are dlwp_gc_linear_f32 with torch's [out][in] weight as its [k][n] operand
+ * (and the act' epilogue above); the entry points below add the weight gradients, the LayerNorm backward and the
+ * fixed-order segment sums.  No atomics: every result is bitwise reproducible. */
+
+/* dW = A^T dZ (+ db = column sums of dZ) over batch * rows rows, dW written in torch's [n][k] layout at
+ * dw[j * ldw + k] (ldw >= k: a column block of a wider weight), db[j] (optional).  The A operand takes the A fields of
+ * dlwp_gc_linear_args (a_mode 0 / 1 / 2, a, a_batch_stride, lda, agg_e, agg_batch_stride, agg_width, row_ptr, agg_mean,
+ * a_act; k, n, batch, rows); dZ is row-major dz[m * ldz + j] (dz_layout 0) or channels-first dz[(b * n + j) * rows + p]
+ * (dz_layout 1).  The rows are split into slices; each workgroup writes its partial tile to the workspace and a second
+ * kernel adds the slices in order.  Envelope as dlwp_gc_linear_f32 with k and n exchanged: k <= 4096, n <= 512.
+ *   dlwp_gc_weight_grad_workspace_bytes: the slice partials (bounded: at most 32 MiB of dW partials), 0 outside. */
+size_t dlwp_gc_weight_grad_workspace_bytes(int32_t k, int32_t n, int32_t batch, int32_t rows);
+int32_t dlwp_gc_weight_grad_f32(const dlwp_gc_linear_args* a_operand, const float* dz, int32_t dz_layout, int32_t ldz,
+                                float* dw, int32_t ldw, float* db, void* workspace, size_t workspace_bytes, void* stream);
+
+/* LayerNorm backward over batch * rows rows of `width` <= 512, one wave per row, mean / rstd recomputed from the saved
+ * LayerNorm input x.  The row's output gradient is
+ *   g[m] = gy[m] (optional) + g_agg[b * g_agg_batch_stride + idx[p] * width] (optional) / deg[idx[p]] (deg optional)
+ * (the residual edge gradient plus the node MLP's aggregate gradient gathered by the edge's destination).  Writes g to
+ * g_total (optional), the input gradient to gx, and dgamma / dbeta (fixed-order per-workgroup partials, then summed in
+ * order).  dlwp_gc_layernorm_bwd_workspace_bytes: the partials. */
+size_t dlwp_gc_layernorm_bwd_workspace_bytes(int32_t batch, int32_t rows, int32_t width);
+int32_t dlwp_gc_layernorm_bwd_f32(const float* x, const float* gamma, float eps, const float* gy, const float* g_agg,
+                                  int64_t g_agg_batch_stride, const int32_t* idx, const int32_t* deg, int32_t batch,
+                                  int32_t rows, int32_t width, float* g_total, float* gx, float* dgamma, float* dbeta,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* out[b'][n][c] = sum over the segment of n of in[b][i][c], i = perm[j] (perm optional) for row_ptr[n] <= j <
+ * row_ptr[n + 1] (row_ptr NULL: the segment of n is row n alone), in order; an empty segment is 0.  in: sample b at
+ * in + b * in_batch_stride.  batch_sum 0: b' = b; 1: one output, summed over the batch in sample order (the gradient of
+ * a table the batch shares). */
+int32_t dlwp_gc_segment_sum_f32(const float* in, int64_t in_batch_stride, const int32_t* row_ptr, const int32_t* perm,
+                                int32_t n_segments, int32_t width, int32_t batch, int32_t batch_sum, float* out,
+                                void* stream);
 
 #ifdef __cplusplus
 }

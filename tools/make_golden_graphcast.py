@@ -12,7 +12,7 @@ these fixtures.
 The reference's in-model rollout crashes on its second step (graph_cast_net.py:640-643), so trajectories are driven one
 step at a time, and the reference raises for B != 1, so every case is B = 1.
 
-Runs where the reference tree is available:  python tools/make_golden_graphcast.py [graphs] [rollouts] [grad]"""
+Runs where the reference tree is available:  python tools/make_golden_graphcast.py [graphs] [rollouts] [grad] [train]"""
 import hashlib
 import importlib
 import json
@@ -56,6 +56,9 @@ ROLLOUT_CASES = {
     "d512_l1_8x16": (_small(hidden_dim=512, processor_layers=4), 1, 2),
 }
 GRAD_CASE = ("grad_l1_8x16", _small(hidden_dim=24), 1, 3)
+# more gradient cases (tests/golden/graphcast_train_<tag>.npz; B = 1: the reference raises for B > 1): the rollout cases'
+# models, through their multi-step training rollouts
+TRAIN_GRAD_CASES = [(f"train_{tag}", kw, level, frames) for tag, (kw, level, frames) in ROLLOUT_CASES.items()]
 GRAPH_CASES = [(16, 32, 2), (32, 64, 3)]
 
 
@@ -196,9 +199,10 @@ def gen_rollouts(mod, tmp):
                          state_spec=np.array(json.dumps([[k, list(v.shape)] for k, v in m.state_dict().items()])))
 
 
-def gen_grad(mod, tmp):
-    tag, kw, level, frames = GRAD_CASE
-    torch.set_num_threads(1)
+def gen_grad(mod, tmp, case=GRAD_CASE):
+    tag, kw, level, frames = case
+    if case is GRAD_CASE:
+        torch.set_num_threads(1)
     path, mesh_sha = mesh_file(tmp, level)
     m = mod.GraphCastNet(path, **kw)
     sha = mgn_golden.fill(m)
@@ -233,6 +237,9 @@ def main():
             gen_rollouts(mod, tmp)
         if not only or "grad" in only:
             gen_grad(mod, tmp)
+        if not only or "train" in only:
+            for case in TRAIN_GRAD_CASES:
+                gen_grad(mod, tmp, case)
 
 
 if __name__ == "__main__":

@@ -21,7 +21,8 @@ composition at the benchmarked shapes, so training keeps 
 `set_hip_training(True)` opts in for the memory (`uses_hip_training`).  The composition (`_step_torch`) also trains MLPs
 outside the envelope (ops.gc_mlp_supported, or no LayerNorm), `set_hip_step(False)` models and CPU tensors; eval MLPs
 outside the envelope and `set_hip_step(False)` (A/B timing) run it too.  DLWP_TRAIN_TORCH_BACKWARD=1 keeps the HIP
-forward and differentiates the composition instead (a cross-check).
+forward and differentiates the composition instead (a cross-check).  The three forms share one walk of the step
+(`_step`), given the MLP and layer functions of ops, training or the composition.
 """
 import os
 import re
@@ -205,21 +206,25 @@ class GraphCastNet(HipBackbone):
         self._pk = {}
         self._static = None
         self._static_train = None   # the static embeddings of the current training forward
-        self._train_graphs = {}
+        self._graphs = {}
         self.hip_step = True
         self.hip_training = HIP_TRAINING_DEFAULT
 
     # ---- bookkeeping ---------------------------------------------------------------------------------------------------
+    def _layer_mlps(self):
+        """the (edge, node) MLP `model`s of every message-passing layer in step order: grid -> mesh, the processor layers,
+        mesh -> grid"""
+        enc, dec = self.encoder, self.decoder
+        return ([(enc.edge_mlp.model, enc.dst_node_mlp.model)]
+                + [pair for p in (self.processor_encoder, self.processor, self.processor_decoder) for pair in p.pairs()]
+                + [(dec.edge_mlp.model, dec.node_mlp.model)])
+
     def _mlps(self):
         ee, de = self.encoder_embedder, self.decoder_embedder
         yield from (ee.grid_node_mlp.model, ee.mesh_node_mlp.model, ee.mesh_edge_mlp.model, ee.grid2mesh_edge_mlp.model,
-                    de.mesh2grid_edge_mlp.model, self.encoder.edge_mlp.model, self.encoder.src_node_mlp.model,
-                    self.encoder.dst_node_mlp.model, self.decoder.edge_mlp.model, self.decoder.node_mlp.model,
-                    self.finale.model)
-        for p in (self.processor_encoder, self.processor, self.processor_decoder):
-            for e, n in p.pairs():
-                yield e
-                yield n
+                    de.mesh2grid_edge_mlp.model, self.encoder.src_node_mlp.model, self.finale.model)
+        for pair in self._layer_mlps():
+            yield from pair
 
     def hip_supported(self) -> bool:
         return all(ops.gc_mlp_supported(m) for m in self._mlps())
@@ -242,13 +247,8 @@ class GraphCastNet(HipBackbone):
     def uses_hip_training(self) -> bool:
         """training with gradients runs on csrc/graphcast.hip + csrc/graphcast_bwd.hip: opted in, the HIP step on, every
         MLP inside the envelope (ops.gc_mlp_supported) and every message-passing MLP ending in its LayerNorm"""
-        layers = [self.encoder.edge_mlp.model, self.encoder.dst_node_mlp.model, self.decoder.edge_mlp.model,
-                  self.decoder.node_mlp.model]
-        for p in (self.processor_encoder, self.processor, self.processor_decoder):
-            for e, n in p.pairs():
-                layers += [e, n]
         return (self.hip_training and self.uses_hip_step()
-                and all(ops.mgn_parts(m)[1] is not None for m in layers))
+                and all(ops.mgn_parts(m)[1] is not None for pair in self._layer_mlps() for m in pair))
 
     def _packed(self, seq, split=None, perm=None) -> ops.GcMlpWeights:
         p = self._pk.get(id(seq))
@@ -260,181 +260,113 @@ class GraphCastNet(HipBackbone):
         d = seq[0].in_features // 3
         return self._packed(seq, split=(d, d, d))
 
-    # ---- HIP step --------------------------------------------------------------------------------------------------------
-    def _static_embeddings(self):
-        key = self._param_key()
-        if self._static is None or self._static[0] != key:
-            ee = self.encoder_embedder
-
-            def emb(seq, x):
-                return ops.gc_mlp(self._packed(seq), seq, 1, x.shape[0],
-                                  dict(a_mode=0, a=x, a_batch_stride=0, lda=x.shape[1]))
-
-            self._static = (key, dict(mesh_n=emb(ee.mesh_node_mlp.model, self.mesh_ndata),
-                                      mesh_e=emb(ee.mesh_edge_mlp.model, self.mesh_edata),
-                                      g2m_e=emb(ee.grid2mesh_edge_mlp.model, self.g2m_edata),
-                                      m2g_e=emb(self.decoder_embedder.mesh2grid_edge_mlp.model, self.m2g_edata)))
-        return self._static[1]
-
-    def _edge_mlp(self, seq, b, name, e, e_bs, xs, xs_bs, n_src, xd, xd_bs, n_dst, residual):
-        """e' = LN(mlp([e, x_src[src], x_dst[dst]])) (+ e): node products once per node, gathered in the epilogue"""
-        pk = self._edge_packed(seq)
-        d = seq[0].out_features
-        ps = ops.gc_node_products(pk, 1, xs, b if xs_bs else 1, n_src, xs_bs)
-        pd = ops.gc_node_products(pk, 2, xd, b if xd_bs else 1, n_dst, xd_bs)
-        src, dst = getattr(self, f"{name}_src"), getattr(self, f"{name}_dst")
-        n_e = src.numel()
-        first = dict(a_mode=0, a=e, a_batch_stride=e_bs, lda=e.shape[-1], wt=pk.first[0],
-                     src_products=ps, src_index=src, src_products_batch_stride=n_src * d if xs_bs else 0, ld_src_products=d,
-                     dst_products=pd, dst_index=dst, dst_products_batch_stride=n_dst * d if xd_bs else 0, ld_dst_products=d)
-        return ops.gc_mlp(pk, seq, b, n_e, first, res=e if residual else None, res_bs=e_bs)
-
-    def _node_mlp(self, seq, b, name, e_new, x, x_bs, n):
-        """x' = LN(mlp([agg e', x])) + x, the aggregate and the concat read in the A-operand load"""
-        d = x.shape[-1]
-        n_e = getattr(self, f"{name}_src").numel()
-        first = dict(a_mode=2, a=x, a_batch_stride=x_bs, lda=d, agg_e=e_new, agg_batch_stride=n_e * e_new.shape[-1],
-                     agg_width=e_new.shape[-1], row_ptr=getattr(self, f"{name}_row_ptr"),
-                     agg_mean=int(self.aggregation == "mean"))
-        return ops.gc_mlp(self._packed(seq), seq, b, n, first, res=x, res_bs=x_bs)
-
-    def _step_hip(self, x_t: torch.Tensor) -> torch.Tensor:
-        b = x_t.shape[0]
-        G, N = self.n_grid, self.n_mesh
-        st = self._static_embeddings()
-        gm = self.encoder_embedder.grid_node_mlp.model
-        x_t = x_t.contiguous()
-        grid = ops.gc_mlp(self._packed(gm, perm=self._from_ref_order), gm, b, G,
-                          dict(a_mode=1, a=x_t, a_batch_stride=gm[0].in_features * G))
-        d = grid.shape[-1]
-        enc = self.encoder
-        # grid -> mesh (mesh_graph_encoder.py): edge MLP without residual, dst node MLP + mesh_n, src node MLP + grid
-        e = self._edge_mlp(enc.edge_mlp.model, b, "g2m", st["g2m_e"], 0, grid, G * d, G, st["mesh_n"], 0, N, False)
-        mesh = self._node_mlp(enc.dst_node_mlp.model, b, "g2m", e, st["mesh_n"], 0, N)
-        grid = ops.gc_mlp(self._packed(enc.src_node_mlp.model), enc.src_node_mlp.model, b, G,
-                          dict(a_mode=0, a=grid, a_batch_stride=G * d, lda=d), res=grid, res_bs=G * d)
-        # processor: processor_encoder, processor, processor_decoder (its edge output is discarded)
-        e, e_bs = st["mesh_e"], 0
-        n_e = self.mesh_src.numel()
-        for p in (self.processor_encoder, self.processor, self.processor_decoder):
-            for em, nm in p.pairs():
-                e = self._edge_mlp(em, b, "mesh", e, e_bs, mesh, N * d, N, mesh, N * d, N, True)
-                e_bs = n_e * d
-                mesh = self._node_mlp(nm, b, "mesh", e, mesh, N * d, N)
-        # mesh -> grid (mesh_graph_decoder.py), then the norm-free finale, channels-first
-        dec = self.decoder
-        e = self._edge_mlp(dec.edge_mlp.model, b, "m2g", st["m2g_e"], 0, mesh, N * d, N, grid, G * d, G, False)
-        grid = self._node_mlp(dec.node_mlp.model, b, "m2g", e, grid, G * d, G)
-        y = ops.gc_mlp(self._packed(self.finale.model), self.finale.model, b, G,
-                       dict(a_mode=0, a=grid, a_batch_stride=G * d, lda=d), out_cf=True)
-        return y.view(b, self.prognostic_channels, self.height, self.width)
-
-    # ---- HIP training step ----------------------------------------------------------------------------------------------
-    def _graph_train(self, name: str, n_src: int, n_dst: int) -> dict:
+    def _graph(self, name: str) -> dict:
+        """graph `name` ("mesh", "g2m", "m2g") as the layers take it (training.gc_layer): row_ptr, src, dst, deg (CSC by
+        destination), src_row_ptr, src_perm (ops.mgn_source_csr), n_src, n_dst; rebuilt when the buffers are replaced
+        (.to(device))"""
         src = getattr(self, f"{name}_src")
-        g = self._train_graphs.get(name)
+        g = self._graphs.get(name)
         if g is None or g["src"] is not src:
+            n_src, n_dst = {"mesh": (self.n_mesh, self.n_mesh), "g2m": (self.n_grid, self.n_mesh),
+                            "m2g": (self.n_mesh, self.n_grid)}[name]
             src_row_ptr, src_perm = ops.mgn_source_csr(src, n_src)
-            g = self._train_graphs[name] = dict(row_ptr=getattr(self, f"{name}_row_ptr"), src=src,
-                                                dst=getattr(self, f"{name}_dst"), deg=getattr(self, f"{name}_deg"),
-                                                src_row_ptr=src_row_ptr, src_perm=src_perm, n_src=n_src, n_dst=n_dst)
+            g = self._graphs[name] = dict(row_ptr=getattr(self, f"{name}_row_ptr"), src=src, dst=getattr(self, f"{name}_dst"),
+                                          deg=getattr(self, f"{name}_deg"), src_row_ptr=src_row_ptr, src_perm=src_perm,
+                                          n_src=n_src, n_dst=n_dst)
         return g
 
-    def _static_embeddings_train(self):
-        """the four static embeddings through training.gc_mlp: one [rows, D] table each, shared by the batch"""
+    # ---- the step --------------------------------------------------------------------------------------------------------
+    def _step(self, x_t: torch.Tensor, mlp, layer, table) -> torch.Tensor:
+        """the step, on one of three sets of functions:
+        mlp(seq, x, batch, rows, mode=0, x_bs=None, residual=False, out_cf=False): one MLP in the layouts of
+            training.gc_mlp (mode 1: the grid embedder on the channels-first input, in the rollout's channel order);
+        layer(edge_seq, node_seq, graph name, batch, e, xs, xd, residual) -> (x', e'): one message-passing layer;
+        table(name): the static embedding `name` (_static_table), asked for where the step first reads it"""
+        b = x_t.shape[0]
+        G = self.n_grid
+        grid = mlp(self.encoder_embedder.grid_node_mlp.model, x_t.contiguous(), b, G, mode=1)
+        g2m, *processor, m2g = self._layer_mlps()
+        # grid -> mesh (mesh_graph_encoder.py): edge MLP without residual, dst node MLP + mesh_n, src node MLP + grid;
+        # an edge output no later layer reads is not bound, so it is freed as soon as its layer returns
+        mesh = layer(*g2m, "g2m", b, table("g2m_e"), grid, table("mesh_n"), False)[0]
+        grid = mlp(self.encoder.src_node_mlp.model, grid, b, G, residual=True)
+        # processor: processor_encoder, processor, processor_decoder (its edge output is discarded)
+        e = table("mesh_e")
+        for em, nm in processor:
+            mesh, e = layer(em, nm, "mesh", b, e, mesh, mesh, True)
+        # mesh -> grid (mesh_graph_decoder.py), then the norm-free finale, channels-first
+        grid = layer(*m2g, "m2g", b, table("m2g_e"), mesh, grid, False)[0]
+        y = mlp(self.finale.model, grid, b, G, out_cf=True)
+        return y.view(b, self.prognostic_channels, self.height, self.width)
+
+    def _static_table(self, mlp, name: str) -> torch.Tensor:
+        """one static embedding (mesh nodes, mesh / g2m / m2g edges): a [rows, D] table the batch shares"""
         ee = self.encoder_embedder
+        m, x = {"mesh_n": (ee.mesh_node_mlp, self.mesh_ndata), "mesh_e": (ee.mesh_edge_mlp, self.mesh_edata),
+                "g2m_e": (ee.grid2mesh_edge_mlp, self.g2m_edata),
+                "m2g_e": (self.decoder_embedder.mesh2grid_edge_mlp, self.m2g_edata)}[name]
+        return mlp(m.model, x, 1, x.shape[0], x_bs=0)
 
-        def emb(seq, x):
-            return training.gc_mlp(seq, self._packed(seq), x, 1, x.shape[0], x_bs=0)
+    def _static_tables(self, mlp) -> dict:
+        return {k: self._static_table(mlp, k) for k in ("mesh_n", "mesh_e", "g2m_e", "m2g_e")}
 
-        return dict(mesh_n=emb(ee.mesh_node_mlp.model, self.mesh_ndata), mesh_e=emb(ee.mesh_edge_mlp.model, self.mesh_edata),
-                    g2m_e=emb(ee.grid2mesh_edge_mlp.model, self.g2m_edata),
-                    m2g_e=emb(self.decoder_embedder.mesh2grid_edge_mlp.model, self.m2g_edata))
+    # HIP step: ops.gc_mlp / ops.gc_layer, the static embeddings once per weight version
+    def _hip_mlp(self, seq, x, batch, rows, mode=0, x_bs=None, residual=False, out_cf=False):
+        x_bs = x.numel() // batch if x_bs is None else x_bs
+        pk = self._packed(seq, perm=self._from_ref_order if mode == 1 else None)
+        return ops.gc_mlp(pk, seq, batch, rows, ops.gc_a_fields(mode, x, x_bs), res=x if residual else None,
+                          res_bs=x_bs if residual else 0, out_cf=out_cf)
 
-    def _layer_train(self, edge, node, name, b, e, xs, xd, n_src, n_dst, residual):
+    def _step_hip(self, x_t: torch.Tensor) -> torch.Tensor:
+        key = self._param_key()
+        if self._static is None or self._static[0] != key:
+            self._static = (key, self._static_tables(self._hip_mlp))
+        st = self._static[1]
+
+        def layer(edge, node, name, b, e, xs, xd, residual):
+            g = self._graph(name)
+            # batch strides: 0 for the static tables, which the batch shares (at B = 1 too)
+            bs = [0 if any(t is s for s in st.values()) else rows * t.shape[-1]
+                  for t, rows in ((e, g["src"].numel()), (xs, g["n_src"]), (xd, g["n_dst"]))]
+            return ops.gc_layer(self._edge_packed(edge), edge, self._packed(node), node, self.aggregation, g, b, e, xs, xd,
+                                bs, residual)
+
+        return self._step(x_t, self._hip_mlp, layer, st.__getitem__)
+
+    # HIP training step: training.gc_mlp / training.gc_layer, the static embeddings once per forward
+    def _train_mlp(self, seq, x, batch, rows, mode=0, x_bs=None, residual=False, out_cf=False):
+        perm, col_order = (self._from_ref_order, self._to_ref_order) if mode == 1 else (None, None)
+        return training.gc_mlp(seq, self._packed(seq, perm=perm), x, batch, rows, mode, x_bs, residual, out_cf, col_order)
+
+    def _train_layer(self, edge, node, name, b, e, xs, xd, residual):
         return training.gc_layer(edge, self._edge_packed(edge), node, self._packed(node), self.aggregation,
-                                 self._graph_train(name, n_src, n_dst), b, e, xs, xd, residual)
+                                 self._graph(name), b, e, xs, xd, residual)
 
     def _step_train(self, x_t: torch.Tensor) -> torch.Tensor:
-        """_step_hip with autograd: every MLP through training.gc_mlp / training.gc_layer"""
-        b = x_t.shape[0]
-        G, N = self.n_grid, self.n_mesh
-        st = self._static_train if self._static_train is not None else self._static_embeddings_train()
-        gm = self.encoder_embedder.grid_node_mlp.model
-        grid = training.gc_mlp(gm, self._packed(gm, perm=self._from_ref_order), x_t.contiguous(), b, G, mode=1,
-                               col_order=self._to_ref_order)
-        enc = self.encoder
-        mesh, _ = self._layer_train(enc.edge_mlp.model, enc.dst_node_mlp.model, "g2m", b, st["g2m_e"], grid, st["mesh_n"],
-                                    G, N, False)
-        sm = enc.src_node_mlp.model
-        grid = training.gc_mlp(sm, self._packed(sm), grid, b, G, residual=True)
-        e = st["mesh_e"]
-        for p in (self.processor_encoder, self.processor, self.processor_decoder):
-            for em, nm in p.pairs():
-                mesh, e = self._layer_train(em, nm, "mesh", b, e, mesh, mesh, N, N, True)
-        dec = self.decoder
-        grid, _ = self._layer_train(dec.edge_mlp.model, dec.node_mlp.model, "m2g", b, st["m2g_e"], mesh, grid, N, G, False)
-        fm = self.finale.model
-        y = training.gc_mlp(fm, self._packed(fm), grid, b, G, out_cf=True)
-        return y.view(b, self.prognostic_channels, self.height, self.width)
+        st = self._static_train if self._static_train is not None else self._static_tables(self._train_mlp)
+        return self._step(x_t, self._train_mlp, self._train_layer, st.__getitem__)
 
     def _forward_train(self, constants, prescribed, prognostic):
         """the static embeddings once per forward (their gradients accumulate over the rollout steps), then the rollout"""
         if not (prognostic.is_cuda and self.uses_hip_training()):
             return super()._forward_train(constants, prescribed, prognostic)
-        self._static_train = self._static_embeddings_train()
+        self._static_train = self._static_tables(self._train_mlp)
         try:
             return super()._forward_train(constants, prescribed, prognostic)
         finally:
             self._static_train = None
 
-    # ---- torch composition -----------------------------------------------------------------------------------------------
-    def _edge_torch(self, seq, b, name, e, xs, n_src, xd, n_dst):
-        src, dst = getattr(self, f"{name}_src").long(), getattr(self, f"{name}_dst").long()
-        ne = src.numel()
-        if e.shape[0] != b * ne:
-            e = e.repeat(b, 1)
-        off_s = (torch.arange(b, device=e.device) * n_src).repeat_interleave(ne) if xs.shape[0] == b * n_src else 0
-        off_d = (torch.arange(b, device=e.device) * n_dst).repeat_interleave(ne) if xd.shape[0] == b * n_dst else 0
-        return seq(torch.cat((e, xs[src.repeat(b) + off_s], xd[dst.repeat(b) + off_d]), dim=1))
+    # torch composition (autograd; outside the envelope): training.gc_mlp_torch / training.gc_layer_torch, concat-
+    # materialising like the reference, each static embedding every step where it is read (so autograd runs its
+    # backward as soon as its gradient is complete)
+    def _torch_mlp(self, seq, x, batch, rows, mode=0, x_bs=None, residual=False, out_cf=False):
+        return training.gc_mlp_torch(seq, x, batch, rows, mode, x_bs, residual, out_cf, self._to_ref_order)
 
-    def _node_torch(self, seq, b, name, e, x, n):
-        dst = getattr(self, f"{name}_dst").long()
-        ne = dst.numel()
-        t = dst.repeat(b) + (torch.arange(b, device=e.device) * n).repeat_interleave(ne)
-        agg = torch.zeros(b * n, e.shape[1], device=e.device, dtype=e.dtype).index_add(0, t, e)
-        if self.aggregation == "mean":
-            deg = getattr(self, f"{name}_deg").clamp(min=1).to(e.dtype).repeat(b).unsqueeze(1)
-            agg = agg / deg
-        if x.shape[0] != b * n:
-            x = x.repeat(b, 1)
-        return seq(torch.cat((agg, x), dim=1)) + x
+    def _torch_layer(self, edge, node, name, b, e, xs, xd, residual):
+        return training.gc_layer_torch(edge, node, self.aggregation, self._graph(name), b, e, xs, xd, residual)
 
     def _step_torch(self, x_t: torch.Tensor) -> torch.Tensor:
-        """the same step as a torch composition, concat-materialising like the reference (autograd; outside the envelope)"""
-        b = x_t.shape[0]
-        G, N = self.n_grid, self.n_mesh
-        ee = self.encoder_embedder
-        x = x_t[:, self._to_ref_order].reshape(b, -1, G).permute(0, 2, 1).reshape(b * G, -1)
-        grid = ee.grid_node_mlp(x)
-        mesh_n = ee.mesh_node_mlp(self.mesh_ndata)
-        g2m_e = ee.grid2mesh_edge_mlp(self.g2m_edata)
-        mesh_e = ee.mesh_edge_mlp(self.mesh_edata)
-        enc = self.encoder
-        e = self._edge_torch(enc.edge_mlp.model, b, "g2m", g2m_e, grid, G, mesh_n, N)
-        mesh = self._node_torch(enc.dst_node_mlp.model, b, "g2m", e, mesh_n, N)
-        grid = grid + enc.src_node_mlp(grid)
-        e = mesh_e
-        for p in (self.processor_encoder, self.processor, self.processor_decoder):
-            for em, nm in p.pairs():
-                e_new = self._edge_torch(em, b, "mesh", e, mesh, N, mesh, N)
-                e = e_new + (e if e.shape[0] == e_new.shape[0] else e.repeat(b, 1))
-                mesh = self._node_torch(nm, b, "mesh", e, mesh, N)
-        m2g_e = self.decoder_embedder.mesh2grid_edge_mlp(self.m2g_edata)
-        e = self._edge_torch(self.decoder.edge_mlp.model, b, "m2g", m2g_e, mesh, N, grid, G)
-        grid = self._node_torch(self.decoder.node_mlp.model, b, "m2g", e, grid, G)
-        y = self.finale(grid)
-        return y.view(b, self.height, self.width, -1).permute(0, 3, 1, 2)
+        return self._step(x_t, self._torch_mlp, self._torch_layer, lambda name: self._static_table(self._torch_mlp, name))
 
     # ---- rollout ---------------------------------------------------------------------------------------------------------
     def one_step(self, x_t: torch.Tensor) -> torch.Tensor:

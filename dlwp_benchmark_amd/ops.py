@@ -1547,38 +1547,56 @@ def gc_layernorm(x: torch.Tensor, batch: int, rows: int, ln: torch.nn.LayerNorm,
     return out
 
 
+def gc_a_fields(mode: int, x: torch.Tensor, x_bs: int) -> dict:
+    """the A fields of a first Linear reading x: mode 0 rows [rows, D] per sample (x_bs 0: one table for the batch),
+    mode 1 channels-first [B, C, rows...]"""
+    return dict(a_mode=mode, a=x, a_batch_stride=x_bs, lda=x.shape[-1] if mode == 0 else 0)
+
+
+def gc_agg_a_fields(x: torch.Tensor, x_bs: int, e_new: torch.Tensor, graph: dict, aggregation: str) -> dict:
+    """the A fields of a node MLP's first Linear reading [agg e', x] (mode 2): e' [batch * E, D] summed by destination
+    in CSC order (/ in-degree for mean), x [rows, D] per sample (x_bs 0: one table for the batch)"""
+    d = e_new.shape[-1]
+    return dict(a_mode=2, a=x, a_batch_stride=x_bs, lda=x.shape[-1], agg_e=e_new, agg_batch_stride=graph["src"].numel() * d,
+                agg_width=d, row_ptr=graph["row_ptr"], agg_mean=int(aggregation == "mean"))
+
+
 def gc_mlp(pk: GcMlpWeights, seq: torch.nn.Sequential, batch: int, rows: int, first: dict, res: Optional[torch.Tensor] = None,
-           res_bs: int = 0, out_cf: bool = False) -> torch.Tensor:
+           res_bs: int = 0, out_cf: bool = False, save: bool = False):
     """One MeshGraphMLP over batch * rows rows on dlwp_gc_linear_f32 / dlwp_gc_layernorm_f32.  `first`: the A operand (and
     gathered products) of the first Linear as dlwp_gc_linear_args fields; its weight is `first["wt"]` if given, else the
     whole transposed first weight.  Then act -> Linears -> [LayerNorm] [+ res].  Returns [batch * rows, D_out], or
-    channels-first [batch, D_out, rows] when out_cf (no norm)."""
+    channels-first [batch, D_out, rows] when out_cf (no norm).
+    save (training): every Linear writes its pre-activation z_i (the next one applies act on its A load, so act(z_i)
+    never exists) and the LayerNorm writes a fresh tensor, so its input survives.  Returns (output, [z_0 .. z_last])."""
     w = pk.get(seq)
     lins, ln = mgn_parts(seq)
     act = GC_ACT[type(seq[1])]
     dev = w.wt[0].device
-    cur = None
+    cur, zs = None, []
     for i, l in enumerate(lins):
         last = i + 1 == len(lins)
         n = l.out_features
-        if last and out_cf:
-            out = torch.empty(batch, n, rows, device=dev, dtype=torch.float32)
-        else:
-            out = torch.empty(batch * rows, n, device=dev, dtype=torch.float32)
-        kw = dict(wt=w.wt[i], bias=l.bias, k=l.in_features, n=n, batch=batch, rows=rows, act=0 if last else act, out=out,
-                  out_layout=int(last and out_cf), ldo=n)
+        cf = last and out_cf
+        out = torch.empty((batch, n, rows) if cf else (batch * rows, n), device=dev, dtype=torch.float32)
+        kw = dict(wt=w.wt[i], bias=l.bias, k=l.in_features, n=n, batch=batch, rows=rows, act=0 if last or save else act,
+                  out=out, out_layout=int(cf), ldo=n)
         if i == 0:
             kw.update(first)
             kw["k"] = kw["wt"].shape[0]     # the e-part of a split edge Linear
         else:
             kw.update(a_mode=0, a=cur, a_batch_stride=rows * l.in_features, lda=l.in_features)
+            if save:
+                kw["a_act"] = act
         if last and ln is None and res is not None:
             kw.update(res=res, res_batch_stride=res_bs)
         gc_linear(_gc_args(**kw))
         cur = out
+        if save:
+            zs.append(out)
     if ln is not None:
-        gc_layernorm(cur, batch, rows, ln, res, res_bs)
-    return cur
+        cur = gc_layernorm(cur, batch, rows, ln, res, res_bs, out=torch.empty_like(cur) if save else None)
+    return (cur, zs) if save else cur
 
 
 def gc_node_products(pk: GcMlpWeights, part: int, x: torch.Tensor, batch: int, rows: int, x_bs: int) -> torch.Tensor:
@@ -1591,39 +1609,32 @@ def gc_node_products(pk: GcMlpWeights, part: int, x: torch.Tensor, batch: int, r
     return out
 
 
+def gc_layer(edge_pk: GcMlpWeights, edge_seq: torch.nn.Sequential, node_pk: GcMlpWeights, node_seq: torch.nn.Sequential,
+             aggregation: str, graph: dict, batch: int, e: torch.Tensor, xs: torch.Tensor, xd: torch.Tensor, bs,
+             residual: bool, save: bool = False):
+    """One message-passing layer: e' = LN(mlp([e, xs[src], xd[dst]])) (+ e) with the node products W_s xs, W_d xd
+    computed once per node and gathered in the first Linear's epilogue, then x' = LN(mlp([agg e', xd])) + xd with the
+    aggregate and the concat read in the A-operand load.  bs: the batch strides of e, xs, xd (0: one [rows, D] table the
+    batch shares).  graph: as training.gc_layer takes it.  Returns (x', e'), and with save also the pre-activations of
+    the edge and the node MLP (gc_mlp)."""
+    e_bs, xs_bs, xd_bs = bs
+    n_src, n_dst, ne = graph["n_src"], graph["n_dst"], graph["src"].numel()
+    pk = edge_pk.get(edge_seq)
+    d = edge_seq[0].out_features
+    first = dict(a_mode=0, a=e, a_batch_stride=e_bs, lda=e.shape[-1], wt=pk.first[0],
+                 src_products=gc_node_products(pk, 1, xs, batch if xs_bs else 1, n_src, xs_bs), src_index=graph["src"],
+                 src_products_batch_stride=n_src * d if xs_bs else 0, ld_src_products=d,
+                 dst_products=gc_node_products(pk, 2, xd, batch if xd_bs else 1, n_dst, xd_bs), dst_index=graph["dst"],
+                 dst_products_batch_stride=n_dst * d if xd_bs else 0, ld_dst_products=d)
+    edge = gc_mlp(pk, edge_seq, batch, ne, first, res=e if residual else None, res_bs=e_bs, save=save)
+    del first                               # the node products
+    e_new = edge[0] if save else edge
+    node = gc_mlp(node_pk, node_seq, batch, n_dst, gc_agg_a_fields(xd, xd_bs, e_new, graph, aggregation), res=xd,
+                  res_bs=xd_bs, save=save)
+    return (node[0], e_new, edge[1], node[1]) if save else (node, e_new)
+
+
 # ---- GraphCastNet backward (training.gc_mlp / training.gc_layer; csrc/graphcast_bwd.hip) ----------------------------------
-def gc_mlp_train(pk: GcMlpWeights, seq: torch.nn.Sequential, batch: int, rows: int, first: dict,
-                 res: Optional[torch.Tensor] = None, res_bs: int = 0, out_cf: bool = False):
-    """gc_mlp for training: every Linear writes its pre-activation z_i (the next one applies act on its A load, so act(z_i)
-    never exists) and the LayerNorm writes a fresh tensor, so its input survives.  Returns (output, [z_0 .. z_last])."""
-    w = pk.get(seq)
-    lins, ln = mgn_parts(seq)
-    act = GC_ACT[type(seq[1])]
-    dev = w.wt[0].device
-    zs = []
-    for i, l in enumerate(lins):
-        last = i + 1 == len(lins)
-        n = l.out_features
-        cf = last and out_cf
-        out = torch.empty((batch, n, rows) if cf else (batch * rows, n), device=dev, dtype=torch.float32)
-        kw = dict(wt=w.wt[i], bias=l.bias, k=l.in_features, n=n, batch=batch, rows=rows, act=0, out=out,
-                  out_layout=int(cf), ldo=n)
-        if i == 0:
-            kw.update(first)
-            kw["k"] = kw["wt"].shape[0]
-        else:
-            kw.update(a_mode=0, a=zs[-1], a_batch_stride=rows * l.in_features, lda=l.in_features, a_act=act)
-        if last and ln is None and res is not None:
-            kw.update(res=res, res_batch_stride=res_bs)
-        gc_linear(_gc_args(**kw))
-        zs.append(out)
-    if ln is None:
-        return zs[-1], zs
-    y = torch.empty_like(zs[-1])
-    gc_layernorm(zs[-1], batch, rows, ln, res, res_bs, out=y)
-    return y, zs
-
-
 def gc_weight_grad(a_fields: dict, k: int, n: int, batch: int, rows: int, dz: torch.Tensor, dz_cf: bool = False,
                    dw: Optional[torch.Tensor] = None, db: Optional[torch.Tensor] = None, bias: bool = True):
     """dlwp_gc_weight_grad_f32: (dW [n, k] = A^T dZ in torch's layout, db = column sums of dZ or None).  a_fields: the A

@@ -720,12 +720,6 @@ def mgn_layer(edge_seq, edge_packed, node_seq, node_packed, aggregation: str, gr
 
 
 # ---- GraphCastNet (models/graphcast.py; csrc/graphcast.hip forward, csrc/graphcast_bwd.hip backward) --------------------
-def _gc_first(mode: int, x: torch.Tensor, x_bs: int) -> dict:
-    """the A fields of a first Linear reading x: mode 0 rows [rows, D] per sample (x_bs 0: one table for the batch),
-    mode 1 channels-first [B, C, rows...]"""
-    return dict(a_mode=mode, a=x, a_batch_stride=x_bs, lda=x.shape[-1] if mode == 0 else 0)
-
-
 def _gc_tail_backward(seq, batch: int, rows: int, zs, gy, out_cf: bool, ln_gather: Optional[dict] = None,
                       want_total: bool = False):
     """the backward of a MeshGraphMLP above its first Linear from the saved pre-activations zs: (dZ_0 [batch * rows, H],
@@ -761,15 +755,17 @@ def _gc_batch_sum(t: torch.Tensor, batch: int) -> torch.Tensor:
     return ops.gc_segment_sum(t, batch, None, None, t.shape[0] // batch, batch_sum=True)
 
 
-def gc_mlp_torch(seq, x, batch: int, rows: int, mode: int, x_bs: int, residual: bool, out_cf: bool, col_order=None):
-    """torch composition of one GraphCast MLP in the layouts of gc_mlp (DLWP_TRAIN_TORCH_BACKWARD=1, tests)"""
+def gc_mlp_torch(seq, x, batch: int, rows: int, mode: int = 0, x_bs: Optional[int] = None, residual: bool = False,
+                 out_cf: bool = False, col_order=None):
+    """torch composition of one GraphCast MLP in the layouts of gc_mlp (GraphCastNet's composition,
+    DLWP_TRAIN_TORCH_BACKWARD=1, tests)"""
     if mode == 1:
         a = x.reshape(batch, -1, rows)
         if col_order is not None:
             a = a[:, col_order]
         a = a.permute(0, 2, 1).reshape(batch * rows, -1)
     else:
-        a = x if x_bs else x.repeat(batch, 1)
+        a = x.repeat(batch, 1) if x_bs == 0 and batch > 1 else x
     y = seq(a)
     if residual:
         y = y + a
@@ -790,8 +786,8 @@ class _GcMlpFn(torch.autograd.Function):
         seq, pk, batch, rows, mode, x_bs, residual, out_cf, col_order = cfg
         with torch.no_grad():
             xd = x.detach()
-            y, zs = ops.gc_mlp_train(pk, seq, batch, rows, _gc_first(mode, xd, x_bs), res=xd if residual else None,
-                                     res_bs=x_bs, out_cf=out_cf)
+            y, zs = ops.gc_mlp(pk, seq, batch, rows, ops.gc_a_fields(mode, xd, x_bs), res=xd if residual else None,
+                               res_bs=x_bs, out_cf=out_cf, save=True)
         ctx.save_for_backward(x, *zs, *params)    # the parameters too: autograd's version check sees in-place edits
         ctx.cfg, ctx.n_z = cfg, len(zs)
         return y
@@ -815,7 +811,7 @@ class _GcMlpFn(torch.autograd.Function):
         lins, _ = ops.mgn_parts(seq)
         g0, _, grads = _gc_tail_backward(seq, batch, rows, zs, gy, out_cf)
         l0 = lins[0]
-        dw, grads[1] = ops.gc_weight_grad(_gc_first(mode, x, x_bs), l0.in_features, l0.out_features, batch, rows, g0)
+        dw, grads[1] = ops.gc_weight_grad(ops.gc_a_fields(mode, x, x_bs), l0.in_features, l0.out_features, batch, rows, g0)
         grads[0] = dw[:, col_order] if col_order is not None else dw
         gx = None
         if need_x:
@@ -870,29 +866,14 @@ class _GcLayerFn(torch.autograd.Function):
         from . import ops
 
         edge_seq, epk, node_seq, npk, aggregation, graph, batch, residual = cfg
-        n_src, n_dst, ne = graph["n_src"], graph["n_dst"], graph["src"].numel()
-        d = edge_seq[0].out_features
-        e_bs = ne * e.shape[-1] if e.shape[0] == batch * ne else 0
-        xs_bs = n_src * xs.shape[-1] if xs.shape[0] == batch * n_src else 0
-        xd_bs = n_dst * xd.shape[-1] if xd.shape[0] == batch * n_dst else 0
+        # batch strides: 0 for one [rows, D] table the batch shares (at batch 1 every operand counts as per sample)
+        bs = tuple(rows * t.shape[-1] if t.shape[0] == batch * rows else 0
+                   for t, rows in ((e, graph["src"].numel()), (xs, graph["n_src"]), (xd, graph["n_dst"])))
         with torch.no_grad():
-            e_, xs_, xd_ = e.detach(), xs.detach(), xd.detach()
-            pk = epk.get(edge_seq)
-            ps = ops.gc_node_products(pk, 1, xs_, batch if xs_bs else 1, n_src, xs_bs)
-            pd = ops.gc_node_products(pk, 2, xd_, batch if xd_bs else 1, n_dst, xd_bs)
-            first = dict(a_mode=0, a=e_, a_batch_stride=e_bs, lda=e.shape[-1], wt=pk.first[0],
-                         src_products=ps, src_index=graph["src"], src_products_batch_stride=n_src * d if xs_bs else 0,
-                         ld_src_products=d, dst_products=pd, dst_index=graph["dst"],
-                         dst_products_batch_stride=n_dst * d if xd_bs else 0, ld_dst_products=d)
-            e_new, ze = ops.gc_mlp_train(epk, edge_seq, batch, ne, first, res=e_ if residual else None, res_bs=e_bs)
-            del ps, pd
-            nfirst = dict(a_mode=2, a=xd_, a_batch_stride=xd_bs, lda=xd.shape[-1], agg_e=e_new,
-                          agg_batch_stride=ne * e_new.shape[-1], agg_width=e_new.shape[-1], row_ptr=graph["row_ptr"],
-                          agg_mean=int(aggregation == "mean"))
-            x_new, zn = ops.gc_mlp_train(npk, node_seq, batch, n_dst, nfirst, res=xd_, res_bs=xd_bs)
+            x_new, e_new, ze, zn = ops.gc_layer(epk, edge_seq, npk, node_seq, aggregation, graph, batch, e.detach(),
+                                                xs.detach(), xd.detach(), bs, residual, save=True)
         ctx.save_for_backward(e, xs, xd, e_new, *ze, *zn, *params)   # the parameters: in-place edits raise
-        ctx.cfg, ctx.n_ze, ctx.n_zn = cfg, len(ze), len(zn)
-        ctx.bs = (e_bs, xs_bs, xd_bs)
+        ctx.cfg, ctx.n_ze, ctx.n_zn, ctx.bs = cfg, len(ze), len(zn), bs
         ctx.set_materialize_grads(False)
         return x_new, e_new
 
@@ -926,10 +907,8 @@ class _GcLayerFn(torch.autograd.Function):
         # node MLP: x' = LN(mlp([agg e', x])) + x
         gu, _, gn = _gc_tail_backward(node_seq, batch, n_dst, zn, gx_out, False)
         nl0 = ops.mgn_parts(node_seq)[0][0]
-        gn[0], gn[1] = ops.gc_weight_grad(
-            dict(a_mode=2, a=xd, a_batch_stride=xd_bs, lda=xd.shape[-1], agg_e=e_new, agg_batch_stride=ne * d, agg_width=d,
-                 row_ptr=graph["row_ptr"], agg_mean=int(aggregation == "mean")),
-            nl0.in_features, nl0.out_features, batch, n_dst, gu)
+        gn[0], gn[1] = ops.gc_weight_grad(ops.gc_agg_a_fields(xd, xd_bs, e_new, graph, aggregation), nl0.in_features,
+                                          nl0.out_features, batch, n_dst, gu)
         v_agg, v_x = npk.backward_first(node_seq, (d, nl0.in_features - d))
         g_agg = ops.gc_data_grad(gu, v_agg, batch, n_dst)
         gxd = ops.gc_data_grad(gu, v_x, batch, n_dst, res=gx_out, res_bs=n_dst * xd.shape[-1])
@@ -943,13 +922,13 @@ class _GcLayerFn(torch.autograd.Function):
         h, de = el0.out_features, e.shape[-1]
         w_e, w_s, w_d = epk.backward_first(edge_seq)
         dw0 = torch.empty(h, el0.in_features, device=e.device, dtype=torch.float32)
-        _, gedge[1] = ops.gc_weight_grad(_gc_first(0, e, e_bs), de, h, batch, ne, gz, dw=dw0[:, :de])
+        _, gedge[1] = ops.gc_weight_grad(ops.gc_a_fields(0, e, e_bs), de, h, batch, ne, gz, dw=dw0[:, :de])
         gps = ops.gc_segment_sum(gz, batch, graph["src_row_ptr"], graph["src_perm"], n_src, batch_sum=not xs_bs)
         gpd = ops.gc_segment_sum(gz, batch, graph["row_ptr"], None, n_dst, batch_sum=not xd_bs)
         bs_s, bs_d = (batch if xs_bs else 1), (batch if xd_bs else 1)
         ds = xs.shape[-1]
-        ops.gc_weight_grad(_gc_first(0, xs, xs_bs), ds, h, bs_s, n_src, gps, dw=dw0[:, de:de + ds], bias=False)
-        ops.gc_weight_grad(_gc_first(0, xd, xd_bs), xd.shape[-1], h, bs_d, n_dst, gpd, dw=dw0[:, de + ds:], bias=False)
+        ops.gc_weight_grad(ops.gc_a_fields(0, xs, xs_bs), ds, h, bs_s, n_src, gps, dw=dw0[:, de:de + ds], bias=False)
+        ops.gc_weight_grad(ops.gc_a_fields(0, xd, xd_bs), xd.shape[-1], h, bs_d, n_dst, gpd, dw=dw0[:, de + ds:], bias=False)
         gedge[0] = dw0
         gxs = ops.gc_data_grad(gps, w_s, bs_s, n_src) if ctx.needs_input_grad[1] else None
         gxd_out = None

@@ -179,6 +179,11 @@ SIGNATURES = {
                                                c_int32, c_int32, c_int32, c_void_p]),
     "dlwp_weighted_error_sums_acc_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                                    c_int32, c_int32, c_int32, c_void_p]),
+    "dlwp_zonal_power_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "dlwp_zonal_power_sums_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                            c_int32, c_void_p, c_size_t, c_void_p]),
+    "dlwp_zonal_power_sums_acc_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                                c_int32, c_void_p, c_size_t, c_void_p]),
     "dlwp_spectral_conv2d_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_size_t, c_void_p]),
     "dlwp_global_attn_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "dlwp_global_attn_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_size_t,

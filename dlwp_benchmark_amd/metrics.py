@@ -6,6 +6,9 @@ scripts/evaluate.py:786-821 computes with xarray after copying every trajectory 
 per-variable de-normalisation of evaluate.py:281-296 folded in as a scale (the means cancel).
 Multi-GPU: the [4, K, C] double sums are all-reduced (a few hundred bytes) instead of gathering
 trajectories.
+
+`ZonalSpectrumMetrics` reduces the same tensors to zonal energy spectra and the mean energy log ratio (MELR) of
+reference scripts/losses.py:16-152, the spectral-blurring score scripts/train.py:434-445 takes of validation rollouts.
 """
 import math
 from typing import Optional
@@ -90,3 +93,107 @@ class RolloutMetrics:
         rmse = torch.sqrt(s[0] / count)
         acc = s[1] / torch.sqrt(s[2] * s[3]) if self.clim is not None else None
         return {"rmse": rmse, "acc": acc}
+
+
+EARTH_RADIUS_M = 1000 * (6357 + 6378) / 2   # reference scripts/losses.py:13
+MELR_EPS = 1e-10                            # losses.py:117, absolute
+
+
+def circumference_weights(lats_deg: torch.Tensor) -> torch.Tensor:
+    """cos(lat_h) * 2 pi R in float64: the length of each circle of latitude (losses.py:20-23)."""
+    return torch.cos(lats_deg.double() * (math.pi / 180)) * (2 * math.pi * EARTH_RADIUS_M)
+
+
+class ZonalSpectrumMetrics:
+    """Zonal energy spectra of a rollout [B, K, C, H, W] and its targets, and their mean energy log ratio (reference
+    scripts/losses.py:16-152, `ZonalSpectrum` + `MELRCalculator`), reduced on the device (dlwp_zonal_power_sums_f32).
+
+    E[k, c, m] = mean over samples b and latitudes h of circ_h P[b, k, c, h, m], P = |rfft(norm="forward")|^2 along the
+    W longitudes with every m > 0 doubled; log_ratio = ln((E_pred + 1e-10) / (E_true + 1e-10)); MELR = its mean over
+    m = 0 .. W/2.  The reference places its latitudes at np.linspace(-90, 90, H) (losses.py:88): pass
+    `torch.linspace(-90, 90, H)` as `lats_deg` to reproduce scripts/train.py:434-445, or the grid's own cell centres.
+    Fields are scored as given (the reference scores normalised fields).  W must be a power of two from 32 to 512;
+    HEALPix [B, K, F, C, H, W] rollouts are not remapped to lat-lon and are refused."""
+
+    def __init__(self, lats_deg: torch.Tensor, group=None):
+        self.circ = circumference_weights(torch.as_tensor(lats_deg))
+        self.height = int(self.circ.numel())
+        self.group = group
+        self._dev = {}   # device -> circumference weights on it
+        self._ws = {}    # device -> workspaces, the last one the largest and the one in use
+
+    def _on(self, dev):
+        key = str(dev)
+        if key not in self._dev:
+            self._dev[key] = self.circ.to(dev).contiguous()
+        return self._dev[key]
+
+    def _workspace(self, dev, shape):
+        """One workspace per device, shared by every shape: a shape that needs more replaces it by one at least twice as large.
+        The replaced ones stay allocated because a recorded step (sharding.CapturedStep) keeps the address it was recorded
+        with; with the doubling they add up to less than the one in use."""
+        n = max(int(_lib.load().dlwp_zonal_power_workspace_bytes(*shape)), 8)
+        bufs = self._ws.setdefault(str(dev), [])
+        if not bufs or bufs[-1].numel() < n:
+            bufs.append(torch.empty(max(n, 2 * bufs[-1].numel()) if bufs else n, dtype=torch.uint8, device=dev))
+        return bufs[-1]
+
+    def sums(self, out: torch.Tensor, target: torch.Tensor, into: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """double [2, K, C, W//2 + 1]: 0 = sum over this rank's samples and latitudes of circ_h P(out), 1 = of P(target)
+        (dlwp_zonal_power_sums_f32).  `into`: a [2, K, C, W//2 + 1] double tensor of running sums the new ones are ADDED to
+        (dlwp_zonal_power_sums_acc_f32); it is returned."""
+        _lib.require_cuda_tensor(out, "out")
+        _lib.require_cuda_tensor(target, "target")
+        if out.dim() != 5:
+            raise _lib.DlwpError(f"zonal spectrum: expected a lat-lon rollout [B, K, C, H, W], got {out.dim()}-D shape "
+                                 f"{tuple(out.shape)} (HEALPix rollouts are not remapped to lat-lon)")
+        if target.shape != out.shape:
+            raise _lib.DlwpError(f"target shape {tuple(target.shape)} != output shape {tuple(out.shape)}")
+        if target.device != out.device:
+            raise _lib.DlwpError(f"target is on {target.device}, output on {out.device}: both must be on one device")
+        b, k, c, h, w = out.shape
+        if h != self.height:
+            raise _lib.DlwpError(f"zonal spectrum: {h} latitudes in the rollout, {self.height} given to the metric")
+        out, target = out.contiguous(), target.contiguous()
+        dev = out.device
+        nb = w // 2 + 1
+        if into is not None:
+            if not isinstance(into, torch.Tensor) or not into.is_cuda:
+                raise _lib.DlwpError("running sums must be a tensor on an MI355X device")
+            if tuple(into.shape) != (2, k, c, nb) or into.dtype != torch.float64 or not into.is_contiguous() or into.device != dev:
+                raise _lib.DlwpError(f"running sums must be a contiguous double [2, {k}, {c}, {nb}] tensor on {dev}")
+        circ = self._on(dev)
+        ws = self._workspace(dev, (b, k, c, h, w))
+        sums = into if into is not None else torch.empty(2, k, c, nb, dtype=torch.float64, device=dev)
+        lib = _lib.load()
+        fn = lib.dlwp_zonal_power_sums_acc_f32 if into is not None else lib.dlwp_zonal_power_sums_f32
+        with torch.cuda.device(dev):
+            _lib.check(fn(out.data_ptr(), target.data_ptr(), circ.data_ptr(), sums.data_ptr(), b, k, c, h, w, ws.data_ptr(),
+                          ws.numel(), _lib.stream_ptr()), "dlwp_zonal_power_sums_f32")
+        return sums
+
+    def __call__(self, out: torch.Tensor, target: torch.Tensor, world_size: int = 1):
+        """Energies, log ratio and MELR over ALL ranks' samples (see finalize)."""
+        return self.finalize(self.sums(out, target), float(out.shape[0]), world_size)
+
+    def finalize(self, s: torch.Tensor, n_samples: float, world_size: int = 1):
+        """Scores from accumulated sums: `s` = this rank's [2, K, C, W//2 + 1] sums (of one batch or added up over many),
+        n_samples = how many samples went into them.  With world_size > 1 ONE all-reduce moves the sums and the sample
+        count (shards may differ in size).  Returns {"energy_pred", "energy_true", "log_ratio": [K, C, W//2 + 1],
+        "melr": [K, C]} in float64."""
+        if world_size > 1:
+            import torch.distributed as dist
+
+            host = dist.get_backend(self.group) != "nccl"
+            dev = s.device
+            buf = torch.empty(s.numel() + 1, dtype=torch.float64, device=dev)
+            buf[:-1].copy_(s.flatten())
+            buf[-1:].fill_(n_samples)   # the count travels with the sums
+            if host:
+                buf = buf.cpu()
+            dist.all_reduce(buf, group=self.group)
+            buf = buf.to(dev)
+            s, n_samples = buf[:-1].view_as(s), buf[-1:]
+        energy = s / (n_samples * self.height)
+        log_ratio = torch.log((energy[0] + MELR_EPS) / (energy[1] + MELR_EPS))
+        return {"energy_pred": energy[0], "energy_true": energy[1], "log_ratio": log_ratio, "melr": log_ratio.mean(dim=-1)}

@@ -603,6 +603,26 @@ int32_t dlwp_weighted_error_sums_acc_f32(const float* out_dev, const float* targ
                                          int32_t batch, int32_t steps, int32_t channels, int32_t height, int32_t width,
                                          void* stream);
 
+/* On-device zonal energy spectrum sums (reference scripts/losses.py:16-152 `ZonalSpectrum` / `MELRCalculator`):
+ * out_dev, target_dev [B, K, C, H, W] fp32, contiguous, 16-byte aligned; circumference_dev double [H] (circ_h =
+ * cos(lat_h) 2 pi R, losses.py:20-23).  For every row, F = rfft(norm='forward') over W and P[m] = |F[m]|^2 (doubled for
+ * m > 0, the Nyquist bin included; losses.py:39-43).  sums_dev: double [2, K, C, W/2 + 1], written by the call:
+ *   0: sum_{b,h} circ_h P_out,  1: the same for target.
+ * E = sums / (B_total H) (losses.py:107-108); log ratio ln((E_0 + 1e-10) / (E_1 + 1e-10)) and its mean over m (MELR,
+ * :117-121) are left to the caller.  W a power of two from 32 to 512 (else DLWP_ERR_UNSUPPORTED), any H, K C <= 65535.
+ * fp32 transforms, fp64 weights and sums; fixed-order reduction through the workspace (no atomics: bitwise reproducible),
+ * two launches on `stream`, no host synchronisation.
+ *   dlwp_zonal_power_workspace_bytes: the per-workgroup partials (0 for an unsupported shape); a smaller workspace
+ *   returns DLWP_ERR_WORKSPACE. */
+size_t dlwp_zonal_power_workspace_bytes(int32_t batch, int32_t steps, int32_t channels, int32_t height, int32_t width);
+int32_t dlwp_zonal_power_sums_f32(const float* out_dev, const float* target_dev, const double* circumference_dev,
+                                  double* sums_dev, int32_t batch, int32_t steps, int32_t channels, int32_t height,
+                                  int32_t width, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* The same sums ADDED to the contents of sums_dev (running sums over the batches of an evaluation). */
+int32_t dlwp_zonal_power_sums_acc_f32(const float* out_dev, const float* target_dev, const double* circumference_dev,
+                                      double* sums_dev, int32_t batch, int32_t steps, int32_t channels, int32_t height,
+                                      int32_t width, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Global multi-head self-attention of the diffusion U-Net's AttentionBlock (reference
  * models/diffusion_models/modern_unet/modern_unet.py:565-571: einsum -> softmax(dim=1) -> einsum, between the `projection`
  * and `output` Linears), fp32-accurate (v_mfma_f32_16x16x4_f32), with no N x N tensor anywhere.

@@ -3391,6 +3391,17 @@ struct dlwp_spectral_plan {
   SpectralCore sc;
   DevBuf wt, zero_bias;
   std::unique_ptr<sany::Geom> gen;   // shapes outside the 32-channel kernels' domain (spectral_any.hip); wt is its image
+  // The weight gradient has the generic form only.  A plan of the specialised kernels keeps its own description and
+  // builds a Geom from it on the first weight-gradient call (wgen); a generic plan uses gen.  One thread per plan.
+  int H = 0, W = 0, n_cols = 0;
+  float fwd_scale = 1.f, inv_scale = 1.f;
+  std::vector<int32_t> rows_in, rows_out;
+  mutable std::unique_ptr<sany::Geom> wgen;
+  void describe(int H_, int W_, int nr, int nc, const int32_t* ri, const int32_t* ro, float fwd, float inv) {
+    H = H_; W = W_; n_cols = nc; fwd_scale = fwd; inv_scale = inv;
+    rows_in.assign(ri, ri + nr);
+    rows_out.assign(ro, ro + nr);
+  }
 };
 
 // The 32-channel kernels' domain; every other shape gets a width-generic plan.
@@ -3447,6 +3458,7 @@ extern "C" int32_t dlwp_spectral_conv2d_plan_create(dlwp_spectral_plan** out, in
   for (int r = 0; r < m1; ++r) { rows[r] = r; rows[m1 + r] = H - m1 + r; }
   int32_t rc = p->sc.build(H, W, 2 * m1, m2, rows.data(), rows.data(), 1.0f, 1.0f / ((float)H * (float)W), s);
   if (rc != DLWP_OK) { delete p; return rc; }
+  p->describe(H, W, 2 * m1, m2, rows.data(), rows.data(), 1.0f, 1.0f / ((float)H * (float)W));
   std::vector<float> w((size_t)m2 * 2 * m1 * ci * co * 2, 0.f);
   pack_spectral(w, w1, ci, co, m1, m2, 2 * m1, 0);
   pack_spectral(w, w2, ci, co, m1, m2, 2 * m1, m1);
@@ -3479,6 +3491,7 @@ extern "C" int32_t dlwp_spectral_conv2d_plan_create_ex(dlwp_spectral_plan** out,
   p->ci = ci; p->co = co;
   int32_t rc = p->sc.build(H, W, n_rows, n_cols, rows_in, rows_out, fwd_scale, inv_scale, s);
   if (rc != DLWP_OK) { delete p; return rc; }
+  p->describe(H, W, n_rows, n_cols, rows_in, rows_out, fwd_scale, inv_scale);
   std::vector<float> zb(kC, 0.f);
   hipError_t e = p->wt.alloc((size_t)n_cols * n_rows * ci * co * 2 * sizeof(float));
   if (e == hipSuccess) e = hipMemsetAsync(p->wt.p, 0, p->wt.bytes, s);
@@ -3547,4 +3560,49 @@ extern "C" int32_t dlwp_spectral_conv2d_f32(const dlwp_spectral_plan* plan, cons
   lp.B = batch; lp.H = sc.H; lp.W = sc.W;
   lp.stagger = 0;
   return launch_layer<false, false, false>(sc, lp, s);
+}
+
+// Weight gradient (spectral_any.hip): the Geom it runs on, built on first use.  The build uploads tables and
+// synchronises `s`, so the first call of a plan must not be inside a stream capture.
+static int32_t spectral_wgrad_geom(const dlwp_spectral_plan* plan, hipStream_t s, sany::Geom** out) {
+  sany::Geom* g = plan->gen.get();
+  if (!g) {
+    if (!plan->wgen) {
+      std::unique_ptr<sany::Geom> w(new sany::Geom());
+      const int32_t rc = sany::geom_build(*w, plan->ci, plan->co, plan->H, plan->W, (int)plan->rows_in.size(), plan->n_cols,
+                                          plan->rows_in.data(), plan->rows_out.data(), plan->fwd_scale, plan->inv_scale, s);
+      if (rc != DLWP_OK) return rc;
+      plan->wgen = std::move(w);
+    }
+    g = plan->wgen.get();
+  }
+  const int32_t rc = sany::wgrad_prepare(*g, s);
+  if (rc != DLWP_OK) return rc;
+  *out = g;
+  return DLWP_OK;
+}
+
+extern "C" size_t dlwp_spectral_conv2d_wgrad_workspace_bytes(const dlwp_spectral_plan* plan, int32_t batch) {
+  if (!plan || batch <= 0) return 0;
+  // shape arithmetic only: the same for gen and for the Geom a specialised plan would build
+  const size_t nm = plan->gen ? (size_t)plan->gen->nr * plan->gen->nc : plan->rows_in.size() * (size_t)plan->n_cols;
+  return align_up(nm * batch * plan->ci * sizeof(float2), 256) + align_up(nm * batch * plan->co * sizeof(float2), 256) +
+         align_up(nm * plan->ci * plan->co * sizeof(float2), 256);
+}
+
+extern "C" int32_t dlwp_spectral_conv2d_wgrad_f32(const dlwp_spectral_plan* plan, const float* x, const float* grad_y,
+                                                  float* grad_w, int32_t batch, void* workspace, size_t workspace_bytes,
+                                                  void* stream) {
+  DLWP_REQUIRE(plan && x && grad_y && grad_w && workspace, DLWP_ERR_INVALID_ARGUMENT, "null argument");
+  DLWP_REQUIRE(batch > 0, DLWP_ERR_INVALID_ARGUMENT, "batch must be positive");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  sany::Geom* g = nullptr;
+  const int32_t rc = spectral_wgrad_geom(plan, s, &g);
+  if (rc != DLWP_OK) return rc;
+  const size_t need = sany::wgrad_workspace_bytes(*g, batch);
+  DLWP_REQUIRE(workspace_bytes >= need, DLWP_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, need);
+  DLWP_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(grad_y) & 15) == 0 &&
+                   (reinterpret_cast<uintptr_t>(grad_w) & 7) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
+               DLWP_ERR_INVALID_ARGUMENT, "x / grad_y must be 16-byte, grad_w 8-byte, workspace 256-byte aligned");
+  return sany::run_wgrad(*g, x, grad_y, grad_w, batch, workspace, s);
 }

@@ -220,6 +220,75 @@ __global__ __launch_bounds__(256) void pack_kernel(const float2* __restrict__ sr
 }
 
 // ---------------------------------------------------------------------------------------------
+// weight gradient: G[i][o][r][k] = ck[k] sum_b conj(Xh[m][b][i]) DYh[m][b][o], m = k * nr + r
+// ---------------------------------------------------------------------------------------------
+// Xh (fwd_scale folded in by fwd_kernel) and DYh are the kept spectra of x and grad_y in the [mode][B][C] layout the
+// forward uses.  Each output is one thread's fp32 FMA chain over b in index order: no atomics, bitwise repeatable.
+// One workgroup per (mode, 64 out-channels, 32 in-channels) writes the packed image G [mode][Ci][Co] coalesced along o;
+// unpack_kernel (the inverse of pack_kernel, through a 64-mode x 32-pair LDS tile) turns it into PyTorch layout, where
+// the mode axes are innermost.  (A direct form -- lanes along the modes, a 4 x 8 tile of (i, o) pairs per thread, 512
+// contiguous bytes per wave store and no packed image -- was measured and lost: DESIGN.md section 19.)
+__global__ __launch_bounds__(256) void wgrad_kernel(const float2* __restrict__ xh, const float2* __restrict__ dyh,
+                                                           const float* __restrict__ ck, float2* __restrict__ g,
+                                                           const Dims d) {
+  __shared__ float2 s_x[kMixB][33];
+  const int m = blockIdx.y;
+  const int o = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int i0 = blockIdx.z * 32, ig = threadIdx.x >> 6;   // wave: in-channels i0 + ig + 4 j
+  const float2* xa = xh + (long long)m * d.B * d.ci;
+  const float2* da = dyh + (long long)m * d.B * d.co;
+  float2 acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = float2{0.f, 0.f};
+  for (int b0 = 0; b0 < d.B; b0 += kMixB) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < kMixB * 32; i += 256) {
+      const int bb = i >> 5, cc = i & 31;
+      s_x[bb][cc] = (b0 + bb < d.B && i0 + cc < d.ci) ? xa[(long long)(b0 + bb) * d.ci + i0 + cc] : float2{0.f, 0.f};
+    }
+    __syncthreads();
+    const int bn = min(kMixB, d.B - b0);
+    for (int bb = 0; bb < bn; ++bb) {
+      const float2 dv = (o < d.co) ? da[(long long)(b0 + bb) * d.co + o] : float2{0.f, 0.f};
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float2 xv = s_x[bb][ig + 4 * j];
+        acc[j].x = fmaf(xv.x, dv.x, acc[j].x);
+        acc[j].x = fmaf(xv.y, dv.y, acc[j].x);
+        acc[j].y = fmaf(xv.x, dv.y, acc[j].y);
+        acc[j].y = fmaf(-xv.y, dv.x, acc[j].y);
+      }
+    }
+  }
+  const float sc = ck[m / d.nr];
+  if (o < d.co)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int i = i0 + ig + 4 * j;
+      if (i < d.ci) g[((long long)m * d.ci + i) * d.co + o] = float2{acc[j].x * sc, acc[j].y * sc};
+    }
+}
+
+__global__ __launch_bounds__(256) void unpack_kernel(const float2* __restrict__ src, float2* __restrict__ dst, int npair,
+                                                     int nr, int nc) {
+  __shared__ float2 s_t[64][33];
+  const int nm = nr * nc;
+  const int mp0 = blockIdx.x * 64, q0 = blockIdx.y * 32;
+  for (int i = threadIdx.x; i < 64 * 32; i += 256) {
+    const int mm = i >> 5, q = i & 31, mp = mp0 + mm;
+    if (mp < nm && q0 + q < npair) {
+      const int r = mp / nc, ky = mp - r * nc;
+      s_t[mm][q] = src[((long long)ky * nr + r) * npair + q0 + q];
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 64 * 32; i += 256) {
+    const int q = i >> 6, mm = i & 63;
+    if (mp0 + mm < nm && q0 + q < npair) dst[(long long)(q0 + q) * nm + mp0 + mm] = s_t[mm][q];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // 1x1 convolution: y[b][o][p] = act(bias[o] + sum_c w[o][c] x[b][c][p] + resid[b][o][p])
 // ---------------------------------------------------------------------------------------------
 struct PwArgs {
@@ -309,6 +378,7 @@ int32_t geom_build(Geom& g, int ci, int co, int H, int W, int nr, int nc, const 
   g.ci = ci; g.co = co; g.H = H; g.W = W; g.nr = nr; g.nc = nc;
   g.Hp = round16(H); g.Wp = round16(W); g.KPp = round16(2 * nc);
   g.fwd = fwd_scale;
+  g.rows_o.assign(rows_out, rows_out + nr);
   DLWP_REQUIRE(g.fwd_lds() <= kMaxLdsBytes && g.inv_lds() <= kMaxLdsBytes, DLWP_ERR_UNSUPPORTED,
                "grid height %d x %d kept columns: the per-plane transform image (%zu bytes) exceeds %zu bytes of LDS", H,
                nc, g.inv_lds() > g.fwd_lds() ? g.inv_lds() : g.fwd_lds(), kMaxLdsBytes);
@@ -394,6 +464,48 @@ int32_t run_inv(const Geom& g, float* y, int B, void* ws, hipStream_t s) {
   const float2* z = reinterpret_cast<const float2*>(reinterpret_cast<char*>(ws) + xh_bytes(g, B));
   hipLaunchKernelGGL(inv_kernel, dim3(B * g.co), dim3(256), g.inv_lds(), s, z, g.ei.as<float2>(), g.ck.as<float>(),
                      g.ti.as<float>(), y, d);
+  DLWP_HIP_CHECK(hipGetLastError());
+  return DLWP_OK;
+}
+
+int32_t wgrad_prepare(Geom& g, hipStream_t s) {
+  if (g.efo.p) return DLWP_OK;
+  const double two_pi = 6.283185307179586476925286766559;
+  std::vector<float> h((size_t)g.nr * g.H * 2);
+  for (int r = 0; r < g.nr; ++r)
+    for (int hh = 0; hh < g.H; ++hh) {
+      const double a = two_pi * (double)(((long long)g.rows_o[r] * hh) % g.H) / (double)g.H;
+      h[((size_t)r * g.H + hh) * 2 + 0] = (float)std::cos(a);
+      h[((size_t)r * g.H + hh) * 2 + 1] = (float)(-std::sin(a));
+    }
+  DLWP_HIP_CHECK(g.efo.upload(h.data(), h.size() * 4, s));
+  DLWP_HIP_CHECK(hipStreamSynchronize(s));   // the staging vector dies at scope exit
+  return DLWP_OK;
+}
+
+size_t wgrad_workspace_bytes(const Geom& g, int B) {
+  return xh_bytes(g, B) + z_bytes(g, B) + align_up((size_t)g.nr * g.nc * g.ci * g.co * sizeof(float2), 256);
+}
+
+int32_t run_wgrad(const Geom& g, const float* x, const float* grad_y, float* grad_w, int B, void* ws, hipStream_t s) {
+  DLWP_REQUIRE(g.efo.p, DLWP_ERR_INVALID_ARGUMENT, "weight gradient before wgrad_prepare");
+  const Dims dx = dims(g, B);
+  Dims dy = dx;   // grad_y planes: Co channels, no forward scale (ck carries inv_scale)
+  dy.ci = g.co; dy.fwd = 1.f;
+  float2* xh = reinterpret_cast<float2*>(ws);
+  float2* dyh = reinterpret_cast<float2*>(reinterpret_cast<char*>(ws) + xh_bytes(g, B));
+  float2* gp = reinterpret_cast<float2*>(reinterpret_cast<char*>(ws) + xh_bytes(g, B) + z_bytes(g, B));
+  hipLaunchKernelGGL(fwd_kernel, dim3(B * g.ci), dim3(256), g.fwd_lds(), s, x, g.tf.as<float>(), g.ef.as<float2>(), xh, dx);
+  DLWP_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(fwd_kernel, dim3(B * g.co), dim3(256), g.fwd_lds(), s, grad_y, g.tf.as<float>(), g.efo.as<float2>(),
+                     dyh, dy);
+  DLWP_HIP_CHECK(hipGetLastError());
+  const int nm = g.nr * g.nc;
+  hipLaunchKernelGGL(wgrad_kernel, dim3((g.co + 63) / 64, nm, (g.ci + 31) / 32), dim3(256), 0, s, xh, dyh, g.ck.as<float>(),
+                     gp, dx);
+  DLWP_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(unpack_kernel, dim3((nm + 63) / 64, (g.ci * g.co + 31) / 32), dim3(256), 0, s, gp,
+                     reinterpret_cast<float2*>(grad_w), g.ci * g.co, g.nr, g.nc);
   DLWP_HIP_CHECK(hipGetLastError());
   return DLWP_OK;
 }

@@ -21,6 +21,9 @@ struct Geom {
   DevBuf ef;   // [nr][H] float2: e^{-2 pi i rows_in[r] h / H}
   DevBuf ei;   // [nr][H] float2: e^{+2 pi i rows_out[r] h / H}
   DevBuf ck;   // [nc]: inv_scale x (1 for the DC and Nyquist columns, 2 otherwise)
+  DevBuf efo;  // [nr][H] float2: e^{-2 pi i rows_out[r] h / H}, the weight gradient's transform of grad_y; built by
+               // wgrad_prepare on first use, so inference plans pay nothing
+  std::vector<int32_t> rows_o;   // host copy of rows_out (what efo is built from)
   size_t fwd_lds() const { return (size_t)Hp * (KPp + 1) * sizeof(float); }
   size_t inv_lds() const { return (size_t)Hp * (KPp + 4) * sizeof(float) + (size_t)nr * nc * sizeof(float2); }
 };
@@ -39,6 +42,14 @@ size_t workspace_bytes(const Geom& g, int batch);
 // y = S(x), x [B, ci, H, W], y [B, co, H, W]; in two halves (forward transform + mode mix, inverse transform)
 int32_t run_fwd_mix(const Geom& g, const float2* wt, const float* x, int batch, void* ws, hipStream_t s);
 int32_t run_inv(const Geom& g, float* y, int batch, void* ws, hipStream_t s);
+// Weight gradient of y = S_W(x): grad_w [Ci][Co][nr][nc][2] (PyTorch layout, overwritten)
+//   = ck[k] * sum_b conj(fwd X[b, i, rows_in[r], k]) DY[b, o, rows_out[r], k]
+// wgrad_prepare uploads efo once (it synchronises `s`: call it outside a stream capture, which the first
+// first weight-gradient call of a plan does); run_wgrad is fwd_kernel on x, fwd_kernel on grad_y, wgrad_kernel into the
+// packed [mode][Ci][Co] image in the workspace, unpack_kernel.
+int32_t wgrad_prepare(Geom& g, hipStream_t s);
+size_t wgrad_workspace_bytes(const Geom& g, int batch);
+int32_t run_wgrad(const Geom& g, const float* x, const float* grad_y, float* grad_w, int batch, void* ws, hipStream_t s);
 
 // Generic FNO2d plan (fno2d.hip's dlwp_fno2d_plan owns one when the shape is outside the specialised domain).
 struct Fno;

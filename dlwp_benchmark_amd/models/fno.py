@@ -345,8 +345,8 @@ class FNO2DModule(HipBackbone):
 
     # ------------------------------------------------------------------ training (first slice)
     def _train_step(self, x_t: torch.Tensor) -> torch.Tensor:
-        """One differentiable backbone step: spectral convolutions through the HIP kernels (forward and
-        backward-data, dlwp_benchmark_amd/training.py), the pointwise parts through torch ops."""
+        """One differentiable backbone step: spectral convolutions through the HIP kernels (forward, backward-data
+        and weight gradient, dlwp_benchmark_amd/training.py), the pointwise parts through torch ops."""
         import torch.nn.functional as F
 
         from .. import training as T

@@ -9,13 +9,18 @@ convolutions (models/unet/unet.py:46-69 `SpectralConv2d`, and neuralop's Spectra
                                                        conjugate-transposed on the device (exact adjoint: the
                                                        Hermitian weights of the half spectrum cancel per column)
   backward-weight dW[i,o,r,k] = sum_b conj(fwd * X[b,i,rows_in[r],k]) * inv * c_k * DY[b,o,rows_out[r],k]
-                                                       two rfft2 (rocFFT) at the kept modes + one einsum
+                                                       dlwp_spectral_conv2d_wgrad_f32: the pruned forward transform of x
+                                                       and of grad_y at the kept modes, one fp32 contraction kernel, one transpose
+                                                       (csrc/spectral_any.hip; no rocFFT plan, no torch GEMM)
 
 with c_k = 1 for k = 0 and the Nyquist column, 2 otherwise.  The identities are checked against autograd of
-the reference operator in tests (CPU, double) and against reference gradients on the GPU.
+the reference operator in tests (CPU, double) and against reference gradients on the GPU.  `spectral_weight_grad` below
+is the same formula in plain torch on any device: the checker of the kernel and the timing baseline, not what the GPU
+path calls.
 
 Everything pointwise around the spectral operator (1x1 convolutions, GELU, residuals) stays in torch ops on
-the GPU in training mode; window-attention backward is not built yet.
+the GPU in training mode.  The other hot kernels' training paths (window and global attention, Linear, the AFNO
+filter, the cylinder and HEALPix convolutions, MeshGraphNet, GraphCastNet) follow below, each with its HIP backward.
 """
 import ctypes
 from typing import List, Optional, Sequence
@@ -41,28 +46,39 @@ def spectral_weight_grad(x, grad_y, rows_in, rows_out, n_cols: int, fwd_scale: f
 
 
 class SpectralOperator:
-    """Forward + adjoint plans of one mode-truncated spectral convolution geometry, C -> C channels.  32 channels on a
-    width that is a multiple of 64 with at most 16 kept columns run the specialised kernels; every other shape up to
-    C = 512 (width a multiple of 4) the width-generic ones (csrc/spectral_any.hip)."""
+    """Forward + adjoint plans of one mode-truncated spectral convolution geometry, `channels` -> `out_channels`
+    (square when `out_channels` is omitted); the adjoint plan is `out_channels` -> `channels` with the row lists swapped.
+    32 -> 32 channels on a width that is a multiple of 64 with at most 16 kept columns run the specialised kernels;
+    every other shape up to 512 channels (width a multiple of 4) the width-generic ones (csrc/spectral_any.hip).
+
+    The weight gradient has the width-generic form only (Ci, Co <= 512, width a multiple of 4, the [H16][2 n_cols16 + 1]
+    fp32 LDS image of one plane within 128 KB).  The specialised forward's shapes lie inside that domain up to about 990
+    rows; a taller 32-channel grid runs forward and backward-data but `backward_weight` raises DlwpError.  There is no
+    torch fallback."""
 
     def __init__(self, channels: int, height: int, width: int, rows_in: Sequence[int], rows_out: Sequence[int],
-                 n_cols: int, fwd_scale: float, inv_scale: float, device):
-        self.channels, self.h, self.w = channels, height, width
+                 n_cols: int, fwd_scale: float, inv_scale: float, device, out_channels: Optional[int] = None):
+        self.channels, self.h, self.w = int(channels), height, width
+        self.out_channels = self.channels if out_channels is None else int(out_channels)
         self.rows_in = [int(r) for r in rows_in]
         self.rows_out = [int(r) for r in rows_out]
         self.n_cols = int(n_cols)
         self.fwd_scale, self.inv_scale = float(fwd_scale), float(inv_scale)
         self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.DlwpError(f"SpectralOperator runs HIP kernels on an MI355X device, got {self.device}: "
+                                 "the HIP path has no CPU fallback")
         lib = _lib.load()
         n = len(self.rows_in)
         ri = (ctypes.c_int32 * n)(*self.rows_in)
         ro = (ctypes.c_int32 * n)(*self.rows_out)
+        ci, co = self.channels, self.out_channels
         self._fwd, self._adj = ctypes.c_void_p(), ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(lib.dlwp_spectral_conv2d_plan_create_ex(ctypes.byref(self._fwd), channels, channels, height, width,
+            _lib.check(lib.dlwp_spectral_conv2d_plan_create_ex(ctypes.byref(self._fwd), ci, co, height, width,
                                                                n, self.n_cols, ri, ro, self.fwd_scale, self.inv_scale,
                                                                _lib.stream_ptr()), "dlwp_spectral_conv2d_plan_create_ex")
-            _lib.check(lib.dlwp_spectral_conv2d_plan_create_ex(ctypes.byref(self._adj), channels, channels, height, width,
+            _lib.check(lib.dlwp_spectral_conv2d_plan_create_ex(ctypes.byref(self._adj), co, ci, height, width,
                                                                n, self.n_cols, ro, ri, self.fwd_scale, self.inv_scale,
                                                                _lib.stream_ptr()), "dlwp_spectral_conv2d_plan_create_ex")
         self._ws = None
@@ -76,24 +92,32 @@ class SpectralOperator:
         except Exception:
             pass
 
+    def _workspace(self, nbytes: int, device) -> torch.Tensor:
+        """grown, never shrunk"""
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+        return self._ws
+
     def _run(self, plan, x: torch.Tensor, weight_real: torch.Tensor, adjoint: bool) -> torch.Tensor:
         _lib.require_cuda_tensor(x, "x")
         x = x.contiguous().float()
         w = weight_real.detach().contiguous().float()
         b, c, h, wd = x.shape
         n = len(self.rows_in)
-        if (c, h, wd) != (self.channels, self.h, self.w) or tuple(w.shape) != (c, c, n, self.n_cols, 2):
-            raise _lib.DlwpError(f"spectral operator built for {self.channels}x{self.h}x{self.w}, "
-                                 f"{n}x{self.n_cols} modes; got x {tuple(x.shape)}, weight {tuple(w.shape)}")
+        ci, co = self.channels, self.out_channels
+        c_in, c_out = (co, ci) if adjoint else (ci, co)
+        if (c, h, wd) != (c_in, self.h, self.w) or tuple(w.shape) != (ci, co, n, self.n_cols, 2):
+            raise _lib.DlwpError(f"spectral operator built for {ci}->{co} channels on {self.h}x{self.w}, "
+                                 f"{n}x{self.n_cols} modes; got x {tuple(x.shape)}, weight {tuple(w.shape)}"
+                                 + (" (adjoint)" if adjoint else ""))
         lib = _lib.load()
         nbytes = lib.dlwp_spectral_conv2d_workspace_bytes(plan, b)
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=x.device)
-        y = torch.empty_like(x)
+        ws = self._workspace(nbytes, x.device)
+        y = torch.empty(b, c_out, h, wd, device=x.device, dtype=torch.float32)
         with torch.cuda.device(x.device):
             _lib.check(lib.dlwp_spectral_conv2d_set_weights_dev(plan, w.data_ptr(), 1 if adjoint else 0, _lib.stream_ptr()),
                        "dlwp_spectral_conv2d_set_weights_dev")
-            _lib.check(lib.dlwp_spectral_conv2d_f32(plan, x.data_ptr(), y.data_ptr(), b, self._ws.data_ptr(), nbytes,
+            _lib.check(lib.dlwp_spectral_conv2d_f32(plan, x.data_ptr(), y.data_ptr(), b, ws.data_ptr(), nbytes,
                                                     _lib.stream_ptr()), "dlwp_spectral_conv2d_f32")
         return y
 
@@ -104,9 +128,26 @@ class SpectralOperator:
         return self._run(self._adj, grad_y, weight_real, True)
 
     def backward_weight(self, x, grad_y):
-        """[C, C, n_rows, n_cols, 2] gradient of the real view of the weights."""
-        return spectral_weight_grad(x.float(), grad_y.float(), self.rows_in, self.rows_out, self.n_cols, self.fwd_scale,
-                                    self.inv_scale)
+        """[Ci, Co, n_rows, n_cols, 2] gradient of the real view of the weights: dlwp_spectral_conv2d_wgrad_f32 on the
+        forward plan (four launches on the current stream; bitwise repeatable)."""
+        _lib.require_cuda_tensor(x, "x")
+        _lib.require_cuda_tensor(grad_y, "grad_y")
+        x = x.detach().contiguous().float()
+        grad_y = grad_y.detach().contiguous().float()
+        b = x.shape[0]
+        ci, co = self.channels, self.out_channels
+        if tuple(x.shape) != (b, ci, self.h, self.w) or tuple(grad_y.shape) != (b, co, self.h, self.w):
+            raise _lib.DlwpError(f"spectral operator built for {ci}->{co} channels on {self.h}x{self.w}; "
+                                 f"got x {tuple(x.shape)}, grad_y {tuple(grad_y.shape)}")
+        lib = _lib.load()
+        nbytes = lib.dlwp_spectral_conv2d_wgrad_workspace_bytes(self._fwd, b)
+        ws = self._workspace(nbytes, x.device)
+        gw = torch.empty(ci, co, len(self.rows_in), self.n_cols, 2, device=x.device, dtype=torch.float32)
+        with torch.cuda.device(x.device):
+            _lib.check(lib.dlwp_spectral_conv2d_wgrad_f32(self._fwd, x.data_ptr(), grad_y.data_ptr(), gw.data_ptr(), b,
+                                                          ws.data_ptr(), nbytes, _lib.stream_ptr()),
+                       "dlwp_spectral_conv2d_wgrad_f32")
+        return gw
 
 
 class _SpectralConvFn(torch.autograd.Function):
@@ -127,7 +168,7 @@ class _SpectralConvFn(torch.autograd.Function):
 
 
 def spectral_conv(x: torch.Tensor, weight_real: torch.Tensor, op: SpectralOperator) -> torch.Tensor:
-    """Differentiable mode-truncated spectral convolution; weight_real [C, C, n_rows, n_cols, 2]."""
+    """Differentiable mode-truncated spectral convolution; weight_real [Ci, Co, n_rows, n_cols, 2]."""
     return _SpectralConvFn.apply(x, weight_real, op)
 
 

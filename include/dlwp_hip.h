@@ -196,6 +196,23 @@ size_t dlwp_spectral_conv2d_workspace_bytes(const dlwp_spectral_plan* plan, int3
 int32_t dlwp_spectral_conv2d_f32(const dlwp_spectral_plan* plan, const float* x_dev, float* y_dev,
                                  int32_t batch, void* workspace_dev, size_t workspace_bytes,
                                  void* stream);
+/* Weight gradient of the FORWARD plan `plan` (reference scripts/train.py:263-271 `loss.backward()` through
+ * models/unet/unet.py:46-69: what autograd derives from rfft2 :56, the two einsums of batchmul2d :15-17 / :60-65 and
+ * irfft2 :68; the same for neuralop's SpectralConv inside FNO2DModule, fno.py:38-47):
+ *   grad_w[i, o, r, k] = sum_b conj(fwd_scale X[b, i, rows_in[r], k]) * inv_scale c_k * DY[b, o, rows_out[r], k]
+ * with X = rfft2(x), DY = rfft2(grad_y) un-normalised and c_k = 1 for k = 0 and the Nyquist column, 2 otherwise.
+ * x_dev [B, Ci, H, W], grad_y_dev [B, Co, H, W]; grad_w_dev [Ci, Co, n_rows, n_cols, 2] fp32 (PyTorch layout) is
+ * OVERWRITTEN.  Four launches on `stream`, no host synchronisation: the pruned forward transform of x and of grad_y
+ * at the kept modes, one fp32 FMA contraction whose sum over b runs in index order in one thread (no atomics:
+ * bitwise repeatable) into a packed [mode][Ci][Co] image in the workspace, and its transpose into PyTorch layout.  The width-generic kernels (csrc/spectral_any.hip) are the only form: Ci, Co in [1, 512],
+ * width a multiple of 4, one plane's LDS image within 128 KB; a plan of the specialised 32-channel kernels builds the
+ * generic tables from its own description on its first call here.  Outside that domain: DLWP_ERR_UNSUPPORTED naming
+ * the limit.  The first dlwp_spectral_conv2d_wgrad_f32 of a plan uploads tables and synchronises `stream`: make it
+ * before a stream capture.  A plan is used from one thread at a time. */
+size_t dlwp_spectral_conv2d_wgrad_workspace_bytes(const dlwp_spectral_plan* plan, int32_t batch);
+int32_t dlwp_spectral_conv2d_wgrad_f32(const dlwp_spectral_plan* plan, const float* x_dev, const float* grad_y_dev,
+                                       float* grad_w_dev, int32_t batch, void* workspace_dev, size_t workspace_bytes,
+                                       void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Fused (shifted-)window attention, fp32.  Replaces everything between the qkv Linear and the proj

@@ -24,11 +24,12 @@ class HipBackbone(torch.nn.Module):
         self._graphed = None
 
     # ---- precision forms (per-module state, no process-wide switch) ------------------------------------------------
-    # name -> (attention precision, Linear form, block-tail MLP form).  "fp32" is the parity path of every mirror;
-    # "f16x3" is fp32-grade too (two-part f16 splits); "bf16" is what the reference gets from
-    # autocast(bfloat16) and what BASELINE.json names for the Swin and Pangu configs.
-    COMPUTE_PRECISIONS = {"fp32": ("fp32", "bf16x6", "bf16x6"), "f16x3": ("fp32", "f16x3", "f16x3"),
-                          "bf16attn": ("bf16", "bf16x6", "bf16x6"), "bf16": ("bf16", "bf16", "bf16x6")}
+    # name -> (attention precision, Linear form, block-tail MLP form, 3x3 convolution form).  "fp32" is the parity path of
+    # every mirror; "f16x3" is fp32-grade too (two-part f16 splits); "bf16" is what the reference gets from
+    # autocast(bfloat16) and what BASELINE.json names for the Swin and Pangu configs.  The convolution has no f16 split form:
+    # under "f16x3" it takes "bf16x6", the family's fp32-grade matrix-pipe form; "fp32" keeps the direct kernel.
+    COMPUTE_PRECISIONS = {"fp32": ("fp32", "bf16x6", "bf16x6", "direct"), "f16x3": ("fp32", "f16x3", "f16x3", "bf16x6"),
+                          "bf16attn": ("bf16", "bf16x6", "bf16x6", "direct"), "bf16": ("bf16", "bf16", "bf16x6", "bf16")}
 
     def _set_on_submodules(self, attr: str, value) -> int:
         n = 0
@@ -66,17 +67,29 @@ class HipBackbone(torch.nn.Module):
         self._set_on_submodules("mlp_form", form)
         return self
 
+    def set_conv_form(self, form: str):
+        """pad(1) + Conv2d(3x3) of the U-Net / ConvLSTM / diffusion families: "direct" (default; the scalar-FMA kernel,
+        dlwp_conv3x3_ex_f32), "bf16x6" (dlwp_conv3x3_mfma_f32: fp32-grade, six products of exact three-part bf16 splits) or
+        "bf16" (the same kernel on RNE bf16 operands, fp32 accumulation).  Inference only: training keeps the direct kernel."""
+        from .. import ops
+
+        if form not in ops.CONV_FORMS:
+            raise _lib.DlwpError(f"unknown conv form {form!r} (one of {ops.CONV_FORMS})")
+        self._set_on_submodules("conv_form", form)
+        return self
+
     def set_compute_precision(self, name: str):
-        """ONE knob over the three above -- also the constructor kwarg `compute_precision` (a key the reference ignores:
+        """ONE knob over the four above -- also the constructor kwarg `compute_precision` (a key the reference ignores:
         every reference constructor swallows unknown keys through **kwargs, so a config that carries it still builds
         there): "fp32" | "f16x3" | "bf16attn" | "bf16".  A drop-in user selects the config's named precision in
         `configs/model/*.yaml` and never calls a setter."""
         if name not in self.COMPUTE_PRECISIONS:
             raise _lib.DlwpError(f"unknown compute_precision {name!r} (one of {sorted(self.COMPUTE_PRECISIONS)})")
-        attn, lin, mlp = self.COMPUTE_PRECISIONS[name]
+        attn, lin, mlp, conv = self.COMPUTE_PRECISIONS[name]
         self._set_on_submodules("attention_precision", attn)
         self._set_on_submodules("linear_form", lin)
         self._set_on_submodules("mlp_form", mlp)
+        self._set_on_submodules("conv_form", conv)
         self.compute_precision = name
         return self
 

@@ -31,6 +31,7 @@ from torch import nn
 from .. import lib as _lib
 from .. import ops
 from .. import training as _T
+from ._base import HipBackbone
 from .unet import CylinderPad, HEALPixPadding, _resolve_activation
 
 
@@ -109,6 +110,7 @@ class ResidualBlock(nn.Module):
         self.activation = activation
         self.use_scale_shift_norm = use_scale_shift_norm
         self.mesh = mesh
+        self.conv_form = "direct"       # ops.CONV_FORMS, set through HipBackbone.set_conv_form / set_compute_precision
         self.cylinder_pad = HEALPixPadding(padding=1) if mesh == "healpix" else CylinderPad(padding)
         self.conv1 = nn.Conv2d(in_channels, out_channels, kernel_size=3, padding=0)
         self.conv2 = _zero_module(nn.Conv2d(out_channels, out_channels, kernel_size=3, padding=0))
@@ -121,27 +123,27 @@ class ResidualBlock(nn.Module):
         """modern_unet.py:620-650.  `emb` [B', cond]: B' = the leading dimension of x (on the HEALPix mesh the caller has
         already repeated it per face -- the reference cannot broadcast [B, C] against [(B 12), C, h, w] either)."""
         gelu = ops.act_code(self.activation)
-        hpx = self.mesh == "healpix"
+        hpx, form = self.mesh == "healpix", self.conv_form
         x = x.contiguous()
         short = x if isinstance(self.shortcut, nn.Identity) else ops.conv2d(x, self.shortcut.weight, self.shortcut.bias)
         n1, n2 = self.norm1, self.norm2
         if isinstance(n1, nn.Identity):
-            h = ops.conv3x3(x, self.conv1.weight, self.conv1.bias, pre_act=gelu, hpx=hpx)
+            h = ops.conv3x3(x, self.conv1.weight, self.conv1.bias, pre_act=gelu, hpx=hpx, form=form)
         else:
             h = ops.groupnorm_act(x, n1.weight, n1.bias, n1.num_groups, n1.eps, gelu)
-            h = ops.conv3x3(h, self.conv1.weight, self.conv1.bias, hpx=hpx)
+            h = ops.conv3x3(h, self.conv1.weight, self.conv1.bias, hpx=hpx, form=form)
         emb_out = self.cond_emb(emb)[:, :, None, None]
         if not isinstance(n2, nn.Identity) and self.use_scale_shift_norm:
             h = ops.groupnorm_act(h, n2.weight, n2.bias, n2.num_groups, n2.eps, 0)
         if self.use_scale_shift_norm:
             scale, shift = torch.chunk(emb_out, 2, dim=1)
             h = torch.addcmul(shift, h, 1 + scale)                     # norm2(h) * (1 + scale) + shift
-            return ops.conv3x3(h, self.conv2.weight, self.conv2.bias, pre_act=gelu, resid=short, hpx=hpx)
+            return ops.conv3x3(h, self.conv2.weight, self.conv2.bias, pre_act=gelu, resid=short, hpx=hpx, form=form)
         h = h + emb_out
         if isinstance(n2, nn.Identity):
-            return ops.conv3x3(h, self.conv2.weight, self.conv2.bias, pre_act=gelu, resid=short, hpx=hpx)
+            return ops.conv3x3(h, self.conv2.weight, self.conv2.bias, pre_act=gelu, resid=short, hpx=hpx, form=form)
         h = ops.groupnorm_act(h, n2.weight, n2.bias, n2.num_groups, n2.eps, gelu)
-        return ops.conv3x3(h, self.conv2.weight, self.conv2.bias, resid=short, hpx=hpx)
+        return ops.conv3x3(h, self.conv2.weight, self.conv2.bias, resid=short, hpx=hpx, form=form)
 
 
 class ConditionalHEALPixLayer(nn.Module):
@@ -254,8 +256,9 @@ class ModernUNetDecoder(nn.Module):
         return ops.small_module(self.output_layer, x)
 
 
-class DiffModernUNet(nn.Module):
-    """modern_unet.py:46-293."""
+class DiffModernUNet(HipBackbone):
+    """modern_unet.py:46-293.  A HipBackbone for its precision knobs (`compute_precision`, set_conv_form); the denoising
+    loop below is its own, no step graph is captured."""
 
     def __init__(self, constant_channels: int = 4, prescribed_channels: int = 0, prognostic_channels: int = 1,
                  hidden_channels=(64, 128, 256, 1024), activation=None, context_size: int = 1, mesh: str = "equirectangular",
@@ -282,6 +285,14 @@ class DiffModernUNet(nn.Module):
         self.decoder = ModernUNetDecoder(hidden_channels=self.hidden_channels, out_channels=prognostic_channels,
                                          time_embed_dim=time_embed_dim, activation=activation, mesh=mesh,
                                          use_scale_shift_norm=use_scale_shift_norm)
+        self._init_compute_precision(kwargs)
+
+    def set_step_graphs(self, on: bool = True):
+        """The denoising loop draws host noise and steps a host scheduler between network calls: there is no `one_step` to
+        capture, so asking for step graphs is an error rather than a silent no-op."""
+        if on:
+            raise _lib.DlwpError(f"{type(self).__name__} has no captured step: its refinement loop runs on the host")
+        return super().set_step_graphs(False)
 
     # ---- modern_unet.py:120-139
     def _prepare_inputs(self, constants=None, prescribed=None, prognostic=None) -> torch.Tensor:
@@ -367,7 +378,7 @@ class DiffMUNetHPX(DiffModernUNet):
                          prognostic_channels=prognostic_channels, hidden_channels=hidden_channels, activation=activation,
                          context_size=context_size, mesh="healpix", attention=attention, norm=norm,
                          use_scale_shift_norm=use_scale_shift_norm, predict_diff=predict_diff,
-                         num_refinement_step=num_refinement_step)
+                         num_refinement_step=num_refinement_step, **kwargs)
 
     def _prepare_inputs(self, constants=None, prescribed=None, prognostic=None) -> torch.Tensor:
         """:314-327: [(B F), (T C), H, W]."""

@@ -56,6 +56,7 @@ class HEALPixLayer(nn.Module):
 
     def __init__(self, layer=nn.Conv2d, **kwargs):
         super().__init__()
+        self.conv_form = "direct"       # ops.CONV_FORMS, set through HipBackbone.set_conv_form / set_compute_precision
         kwargs = dict(kwargs)
         kwargs.pop("enable_nhwc", None), kwargs.pop("enable_healpixpad", None)
         if layer is ResidualBlock or layer == "ResidualBlock":
@@ -73,7 +74,7 @@ class HEALPixLayer(nn.Module):
         if isinstance(self.layers[0], ResidualBlock):
             return self.layers[0](x)
         conv = self.layers[1]
-        return ops.conv3x3_hpx(x, conv.weight, conv.bias, act, x1=x1)
+        return ops.conv3x3_hpx(x, conv.weight, conv.bias, act, x1=x1, form=self.conv_form)
 
 
 class ResidualBlock(nn.Module):
@@ -90,6 +91,7 @@ class ResidualBlock(nn.Module):
         if not isinstance(activation, nn.GELU):
             raise NotImplementedError("ResidualBlock: only GELU (the reference default) is wired to the fused kernels")
         self.activation = activation
+        self.conv_form = "direct"
         self.mesh = mesh
         # unet.py:867-872: HEALPixPadding on the HEALPix mesh, CylinderPad otherwise; either way the padding happens
         # inside the fused convolution kernel
@@ -108,7 +110,7 @@ class ResidualBlock(nn.Module):
         second activation in its epilogue; with GroupNorm each `act(norm(.))` is one dlwp_groupnorm_act_f32 launch.
         The shortcut (identity or 1x1 convolution) is added in conv2's epilogue."""
         gelu = ops.act_code(self.activation)
-        hpx = self.mesh == "healpix"
+        hpx, form = self.mesh == "healpix", self.conv_form
         x = x.contiguous()
         short = x if isinstance(self.shortcut, nn.Identity) else ops.conv2d(x, self.shortcut.weight, self.shortcut.bias)
         n1, n2 = self.norm1, self.norm2
@@ -117,11 +119,11 @@ class ResidualBlock(nn.Module):
         else:
             h, pre = ops.groupnorm_act(x, n1.weight, n1.bias, n1.num_groups, n1.eps, gelu), 0
         if isinstance(n2, nn.Identity):
-            h = ops.conv3x3(h, self.conv1.weight, self.conv1.bias, act=gelu, pre_act=pre, hpx=hpx)
+            h = ops.conv3x3(h, self.conv1.weight, self.conv1.bias, act=gelu, pre_act=pre, hpx=hpx, form=form)
         else:
-            h = ops.conv3x3(h, self.conv1.weight, self.conv1.bias, act=0, pre_act=pre, hpx=hpx)
+            h = ops.conv3x3(h, self.conv1.weight, self.conv1.bias, act=0, pre_act=pre, hpx=hpx, form=form)
             h = ops.groupnorm_act(h, n2.weight, n2.bias, n2.num_groups, n2.eps, gelu)
-        return ops.conv3x3(h, self.conv2.weight, self.conv2.bias, act=0, resid=short, hpx=hpx)
+        return ops.conv3x3(h, self.conv2.weight, self.conv2.bias, act=0, resid=short, hpx=hpx, form=form)
 
 
 class MiddleBlock(nn.Module):
@@ -152,10 +154,11 @@ def _resolve_activation(activation):
 _STRUCTURAL = (CylinderPad, HEALPixLayer, nn.Conv2d, nn.ConvTranspose2d, nn.AvgPool2d)
 
 
-def _run_stack(seq: nn.Sequential, x, skip=None):
+def _run_stack(seq: nn.Sequential, x, skip=None, form: str = "direct"):
     """Executes a reference-shaped Sequential of [AvgPool] (CylinderPad, Conv2d, act)* [ConvTranspose2d]
     with each (pad, conv, act) triple fused into one kernel call; `skip` is concatenated in front
-    of x for the first conv (torch.cat([skip, x], 1), unet.py:553)."""
+    of x for the first conv (torch.cat([skip, x], 1), unet.py:553).  `form` is the caller's conv_form for the
+    CylinderPad triples; a HEALPixLayer carries its own."""
     mods = list(seq)
     i = 0
     while i < len(mods):
@@ -175,10 +178,10 @@ def _run_stack(seq: nn.Sequential, x, skip=None):
                 act = ops.act_code(mods[i + 2])
                 step = 3
             if skip is not None:
-                x = ops.conv3x3_cyl(skip, conv.weight, conv.bias, act, x1=x)
+                x = ops.conv3x3_cyl(skip, conv.weight, conv.bias, act, x1=x, form=form)
                 skip = None
             else:
-                x = ops.conv3x3_cyl(x, conv.weight, conv.bias, act)
+                x = ops.conv3x3_cyl(x, conv.weight, conv.bias, act, form=form)
             i += step
         else:
             if skip is not None:
@@ -210,11 +213,12 @@ class _UNetEncoder(nn.Module):
                 layer += _conv_block(c_in if n_conv == 0 else c_out, c_out, activation, mesh)
             layers.append(nn.Sequential(*layer))
         self.layers = nn.ModuleList(layers)
+        self.conv_form = "direct"
 
     def forward(self, x):
         outs = []
         for layer in self.layers:
-            x = _run_stack(layer, x)
+            x = _run_stack(layer, x, form=self.conv_form)
             outs.append(x)
         return outs
 
@@ -237,10 +241,11 @@ class _UNetDecoder(nn.Module):
             layers.append(nn.Sequential(*layer))
         self.layers = nn.ModuleList(layers)
         self.output_layer = nn.Conv2d(c_out, out_channels, kernel_size=1)
+        self.conv_form = "direct"
 
     def forward(self, x, skips):
         for l_idx, layer in enumerate(self.layers):
-            x = _run_stack(layer, x, skip=skips[l_idx] if l_idx > 0 else None)
+            x = _run_stack(layer, x, skip=skips[l_idx] if l_idx > 0 else None, form=self.conv_form)
         return ops.small_module(self.output_layer, x)
 
 
@@ -257,6 +262,7 @@ class UNet(HipBackbone):
         in_channels = constant_channels + (prescribed_channels + prognostic_channels) * context_size
         self.encoder = _UNetEncoder(in_channels, list(hidden_channels), n_convolutions, activation, mesh)
         self.decoder = _UNetDecoder(list(hidden_channels), prognostic_channels, n_convolutions, activation, mesh)
+        self._init_compute_precision(kwargs)
 
     def one_step(self, x):
         enc = self.encoder(x)
@@ -289,7 +295,8 @@ class UNetHPX(UNet):
                  context_size: int = 1, mesh: str = "healpix", **kwargs):
         super().__init__(constant_channels=constant_channels, prescribed_channels=prescribed_channels,
                          prognostic_channels=prognostic_channels, hidden_channels=hidden_channels,
-                         n_convolutions=n_convolutions, activation=activation, context_size=context_size, mesh="healpix")
+                         n_convolutions=n_convolutions, activation=activation, context_size=context_size, mesh="healpix",
+                         **kwargs)
 
     @staticmethod
     def _fold(t):
@@ -411,6 +418,7 @@ class MUNetHPX(UNetHPX):
         self.encoder = _ModernUNetEncoder(in_channels, list(hidden_channels))
         self.middle = MiddleBlock(in_channels=hidden_channels[-1], norm=norm, activation=activation, mesh="healpix")
         self.decoder = _ModernUNetDecoder(list(hidden_channels), prognostic_channels, activation)
+        self._init_compute_precision(kwargs)
 
     def one_step(self, x):
         return self.decoder(self.middle(self.encoder(x)))
@@ -453,6 +461,7 @@ class ModernUNet(UNet):
         self.encoder = _ModernUNetEncoder(in_channels, hidden_channels, mesh=None)
         self.middle = MiddleBlock(in_channels=hidden_channels[-1], norm=norm, activation=activation, mesh=None)
         self.decoder = _ModernUNetDecoder(hidden_channels, prognostic_channels, activation, mesh=None)
+        self._init_compute_precision(kwargs)
 
     def one_step(self, x):
         return self.decoder(self.middle(self.encoder(x)))
@@ -462,6 +471,7 @@ class _ConvLSTMCell(nn.Module):
     def __init__(self, input_size, hidden_size, bias=True, mesh="equirectangular"):
         super().__init__()
         self.hidden_size = hidden_size
+        self.conv_form = "direct"
         if mesh == "healpix":   # convlstm.py:56-63: state-dict key conv.layers.1.*
             self.conv = HEALPixLayer(layer=nn.Conv2d, in_channels=input_size + hidden_size, out_channels=hidden_size * 4,
                                      kernel_size=3, padding=1, bias=bias)
@@ -474,7 +484,7 @@ class _ConvLSTMCell(nn.Module):
         if isinstance(self.conv, HEALPixLayer):
             return self.conv(x, 0, x1=h_prev)
         conv = self.conv[1]
-        return ops.conv3x3_cyl(x, conv.weight, conv.bias, 0, x1=h_prev)
+        return ops.conv3x3_cyl(x, conv.weight, conv.bias, 0, x1=h_prev, form=self.conv_form)
 
 
 class ConvLSTM(HipBackbone):
@@ -489,6 +499,7 @@ class ConvLSTM(HipBackbone):
         if mesh not in ("equirectangular", "healpix"):
             raise ValueError(f"unknown mesh {mesh!r}")
         self.mesh = mesh
+        self.conv_form = "direct"       # the encoder / decoder stacks run from this module (_run_stack)
         self.hidden_sizes = list(hidden_sizes)
         self.context_size = int(context_size)
         in_size = constant_channels + prescribed_channels + prognostic_channels
@@ -508,9 +519,12 @@ class ConvLSTM(HipBackbone):
         else:
             self.decoder = nn.Sequential(CylinderPad(1), nn.Conv2d(self.hidden_sizes[-1], prognostic_channels,
                                                                    kernel_size=3, padding=0))
+        self._init_compute_precision(kwargs)
 
     def _decode(self, x):
-        return self.decoder(x) if isinstance(self.decoder, HEALPixLayer) else _run_stack(self.decoder, x)
+        if isinstance(self.decoder, HEALPixLayer):
+            return self.decoder(x)
+        return _run_stack(self.decoder, x, form=self.conv_form)
 
     def _rollout(self, constants, prescribed, prognostic):
         """convlstm.py:210-251 on [N, T, C, H, W] tensors (N = batch, or batch * 12 faces): loop from t = 0, teacher
@@ -535,7 +549,7 @@ class ConvLSTM(HipBackbone):
             if prescribed is not None:
                 parts.append(prescribed[:, t])
             parts.append(prog_t)
-            x = _run_stack(self.encoder, torch.cat(parts, dim=1))
+            x = _run_stack(self.encoder, torch.cat(parts, dim=1), form=self.conv_form)
             for i, cell in enumerate(self.clstm):
                 hs[i], cs[i] = ops.convlstm_gates(cell.gates(x, hs[i]), cs[i])
                 x = hs[i]
@@ -572,7 +586,7 @@ class ConvLSTMHPX(ConvLSTM):
         super().__init__(batch_size=batch_size, constant_channels=constant_channels,
                          prescribed_channels=prescribed_channels, prognostic_channels=prognostic_channels,
                          hidden_sizes=hidden_sizes, height=height, width=width, device=device, bias=bias,
-                         context_size=context_size, mesh="healpix")
+                         context_size=context_size, mesh="healpix", **kwargs)
 
     def forward(self, constants: Optional[torch.Tensor] = None, prescribed: Optional[torch.Tensor] = None,
                 prognostic: torch.Tensor = None) -> torch.Tensor:

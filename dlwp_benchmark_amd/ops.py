@@ -193,12 +193,73 @@ def act_code(activation) -> int:
     raise _lib.DlwpError(f"activation {activation!r} has no fused kernel (supported: GELU, Tanh, ReLU, SiLU)")
 
 
+# forms of pad(1) + Conv2d(3x3): "direct" (default) is the scalar-FMA kernel of csrc/conv.hip; "bf16x6" / "bf16" are the
+# implicit GEMM of csrc/conv_mfma.hip on the bf16 matrix instructions (fp32-grade three-part splits / RNE bf16 operands)
+CONV_FORMS = ("direct", "bf16x6", "bf16")
+
+
+class Conv3x3Weights:
+    """A 3x3 convolution weight [cout, cin, 3, 3] in the MFMA operand layout dlwp_conv3x3_mfma_f32 reads (three bf16 images;
+    form "bf16" reads the first), re-packed on the device whenever the parameter has been written to -- the derivation rule of
+    LinearWeights.  Packing is a launch of its own and allocates: it happens in the eager or warm-up pass; inside a graph
+    capture a stale or missing pack is an error."""
+
+    def __init__(self):
+        self._key = None
+        self._buf = None
+
+    def get(self, weight: torch.Tensor) -> torch.Tensor:
+        key = (weight.data_ptr(), weight._version, str(weight.device), pack_epoch())
+        if key != self._key:
+            if torch.cuda.is_current_stream_capturing():
+                raise _lib.DlwpError("conv3x3: the weight pack must be made before a graph capture (run one eager step first)")
+            cout, cin = weight.shape[:2]
+            lib = _lib.load()
+            nbytes = int(lib.dlwp_conv3x3_mfma_packed_bytes(cout, cin))
+            if nbytes == 0:
+                raise _lib.DlwpError(f"conv3x3: unsupported shape cout={cout} cin={cin} for the matrix-pipe forms")
+            buf = torch.empty(nbytes // 4, dtype=torch.int32, device=weight.device)
+            with torch.cuda.device(weight.device):
+                _lib.check(lib.dlwp_conv3x3_mfma_pack_f32(weight.detach().contiguous().data_ptr(), cout, cin, buf.data_ptr(),
+                                                          _lib.stream_ptr()), "dlwp_conv3x3_mfma_pack_f32")
+            self._key, self._buf = key, buf
+        return self._buf
+
+
+# id(weight) -> (weak reference, Conv3x3Weights): a pack lives exactly as long as the tensor it was derived from (the
+# finalizer drops it), so a captured step graph -- which keeps its module, hence its parameters, alive -- never replays
+# against a freed pack; nothing here is ever cleared wholesale
+_CONV_PACKS = {}
+
+
+def _drop_conv_pack(wid: int, ref) -> None:
+    hit = _CONV_PACKS.get(wid)
+    if hit is not None and hit[0] is ref:       # (ids are reused after a free: only the entry of THIS tensor)
+        del _CONV_PACKS[wid]
+
+
+def conv3x3_weights(weight: torch.Tensor) -> Conv3x3Weights:
+    """The pack cache that belongs to `weight` (a Parameter, or any tensor the caller keeps alive)."""
+    wid = id(weight)
+    hit = _CONV_PACKS.get(wid)
+    if hit is None or hit[0]() is not weight:
+        hit = (weakref.ref(weight, functools.partial(_drop_conv_pack, wid)), Conv3x3Weights())
+        _CONV_PACKS[wid] = hit
+    return hit[1]
+
+
+def _conv_form(form: str) -> str:
+    if form not in CONV_FORMS:
+        raise _lib.DlwpError(f"unknown conv form {form!r} (one of {CONV_FORMS})")
+    return form
+
+
 def conv3x3_cyl(x0: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], act: int = 0,
-                x1: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """CylinderPad(1) + Conv2d(3x3) + bias + activation on cat([x0, x1], 1) without the cat."""
+                x1: Optional[torch.Tensor] = None, form: str = "direct") -> torch.Tensor:
+    """CylinderPad(1) + Conv2d(3x3) + bias + activation on cat([x0, x1], 1) without the cat.  `form`: CONV_FORMS."""
     from . import training as _T
-    if _T.wants_grad(x0, x1, weight, bias):
-        return conv3x3(x0, weight, bias, act=act, x1=x1)
+    if _conv_form(form) != "direct" or _T.wants_grad(x0, x1, weight, bias):      # (conv3x3 ignores `form` under autograd)
+        return conv3x3(x0, weight, bias, act=act, x1=x1, form=form)
     _lib.require_cuda_tensor(x0, "x0")
     _lib.require_cuda_tensor(x1, "x1")
     _lib.require_cuda_tensor(weight, "weight")
@@ -220,12 +281,12 @@ def conv3x3_cyl(x0: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Ten
 
 
 def conv3x3_hpx(x0: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], act: int = 0,
-                x1: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """HEALPixPadding(1) + Conv2d(3x3) + bias + activation on cat([x0, x1], 1); x [(B*12), C, H, W]."""
+                x1: Optional[torch.Tensor] = None, form: str = "direct") -> torch.Tensor:
+    """HEALPixPadding(1) + Conv2d(3x3) + bias + activation on cat([x0, x1], 1); x [(B*12), C, H, W].  `form`: CONV_FORMS."""
     from . import healpix as _hpx
     from . import training as _T
-    if _T.wants_grad(x0, x1, weight, bias):
-        return conv3x3(x0, weight, bias, act=act, x1=x1, hpx=True)
+    if _conv_form(form) != "direct" or _T.wants_grad(x0, x1, weight, bias):      # (conv3x3 ignores `form` under autograd)
+        return conv3x3(x0, weight, bias, act=act, x1=x1, hpx=True, form=form)
 
     _lib.require_cuda_tensor(x0, "x0")
     _lib.require_cuda_tensor(x1, "x1")
@@ -253,14 +314,18 @@ def conv3x3_hpx(x0: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Ten
 
 def conv3x3(x0: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], act: int = 0,
             x1: Optional[torch.Tensor] = None, pre_act: int = 0, resid: Optional[torch.Tensor] = None,
-            hpx: bool = False) -> torch.Tensor:
+            hpx: bool = False, form: str = "direct") -> torch.Tensor:
     """pad(1) + Conv2d(3x3) on cat([x0, x1], 1) with the input activation `pre_act` applied while staging and
-    `resid` added before `act`; padding rule: CylinderPad, or HEALPixPadding when hpx (x [(B*12), C, H, W])."""
+    `resid` added before `act`; padding rule: CylinderPad, or HEALPixPadding when hpx (x [(B*12), C, H, W]).
+    `form` (CONV_FORMS): "direct" the scalar-FMA kernel; "bf16x6" / "bf16" dlwp_conv3x3_mfma_f32 (inference only: with
+    gradients wanted every form runs the differentiable direct path)."""
+    _conv_form(form)
     for t, n in ((x0, "x0"), (x1, "x1"), (weight, "weight"), (resid, "resid")):
         _lib.require_cuda_tensor(t, n)
     from . import training as _T
     if _T.wants_grad(x0, x1, weight, bias, resid):
         return _T.conv3x3(x0, weight, bias, act=act, x1=x1, pre_act=pre_act, resid=resid, hpx=hpx)   # HIP forward, differentiable
+    owner = weight          # the pack belongs to the caller's tensor, not to a contiguous copy made below
     x0 = x0.contiguous()
     x1 = x1.contiguous() if x1 is not None else None
     weight = weight.contiguous()
@@ -280,6 +345,15 @@ def conv3x3(x0: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]
         table = _hpx.device_table(h, w, 1, x0.device)
     y = torch.empty(n, cout, h, w, device=x0.device, dtype=torch.float32)
     lib = _lib.load()
+    if form != "direct":
+        packed = conv3x3_weights(owner).get(owner)
+        with torch.cuda.device(x0.device):
+            _lib.check(lib.dlwp_conv3x3_mfma_f32(x0.data_ptr(), c0, x1.data_ptr() if x1 is not None else None, c1,
+                                                 packed.data_ptr(), bias.contiguous().data_ptr() if bias is not None else None,
+                                                 resid.data_ptr() if resid is not None else None, y.data_ptr(), n, h, w, cout,
+                                                 int(pre_act), int(act), table.data_ptr() if table is not None else None,
+                                                 CONV_FORMS.index(form) - 1, _lib.stream_ptr()), "dlwp_conv3x3_mfma_f32")
+        return y
     with torch.cuda.device(x0.device):
         _lib.check(lib.dlwp_conv3x3_ex_f32(x0.data_ptr(), c0, x1.data_ptr() if x1 is not None else None, c1, weight.data_ptr(),
                                            bias.contiguous().data_ptr() if bias is not None else None,

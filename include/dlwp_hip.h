@@ -379,6 +379,24 @@ int32_t dlwp_conv3x3_ex_f32(const float* x0_dev, int32_t c0, const float* x1_dev
                             const float* bias_dev, const float* resid_dev, float* y_dev, int32_t batch, int32_t height,
                             int32_t width, int32_t cout, int32_t pre_act, int32_t act, const int32_t* ring_table, void* stream);
 
+/* dlwp_conv3x3_ex_f32 as an implicit GEMM on the bf16 matrix instructions (csrc/conv_mfma.hip; same reference lines:
+ * utils/utils.py:11-26; models/unet/unet.py:456-470, :512-525, :553, :886, :901; models/convlstm/convlstm.py:47-55, :94,
+ * :148-157; utils/healpix.py:316-368).  The weight [cout, cin, 3, 3] is packed once into MFMA operand order (three bf16
+ * images, tap-major, cin zero-filled to 32 and cout to 16): dlwp_conv3x3_mfma_packed_bytes gives the size (0 = unsupported
+ * shape), dlwp_conv3x3_mfma_pack_f32 fills it.  form 0 "bf16x6": exact three-part bf16 splits of both operands, six products,
+ * fp32 accumulation -- fp32-grade; form 1 "bf16": RNE bf16 operands (first image only), fp32 accumulation.  Every other
+ * argument and check as dlwp_conv3x3_ex_f32; shapes whose per-sample offsets leave 32 bits return DLWP_ERR_UNSUPPORTED.
+ * One writer per output element: results are bit-identical from run to run.
+ * dlwp_conv3x3_mfma_variant names the kernel instance the launcher takes for a shape: 16 * tile width (16: 8 x 16 pixels,
+ * 8: 16 x 8) + output fragments per workgroup (4, 2 or 1); 0 for a non-positive size.  For tests and tools. */
+size_t dlwp_conv3x3_mfma_packed_bytes(int32_t cout, int32_t cin);
+int32_t dlwp_conv3x3_mfma_variant(int32_t batch, int32_t height, int32_t width, int32_t cout);
+int32_t dlwp_conv3x3_mfma_pack_f32(const float* weight_dev, int32_t cout, int32_t cin, void* packed_dev, void* stream);
+int32_t dlwp_conv3x3_mfma_f32(const float* x0_dev, int32_t c0, const float* x1_dev, int32_t c1, const void* packed_dev,
+                              const float* bias_dev, const float* resid_dev, float* y_dev, int32_t batch, int32_t height,
+                              int32_t width, int32_t cout, int32_t pre_act, int32_t act, const int32_t* ring_table,
+                              int32_t form, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * fp32 Linear layers on the bf16 matrix pipe with the block's pointwise work fused (csrc/linear.hip): the qkv / proj /
  * fc1 / fc2 Linears, GELU and residual adds of the Swin and Pangu blocks (swin_transformer.py:21-39, :107-120, :254-262;

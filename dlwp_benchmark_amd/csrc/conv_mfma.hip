@@ -16,31 +16,12 @@
 //   * A = weights, B = pixels: accumulator register r of lane l is channel 4 (l >> 4) + r of pixel l & 15, so a store
 //     instruction writes runs of 16 (or 8) consecutive pixels of the NCHW output.
 // No atomics, no split-K across workgroups: one writer per output, reruns are bit-identical.
-#include "common.hpp"
+#include "conv_mfma_common.hpp"
 
 namespace dlwp {
 namespace convm {
 
-enum Act { ACT_NONE = 0, ACT_GELU = 1, ACT_TANH = 2, ACT_RELU = 3, ACT_SILU = 4 };
-
-__device__ __forceinline__ float apply_act(float v, int act) {   // conv.hip's
-  switch (act) {
-    case ACT_GELU: return gelu_erf(v);
-    case ACT_TANH: return tanhf(v);
-    case ACT_RELU: return fmaxf(v, 0.f);
-    case ACT_SILU: return v / (1.f + __expf(-v));
-    default: return v;
-  }
-}
-
-constexpr int KSLAB = 32;    // input channels per K-slab: one v_mfma_f32_16x16x32_bf16 per tap and slab
-constexpr int HALO = 180;    // (8 + 2) * (16 + 2) = (16 + 2) * (8 + 2) halo pixels
-// dwords per halo pixel in LDS (16 hold the 32 channels).  24: the four 16-lane groups of a ds_read_b128 (lanes
-// {0-3, 12-15, 20-27}, ...) then start at bank (6 i + g) * 4 mod 64 for pixel i, channel group g -- even for one g, odd for
-// the other, all distinct over a row of 16 pixels: the tap reads of the 8 x 16 tile are conflict-free (16 would be 4-way,
-// 20 2-way).  In the 16 x 8 tile a fragment is two rows of 8 pixels, 10 halo pixels apart: lanes 0-3 and 12-15 of a group
-// then meet 2-way.  The staging stores are 16-byte stores of consecutive pixels, the same address pattern as the reads.
-constexpr int PS = 24;
+constexpr int HALO = 180;    // (8 + 2) * (16 + 2) = (16 + 2) * (8 + 2) halo pixels; PS dwords each (conv_mfma_common.hpp)
 
 struct Params {
   const float* x0; int c0;   // first input segment [B][c0][H][W]
@@ -138,13 +119,7 @@ __global__ __launch_bounds__(256) void conv3x3_mfma_kernel(const Params p) {
 #pragma unroll
       for (int q = 0; q < 8; ++q) v[q] = e.x >= 0 ? fetch(p, e, c + q, HW) : 0.f;   // padding zeros stay zero (act(0) = 0)
       u32x4 part[3];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        unsigned h, m, l;
-        if (NIMG == 3) split3_pair(v[2 * q], v[2 * q + 1], h, m, l);
-        else { h = cvt_pk_bf16(v[2 * q], v[2 * q + 1]); m = 0u; l = 0u; }
-        part[0][q] = h; part[1][q] = m; part[2][q] = l;
-      }
+      convert_group<NIMG>(v, part);
 #pragma unroll
       for (int q = 0; q < NIMG; ++q) *reinterpret_cast<u32x4*>(&s_x[q][pix * PS + kg * 4]) = part[q];
     }
@@ -211,11 +186,7 @@ __global__ __launch_bounds__(256) void conv3x3_mfma_pack_kernel(const float* __r
     const int tap = (int)(rest / kslabs);
     const int co = nf * 16 + (lane & 15), c = ks * KSLAB + 8 * (lane >> 4) + e;
     const float v = (co < cout && c < cin) ? w[((long long)co * cin + c) * 9 + tap] : 0.f;
-    unsigned h, m, l;
-    split3_pair(v, 0.f, h, m, l);
-    out[i] = (unsigned short)(h & 0xffffu);
-    out[total + i] = (unsigned short)(m & 0xffffu);
-    out[2 * total + i] = (unsigned short)(l & 0xffffu);
+    pack_store(v, out, i, total);
   }
 }
 

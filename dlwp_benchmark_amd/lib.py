@@ -128,6 +128,13 @@ SIGNATURES = {
     "dlwp_conv3x3_mfma_pack_f32": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "dlwp_conv3x3_mfma_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                         c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
+    "dlwp_conv2d_mfma_packed_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "dlwp_conv2d_mfma_variant": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "dlwp_conv2d_mfma_pack_f32": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "dlwp_conv2d_mfma_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                       c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "dlwp_conv_transpose2d_mfma_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                                 c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "dlwp_linear_packed_bytes": (c_size_t, [c_int32, c_int32]),
     "dlwp_linear_pack_f32": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "dlwp_linear_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int32, c_int32, c_int32,

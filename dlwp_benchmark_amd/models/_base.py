@@ -78,6 +78,19 @@ class HipBackbone(torch.nn.Module):
         self._set_on_submodules("conv_form", form)
         return self
 
+    def set_aux_conv_form(self, form: str):
+        """The family's other convolutions (1x1 shortcuts and heads, strided Conv2d, ConvTranspose2d -- everything that runs
+        through ops.conv2d / ops.conv_transpose2d / ops.small_module): "direct" (default; one thread per output,
+        dlwp_conv2d_f32 / dlwp_conv_transpose2d_f32), "bf16x6" or "bf16" (dlwp_conv2d_mfma_f32 /
+        dlwp_conv_transpose2d_mfma_f32, the arithmetic of set_conv_form's forms).  Also the constructor kwarg `aux_conv_form`.
+        A knob of its own: set_conv_form and set_compute_precision leave it alone.  Inference only."""
+        from .. import ops
+
+        if form not in ops.CONV_FORMS:
+            raise _lib.DlwpError(f"unknown conv form {form!r} (one of {ops.CONV_FORMS})")
+        self._set_on_submodules("aux_conv_form", form)
+        return self
+
     def set_compute_precision(self, name: str):
         """ONE knob over the four above -- also the constructor kwarg `compute_precision` (a key the reference ignores:
         every reference constructor swallows unknown keys through **kwargs, so a config that carries it still builds
@@ -99,6 +112,9 @@ class HipBackbone(torch.nn.Module):
         self.compute_precision = "fp32"
         if cp is not None:
             self.set_compute_precision(str(cp))
+        aux = kwargs.get("aux_conv_form")       # a key of this project, swallowed by the reference constructors like the one above
+        if aux is not None:
+            self.set_aux_conv_form(str(aux))
 
     def invalidate_packed(self):
         """Derived operands (packed bf16 / f16 weight images, FNO plans, step graphs) are keyed on (data_ptr, _version) of

@@ -111,6 +111,7 @@ class ResidualBlock(nn.Module):
         self.use_scale_shift_norm = use_scale_shift_norm
         self.mesh = mesh
         self.conv_form = "direct"       # ops.CONV_FORMS, set through HipBackbone.set_conv_form / set_compute_precision
+        self.aux_conv_form = "direct"   # ops.CONV_FORMS of the 1x1 shortcut, set through HipBackbone.set_aux_conv_form
         self.cylinder_pad = HEALPixPadding(padding=1) if mesh == "healpix" else CylinderPad(padding)
         self.conv1 = nn.Conv2d(in_channels, out_channels, kernel_size=3, padding=0)
         self.conv2 = _zero_module(nn.Conv2d(out_channels, out_channels, kernel_size=3, padding=0))
@@ -125,7 +126,8 @@ class ResidualBlock(nn.Module):
         gelu = ops.act_code(self.activation)
         hpx, form = self.mesh == "healpix", self.conv_form
         x = x.contiguous()
-        short = x if isinstance(self.shortcut, nn.Identity) else ops.conv2d(x, self.shortcut.weight, self.shortcut.bias)
+        short = x if isinstance(self.shortcut, nn.Identity) else \
+            ops.conv2d(x, self.shortcut.weight, self.shortcut.bias, form=self.aux_conv_form)
         n1, n2 = self.norm1, self.norm2
         if isinstance(n1, nn.Identity):
             h = ops.conv3x3(x, self.conv1.weight, self.conv1.bias, pre_act=gelu, hpx=hpx, form=form)
@@ -204,13 +206,14 @@ class ModernUNetEncoder(nn.Module):
             layer.append(self.attn)
             layers.append(nn.Sequential(*layer))
         self.layers = nn.ModuleList(layers)
+        self.aux_conv_form = "direct"
 
     def forward(self, x, emb):
         outs = []
         for layer in self.layers:
             for m in layer:
                 if isinstance(m, nn.Conv2d):
-                    x = ops.small_module(m, x)
+                    x = ops.small_module(m, x, form=self.aux_conv_form)
                 elif isinstance(m, AttentionBlock):
                     x = m(x)
                 elif not isinstance(m, nn.Identity):
@@ -239,6 +242,7 @@ class ModernUNetDecoder(nn.Module):
         self.layers = nn.ModuleList(layers)
         self.output_layer = _zero_module(nn.Conv2d(hidden[-1], out_channels, kernel_size=1))
         self.final_norm = nn.GroupNorm(4, hidden[-1])
+        self.aux_conv_form = "direct"
 
     def forward(self, x, skips, emb):
         for i, layer in enumerate(self.layers):
@@ -246,14 +250,14 @@ class ModernUNetDecoder(nn.Module):
                 x = torch.cat([skips[i], x], dim=1)
             for m in layer:
                 if isinstance(m, nn.ConvTranspose2d):
-                    x = ops.small_module(m, x)
+                    x = ops.small_module(m, x, form=self.aux_conv_form)
                 elif isinstance(m, AttentionBlock):
                     x = m(x)
                 elif not isinstance(m, nn.Identity):
                     x = m(x, emb)
         fn = self.final_norm
         x = ops.groupnorm_act(x, fn.weight, fn.bias, fn.num_groups, fn.eps, ops.act_code(self.activation))
-        return ops.small_module(self.output_layer, x)
+        return ops.small_module(self.output_layer, x, form=self.aux_conv_form)
 
 
 class DiffModernUNet(HipBackbone):

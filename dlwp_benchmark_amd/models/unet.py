@@ -92,6 +92,7 @@ class ResidualBlock(nn.Module):
             raise NotImplementedError("ResidualBlock: only GELU (the reference default) is wired to the fused kernels")
         self.activation = activation
         self.conv_form = "direct"
+        self.aux_conv_form = "direct"   # ops.CONV_FORMS of the 1x1 shortcut, set through HipBackbone.set_aux_conv_form
         self.mesh = mesh
         # unet.py:867-872: HEALPixPadding on the HEALPix mesh, CylinderPad otherwise; either way the padding happens
         # inside the fused convolution kernel
@@ -112,7 +113,8 @@ class ResidualBlock(nn.Module):
         gelu = ops.act_code(self.activation)
         hpx, form = self.mesh == "healpix", self.conv_form
         x = x.contiguous()
-        short = x if isinstance(self.shortcut, nn.Identity) else ops.conv2d(x, self.shortcut.weight, self.shortcut.bias)
+        short = x if isinstance(self.shortcut, nn.Identity) else \
+            ops.conv2d(x, self.shortcut.weight, self.shortcut.bias, form=self.aux_conv_form)
         n1, n2 = self.norm1, self.norm2
         if isinstance(n1, nn.Identity):
             h, pre = x, gelu
@@ -154,11 +156,12 @@ def _resolve_activation(activation):
 _STRUCTURAL = (CylinderPad, HEALPixLayer, nn.Conv2d, nn.ConvTranspose2d, nn.AvgPool2d)
 
 
-def _run_stack(seq: nn.Sequential, x, skip=None, form: str = "direct"):
+def _run_stack(seq: nn.Sequential, x, skip=None, form: str = "direct", aux_form: str = "direct"):
     """Executes a reference-shaped Sequential of [AvgPool] (CylinderPad, Conv2d, act)* [ConvTranspose2d]
     with each (pad, conv, act) triple fused into one kernel call; `skip` is concatenated in front
     of x for the first conv (torch.cat([skip, x], 1), unet.py:553).  `form` is the caller's conv_form for the
-    CylinderPad triples; a HEALPixLayer carries its own."""
+    CylinderPad triples; a HEALPixLayer carries its own.  `aux_form` is the caller's aux_conv_form for the layers that go
+    through ops.small_module."""
     mods = list(seq)
     i = 0
     while i < len(mods):
@@ -187,7 +190,7 @@ def _run_stack(seq: nn.Sequential, x, skip=None, form: str = "direct"):
             if skip is not None:
                 x = torch.cat([skip, x], dim=1)
                 skip = None
-            x = ops.small_module(m, x)      # AvgPool2d(2) / ConvTranspose2d / plain Conv2d: HIP kernels, no torch op
+            x = ops.small_module(m, x, form=aux_form)      # AvgPool2d(2) / ConvTranspose2d / plain Conv2d: HIP kernels, no torch op
             i += 1
     return x
 
@@ -214,11 +217,12 @@ class _UNetEncoder(nn.Module):
             layers.append(nn.Sequential(*layer))
         self.layers = nn.ModuleList(layers)
         self.conv_form = "direct"
+        self.aux_conv_form = "direct"
 
     def forward(self, x):
         outs = []
         for layer in self.layers:
-            x = _run_stack(layer, x, form=self.conv_form)
+            x = _run_stack(layer, x, form=self.conv_form, aux_form=self.aux_conv_form)
             outs.append(x)
         return outs
 
@@ -242,11 +246,12 @@ class _UNetDecoder(nn.Module):
         self.layers = nn.ModuleList(layers)
         self.output_layer = nn.Conv2d(c_out, out_channels, kernel_size=1)
         self.conv_form = "direct"
+        self.aux_conv_form = "direct"
 
     def forward(self, x, skips):
         for l_idx, layer in enumerate(self.layers):
-            x = _run_stack(layer, x, skip=skips[l_idx] if l_idx > 0 else None, form=self.conv_form)
-        return ops.small_module(self.output_layer, x)
+            x = _run_stack(layer, x, skip=skips[l_idx] if l_idx > 0 else None, form=self.conv_form, aux_form=self.aux_conv_form)
+        return ops.small_module(self.output_layer, x, form=self.aux_conv_form)
 
 
 class UNet(HipBackbone):
@@ -354,10 +359,11 @@ class _ModernUNetEncoder(nn.Module):
             first = nn.Conv2d(c_in, c_in, (3, 3), (2, 2), (1, 1)) if c_idx > 0 else nn.Conv2d(c_in, c_in, (1, 1), (1, 1), (0, 0))
             layers.append(nn.Sequential(first, _res_layer(c_in, c_out, mesh), self.attn))
         self.layers = nn.ModuleList(layers)
+        self.aux_conv_form = "direct"
 
     def forward(self, x):
         for layer in self.layers:
-            x = layer[1](ops.small_module(layer[0], x))    # strided 3x3 / 1x1 convolution, then the residual block
+            x = layer[1](ops.small_module(layer[0], x, form=self.aux_conv_form))    # strided 3x3 / 1x1 convolution, then the residual block
         return x
 
 
@@ -387,14 +393,15 @@ class _ModernUNetDecoder(nn.Module):
         with torch.no_grad():   # zero_module
             self.output_layer.weight.zero_(), self.output_layer.bias.zero_()
         self.final_norm = nn.GroupNorm(8, final_out)
+        self.aux_conv_form = "direct"
 
     def forward(self, x):
         for layer in self.layers:
             for sub in layer:
-                x = ops.small_module(sub, x) if isinstance(sub, nn.ConvTranspose2d) else sub(x)
+                x = ops.small_module(sub, x, form=self.aux_conv_form) if isinstance(sub, nn.ConvTranspose2d) else sub(x)
         fn = self.final_norm
         x = ops.groupnorm_act(x, fn.weight, fn.bias, fn.num_groups, fn.eps, ops.act_code(self.activation))
-        return ops.small_module(self.output_layer, x)
+        return ops.small_module(self.output_layer, x, form=self.aux_conv_form)
 
 
 class MUNetHPX(UNetHPX):

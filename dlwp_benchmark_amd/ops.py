@@ -195,6 +195,7 @@ def act_code(activation) -> int:
 
 # forms of pad(1) + Conv2d(3x3): "direct" (default) is the scalar-FMA kernel of csrc/conv.hip; "bf16x6" / "bf16" are the
 # implicit GEMM of csrc/conv_mfma.hip on the bf16 matrix instructions (fp32-grade three-part splits / RNE bf16 operands)
+# -- and of conv2d / conv_transpose2d / small_module, whose "direct" is csrc/conv2.hip and whose matrix forms are csrc/conv2_mfma.hip
 CONV_FORMS = ("direct", "bf16x6", "bf16")
 
 
@@ -245,6 +246,56 @@ def conv3x3_weights(weight: torch.Tensor) -> Conv3x3Weights:
     if hit is None or hit[0]() is not weight:
         hit = (weakref.ref(weight, functools.partial(_drop_conv_pack, wid)), Conv3x3Weights())
         _CONV_PACKS[wid] = hit
+    return hit[1]
+
+
+class Conv2dWeights:
+    """A k x k convolution weight ([cout, cin, k, k]; transposed: ConvTranspose2d's [cin, cout, k, k]) in the MFMA operand
+    layout dlwp_conv2d_mfma_f32 / dlwp_conv_transpose2d_mfma_f32 read: Conv3x3Weights' rule for csrc/conv2_mfma.hip."""
+
+    def __init__(self, transposed: bool):
+        self._key = None
+        self._buf = None
+        self._transposed = bool(transposed)
+
+    def get(self, weight: torch.Tensor) -> torch.Tensor:
+        key = (weight.data_ptr(), weight._version, str(weight.device), pack_epoch())
+        if key != self._key:
+            if torch.cuda.is_current_stream_capturing():
+                raise _lib.DlwpError("conv2d: the weight pack must be made before a graph capture (run one eager step first)")
+            cout, cin = (weight.shape[1], weight.shape[0]) if self._transposed else weight.shape[:2]
+            k = weight.shape[2]
+            lib = _lib.load()
+            nbytes = int(lib.dlwp_conv2d_mfma_packed_bytes(cout, cin, k))
+            if nbytes == 0:
+                raise _lib.DlwpError(f"conv2d: unsupported shape cout={cout} cin={cin} k={k} for the matrix-pipe forms")
+            buf = torch.empty(nbytes // 4, dtype=torch.int32, device=weight.device)
+            with torch.cuda.device(weight.device):
+                _lib.check(lib.dlwp_conv2d_mfma_pack_f32(weight.detach().contiguous().data_ptr(), cout, cin, k,
+                                                         int(self._transposed), buf.data_ptr(), _lib.stream_ptr()),
+                           "dlwp_conv2d_mfma_pack_f32")
+            self._key, self._buf = key, buf
+        return self._buf
+
+
+# (id(weight), transposed) -> (weak reference, Conv2dWeights): the rule of _CONV_PACKS; the layout flag is part of the key, so
+# a ConvTranspose2d weight and a Conv2d weight of the same shape never share a pack
+_CONV2D_PACKS = {}
+
+
+def _drop_conv2d_pack(key, ref) -> None:
+    hit = _CONV2D_PACKS.get(key)
+    if hit is not None and hit[0] is ref:
+        del _CONV2D_PACKS[key]
+
+
+def conv2d_weights(weight: torch.Tensor, transposed: bool = False) -> Conv2dWeights:
+    """The pack cache of ops.conv2d (transposed: of ops.conv_transpose2d) that belongs to `weight`."""
+    key = (id(weight), bool(transposed))
+    hit = _CONV2D_PACKS.get(key)
+    if hit is None or hit[0]() is not weight:
+        hit = (weakref.ref(weight, functools.partial(_drop_conv2d_pack, key)), Conv2dWeights(transposed))
+        _CONV2D_PACKS[key] = hit
     return hit[1]
 
 
@@ -384,14 +435,18 @@ def groupnorm_act(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optiona
 
 
 def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], stride: int = 1, padding: int = 0,
-           pre_act: int = 0, act: int = 0, resid: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """zero-padded Conv2d (square kernel / stride / padding): the strided and 1x1 convolutions of unet.py:583-584, :879, :450."""
+           pre_act: int = 0, act: int = 0, resid: Optional[torch.Tensor] = None, form: str = "direct") -> torch.Tensor:
+    """zero-padded Conv2d (square kernel / stride / padding): the strided and 1x1 convolutions of unet.py:583-584, :879, :450.
+    `form` (CONV_FORMS): "direct" the one-thread-per-output kernel; "bf16x6" / "bf16" dlwp_conv2d_mfma_f32 (k <= 4, stride 1 or 2,
+    padding < k; anything else raises.  Inference only: with gradients wanted every form runs the differentiable torch path)."""
+    _conv_form(form)
     for t, n in ((x, "x"), (weight, "weight"), (resid, "resid")):
         _lib.require_cuda_tensor(t, n)
     from . import training as _T
     if _T.wants_grad(x, weight, bias, resid):
         y = torch.nn.functional.conv2d(_T._ACT_FNS[int(pre_act)](x), weight, bias, stride=stride, padding=padding)
         return _T._ACT_FNS[int(act)](y if resid is None else y + resid)
+    owner = weight          # the pack belongs to the caller's tensor, not to a contiguous copy made below
     x, weight = x.contiguous(), weight.contiguous()
     n, cin, h, w = x.shape
     cout, cin_w, k, k2 = weight.shape
@@ -402,6 +457,15 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], 
         raise _lib.DlwpError("conv2d: resid must be contiguous and shaped like the output")
     y = torch.empty(n, cout, oh, ow, device=x.device, dtype=torch.float32)
     lib = _lib.load()
+    if form != "direct":
+        packed = conv2d_weights(owner).get(owner)
+        with torch.cuda.device(x.device):
+            _lib.check(lib.dlwp_conv2d_mfma_f32(x.data_ptr(), packed.data_ptr(),
+                                                bias.contiguous().data_ptr() if bias is not None else None,
+                                                resid.data_ptr() if resid is not None else None, y.data_ptr(), n, cin, h, w, cout,
+                                                k, int(stride), int(padding), int(pre_act), int(act),
+                                                CONV_FORMS.index(form) - 1, _lib.stream_ptr()), "dlwp_conv2d_mfma_f32")
+        return y
     with torch.cuda.device(x.device):
         _lib.check(lib.dlwp_conv2d_f32(x.data_ptr(), weight.data_ptr(), bias.contiguous().data_ptr() if bias is not None else None,
                                        resid.data_ptr() if resid is not None else None, y.data_ptr(), n, cin, h, w, cout, k,
@@ -410,13 +474,17 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], 
 
 
 def conv_transpose2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], stride: int, padding: int = 0,
-                     act: int = 0) -> torch.Tensor:
-    """ConvTranspose2d (weight [cin, cout, k, k]; unet.py:523 2x2 s2, :719 4x4 s2 p1)."""
+                     act: int = 0, form: str = "direct") -> torch.Tensor:
+    """ConvTranspose2d (weight [cin, cout, k, k]; unet.py:523 2x2 s2, :719 4x4 s2 p1).  `form` (CONV_FORMS): "direct" the
+    one-thread-per-output kernel; "bf16x6" / "bf16" dlwp_conv_transpose2d_mfma_f32 (exactly those two geometries; anything else
+    raises.  Inference only: with gradients wanted every form runs the differentiable torch path)."""
+    _conv_form(form)
     _lib.require_cuda_tensor(x, "x")
     _lib.require_cuda_tensor(weight, "weight")
     from . import training as _T
     if _T.wants_grad(x, weight, bias):
         return _T._ACT_FNS[int(act)](torch.nn.functional.conv_transpose2d(x, weight, bias, stride=stride, padding=padding))
+    owner = weight
     x, weight = x.contiguous(), weight.contiguous()
     n, cin, h, w = x.shape
     cin_w, cout, k, k2 = weight.shape
@@ -425,6 +493,15 @@ def conv_transpose2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch
     oh, ow = (h - 1) * stride - 2 * padding + k, (w - 1) * stride - 2 * padding + k
     y = torch.empty(n, cout, oh, ow, device=x.device, dtype=torch.float32)
     lib = _lib.load()
+    if form != "direct":
+        packed = conv2d_weights(owner, transposed=True).get(owner)
+        with torch.cuda.device(x.device):
+            _lib.check(lib.dlwp_conv_transpose2d_mfma_f32(x.data_ptr(), packed.data_ptr(),
+                                                          bias.contiguous().data_ptr() if bias is not None else None,
+                                                          y.data_ptr(), n, cin, h, w, cout, k, int(stride), int(padding),
+                                                          int(act), CONV_FORMS.index(form) - 1, _lib.stream_ptr()),
+                       "dlwp_conv_transpose2d_mfma_f32")
+        return y
     with torch.cuda.device(x.device):
         _lib.check(lib.dlwp_conv_transpose2d_f32(x.data_ptr(), weight.data_ptr(),
                                                  bias.contiguous().data_ptr() if bias is not None else None, y.data_ptr(), n,
@@ -447,9 +524,11 @@ def avgpool2x2(x: torch.Tensor) -> torch.Tensor:
     return y
 
 
-def small_module(m: torch.nn.Module, x: torch.Tensor, act: int = 0) -> torch.Tensor:
+def small_module(m: torch.nn.Module, x: torch.Tensor, act: int = 0, form: str = "direct") -> torch.Tensor:
     """Runs one of the U-Net family's non-3x3 layers through its HIP kernel: AvgPool2d(2), ConvTranspose2d, Conv2d
-    (zero padding, square); raises for anything else so that nothing silently falls back to a torch op."""
+    (zero padding, square); raises for anything else so that nothing silently falls back to a torch op.  `form` (CONV_FORMS)
+    goes to conv2d / conv_transpose2d; AvgPool2d has one kernel and ignores it."""
+    _conv_form(form)
     nn = torch.nn
     if isinstance(m, nn.AvgPool2d):
         k = m.kernel_size if isinstance(m.kernel_size, int) else m.kernel_size[0]
@@ -461,12 +540,12 @@ def small_module(m: torch.nn.Module, x: torch.Tensor, act: int = 0) -> torch.Ten
         if m.kernel_size[0] != m.kernel_size[1] or m.stride[0] != m.stride[1] or m.padding[0] != m.padding[1] or \
                 m.output_padding != (0, 0) or m.dilation != (1, 1) or m.groups != 1:
             raise _lib.DlwpError("ConvTranspose2d: only square kernel / stride / padding without output_padding, dilation, groups")
-        return conv_transpose2d(x, m.weight, m.bias, m.stride[0], m.padding[0], act)
+        return conv_transpose2d(x, m.weight, m.bias, m.stride[0], m.padding[0], act, form=form)
     if isinstance(m, nn.Conv2d):
         if m.kernel_size[0] != m.kernel_size[1] or m.stride[0] != m.stride[1] or m.padding[0] != m.padding[1] or \
                 m.dilation != (1, 1) or m.groups != 1 or m.padding_mode != "zeros":
             raise _lib.DlwpError("Conv2d: only square kernel / stride / zero padding without dilation or groups")
-        return conv2d(x, m.weight, m.bias, m.stride[0], m.padding[0], act=act)
+        return conv2d(x, m.weight, m.bias, m.stride[0], m.padding[0], act=act, form=form)
     raise _lib.DlwpError(f"no HIP kernel for {type(m).__name__}")
 
 

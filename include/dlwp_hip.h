@@ -397,6 +397,31 @@ int32_t dlwp_conv3x3_mfma_f32(const float* x0_dev, int32_t c0, const float* x1_d
                               int32_t width, int32_t cout, int32_t pre_act, int32_t act, const int32_t* ring_table,
                               int32_t form, void* stream);
 
+/* dlwp_conv2d_f32 and dlwp_conv_transpose2d_f32 as implicit GEMMs on the bf16 matrix instructions (csrc/conv2_mfma.hip; the
+ * same reference lines: models/unet/unet.py:583 (3x3, stride 2, zero padding 1), :584 and :879-881 (1x1), :450 / :533 (1x1
+ * head) for the convolution, :719 (4x4, stride 2, padding 1) and :523 (2x2, stride 2) for the transposed one).  The weight
+ * ([cout, cin, k, k]; transposed != 0: [cin, cout, k, k]) is packed once into MFMA operand order, [image][tap][slab][16-channel
+ * fragment][lane][8 bf16] for the k * k taps, cin zero-filled to 32 and cout to 16: dlwp_conv2d_mfma_packed_bytes gives the
+ * size, 3 * k^2 * ceil(cin / 32) * ceil(cout / 16) * 1024 (0 = unsupported: a non-positive size, k > 4, or 2 GiB and more),
+ * dlwp_conv2d_mfma_pack_f32 fills it.  form 0 "bf16x6" / 1 "bf16" as dlwp_conv3x3_mfma_f32; every other argument as the direct
+ * entries.  Geometries: the convolution takes k <= 4, stride 1 or 2, pad < k; the transposed one k = 4 s = 2 p = 1 and
+ * k = 2 s = 2 p = 0 (y_dev 8-byte aligned); anything else, and shapes whose per-sample offsets leave 32 bits, return
+ * DLWP_ERR_UNSUPPORTED before any launch.  One writer per output element: results are bit-identical from run to run.
+ * dlwp_conv2d_mfma_variant names the kernel instance a launcher takes: 16 * fragment width (16: rows of 16 GEMM pixels, 8: two
+ * rows of 8) + output fragments per workgroup (4, 2 or 1; stride-2 convolutions 4 or 2); 0 for arguments the launcher
+ * refuses.  For tests and tools. */
+size_t dlwp_conv2d_mfma_packed_bytes(int32_t cout, int32_t cin, int32_t k);
+int32_t dlwp_conv2d_mfma_variant(int32_t transposed, int32_t batch, int32_t height, int32_t width, int32_t cout, int32_t k,
+                                 int32_t stride, int32_t pad);
+int32_t dlwp_conv2d_mfma_pack_f32(const float* weight_dev, int32_t cout, int32_t cin, int32_t k, int32_t transposed,
+                                  void* packed_dev, void* stream);
+int32_t dlwp_conv2d_mfma_f32(const float* x_dev, const void* packed_dev, const float* bias_dev, const float* resid_dev,
+                             float* y_dev, int32_t batch, int32_t cin, int32_t height, int32_t width, int32_t cout, int32_t k,
+                             int32_t stride, int32_t pad, int32_t pre_act, int32_t act, int32_t form, void* stream);
+int32_t dlwp_conv_transpose2d_mfma_f32(const float* x_dev, const void* packed_dev, const float* bias_dev, float* y_dev,
+                                       int32_t batch, int32_t cin, int32_t height, int32_t width, int32_t cout, int32_t k,
+                                       int32_t stride, int32_t pad, int32_t act, int32_t form, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * fp32 Linear layers on the bf16 matrix pipe with the block's pointwise work fused (csrc/linear.hip): the qkv / proj /
  * fc1 / fc2 Linears, GELU and residual adds of the Swin and Pangu blocks (swin_transformer.py:21-39, :107-120, :254-262;

@@ -1,0 +1,97 @@
+// Host-side check of the argument checks of csrc/conv2_mfma.hip: a stand-alone program that calls the packed-size and variant
+// entries and the three launch entries with bad and oversized shapes.  Every such call returns before any launch, so the
+// program needs no GPU; build it with the host sanitizers and run it directly:
+//
+//   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
+//         -I include tools/check_conv2_mfma_args.cpp dlwp_benchmark_amd/csrc/conv2_mfma.hip dlwp_benchmark_amd/csrc/core.hip \
+//         -o check_conv2_mfma_args && ./check_conv2_mfma_args
+//
+// Exit status 0 and "ok" on success; a sanitizer report or a failed expectation otherwise.
+#include <cstdint>
+#include <cstdio>
+
+#include "dlwp_hip.h"
+
+static int failures = 0;
+
+#define EXPECT(expr, want)                                                                       \
+  do {                                                                                           \
+    const long long got_ = (long long)(expr);                                                    \
+    if (got_ != (long long)(want)) {                                                             \
+      std::printf("%s:%d: %s = %lld, expected %lld\n", __FILE__, __LINE__, #expr, got_, (long long)(want)); \
+      ++failures;                                                                                \
+    }                                                                                            \
+  } while (0)
+
+int main() {
+  // the pointers are never dereferenced on the host and no call below reaches a launch
+  static float dummy[16];
+  float* x = dummy;
+  void* pk = dummy;
+  const int32_t big = 0x7fffffff;
+
+  EXPECT(dlwp_conv2d_mfma_packed_bytes(136, 272, 1), 3ll * 9 * 9 * 1024);
+  EXPECT(dlwp_conv2d_mfma_packed_bytes(17, 33, 4), 3ll * 16 * 2 * 2 * 1024);
+  EXPECT(dlwp_conv2d_mfma_packed_bytes(1, 1, 1), 3 * 1024);
+  EXPECT(dlwp_conv2d_mfma_packed_bytes(0, 8, 1), 0);
+  EXPECT(dlwp_conv2d_mfma_packed_bytes(8, -1, 1), 0);
+  EXPECT(dlwp_conv2d_mfma_packed_bytes(8, 8, 0), 0);
+  EXPECT(dlwp_conv2d_mfma_packed_bytes(8, 8, 5), 0);
+  EXPECT(dlwp_conv2d_mfma_packed_bytes(big, big, 4), 0);
+  EXPECT(dlwp_conv2d_mfma_packed_bytes(1 << 20, 1 << 20, 1), 0);
+
+  EXPECT(dlwp_conv2d_mfma_variant(0, 384, 32, 32, 136, 1, 1, 0), 16 * 16 + 4);
+  EXPECT(dlwp_conv2d_mfma_variant(0, 12, 8, 8, 6, 3, 2, 1), 8 * 16 + 2);
+  EXPECT(dlwp_conv2d_mfma_variant(1, 384, 16, 16, 272, 4, 2, 1), 16 * 16 + 4);
+  EXPECT(dlwp_conv2d_mfma_variant(1, 1, 8, 16, 8, 2, 2, 0), 16 * 16 + 1);
+  EXPECT(dlwp_conv2d_mfma_variant(0, 0, 8, 8, 8, 1, 1, 0), 0);
+  EXPECT(dlwp_conv2d_mfma_variant(0, 1, 8, 8, 8, 3, 3, 1), 0);
+  EXPECT(dlwp_conv2d_mfma_variant(0, 1, 2, 2, 8, 4, 1, 0), 0);
+  EXPECT(dlwp_conv2d_mfma_variant(1, 1, 8, 8, 8, 3, 2, 1), 0);
+  EXPECT(dlwp_conv2d_mfma_variant(0, big, big, big, big, 1, 1, 0), 0);
+  EXPECT(dlwp_conv2d_mfma_variant(1, big, big, big, big, 4, 2, 1), 0);
+  EXPECT(dlwp_conv2d_mfma_variant(0, big, 46000, 46000, big, 4, 2, 3) > 0, 1);      // the largest grid the rule is asked about
+  EXPECT(dlwp_conv2d_mfma_variant(0, 1, big, 1, 1, 4, 2, 3), 0);
+
+  EXPECT(dlwp_conv2d_mfma_pack_f32(nullptr, 8, 8, 1, 0, pk, nullptr), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(dlwp_conv2d_mfma_pack_f32(x, 8, 8, 5, 0, pk, nullptr), DLWP_ERR_UNSUPPORTED);
+  EXPECT(dlwp_conv2d_mfma_pack_f32(x, big, big, 4, 1, pk, nullptr), DLWP_ERR_UNSUPPORTED);
+
+  auto conv = [&](int32_t batch, int32_t cin, int32_t H, int32_t W, int32_t cout, int32_t k, int32_t s, int32_t p, int32_t form) {
+    return dlwp_conv2d_mfma_f32(x, pk, nullptr, nullptr, x, batch, cin, H, W, cout, k, s, p, 0, 0, form, nullptr);
+  };
+  auto tconv = [&](int32_t batch, int32_t cin, int32_t H, int32_t W, int32_t cout, int32_t k, int32_t s, int32_t p, int32_t form) {
+    return dlwp_conv_transpose2d_mfma_f32(x, pk, nullptr, x, batch, cin, H, W, cout, k, s, p, 0, form, nullptr);
+  };
+  EXPECT(dlwp_conv2d_mfma_f32(nullptr, pk, nullptr, nullptr, x, 1, 4, 8, 8, 4, 1, 1, 0, 0, 0, 0, nullptr), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(dlwp_conv2d_mfma_f32(x, pk, nullptr, nullptr, x, 1, 4, 8, 8, 4, 1, 1, 0, 5, 0, 0, nullptr), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(conv(0, 4, 8, 8, 4, 1, 1, 0, 0), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(conv(1, 4, 8, 8, 4, 1, 1, 0, 2), DLWP_ERR_INVALID_ARGUMENT);            // unknown form
+  EXPECT(conv(1, 4, 2, 2, 4, 4, 1, 0, 0), DLWP_ERR_INVALID_ARGUMENT);            // empty output
+  EXPECT(conv(1, 4, 8, 8, 4, 5, 1, 2, 0), DLWP_ERR_UNSUPPORTED);                 // geometry
+  EXPECT(conv(1, 4, 8, 8, 4, 3, 3, 1, 0), DLWP_ERR_UNSUPPORTED);
+  EXPECT(conv(1, 4, 8, 8, 4, 3, 1, 3, 0), DLWP_ERR_UNSUPPORTED);
+  EXPECT(conv(65536, 4, 8, 8, 4, 1, 1, 0, 0), DLWP_ERR_UNSUPPORTED);             // batch over the grid
+  EXPECT(conv(1, 4, 32768, 32768, 4, 1, 1, 0, 0), DLWP_ERR_UNSUPPORTED);         // 32-bit offsets inside a sample
+  EXPECT(conv(1, 4, big, big, 4, 4, 2, 3, 0), DLWP_ERR_UNSUPPORTED);
+  EXPECT(conv(1, big, 1, 1, 4, 1, 1, 0, 0), DLWP_ERR_UNSUPPORTED);
+  EXPECT(conv(1, 1 << 20, 4, 4, 1 << 20, 1, 1, 0, 0), DLWP_ERR_UNSUPPORTED);     // pack of 2 GiB and more
+  EXPECT(conv(big, big, big, big, big, 4, 2, 3, 1), DLWP_ERR_UNSUPPORTED);
+
+  EXPECT(dlwp_conv_transpose2d_mfma_f32(x, nullptr, nullptr, x, 1, 4, 8, 8, 4, 4, 2, 1, 0, 0, nullptr), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(dlwp_conv_transpose2d_mfma_f32(x, pk, nullptr, x, 1, 4, 8, 8, 4, 4, 2, 1, -1, 0, nullptr), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(tconv(1, 4, 0, 8, 4, 4, 2, 1, 0), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(tconv(1, 4, 8, 8, 4, 4, 2, 1, 7), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(tconv(1, 4, 8, 8, 4, 3, 2, 1, 0), DLWP_ERR_UNSUPPORTED);
+  EXPECT(tconv(1, 4, 8, 8, 4, 4, 2, 0, 0), DLWP_ERR_UNSUPPORTED);
+  EXPECT(tconv(1, 4, 8, 8, 4, 2, 1, 0, 0), DLWP_ERR_UNSUPPORTED);
+  EXPECT(tconv(65536, 4, 8, 8, 4, 2, 2, 0, 0), DLWP_ERR_UNSUPPORTED);
+  EXPECT(tconv(1, 4, 32768, 32768, 4, 4, 2, 1, 0), DLWP_ERR_UNSUPPORTED);
+  EXPECT(tconv(1, 4, big, big, 4, 4, 2, 1, 0), DLWP_ERR_UNSUPPORTED);
+  EXPECT(tconv(1, 1 << 20, 4, 4, 1 << 20, 2, 2, 0, 0), DLWP_ERR_UNSUPPORTED);
+  EXPECT(tconv(big, big, big, big, big, 2, 2, 0, 1), DLWP_ERR_UNSUPPORTED);
+  EXPECT(dlwp_conv_transpose2d_mfma_f32(x, pk, nullptr, x + 1, 1, 4, 8, 8, 4, 2, 2, 0, 0, 0, nullptr), DLWP_ERR_INVALID_ARGUMENT);  // y 4-byte aligned
+
+  if (failures == 0) std::printf("ok\n");
+  return failures ? 1 : 0;
+}

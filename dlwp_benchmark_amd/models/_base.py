@@ -11,6 +11,7 @@ Every reference backbone has the same boundary:
 """
 import torch
 
+from .. import derived
 from .. import lib as _lib
 
 
@@ -117,12 +118,11 @@ class HipBackbone(torch.nn.Module):
             self.set_aux_conv_form(str(aux))
 
     def invalidate_packed(self):
-        """Derived operands (packed bf16 / f16 weight images, FNO plans, step graphs) are keyed on (data_ptr, _version) of
-        their source parameters.  Writes through `.data` (EMA / init code: `p.data.copy_()`, `p.data.mul_()`) keep both --
-        call this after such writes.  `load_state_dict` and `_apply` (.to / .half / .float) call it themselves."""
-        from .. import ops
-
-        ops.bump_pack_epoch()       # part of every derived-operand key (ops.pack_epoch) and of _param_key below
+        """Derived operands (packed bf16 / f16 weight images, FNO plans, step graphs) are keyed on pointer and version of
+        their source parameters (derived.source_key).  Writes through `.data` (EMA / init code: `p.data.copy_()`,
+        `p.data.mul_()`) keep both -- call this after such writes.  `load_state_dict` and `_apply` (.to / .half / .float) call
+        it themselves."""
+        derived.bump_pack_epoch()       # part of every derived-operand key, _param_key below included
         self._graphed = None
         return self
 
@@ -181,6 +181,4 @@ class HipBackbone(torch.nn.Module):
         return self._ws
 
     def _param_key(self):
-        from .. import ops
-
-        return (ops.pack_epoch(),) + tuple((p._version, p.data_ptr()) for p in list(self.parameters()) + list(self.buffers()))
+        return derived.source_key(*self.parameters(), *self.buffers())

@@ -300,7 +300,7 @@ class PanguWeather(HipBackbone):
         first through the residual operand); the output width is padded to a multiple of 4 with zero columns."""
         conv = self.patchrecovery2d.conv
         w, bias = conv.weight, conv.bias
-        key = (w.data_ptr(), w._version, str(w.device), bias.data_ptr(), bias._version, ops.pack_epoch())
+        key = ops.source_key(w, bias)
         halves = self.__dict__.get("_recover_lin")
         if halves is None or halves[0] != key:
             cc, cg = x.shape[-1], w.shape[1]

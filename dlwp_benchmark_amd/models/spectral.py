@@ -10,12 +10,7 @@ import torch
 from torch import nn
 
 from .. import lib as _lib
-
-
-def _ops_epoch():
-    from .. import ops
-
-    return ops.pack_epoch()
+from ..derived import source_key
 
 
 class SpectralConv2d(nn.Module):
@@ -47,8 +42,7 @@ class SpectralConv2d(nn.Module):
             pass
 
     def _get_plan(self, h, w, device):
-        key = (h, w, str(device), self.weights1._version, self.weights1.data_ptr(), self.weights2._version,
-               self.weights2.data_ptr(), _ops_epoch())
+        key = source_key(self.weights1, self.weights2, extra=(h, w, str(device)))
         if self._plan is not None and key == self._plan_key:
             return self._plan
         self._destroy_plan()

@@ -2,7 +2,6 @@
 Every wrapper takes CUDA tensors, passes raw pointers + the current HIP stream, and raises
 `DlwpError` on a non-zero status.  No wrapper has a CPU path."""
 import ctypes
-import weakref
 import functools
 from dataclasses import dataclass
 from typing import Optional, Sequence
@@ -10,6 +9,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import lib as _lib
+from .derived import Derived, bump_pack_epoch, derived_for, live_holders, pack_epoch, source_key  # noqa: F401 (re-exported)
 
 BIG = 1 << 30
 
@@ -104,20 +104,10 @@ def window_attention_io_supported(spec: WindowSpec, batch: int) -> bool:
     return int(_lib.load().dlwp_window_attn_workspace_bytes(ctypes.byref(d), int(batch), 1)) > 0
 
 
-_BIAS16 = {}
-
-
 def _bias_bf16(bias: torch.Tensor) -> torch.Tensor:
     """bfloat16 image of a qkv bias (read by the earth-window kernel for zero-padded tokens), converted once per parameter
-    state instead of once per call: keyed like the packed weights (pointer, version, pack epoch of invalidate_packed())."""
-    key = (bias.data_ptr(), bias._version, str(bias.device), pack_epoch())
-    hit = _BIAS16.get(id(bias))
-    if hit is None or hit[0] != key or hit[2]() is not bias:      # (the weak reference: ids are reused after a free)
-        if len(_BIAS16) > 256:
-            _BIAS16.clear()
-        hit = (key, bias.detach().to(torch.bfloat16).contiguous(), weakref.ref(bias))
-        _BIAS16[id(bias)] = hit
-    return hit[1]
+    state instead of once per call; it lives as long as the bias (a captured step has its pointer baked in)."""
+    return derived_for(bias, "bias_bf16").get(source_key(bias), lambda: bias.detach().to(torch.bfloat16).contiguous())
 
 
 def _window_attention_bf16_io(qkv: torch.Tensor, qkv_bias: Optional[torch.Tensor], table: torch.Tensor, spec: WindowSpec):
@@ -206,14 +196,10 @@ class Conv3x3Weights:
     capture a stale or missing pack is an error."""
 
     def __init__(self):
-        self._key = None
-        self._buf = None
+        self._derived = Derived(eager_only="conv3x3")
 
     def get(self, weight: torch.Tensor) -> torch.Tensor:
-        key = (weight.data_ptr(), weight._version, str(weight.device), pack_epoch())
-        if key != self._key:
-            if torch.cuda.is_current_stream_capturing():
-                raise _lib.DlwpError("conv3x3: the weight pack must be made before a graph capture (run one eager step first)")
+        def build():
             cout, cin = weight.shape[:2]
             lib = _lib.load()
             nbytes = int(lib.dlwp_conv3x3_mfma_packed_bytes(cout, cin))
@@ -223,30 +209,14 @@ class Conv3x3Weights:
             with torch.cuda.device(weight.device):
                 _lib.check(lib.dlwp_conv3x3_mfma_pack_f32(weight.detach().contiguous().data_ptr(), cout, cin, buf.data_ptr(),
                                                           _lib.stream_ptr()), "dlwp_conv3x3_mfma_pack_f32")
-            self._key, self._buf = key, buf
-        return self._buf
+            return buf
 
-
-# id(weight) -> (weak reference, Conv3x3Weights): a pack lives exactly as long as the tensor it was derived from (the
-# finalizer drops it), so a captured step graph -- which keeps its module, hence its parameters, alive -- never replays
-# against a freed pack; nothing here is ever cleared wholesale
-_CONV_PACKS = {}
-
-
-def _drop_conv_pack(wid: int, ref) -> None:
-    hit = _CONV_PACKS.get(wid)
-    if hit is not None and hit[0] is ref:       # (ids are reused after a free: only the entry of THIS tensor)
-        del _CONV_PACKS[wid]
+        return self._derived.get(source_key(weight), build)
 
 
 def conv3x3_weights(weight: torch.Tensor) -> Conv3x3Weights:
     """The pack cache that belongs to `weight` (a Parameter, or any tensor the caller keeps alive)."""
-    wid = id(weight)
-    hit = _CONV_PACKS.get(wid)
-    if hit is None or hit[0]() is not weight:
-        hit = (weakref.ref(weight, functools.partial(_drop_conv_pack, wid)), Conv3x3Weights())
-        _CONV_PACKS[wid] = hit
-    return hit[1]
+    return derived_for(weight, "conv3x3", Conv3x3Weights)
 
 
 class Conv2dWeights:
@@ -254,15 +224,11 @@ class Conv2dWeights:
     layout dlwp_conv2d_mfma_f32 / dlwp_conv_transpose2d_mfma_f32 read: Conv3x3Weights' rule for csrc/conv2_mfma.hip."""
 
     def __init__(self, transposed: bool):
-        self._key = None
-        self._buf = None
+        self._derived = Derived(eager_only="conv2d")
         self._transposed = bool(transposed)
 
     def get(self, weight: torch.Tensor) -> torch.Tensor:
-        key = (weight.data_ptr(), weight._version, str(weight.device), pack_epoch())
-        if key != self._key:
-            if torch.cuda.is_current_stream_capturing():
-                raise _lib.DlwpError("conv2d: the weight pack must be made before a graph capture (run one eager step first)")
+        def build():
             cout, cin = (weight.shape[1], weight.shape[0]) if self._transposed else weight.shape[:2]
             k = weight.shape[2]
             lib = _lib.load()
@@ -274,29 +240,15 @@ class Conv2dWeights:
                 _lib.check(lib.dlwp_conv2d_mfma_pack_f32(weight.detach().contiguous().data_ptr(), cout, cin, k,
                                                          int(self._transposed), buf.data_ptr(), _lib.stream_ptr()),
                            "dlwp_conv2d_mfma_pack_f32")
-            self._key, self._buf = key, buf
-        return self._buf
+            return buf
 
-
-# (id(weight), transposed) -> (weak reference, Conv2dWeights): the rule of _CONV_PACKS; the layout flag is part of the key, so
-# a ConvTranspose2d weight and a Conv2d weight of the same shape never share a pack
-_CONV2D_PACKS = {}
-
-
-def _drop_conv2d_pack(key, ref) -> None:
-    hit = _CONV2D_PACKS.get(key)
-    if hit is not None and hit[0] is ref:
-        del _CONV2D_PACKS[key]
+        return self._derived.get(source_key(weight), build)
 
 
 def conv2d_weights(weight: torch.Tensor, transposed: bool = False) -> Conv2dWeights:
-    """The pack cache of ops.conv2d (transposed: of ops.conv_transpose2d) that belongs to `weight`."""
-    key = (id(weight), bool(transposed))
-    hit = _CONV2D_PACKS.get(key)
-    if hit is None or hit[0]() is not weight:
-        hit = (weakref.ref(weight, functools.partial(_drop_conv2d_pack, key)), Conv2dWeights(transposed))
-        _CONV2D_PACKS[key] = hit
-    return hit[1]
+    """The pack cache of ops.conv2d (transposed: of ops.conv_transpose2d) that belongs to `weight`; the layout flag is part
+    of the slot, so a ConvTranspose2d weight and a Conv2d weight of the same shape never share a pack."""
+    return derived_for(weight, ("conv2d", bool(transposed)), lambda: Conv2dWeights(transposed))
 
 
 def _conv_form(form: str) -> str:
@@ -905,38 +857,20 @@ def token_mlp_supported(channels: int, hidden: int) -> bool:
     return int(_lib.load().dlwp_token_mlp_packed_bytes(int(channels), int(hidden))) > 0
 
 
-# Derived operands are keyed on (data_ptr, _version) of their source parameters; writes through `.data` change neither.
-# HipBackbone.invalidate_packed() (called by load_state_dict / _apply, and by users after `.data` writes) bumps this epoch,
-# which is part of every key below: all packed images, plans and step graphs of the process are re-derived on next use.
-_PACK_EPOCH = [0]
-
-
-def pack_epoch() -> int:
-    return _PACK_EPOCH[0]
-
-
-def bump_pack_epoch() -> int:
-    _PACK_EPOCH[0] += 1
-    return _PACK_EPOCH[0]
-
-
 class TokenMlpWeights:
     """fc1 / fc2 weights of a token MLP in the operand layout of dlwp_token_mlp_f32, re-packed on the device
     whenever a parameter has been written to (optimizer step, load_state_dict, .to()).  With `ln_weight` / `ln_bias`
     (and `b1`) the affine part of the LayerNorm in front of fc1 is folded into the operands, for token_mlp(ln_eps=...)."""
 
     def __init__(self):
-        self._key = None
-        self._buf = None
+        self._derived = Derived()
 
     def get(self, w1: torch.Tensor, w2: torch.Tensor, ln_weight: Optional[torch.Tensor] = None,
             ln_bias: Optional[torch.Tensor] = None, b1: Optional[torch.Tensor] = None, merged: bool = False,
             f16x3: bool = False) -> torch.Tensor:
         """merged=True: the k-slot order afno_block_tail wants (a different permutation of W1's columns);
         f16x3=True: the two f16 images of the f16x3 product form (afno_block_tail(form="f16x3"))."""
-        extra = [t for t in (ln_weight, ln_bias, b1) if t is not None]
-        key = tuple((t.data_ptr(), t._version) for t in (w1, w2, *extra)) + (str(w1.device), ln_weight is not None, merged, f16x3, pack_epoch())
-        if key != self._key:
+        def build():
             hid, c = w1.shape
             if tuple(w2.shape) != (c, hid):
                 raise _lib.DlwpError(f"token MLP: fc2.weight {tuple(w2.shape)} does not match fc1.weight {tuple(w1.shape)}")
@@ -955,8 +889,9 @@ class TokenMlpWeights:
                 packer = "dlwp_token_mlp_pack_f16x3" if f16x3 else "dlwp_token_mlp_pack_f32"
                 _lib.check(getattr(lib, packer)(ptr(w1), ptr(w2), ptr(ln_weight), ptr(ln_bias), ptr(b1), c, hid,
                                                 1 if merged else 0, buf.data_ptr(), _lib.stream_ptr()), packer)
-            self._key, self._buf = key, buf
-        return self._buf
+            return buf
+
+        return self._derived.get(source_key(w1, w2, ln_weight, ln_bias, b1, extra=(merged, f16x3)), build)
 
 
 def token_mlp(n: torch.Tensor, resid: Optional[torch.Tensor], packed: torch.Tensor, b1: Optional[torch.Tensor],
@@ -1068,20 +1003,12 @@ class LinearWeights:
     the parameter has been written to (optimizer step, load_state_dict, .to()).  Derived data: not in any state dict."""
 
     def __init__(self):
-        self._key = None
-        self._buf = None
-        self._f16 = None         # the f16x3 images live in a LinearWeights of their own (same derivation rule)
+        self._derived = (Derived(), Derived())      # the bf16x6 images, the f16x3 images
 
     def get(self, weight: torch.Tensor, f16: bool = False) -> torch.Tensor:
-        if f16:
-            if self._f16 is None:
-                self._f16 = LinearWeights()
-            return self._f16._get(weight, "dlwp_linear_pack_f16x3")
-        return self._get(weight, "dlwp_linear_pack_f32")
+        packer = "dlwp_linear_pack_f16x3" if f16 else "dlwp_linear_pack_f32"
 
-    def _get(self, weight: torch.Tensor, packer: str) -> torch.Tensor:
-        key = (weight.data_ptr(), weight._version, str(weight.device), pack_epoch())
-        if key != self._key:
+        def build():
             n, k = weight.shape
             lib = _lib.load()
             nbytes = int(lib.dlwp_linear_packed_bytes(n, k))
@@ -1091,8 +1018,9 @@ class LinearWeights:
             with torch.cuda.device(weight.device):
                 _lib.check(getattr(lib, packer)(weight.detach().contiguous().data_ptr(), n, k, buf.data_ptr(),
                                                 _lib.stream_ptr()), packer)
-            self._key, self._buf = key, buf
-        return self._buf
+            return buf
+
+        return self._derived[f16].get(source_key(weight), build)
 
 
 def linear_raw(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
@@ -1243,7 +1171,7 @@ class ConvAsLinear:
 
     def refresh(self):
         w, b = self.conv.weight, self.conv.bias
-        key = (w.data_ptr(), w._version, str(w.device), None if b is None else (b.data_ptr(), b._version), pack_epoch())
+        key = source_key(w, b)
         if key == self._key:
             return
         with torch.no_grad():
@@ -1439,20 +1367,21 @@ def mgn_layer_supported(edge_seq: torch.nn.Sequential, node_seq: torch.nn.Sequen
             and all(l.out_features <= d for l in el + nl))
 
 
+def _mlp_key(lins, ln):
+    return source_key(*(t for l in lins for t in (l.weight, l.bias)), *((ln.weight, ln.bias) if ln is not None else ()))
+
+
 class MgnMlpWeights:
     """Derived operand of one MeshGraphMLP: its Linear weights transposed to [in][out] and the descriptor pointing at them,
     re-derived when a parameter's (pointer, version) or the pack epoch changes."""
 
     def __init__(self):
-        self._key = None
-        self._keep = None
-        self._desc = None
+        self._derived = Derived()
 
     def get(self, seq: torch.nn.Sequential) -> "_lib.MgnMlpDesc":
         lins, ln = mgn_parts(seq)
-        params = [t for l in lins for t in (l.weight, l.bias)] + ([ln.weight, ln.bias] if ln is not None else [])
-        key = tuple((t.data_ptr(), t._version) for t in params) + (pack_epoch(),)
-        if key != self._key:
+
+        def build():
             wts = [l.weight.detach().t().contiguous() for l in lins]
             d = _lib.MgnMlpDesc()
             d.n_linear = len(lins)
@@ -1464,8 +1393,9 @@ class MgnMlpWeights:
             d.ln_gamma = ln.weight.data_ptr() if ln is not None else None
             d.ln_beta = ln.bias.data_ptr() if ln is not None else None
             d.ln_eps = float(ln.eps) if ln is not None else 0.0
-            self._keep, self._desc, self._key = wts, d, key
-        return self._desc
+            return d, wts               # (the descriptor points into the transposed weights)
+
+        return self._derived.get(_mlp_key(lins, ln), build)[0]
 
 
 def mgn_mlp(packed: MgnMlpWeights, seq: torch.nn.Sequential, x: torch.Tensor, batch: int, rows: int,
@@ -1645,14 +1575,13 @@ class GcMlpWeights:
 
     def __init__(self, split=None, perm=None):
         self.split, self.perm = split, perm
-        self._key = None
+        self._derived = Derived()
         self.wt = self.first = self.zero = None
 
     def get(self, seq: torch.nn.Sequential):
         lins, ln = mgn_parts(seq)
-        params = [t for l in lins for t in (l.weight, l.bias)] + ([ln.weight, ln.bias] if ln is not None else [])
-        key = tuple((t.data_ptr(), t._version) for t in params) + (pack_epoch(),)
-        if key != self._key:
+
+        def build():
             self.wt = [l.weight.detach().t().contiguous() for l in lins]
             w0 = self.wt[0]
             if self.perm is not None:
@@ -1662,8 +1591,9 @@ class GcMlpWeights:
                 self.first = [p.contiguous() for p in torch.split(w0, list(self.split), dim=0)]
             self.zero = torch.zeros(lins[0].out_features, device=w0.device, dtype=torch.float32)
             self.bwd_first = None
-            self._key = key
-        return self
+            return self
+
+        return self._derived.get(_mlp_key(lins, ln), build)
 
     def backward_first(self, seq: torch.nn.Sequential, split=None):
         """the first Linear's weight in torch's [out][in] layout (the data gradient's [k][n] operand), its input columns

@@ -164,9 +164,9 @@ def test_pack_follows_the_weight():
         assert rel_l2(y2, 2.0 * y1.double()) <= 1e-6
         ops.bump_pack_epoch()
         assert ops.conv3x3_weights(w).get(w) is not buf
-    n = len(ops._CONV_PACKS)
+    n = ops.live_holders()
     del w
-    assert len(ops._CONV_PACKS) == n - 1
+    assert ops.live_holders() == n - 1
 
 
 def _unet_like(tag):

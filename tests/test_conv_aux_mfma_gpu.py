@@ -203,9 +203,9 @@ def test_pack_follows_the_weight():
         assert rel_l2(ops.conv_transpose2d(x, w, None, 2, 0, form="bf16x6"), 2.0 * t1.double()) <= 1e-6
         ops.bump_pack_epoch()
         assert ops.conv2d_weights(w).get(w) is not buf
-    n = len(ops._CONV2D_PACKS)
+    n = ops.live_holders()
     del w
-    assert len(ops._CONV2D_PACKS) == n - 2
+    assert ops.live_holders() == n - 2
 
 
 @pytest.mark.gpu

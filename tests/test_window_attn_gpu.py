@@ -180,6 +180,27 @@ def test_bf16_tensor_handover_is_bit_identical(kind):
     assert torch.equal(got, want.to(torch.bfloat16))
 
 
+def test_bf16_bias_image_lives_as_long_as_its_bias():
+    """The bfloat16 image of a qkv bias (read for the zero-padded tokens; a captured step has its pointer baked in) is
+    evicted by nothing but the death of its bias: not by any number of other live biases."""
+    from dlwp_benchmark_amd import ops
+    from test_window_attn_bwd_gpu import _pangu_spec
+
+    spec, tshape = _pangu_spec(24, 48, 4, 32, False)
+    g = torch.Generator().manual_seed(8)
+    q16 = torch.randn(2, 24 * 48, 3 * 4 * 32, generator=g).cuda().to(torch.bfloat16)
+    bias = (0.3 * torch.randn(3 * 4 * 32, generator=g)).cuda()
+    table = (0.5 * torch.randn(*tshape, generator=g)).cuda()
+    assert ops.window_attention_io_supported(spec, 2)
+    first = ops.window_attention(q16, bias, table, spec, precision="bf16")
+    image = ops._bias_bf16(bias)
+    others = [torch.full_like(bias, float(i)) for i in range(300)]
+    images = [ops._bias_bf16(o) for o in others]
+    assert len({i.data_ptr() for i in images}) == 300
+    assert ops._bias_bf16(bias) is image
+    assert torch.equal(ops.window_attention(q16, bias, table, spec, precision="bf16"), first)
+
+
 def _sub_window_spec(h, w, wh, ww, heads, d, shifted):
     """Swin block with windows smaller than the map (nwin > 1), shift = half a window (swin_transformer.py:217-251)."""
     from dlwp_benchmark_amd import ops

@@ -1,67 +1,18 @@
-// The rest of the U-Net / ModernUNet operator family (reference models/unet/unet.py): GroupNorm (+ activation), strided and
-// 1x1 convolutions, transposed convolutions and 2x2 average pooling as hand-written kernels, so that a step of those
-// backbones never leaves libdlwp_hip (round 1 ran them through nn.GroupNorm / MIOpen).
-//   GroupNorm         unet.py:739 (final_norm, 8 groups), :887-888 (ResidualBlock, n_groups = 1) -- two-sweep statistics
-//                     per (sample, group) in one workgroup, affine + activation fused into the third sweep
+// The rest of the U-Net / ModernUNet operator family (reference models/unet/unet.py): strided and 1x1 convolutions, transposed
+// convolutions and 2x2 average pooling as hand-written kernels, so that a step of those backbones never leaves libdlwp_hip
+// (round 1 ran them through MIOpen).  GroupNorm (+ activation), forward and backward, is groupnorm_bwd.hip.
 //   Conv2d k x k, s   unet.py:583 (3x3, stride 2, zero padding 1), :584 (1x1), :879-881 (1x1 shortcut), :450 / :533 (1x1 head)
 //   ConvTranspose2d   unet.py:719 (4x4, stride 2, padding 1), :523 (2x2, stride 2)
 //   AvgPool2d(2)      unet.py:450
 // These layers work on maps of 2x2 ... 64x64 with 8 ... 1024 channels: each launch is a few microseconds and bound by
 // latency, so the kernels are direct and simple -- one thread per output element, lanes along the map's fastest axis
 // (coalesced), weights through the scalar / L1 path (they are wave-uniform per output channel).
-#include "common.hpp"
+#include "act_common.hpp"
 
 namespace dlwp {
 namespace conv2 {
 
-__device__ __forceinline__ float apply_act(float v, int act) {
-  switch (act) {
-    case 1: return gelu_erf(v);
-    case 2: return tanhf(v);
-    case 3: return fmaxf(v, 0.f);
-    case 4: return v / (1.f + __expf(-v));
-    default: return v;
-  }
-}
-
-__device__ __forceinline__ float block_sum(float v, float* s_red, int tid) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-  __syncthreads();
-  if ((tid & 63) == 0) s_red[tid >> 6] = v;
-  __syncthreads();
-  float t = 0.f;
-  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += s_red[w];
-  return t;
-}
-
-// one workgroup per (sample, group): elements [n][g * cpg .. (g + 1) * cpg)[HW] are contiguous in NCHW
-__global__ __launch_bounds__(256) void groupnorm_act_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta, float* __restrict__ y, int C,
-                                                            int HW, int groups, float eps, int act) {
-  __shared__ float s_red[8];
-  const int tid = threadIdx.x;
-  const int n = blockIdx.x / groups, g = blockIdx.x % groups;
-  const int cpg = C / groups;
-  const long long base = ((long long)n * C + (long long)g * cpg) * HW;
-  const int E = cpg * HW;
-  float s = 0.f;
-  for (int i = tid; i < E; i += 256) s += x[base + i];
-  const float mean = block_sum(s, s_red, tid) / (float)E;
-  float q = 0.f;
-  for (int i = tid; i < E; i += 256) {
-    const float dlt = x[base + i] - mean;
-    q += dlt * dlt;
-  }
-  const float var = block_sum(q, s_red, tid) / (float)E;      // biased, like torch.nn.GroupNorm
-  const float rstd = rsqrtf(var + eps);
-  for (int i = tid; i < E; i += 256) {
-    const int c = g * cpg + i / HW;
-    float v = (x[base + i] - mean) * rstd;
-    v = v * (gamma ? gamma[c] : 1.f) + (beta ? beta[c] : 0.f);
-    y[base + i] = apply_act(v, act);
-  }
-}
+using actc::apply_act;
 
 struct ConvP {
   const float* x;      // [N][Cin][H][W]
@@ -160,19 +111,6 @@ static unsigned grid_for(long long total) {
   long long b = (total + 255) / 256;
   if (b > 256 * 16) b = 256 * 16;
   return (unsigned)(b > 0 ? b : 1);
-}
-
-extern "C" int32_t dlwp_groupnorm_act_f32(const float* x, const float* gamma, const float* beta, float* y, int32_t batch,
-                                          int32_t channels, int32_t hw, int32_t groups, float eps, int32_t act, void* stream) {
-  DLWP_REQUIRE(x && y, DLWP_ERR_INVALID_ARGUMENT, "null argument");
-  DLWP_REQUIRE(batch > 0 && channels > 0 && hw > 0 && groups > 0 && channels % groups == 0, DLWP_ERR_INVALID_ARGUMENT,
-               "bad shape: %d channels in %d groups", channels, groups);
-  DLWP_REQUIRE(act >= 0 && act <= 4, DLWP_ERR_INVALID_ARGUMENT, "unknown activation %d", act);
-  DLWP_REQUIRE((long long)(channels / groups) * hw < (1ll << 31), DLWP_ERR_UNSUPPORTED, "group too large");
-  hipLaunchKernelGGL(conv2::groupnorm_act_kernel, dim3((unsigned)(batch * groups)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), x, gamma, beta, y, channels, hw, groups, eps, act);
-  DLWP_HIP_CHECK(hipGetLastError());
-  return DLWP_OK;
 }
 
 extern "C" int32_t dlwp_conv2d_f32(const float* x, const float* weight, const float* bias, const float* resid, float* y,

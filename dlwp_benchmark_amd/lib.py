@@ -148,6 +148,11 @@ SIGNATURES = {
                                     c_void_p]),
     "dlwp_groupnorm_act_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float,
                                          c_int32, c_void_p]),
+    "dlwp_groupnorm_act_fwd_stats_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                                   c_int32, c_float, c_int32, c_void_p]),
+    "dlwp_groupnorm_act_bwd_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "dlwp_groupnorm_act_bwd_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "dlwp_conv2d_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                   c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "dlwp_conv_transpose2d_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,

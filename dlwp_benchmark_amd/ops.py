@@ -372,7 +372,9 @@ def groupnorm_act(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optiona
     _lib.require_cuda_tensor(x, "x")
     from . import training as _T
     if _T.wants_grad(x, weight, bias):
-        return _T._ACT_FNS[int(act)](torch.nn.functional.group_norm(x, int(groups), weight, bias, eps))
+        if _T._TORCH_BACKWARD():
+            return _T._ACT_FNS[int(act)](torch.nn.functional.group_norm(x, int(groups), weight, bias, eps))
+        return _T.groupnorm_act(x, weight, bias, groups, eps, act)           # HIP forward and backward (training.py)
     x = x.contiguous()
     n, c = x.shape[0], x.shape[1]
     hw = x.numel() // (n * c)
@@ -384,6 +386,55 @@ def groupnorm_act(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optiona
                                               hw, int(groups), float(eps), int(act), _lib.stream_ptr()),
                    "dlwp_groupnorm_act_f32")
     return y
+
+
+def groupnorm_act_fwd_stats(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor], groups: int,
+                            eps: float = 1e-5, act: int = 0):
+    """groupnorm_act that also returns the statistics a backward needs: (y, stats [N, groups, 2] = (mean, rstd)).  y is
+    bit-equal to groupnorm_act's (the same kernel).  Not differentiable: training.groupnorm_act is."""
+    _lib.require_cuda_tensor(x, "x")
+    x = x.contiguous()
+    n, c = x.shape[0], x.shape[1]
+    hw = x.numel() // (n * c)
+    y = torch.empty_like(x)
+    stats = torch.empty(n, max(int(groups), 1), 2, device=x.device, dtype=torch.float32)
+    gm = weight.contiguous() if weight is not None else None
+    bt = bias.contiguous() if bias is not None else None
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dlwp_groupnorm_act_fwd_stats_f32(
+            x.data_ptr(), gm.data_ptr() if gm is not None else None, bt.data_ptr() if bt is not None else None, y.data_ptr(),
+            stats.data_ptr(), n, c, hw, int(groups), float(eps), int(act), _lib.stream_ptr()), "dlwp_groupnorm_act_fwd_stats_f32")
+    return y, stats
+
+
+def groupnorm_act_backward(x: torch.Tensor, stats: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
+                           grad_out: torch.Tensor, groups: int, act: int = 0, need_x: bool = True, need_weight: bool = True,
+                           need_bias: bool = True):
+    """The gradients of groupnorm_act on dlwp_groupnorm_act_bwd_f32 from x, the forward's stats [N, groups, 2] and grad_out
+    (both contiguous, [N, C, *]): (dx, dgamma, dbeta), None where not wanted.  Runs on the current stream without a host
+    synchronisation; reruns are bitwise identical."""
+    for t, name in ((x, "x"), (stats, "stats"), (grad_out, "grad_out")):
+        _lib.require_cuda_tensor(t, name)
+    n, c = x.shape[0], x.shape[1]
+    hw = x.numel() // max(n * c, 1)
+    if grad_out.shape != x.shape or not x.is_contiguous() or not grad_out.is_contiguous():
+        raise _lib.DlwpError(f"groupnorm_act_backward: x {tuple(x.shape)} and grad_out {tuple(grad_out.shape)} must be "
+                             "contiguous and of one shape")
+    if int(groups) <= 0 or stats.numel() != 2 * n * int(groups) or not stats.is_contiguous():
+        raise _lib.DlwpError(f"groupnorm_act_backward: stats of {stats.numel()} values, 2 * {n} * {groups} needed")
+    lib = _lib.load()
+    gm = weight.contiguous() if weight is not None else None
+    bt = bias.contiguous() if bias is not None else None
+    dx = torch.empty_like(x) if need_x else None
+    dw = torch.empty(c, device=x.device, dtype=torch.float32) if need_weight else None
+    db = torch.empty(c, device=x.device, dtype=torch.float32) if need_bias else None
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(x.device):
+        ws = torch.empty(max(int(lib.dlwp_groupnorm_act_bwd_workspace_bytes(n, c)), 4), dtype=torch.uint8, device=x.device)
+        _lib.check(lib.dlwp_groupnorm_act_bwd_f32(x.data_ptr(), stats.data_ptr(), ptr(gm), ptr(bt), grad_out.data_ptr(), ptr(dx),
+                                                  ptr(dw), ptr(db), ws.data_ptr(), n, c, hw, int(groups), int(act),
+                                                  _lib.stream_ptr()), "dlwp_groupnorm_act_bwd_f32")
+    return dx, dw, db
 
 
 def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], stride: int = 1, padding: int = 0,

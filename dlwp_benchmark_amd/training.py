@@ -20,7 +20,7 @@ path calls.
 
 Everything pointwise around the spectral operator (1x1 convolutions, GELU, residuals) stays in torch ops on
 the GPU in training mode.  The other hot kernels' training paths (window and global attention, Linear, the AFNO
-filter, the cylinder and HEALPix convolutions, MeshGraphNet, GraphCastNet) follow below, each with its HIP backward.
+filter, the cylinder and HEALPix convolutions, GroupNorm, MeshGraphNet, GraphCastNet) follow below, each with its HIP backward.
 """
 import ctypes
 from typing import List, Optional, Sequence
@@ -580,6 +580,89 @@ class _Conv3x3Fn(torch.autograd.Function):
 
 def conv3x3(x0, weight, bias, act=0, x1=None, pre_act=0, resid=None, hpx=False):
     return _Conv3x3Fn.apply(x0, x1, weight, bias, resid, pre_act, act, hpx)
+
+
+def _act_grad_torch(v: torch.Tensor, act: int) -> torch.Tensor:
+    """act'(v) for the activation codes of ops.ACTS (0 identity, 1 exact-erf GELU, 2 tanh, 3 ReLU, 4 SiLU)"""
+    if act == 1:
+        return 0.5 * (1.0 + torch.erf(v * 0.7071067811865476)) + v * torch.exp(-0.5 * v * v) * 0.3989422804014327
+    if act == 2:
+        return 1.0 - torch.tanh(v) ** 2
+    if act == 3:
+        return (v > 0).to(v.dtype)
+    if act == 4:
+        s = torch.sigmoid(v)
+        return s * (1.0 + v * (1.0 - s))
+    if act != 0:
+        raise _lib.DlwpError(f"unknown activation {act}")
+    return torch.ones_like(v)
+
+
+def groupnorm_act_backward_torch(x, mean, rstd, gamma, beta, gy, groups: int, act: int):
+    """The backward of y = act(GroupNorm(groups)(x)) (reference unet.py:739 + :761, :887-888 under train.py:271) from x and
+    the forward's statistics alone, as plain torch operators on any device: what dlwp_groupnorm_act_bwd_f32 computes
+    (csrc/groupnorm_bwd.hip), term by term.  x, gy [N, C, *]; mean, rstd [N, groups]; gamma, beta [C] or None.
+
+        xh = (x - mean) rstd      v = xh gamma_c + beta_c      gv = gy act'(v)      E = (C / groups) HW
+        s1[n,c] = sum_hw gv       s2[n,c] = sum_hw gv xh       dbeta_c = sum_n s1   dgamma_c = sum_n s2
+        a[n,g] = sum_{c in g} gamma_c s1 / E                   b[n,g] = sum_{c in g} gamma_c s2 / E
+        dx = rstd (gv gamma_c - a - xh b)
+
+    Returns (dx, dgamma, dbeta); the last two are the sums s2, s1 over n whether or not gamma / beta exist."""
+    n, c = x.shape[0], x.shape[1]
+    cpg = c // groups
+    x4 = x.reshape(n, groups, cpg, -1)
+    e = cpg * x4.shape[-1]
+    mean, rstd = mean.reshape(n, groups, 1, 1), rstd.reshape(n, groups, 1, 1)
+    gm = gamma.reshape(1, groups, cpg, 1) if gamma is not None else torch.ones(1, 1, 1, 1, dtype=x.dtype, device=x.device)
+    bt = beta.reshape(1, groups, cpg, 1) if beta is not None else torch.zeros(1, 1, 1, 1, dtype=x.dtype, device=x.device)
+    xh = (x4 - mean) * rstd
+    gv = gy.reshape(x4.shape) * _act_grad_torch(xh * gm + bt, int(act))
+    s1 = gv.sum(dim=3, keepdim=True)
+    s2 = (gv * xh).sum(dim=3, keepdim=True)
+    a = (gm * s1).sum(dim=2, keepdim=True) / e
+    b = (gm * s2).sum(dim=2, keepdim=True) / e
+    dx = rstd * (gv * gm - a - xh * b)
+    return dx.reshape(x.shape), s2.sum(dim=0).reshape(c), s1.sum(dim=0).reshape(c)
+
+
+class _GroupNormActFn(torch.autograd.Function):
+    """y = act(GroupNorm(groups)(x)) on HIP in both directions: dlwp_groupnorm_act_fwd_stats_f32 (the inference kernel, y bit
+    for bit, which also writes mean and rstd per (sample, group)) and dlwp_groupnorm_act_bwd_f32.  Saved for the backward: x,
+    the statistics and gamma / beta -- no normalised or activated copy of x."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, groups, eps, act):
+        from . import ops
+
+        x = x.contiguous()
+        d = lambda t: t.detach() if t is not None else None
+        with torch.no_grad():
+            y, stats = ops.groupnorm_act_fwd_stats(x.detach(), d(weight), d(bias), groups, eps, act)
+        ctx.cfg = (groups, act, weight is not None, bias is not None)
+        ctx.save_for_backward(x, stats, *[t for t in (weight, bias) if t is not None])
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from . import ops
+
+        groups, act, has_w, has_b = ctx.cfg
+        x, stats, *wb = ctx.saved_tensors
+        weight = wb.pop(0) if has_w else None
+        bias = wb.pop(0) if has_b else None
+        need_x, need_w, need_b = ctx.needs_input_grad[0], has_w and ctx.needs_input_grad[1], has_b and ctx.needs_input_grad[2]
+        dx = dw = db = None
+        if need_x or need_w or need_b:
+            with torch.no_grad():
+                dx, dw, db = ops.groupnorm_act_backward(x, stats, weight, bias, grad_out.contiguous(), groups, act,
+                                                        need_x, need_w, need_b)
+        return dx, dw, db, None, None, None
+
+
+def groupnorm_act(x, weight, bias, groups: int, eps: float = 1e-5, act: int = 0):
+    """differentiable act(GroupNorm(groups)(x)) for x [N, C, *]: HIP forward and HIP backward"""
+    return _GroupNormActFn.apply(x, weight, bias, int(groups), float(eps), int(act))
 
 
 class _LinearFn(torch.autograd.Function):

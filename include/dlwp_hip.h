@@ -459,7 +459,8 @@ int32_t dlwp_linear_f16x3(const float* x_dev, const void* packed_dev, const floa
                           float* out_dev, int64_t rows, int32_t in_features, int32_t out_features, int32_t act, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * The remaining U-Net / ModernUNet operators (csrc/conv2.hip), NCHW fp32, activations as above.
+ * The remaining U-Net / ModernUNet operators (csrc/conv2.hip; GroupNorm: csrc/groupnorm_bwd.hip), NCHW fp32, activations as
+ * above.
  *   dlwp_groupnorm_act_f32     y = act(GroupNorm(groups)(x)): unet.py:739 (+ GELU :761), :887-888; gamma / beta [C] or NULL
  *   dlwp_conv2d_f32            zero-padded Conv2d k x k, stride s: unet.py:583 (3x3 s2 p1), :584 / :879 / :450 (1x1);
  *                              optional pre_act on the input and resid_dev [N, cout, OH, OW] before `act`
@@ -475,6 +476,26 @@ int32_t dlwp_conv_transpose2d_f32(const float* x_dev, const float* weight_dev, c
                                   int32_t cin, int32_t height, int32_t width, int32_t cout, int32_t k, int32_t stride,
                                   int32_t pad, int32_t act, void* stream);
 int32_t dlwp_avgpool2x2_f32(const float* x_dev, float* y_dev, int64_t planes, int32_t height, int32_t width, void* stream);
+
+/* GroupNorm + activation for training (csrc/groupnorm_bwd.hip): unet.py:739 (+ GELU :761), :887-888 under the
+ * `loss.backward()` of scripts/train.py:271.  With v = xh gamma_c + beta_c, xh = (x - mean) rstd, y = act(v):
+ *   dlwp_groupnorm_act_fwd_stats_f32: dlwp_groupnorm_act_f32 (the same kernel, y bit for bit) that also writes
+ *     stats_dev [batch * groups][2] = (mean, rstd) -- with x all that the backward needs; no v, y or xh is kept.
+ *   dlwp_groupnorm_act_bwd_f32: dx = rstd (gv gamma_c - a - xh b), dgamma_c = sum_n sum_hw gv xh, dbeta_c = sum_n sum_hw gv
+ *     with gv = gy act'(v) recomputed from x and stats, a / b the group means of gamma gv / gamma gv xh.  gamma_dev / beta_dev
+ *     may be NULL (gamma = 1, beta = 0); dx_dev, dgamma_dev, dbeta_dev may each be NULL (not wanted, not computed).  Every
+ *     sum has a fixed order (dgamma / dbeta: n ascending) and one writer: reruns are bitwise identical.  16-byte loads are
+ *     used only when hw % 4 == 0 and x_dev, gy_dev, dx_dev are 16-byte aligned; any other input takes the scalar form.
+ *     workspace_dev: dlwp_groupnorm_act_bwd_workspace_bytes(batch, channels) bytes (the per-row sums).
+ *   dlwp_groupnorm_act_bwd_workspace_bytes: 2 * batch * channels floats (0 for a non-positive size). */
+int32_t dlwp_groupnorm_act_fwd_stats_f32(const float* x_dev, const float* gamma_dev, const float* beta_dev, float* y_dev,
+                                         float* stats_dev, int32_t batch, int32_t channels, int32_t hw, int32_t groups,
+                                         float eps, int32_t act, void* stream);
+size_t dlwp_groupnorm_act_bwd_workspace_bytes(int32_t batch, int32_t channels);
+int32_t dlwp_groupnorm_act_bwd_f32(const float* x_dev, const float* stats_dev, const float* gamma_dev, const float* beta_dev,
+                                   const float* gy_dev, float* dx_dev, float* dgamma_dev, float* dbeta_dev,
+                                   void* workspace_dev, int32_t batch, int32_t channels, int32_t hw, int32_t groups, int32_t act,
+                                   void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * HEALPix mesh.  Faces are folded into the batch, [(B*12), C, H, W], face index fastest

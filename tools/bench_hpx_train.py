@@ -43,11 +43,12 @@ CASES = {
 SEQ = 3
 
 
-def build(tag, batch):
+def build(tag, batch, case=None):
+    """the model of CASES[tag] (or of `case`, an entry of the same form) in train mode and a closure that returns its loss"""
     import dlwp_benchmark_amd.models as M
     from dlwp_benchmark_amd.weights import fill_state_dict
 
-    cls, cfg, n = CASES[tag]
+    cls, cfg, n = case or CASES[tag]
     cfg = dict(cfg)
     if cls == "ConvLSTMHPX":
         cfg.update(batch_size=batch, height=n, width=n)

@@ -1,6 +1,6 @@
 // The pointwise activations of the U-Net family (codes 0 identity, 1 exact-erf GELU, 2 tanh, 3 ReLU, 4 SiLU), their
-// derivatives, and the workgroup sum: shared by conv2.hip (convolution epilogues) and groupnorm_bwd.hip (GroupNorm forward
-// and backward).
+// derivatives, and the workgroup sum: shared by the convolutions (conv.hip, conv2.hip, and conv_mfma.hip / conv2_mfma.hip
+// through conv_mfma_common.hpp: staging and epilogues) and groupnorm_bwd.hip (GroupNorm forward and backward).
 #pragma once
 
 #include "common.hpp"
@@ -8,12 +8,14 @@
 namespace dlwp {
 namespace actc {
 
+enum Act { ACT_NONE = 0, ACT_GELU = 1, ACT_TANH = 2, ACT_RELU = 3, ACT_SILU = 4 };
+
 __device__ __forceinline__ float apply_act(float v, int act) {
   switch (act) {
-    case 1: return gelu_erf(v);
-    case 2: return tanhf(v);
-    case 3: return fmaxf(v, 0.f);
-    case 4: return v / (1.f + __expf(-v));
+    case ACT_GELU: return gelu_erf(v);
+    case ACT_TANH: return tanhf(v);
+    case ACT_RELU: return fmaxf(v, 0.f);
+    case ACT_SILU: return v / (1.f + __expf(-v));
     default: return v;
   }
 }

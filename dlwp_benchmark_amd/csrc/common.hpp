@@ -89,6 +89,13 @@ __device__ __forceinline__ f32x4 mfma16x16x4(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
+// sum over the 64 lanes of a wave (xor tree); every lane returns the total
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
 // GELU (exact, erf form: torch.nn.functional.gelu default) without a libm call.
 //   gelu(x) = 0.5 x (1 + erf(x/sqrt2)) = max(x, 0) - |x| * (0.5 erfc(|x|/sqrt2))
 //   0.5 erfc(u/sqrt2), u >= 0, is evaluated as exp2(u * Q(u) - 1) with a degree-5 polynomial Q fitted to

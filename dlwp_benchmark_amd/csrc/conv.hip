@@ -9,22 +9,12 @@
 // tile of a chunk of input channels is staged in LDS with the cylinder rule applied at load time
 // (longitude wraps, latitude pads with zeros), every thread owns one pixel and accumulates a chunk of
 // output channels with weights broadcast from LDS; bias + activation fused in the epilogue.
-#include "common.hpp"
+#include "act_common.hpp"
 
 namespace dlwp {
 namespace conv {
 
-enum Act { ACT_NONE = 0, ACT_GELU = 1, ACT_TANH = 2, ACT_RELU = 3, ACT_SILU = 4 };
-
-__device__ __forceinline__ float apply_act(float v, int act) {
-  switch (act) {
-    case ACT_GELU: return gelu_erf(v);
-    case ACT_TANH: return tanhf(v);
-    case ACT_RELU: return fmaxf(v, 0.f);
-    case ACT_SILU: return v / (1.f + __expf(-v));
-    default: return v;
-  }
-}
+using actc::apply_act;
 
 constexpr int CI_CHUNK = 8;
 

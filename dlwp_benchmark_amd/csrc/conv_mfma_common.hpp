@@ -1,23 +1,14 @@
 // What the matrix-pipe convolutions share (conv_mfma.hip: pad(1) + Conv2d(3x3); conv2_mfma.hip: zero-padded Conv2d and
-// ConvTranspose2d): the activation switch, the K-slab and LDS pitch, and the conversion of a staged K group into the MFMA
-// operand images.  The splits and MFMA wrappers themselves (split3_pair, cvt_pk_bf16, mfma_bf16x6) are common.hpp's.
+// ConvTranspose2d): the K-slab and LDS pitch, and the conversion of a staged K group into the MFMA operand images.  The
+// splits and MFMA wrappers themselves (split3_pair, cvt_pk_bf16, mfma_bf16x6) are common.hpp's, the activation switch is
+// act_common.hpp's.
 #pragma once
-#include "common.hpp"
+#include "act_common.hpp"
 
 namespace dlwp {
 namespace convm {
 
-enum Act { ACT_NONE = 0, ACT_GELU = 1, ACT_TANH = 2, ACT_RELU = 3, ACT_SILU = 4 };
-
-__device__ __forceinline__ float apply_act(float v, int act) {   // conv.hip's
-  switch (act) {
-    case ACT_GELU: return gelu_erf(v);
-    case ACT_TANH: return tanhf(v);
-    case ACT_RELU: return fmaxf(v, 0.f);
-    case ACT_SILU: return v / (1.f + __expf(-v));
-    default: return v;
-  }
-}
+using actc::apply_act;
 
 constexpr int KSLAB = 32;    // input channels per K-slab: one v_mfma_f32_16x16x32_bf16 per tap and slab
 // dwords per staged pixel in LDS (16 hold the 32 channels).  24: the four 16-lane groups of a ds_read_b128 (lanes

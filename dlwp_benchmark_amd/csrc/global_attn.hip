@@ -25,37 +25,12 @@
 // one 16-byte load per lane and chunk.  Tails: queries >= N enter no statistic (score -inf), keys >= N get P = 0, d is
 // padded with zeros to the chunk.  Row bases are 64-bit.  No atomics: results are bitwise reproducible and a sample's
 // result does not depend on its batch neighbours.
-#include "common.hpp"
+#include "global_attn_common.hpp"
 
 namespace dlwp {
 namespace gattn {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr float kLog2e = 1.4426950408889634f;
-constexpr int kWaves = 4;        // waves per workgroup; each owns one 16-row tile
-constexpr int kRegChunks = 8;    // head_dim <= 128: the wave's own 16 x d operand stays in registers (32 VGPRs)
-
-// 4 consecutive values [d0, d0 + 4) of one token row, zero beyond d or for a row that does not exist.
-// VEC: d % 4 == 0 and the tensor is 16-byte aligned, so the four are all in or all out and one 16-byte load fetches them.
-template <bool VEC>
-__device__ __forceinline__ f32x4 load4(const float* __restrict__ row, int d0, int d, bool ok) {
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if (VEC) {
-    if (ok && d0 < d) v = *reinterpret_cast<const f32x4*>(row + d0);
-  } else if (ok) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-      if (d0 + t < d) v[t] = row[d0 + t];
-  }
-  return v;
-}
-
-__device__ __forceinline__ f32x4 mfma4(f32x4 a, f32x4 b, f32x4 acc) {
-#pragma unroll
-  for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t], b[t], acc, 0, 0, 0);
-  return acc;
-}
 
 // merge of two online-softmax states (base 2); the -inf guard keeps a state that has seen nothing yet
 __device__ __forceinline__ void merge(float& m, float& z, float mo, float zo) {

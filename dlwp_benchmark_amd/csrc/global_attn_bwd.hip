@@ -22,38 +22,16 @@
 // Row bases are 64-bit.  No atomics and every output element has one writer: results are bitwise reproducible and a
 // sample's gradients do not depend on its batch neighbours.  dqkv is written in the forward's input layout
 // [Bt, N, heads, {q, k, v}, d], so the projection Linear's backward consumes it as it stands.
-#include "common.hpp"
+#include "global_attn_common.hpp"
 
 namespace dlwp {
 namespace gattn_bwd {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace gattn;   // global_attn_common.hpp: kWaves, kRegChunks, load4, mfma4
 
-constexpr int kWaves = 4;        // waves per workgroup; each owns one 16-row tile
-constexpr int kRegChunks = 8;    // head_dim <= 128: the wave's own 16 x d operands stay in registers
 constexpr int kMaxHeadDim = 1024;
 
 enum Mode { kDV = 0, kDK = 1, kDQ = 2 };
-
-// 4 consecutive values [d0, d0 + 4) of one row, zero beyond d or for a row that does not exist (global_attn.hip's load4)
-template <bool VEC>
-__device__ __forceinline__ f32x4 load4(const float* __restrict__ row, int d0, int d, bool ok) {
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if (VEC) {
-    if (ok && d0 < d) v = *reinterpret_cast<const f32x4*>(row + d0);
-  } else if (ok) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-      if (d0 + t < d) v[t] = row[d0 + t];
-  }
-  return v;
-}
-
-__device__ __forceinline__ f32x4 mfma4(f32x4 a, f32x4 b, f32x4 acc) {
-#pragma unroll
-  for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t], b[t], acc, 0, 0, 0);
-  return acc;
-}
 
 // grid (ceil(tiles / 4), batch * heads, slices), block 256.  qkv [b][n][heads][3][d], go (grad of the output) [b][n][heads d],
 // lse2 / dws [bh][n], dqkv like qkv.

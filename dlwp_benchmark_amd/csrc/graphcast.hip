@@ -28,7 +28,7 @@
 // Products are v_mfma_f32_16x16x4_f32: exact fp32 products, fp32 accumulation.  Every weight is read once per 64-row tile.
 // Every output element has one writer and every sum runs in a fixed order (k order in the MFMA chain, CSC order in the
 // aggregate): no atomics, bitwise reproducible, and a sample's result does not depend on its batch neighbours.
-#include "common.hpp"
+#include "gc_common.hpp"
 
 namespace dlwp {
 namespace gc {
@@ -79,22 +79,6 @@ struct Args {
   int ld_gz;
 };
 
-__device__ __forceinline__ float activate(float v, int act) {
-  if (act == 1) return fmaxf(v, 0.f);
-  if (act == 2) return v / (1.0f + expf(-v));
-  return v;
-}
-
-// d act / d z at the pre-activation z, as torch's relu / silu backward: ReLU z > 0; SiLU s (1 + z (1 - s)), s = sigmoid z
-__device__ __forceinline__ float activate_grad(float z, int act) {
-  if (act == 1) return z > 0.f ? 1.f : 0.f;
-  if (act == 2) {
-    const float s = 1.0f / (1.0f + expf(-z));
-    return s * (1.0f + z * (1.0f - s));
-  }
-  return 1.f;
-}
-
 // One staging row of the A tile, decomposed once per thread before the K loop: the row's base offset in `a` (mode 1: its
 // column p of the channels-first block), mode 2's edge range and the sample's edge-table base.  rows past M have ok = 0.
 struct ARow {
@@ -117,6 +101,7 @@ __device__ __forceinline__ ARow a_row(const Args& p, long long m) {
 }
 
 // A-tile element (row described by `r`, column k); zero outside [M, K)
+// (graphcast_bwd.hip's load_a reads the same operand, decomposing the row per element)
 __device__ __forceinline__ float load_a(const Args& p, const ARow& r, int k) {
   if (!r.ok || k >= p.K) return 0.f;
   if (p.mode == 1) return p.a[r.off + (long long)k * p.rows];
@@ -259,12 +244,6 @@ __global__ void __launch_bounds__(kThreads) linear_kernel(const Args p) {
         p.out[o] = v;
       }
   }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
 }
 
 // out[m] = LN(in[m]) * g + beta [+ res], one wave per row of width d <= kMaxWidth (8 values per lane)

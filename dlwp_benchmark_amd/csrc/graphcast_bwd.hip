@@ -21,10 +21,12 @@
 //
 // Products are v_mfma_f32_16x16x4_f32 (exact fp32 products).  No atomics: every sum has a fixed order, so gradients are
 // bitwise reproducible for a given shape.
-#include "common.hpp"
+#include "gc_common.hpp"
 
 namespace dlwp {
 namespace gcb {
+
+using gc::activate;
 
 constexpr int kThreads = 256;
 constexpr int kWave = 64;
@@ -60,13 +62,7 @@ struct WgArgs {
   float* part_b;                       // [slices][N] or null
 };
 
-__device__ __forceinline__ float activate(float v, int act) {
-  if (act == 1) return fmaxf(v, 0.f);
-  if (act == 2) return v / (1.0f + expf(-v));
-  return v;
-}
-
-// A[m][k] of the forward's operand (zero outside [0, M) x [0, K))
+// A[m][k] of the forward's operand (zero outside [0, M) x [0, K)); graphcast.hip's load_a reads it from a precomputed ARow
 __device__ __forceinline__ float load_a(const WgArgs& p, long long m, int k) {
   if (m >= p.M || k >= p.K) return 0.f;
   const long long b = m / p.rows, q = m - b * p.rows;
@@ -198,12 +194,6 @@ __global__ void __launch_bounds__(kThreads) sum_slices_kernel(const float* __res
   float s = 0.f;
   for (int k = 0; k < S; ++k) s += part[k * stride + i];
   out[(i / cols) * ldo + i % cols] = s;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
 }
 
 struct LnArgs {

@@ -27,67 +27,22 @@
 //   scalar (narrow layers, the yaml config's 32 / 34): fp32 FMA chains in k order; each lane keeps four rows'
 //     accumulators, so one weight load feeds four FMAs and one 16-byte LDS read feeds four more.
 // LDS holds the activations of one tile only; weights stream through the caches.
-#include "common.hpp"
+//
+// kThreads, kWave, round4, dense, layernorm_row, the base of Mlp, fill_mlp and set_lds are mgn_common.hpp's, shared with
+// mgn_bwd.hip.
+#include "mgn_common.hpp"
 
 namespace dlwp {
 namespace mgn {
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
 constexpr int kMaxWidth = 512;        // hidden and output widths
 constexpr int kMaxInWidth = 2048;     // input width of dlwp_mgn_mlp_f32
 constexpr size_t kLdsBudget = 64 * 1024;
 constexpr size_t kLdsMax = 150 * 1024;
 
-struct Mlp {
-  int n;                 // Linear count, 2..5
-  int dims[6];
-  const float* wt[5];
-  const float* bias[5];
-  const float* g;
-  const float* b;
+struct Mlp : MlpBase {
   float eps;
 };
-
-__host__ __device__ inline int round4(int x) { return (x + 3) & ~3; }
-
-// out[r][j] = act(bias[j] + sum_k in[r][k] wt[k][j]) for r < R (R % 4 == 0), j < n_out; in / out are LDS tiles
-__device__ __forceinline__ void dense(const float* in, int ldi, int n_in, float* out, int ldo, int n_out,
-                                      const float* __restrict__ wt, const float* __restrict__ bias, int R, bool relu) {
-  const int pairs = (R >> 2) * n_out;
-  for (int p = threadIdx.x; p < pairs; p += kThreads) {
-    const int j = p % n_out, r0 = (p / n_out) * 4;
-    const float* i0 = in + r0 * ldi;
-    const float* i1 = i0 + ldi;
-    const float* i2 = i1 + ldi;
-    const float* i3 = i2 + ldi;
-    const float bj = bias[j];
-    float a0 = bj, a1 = bj, a2 = bj, a3 = bj;
-    const float* w = wt + j;
-    int k = 0;
-    for (; k + 4 <= n_in; k += 4) {
-      const float w0 = w[(size_t)k * n_out], w1 = w[(size_t)(k + 1) * n_out];
-      const float w2 = w[(size_t)(k + 2) * n_out], w3 = w[(size_t)(k + 3) * n_out];
-      const float4 x0 = *reinterpret_cast<const float4*>(i0 + k);
-      const float4 x1 = *reinterpret_cast<const float4*>(i1 + k);
-      const float4 x2 = *reinterpret_cast<const float4*>(i2 + k);
-      const float4 x3 = *reinterpret_cast<const float4*>(i3 + k);
-      a0 = fmaf(x0.x, w0, a0); a1 = fmaf(x1.x, w0, a1); a2 = fmaf(x2.x, w0, a2); a3 = fmaf(x3.x, w0, a3);
-      a0 = fmaf(x0.y, w1, a0); a1 = fmaf(x1.y, w1, a1); a2 = fmaf(x2.y, w1, a2); a3 = fmaf(x3.y, w1, a3);
-      a0 = fmaf(x0.z, w2, a0); a1 = fmaf(x1.z, w2, a1); a2 = fmaf(x2.z, w2, a2); a3 = fmaf(x3.z, w2, a3);
-      a0 = fmaf(x0.w, w3, a0); a1 = fmaf(x1.w, w3, a1); a2 = fmaf(x2.w, w3, a2); a3 = fmaf(x3.w, w3, a3);
-    }
-    for (; k < n_in; ++k) {
-      const float wk = w[(size_t)k * n_out];
-      a0 = fmaf(i0[k], wk, a0); a1 = fmaf(i1[k], wk, a1); a2 = fmaf(i2[k], wk, a2); a3 = fmaf(i3[k], wk, a3);
-    }
-    if (relu) {
-      a0 = fmaxf(a0, 0.f); a1 = fmaxf(a1, 0.f); a2 = fmaxf(a2, 0.f); a3 = fmaxf(a3, 0.f);
-    }
-    float* o = out + r0 * ldo + j;
-    o[0] = a0; o[ldo] = a1; o[2 * ldo] = a2; o[3 * ldo] = a3;
-  }
-}
 
 // the same product on the matrix pipe; RT = R / 16 row tiles.  Lane l supplies A[i = l & 15][k = l >> 4] and
 // B[k = l >> 4][j = l & 15] and holds D[4 (l >> 4) + r][l & 15] (common.hpp mfma16x16x4).
@@ -151,27 +106,6 @@ __device__ __forceinline__ float* chain(const Mlp& m, float* a, int lda, float* 
   }
   ld_res = lda;
   return a;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-
-// LayerNorm of one row of width d in place (two-pass mean / variance, biased, like torch), one wave
-__device__ __forceinline__ void layernorm_row(float* row, int d, const float* __restrict__ g, const float* __restrict__ b,
-                                              float eps, int lane) {
-  float s = 0.f;
-  for (int k = lane; k < d; k += kWave) s += row[k];
-  const float mean = wave_sum(s) / (float)d;
-  float q = 0.f;
-  for (int k = lane; k < d; k += kWave) {
-    const float c = row[k] - mean;
-    q = fmaf(c, c, q);
-  }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)d + eps);
-  for (int k = lane; k < d; k += kWave) row[k] = fmaf((row[k] - mean) * rstd, g[k], b[k]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -326,23 +260,8 @@ __global__ void __launch_bounds__(kThreads) layer_kernel(Mlp em, Mlp nm, int mea
 }
 
 static int32_t to_mlp(const dlwp_mgn_mlp_desc* d, Mlp& m, int max_in) {
-  DLWP_REQUIRE(d, DLWP_ERR_INVALID_ARGUMENT, "mgn: null MLP descriptor");
-  DLWP_REQUIRE(d->n_linear >= 2 && d->n_linear <= 5, DLWP_ERR_UNSUPPORTED, "mgn: %d Linears (2..5 supported)", d->n_linear);
-  m.n = d->n_linear;
-  for (int i = 0; i <= m.n; ++i) {
-    m.dims[i] = d->dims[i];
-    DLWP_REQUIRE(d->dims[i] > 0, DLWP_ERR_INVALID_ARGUMENT, "mgn: width %d of layer %d", d->dims[i], i);
-    DLWP_REQUIRE(d->dims[i] <= (i == 0 ? max_in : kMaxWidth), DLWP_ERR_UNSUPPORTED, "mgn: width %d of layer %d is outside the envelope",
-                 d->dims[i], i);
-  }
-  for (int i = m.n + 1; i < 6; ++i) m.dims[i] = 0;
-  for (int i = 0; i < 5; ++i) {
-    m.wt[i] = i < m.n ? d->wt[i] : nullptr;
-    m.bias[i] = i < m.n ? d->bias[i] : nullptr;
-    if (i < m.n) DLWP_REQUIRE(d->wt[i] && d->bias[i], DLWP_ERR_INVALID_ARGUMENT, "mgn: null weight of Linear %d", i);
-  }
-  m.g = d->ln_gamma;
-  m.b = d->ln_beta;
+  const int32_t rc = fill_mlp(d, m, max_in, kMaxWidth, "mgn", "envelope");
+  if (rc) return rc;
   m.eps = d->ln_eps;
   DLWP_REQUIRE((m.g == nullptr) == (m.b == nullptr), DLWP_ERR_INVALID_ARGUMENT, "mgn: LayerNorm needs both gamma and beta");
   return DLWP_OK;
@@ -379,13 +298,6 @@ static int pad_ld(int x, bool mfma) {
 }
 
 constexpr int kMfmaMinWidth = 64;     // narrower layers keep the scalar form (16-column tiles would idle too many lanes)
-
-template <class K>
-static int32_t set_lds(K kern, size_t lds) {
-  if (lds > 64 * 1024)
-    DLWP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  return DLWP_OK;
-}
 
 }  // namespace mgn
 }  // namespace dlwp

@@ -26,78 +26,29 @@
 // Every output element has one writer, every sum runs in a fixed order, no atomics: bitwise reproducible, and a sample's
 // input gradients do not depend on its batch neighbours.  Products are fp32 FMA chains (exact fp32 products).
 // Parameter gradients are laid out per MLP as [W_0 (d_0 x d_1, [in][out]), b_0, W_1, b_1, ..., gamma, beta].
-#include "common.hpp"
+//
+// The forward's pieces that are recomputed here -- kThreads, kWave, round4, dense, layernorm_row, the base of Mlp -- and
+// fill_mlp / set_lds are mgn_common.hpp's, the very definitions mgn.hip runs.
+#include "mgn_common.hpp"
 
 namespace dlwp {
 namespace mgn_bwd {
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
+using namespace mgn;   // what mgn_common.hpp defines there
+
 constexpr int kWaves = kThreads / kWave;
 constexpr int kMaxWidth = 64;         // hidden and output widths (include/dlwp_hip.h)
 constexpr int kMaxMlpIn = 256;        // input width of dlwp_mgn_mlp_bwd_f32
 constexpr size_t kLdsTwoPerCu = 80 * 1024;   // two workgroups share a CU's 160 KiB
 constexpr int kPartials = 512;                // partial-writing workgroups: two per CU (MI355X: 256 CUs)
 
-struct Mlp {
-  int n;                 // Linear count, 2..5
-  int dims[6];
-  const float* wt[5];    // [dims[l]][dims[l + 1]]
-  const float* bias[5];
-  const float* g;
-  const float* b;
+struct Mlp : MlpBase {
   float eps;
   int off_w[5];          // offsets in the parameter-gradient layout
   int off_b[5];
   int off_g;             // gamma at off_g, beta at off_g + dims[n]
   int n_params;
 };
-
-__host__ __device__ inline int round4(int x) { return (x + 3) & ~3; }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-
-// out[r][j] = act(bias[j] + sum_k in[r][k] wt[k][j]) for r < R (R % 4 == 0): the forward's product, k order
-__device__ __forceinline__ void dense(const float* in, int ldi, int n_in, float* out, int ldo, int n_out,
-                                      const float* __restrict__ wt, const float* __restrict__ bias, int R, bool relu) {
-  const int pairs = (R >> 2) * n_out;
-  for (int p = threadIdx.x; p < pairs; p += kThreads) {
-    const int j = p % n_out, r0 = (p / n_out) * 4;
-    const float* i0 = in + r0 * ldi;
-    const float* i1 = i0 + ldi;
-    const float* i2 = i1 + ldi;
-    const float* i3 = i2 + ldi;
-    const float bj = bias[j];
-    float a0 = bj, a1 = bj, a2 = bj, a3 = bj;
-    const float* w = wt + j;
-    int k = 0;
-    for (; k + 4 <= n_in; k += 4) {
-      const float w0 = w[(size_t)k * n_out], w1 = w[(size_t)(k + 1) * n_out];
-      const float w2 = w[(size_t)(k + 2) * n_out], w3 = w[(size_t)(k + 3) * n_out];
-      const float4 x0 = *reinterpret_cast<const float4*>(i0 + k);
-      const float4 x1 = *reinterpret_cast<const float4*>(i1 + k);
-      const float4 x2 = *reinterpret_cast<const float4*>(i2 + k);
-      const float4 x3 = *reinterpret_cast<const float4*>(i3 + k);
-      a0 = fmaf(x0.x, w0, a0); a1 = fmaf(x1.x, w0, a1); a2 = fmaf(x2.x, w0, a2); a3 = fmaf(x3.x, w0, a3);
-      a0 = fmaf(x0.y, w1, a0); a1 = fmaf(x1.y, w1, a1); a2 = fmaf(x2.y, w1, a2); a3 = fmaf(x3.y, w1, a3);
-      a0 = fmaf(x0.z, w2, a0); a1 = fmaf(x1.z, w2, a1); a2 = fmaf(x2.z, w2, a2); a3 = fmaf(x3.z, w2, a3);
-      a0 = fmaf(x0.w, w3, a0); a1 = fmaf(x1.w, w3, a1); a2 = fmaf(x2.w, w3, a2); a3 = fmaf(x3.w, w3, a3);
-    }
-    for (; k < n_in; ++k) {
-      const float wk = w[(size_t)k * n_out];
-      a0 = fmaf(i0[k], wk, a0); a1 = fmaf(i1[k], wk, a1); a2 = fmaf(i2[k], wk, a2); a3 = fmaf(i3[k], wk, a3);
-    }
-    if (relu) {
-      a0 = fmaxf(a0, 0.f); a1 = fmaxf(a1, 0.f); a2 = fmaxf(a2, 0.f); a3 = fmaxf(a3, 0.f);
-    }
-    float* o = out + r0 * ldo + j;
-    o[0] = a0; o[ldo] = a1; o[2 * ldo] = a2; o[3 * ldo] = a3;
-  }
-}
 
 // dh[r][k] = sum_j dl[r][j] wt[k][j]  (the input gradient of one Linear, j order), times [mask[r][k] > 0] when mask is
 // given (the ReLU in front of the Linear: mask is the ReLU's output, the Linear's input)
@@ -187,21 +138,6 @@ __device__ __forceinline__ void zero_partials(const Mlp& m, float* part) {
   }
   if (m.g)
     for (int p = threadIdx.x; p < 2 * m.dims[m.n]; p += kThreads) part[m.off_g + p] = 0.f;
-}
-
-// LayerNorm of one row in place (two-pass mean / biased variance, like torch and the forward), one wave
-__device__ __forceinline__ void layernorm_row(float* row, int d, const float* __restrict__ g, const float* __restrict__ b,
-                                              float eps, int lane) {
-  float s = 0.f;
-  for (int k = lane; k < d; k += kWave) s += row[k];
-  const float mean = wave_sum(s) / (float)d;
-  float q = 0.f;
-  for (int k = lane; k < d; k += kWave) {
-    const float c = row[k] - mean;
-    q = fmaf(c, c, q);
-  }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)d + eps);
-  for (int k = lane; k < d; k += kWave) row[k] = fmaf((row[k] - mean) * rstd, g[k], b[k]);
 }
 
 // LayerNorm backward of one row, one wave: z (the pre-norm row) is replaced by xhat, dz = rstd (dy g - mean(dy g)
@@ -623,34 +559,20 @@ __global__ void __launch_bounds__(kThreads) sum_partials_kernel(const float* __r
 }
 
 static int32_t to_mlp(const dlwp_mgn_mlp_desc* d, Mlp& m, int max_in) {
-  DLWP_REQUIRE(d, DLWP_ERR_INVALID_ARGUMENT, "mgn bwd: null MLP descriptor");
-  DLWP_REQUIRE(d->n_linear >= 2 && d->n_linear <= 5, DLWP_ERR_UNSUPPORTED, "mgn bwd: %d Linears (2..5 supported)",
-               d->n_linear);
-  m.n = d->n_linear;
+  const int32_t rc = fill_mlp(d, m, max_in, kMaxWidth, "mgn bwd", "backward envelope");
+  if (rc) return rc;
+  m.eps = d->ln_eps;
+  DLWP_REQUIRE((m.g == nullptr) == (m.b == nullptr), DLWP_ERR_INVALID_ARGUMENT, "mgn bwd: LayerNorm needs gamma and beta");
   int off = 0;
-  for (int i = 0; i <= m.n; ++i) {
-    m.dims[i] = d->dims[i];
-    DLWP_REQUIRE(d->dims[i] > 0, DLWP_ERR_INVALID_ARGUMENT, "mgn bwd: width %d of layer %d", d->dims[i], i);
-    DLWP_REQUIRE(d->dims[i] <= (i == 0 ? max_in : kMaxWidth), DLWP_ERR_UNSUPPORTED,
-                 "mgn bwd: width %d of layer %d is outside the backward envelope", d->dims[i], i);
-  }
-  for (int i = m.n + 1; i < 6; ++i) m.dims[i] = 0;
   for (int i = 0; i < 5; ++i) {
-    m.wt[i] = i < m.n ? d->wt[i] : nullptr;
-    m.bias[i] = i < m.n ? d->bias[i] : nullptr;
     m.off_w[i] = m.off_b[i] = 0;
     if (i < m.n) {
-      DLWP_REQUIRE(d->wt[i] && d->bias[i], DLWP_ERR_INVALID_ARGUMENT, "mgn bwd: null weight of Linear %d", i);
       m.off_w[i] = off;
       off += m.dims[i] * m.dims[i + 1];
       m.off_b[i] = off;
       off += m.dims[i + 1];
     }
   }
-  m.g = d->ln_gamma;
-  m.b = d->ln_beta;
-  m.eps = d->ln_eps;
-  DLWP_REQUIRE((m.g == nullptr) == (m.b == nullptr), DLWP_ERR_INVALID_ARGUMENT, "mgn bwd: LayerNorm needs gamma and beta");
   m.off_g = off;
   if (m.g) off += 2 * m.dims[m.n];
   m.n_params = off;
@@ -730,13 +652,6 @@ static int32_t check_layer(const Mlp& em, const Mlp& nm) {
   for (int i = 1; i < nm.n; ++i)
     DLWP_REQUIRE(nm.dims[i] <= D, DLWP_ERR_UNSUPPORTED, "mgn layer bwd: node hidden %d > %d", nm.dims[i], D);
   DLWP_REQUIRE(em.g && nm.g, DLWP_ERR_INVALID_ARGUMENT, "mgn layer bwd: both MLPs end in a LayerNorm");
-  return DLWP_OK;
-}
-
-template <class K>
-static int32_t set_lds(K kern, size_t lds) {
-  if (lds > 64 * 1024)
-    DLWP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   return DLWP_OK;
 }
 

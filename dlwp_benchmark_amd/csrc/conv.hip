@@ -8,8 +8,10 @@
 // 16-channel output chunk; the (TH+2)x(TW+2) input halo
 // tile of a chunk of input channels is staged in LDS with the cylinder rule applied at load time
 // (longitude wraps, latitude pads with zeros), every thread owns one pixel and accumulates a chunk of
-// output channels with weights broadcast from LDS; bias + activation fused in the epilogue.
+// output channels with weights broadcast from LDS; bias + activation fused in the epilogue.  The per-element load of the
+// halo tile is conv3x3_load.hpp's, which the weight gradient (conv3x3_wgrad.hip) shares.
 #include "act_common.hpp"
+#include "conv3x3_load.hpp"
 
 namespace dlwp {
 namespace conv {
@@ -61,40 +63,7 @@ __global__ __launch_bounds__(TH * TW) void conv3x3_cyl_kernel(const Params p) {
         const int ci = i / ((TH + 2) * (TW + 2));
         const int rem = i % ((TH + 2) * (TW + 2));
         const int r = rem / (TW + 2), cc = rem % (TW + 2);
-        const int c = ci0 + ci;
-        const int ih = h0 + r - 1;
-        int iw = w0 + cc - 1;
-        float v = 0.f;
-        bool corner_done = false;
-        if (p.hpx) {
-          if (c < cin && ih >= -1 && ih <= p.H && iw >= -1 && iw <= p.W) {
-            const bool seg0 = c < p.c0;
-            const float* base = seg0 ? p.x0 : p.x1;
-            const int cs = seg0 ? p.c0 : p.c1, cl = seg0 ? c : c - p.c0;
-            if (ih >= 0 && ih < p.H && iw >= 0 && iw < p.W) {
-              v = base[((long long)b * cs + cl) * HW + (long long)ih * p.W + iw];
-            } else {
-              const int face = b % 12, s0 = b - face;
-              const int2 e = p.hpx[(long long)face * (p.H + 2) * (p.W + 2) + (ih + 1) * (p.W + 2) + (iw + 1)];
-              const int fa = e.x / (int)HW;
-              v = base[((long long)(s0 + fa) * cs + cl) * HW + (e.x - fa * (int)HW)];
-              if (e.y >= 0) {
-                // a synthesised corner is the mean of two cells of the ACTIVATED tensor (the reference pads after the
-                // activation, unet.py:886-887): activate each source, then average; flag the value as done
-                const int fb = e.y / (int)HW;
-                const float v2 = base[((long long)(s0 + fb) * cs + cl) * HW + (e.y - fb * (int)HW)];
-                if (p.pre_act) { v = 0.5f * apply_act(v, p.pre_act) + 0.5f * apply_act(v2, p.pre_act); corner_done = true; }
-                else v = 0.5f * v + 0.5f * v2;
-              }
-            }
-          }
-        } else if (c < cin && ih >= 0 && ih < p.H && iw >= -1 && iw <= p.W) {
-          iw = iw < 0 ? iw + p.W : (iw >= p.W ? iw - p.W : iw);   // circular longitude
-          const float* src = c < p.c0 ? p.x0 + ((long long)b * p.c0 + c) * HW
-                                      : p.x1 + ((long long)b * p.c1 + (c - p.c0)) * HW;
-          v = src[(long long)ih * p.W + iw];
-        }
-        (&s_in[0][0][0])[i] = (p.pre_act && !corner_done) ? apply_act(v, p.pre_act) : v;   // padding zeros stay zero (act(0) = 0)
+        (&s_in[0][0][0])[i] = load_padded_act(p, b, ci0 + ci, h0 + r - 1, w0 + cc - 1);   // conv3x3_load.hpp
       }
       for (int i = tid; i < CO_CHUNK * CI_CHUNK * 9; i += NT) {
         const int k = i / (CI_CHUNK * 9), rem = i % (CI_CHUNK * 9);

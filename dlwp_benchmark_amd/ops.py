@@ -624,6 +624,57 @@ def conv3x3_hpx_backward_data(dy: torch.Tensor, weight: torch.Tensor, cin: int) 
     return dx
 
 
+def conv3x3_weight_grad_supported(batch: int, c0: int, c1: int, cout: int, h: int, w: int, hpx: bool = False) -> bool:
+    """whether dlwp_conv3x3_wgrad_f32 takes the shape (its envelope: include/dlwp_hip.h); needs the library, not a GPU"""
+    if min(int(batch), int(c0), int(cout), int(h), int(w)) < 1 or int(c1) < 0 or (hpx and (int(batch) % 12 or h != w)):
+        return False
+    if max(int(batch), int(c0), int(c1), int(cout), int(h), int(w)) >= 1 << 31:
+        return False
+    return _lib.load().dlwp_conv3x3_wgrad_workspace_bytes(int(batch), int(h), int(w), int(c0) + int(c1), int(cout)) > 0
+
+
+def conv3x3_weight_grad(x0: torch.Tensor, x1: Optional[torch.Tensor], dz: torch.Tensor, pre_act: int = 0, hpx: bool = False,
+                        need_bias: bool = True):
+    """Weight and bias gradient of pad(1) + Conv2d(3x3) on cat([x0, x1], 1) (conv3x3's arguments) from dz [N, cout, H, W], the
+    gradient of the convolution's output: (dw [cout, c0+c1, 3, 3], db [cout] or None) on dlwp_conv3x3_wgrad_f32.  The input is
+    read the way the forward reads it -- segments, `pre_act` and the padding rule applied at load, no copies.  Runs on the
+    current stream without a host synchronisation; reruns are bitwise identical."""
+    for t, name in ((x0, "x0"), (x1, "x1"), (dz, "dz")):
+        _lib.require_cuda_tensor(t, name)
+    x0 = x0.contiguous()
+    x1 = x1.contiguous() if x1 is not None else None
+    dz = dz.contiguous()
+    if x0.dim() != 4 or dz.dim() != 4:
+        raise _lib.DlwpError(f"conv3x3_weight_grad: x0 {tuple(x0.shape)} and dz {tuple(dz.shape)} must be [N, C, H, W]")
+    n, c0, h, w = x0.shape
+    c1 = x1.shape[1] if x1 is not None else 0
+    cout = dz.shape[1]
+    if x1 is not None and (x1.dim() != 4 or tuple(x1.shape) != (n, c1, h, w)):
+        raise _lib.DlwpError(f"conv3x3_weight_grad: x1 {tuple(x1.shape)} does not match x0 {tuple(x0.shape)}")
+    if tuple(dz.shape) != (n, cout, h, w):
+        raise _lib.DlwpError(f"conv3x3_weight_grad: dz {tuple(dz.shape)} does not match the input {(n, c0 + c1, h, w)}")
+    table = None
+    if hpx:
+        from . import healpix as _hpx
+
+        if n % 12:
+            raise _lib.DlwpError(f"leading dimension {n} is not (batch * 12 faces)")
+        table = _hpx.device_table(h, w, 1, x0.device)
+    lib = _lib.load()
+    nbytes = int(lib.dlwp_conv3x3_wgrad_workspace_bytes(n, h, w, c0 + c1, cout)) if max(n, c0, c1, cout, h, w) < 1 << 31 else 0
+    if nbytes == 0 or (hpx and h != w):       # the one query gives the envelope (conv3x3_weight_grad_supported) and the size
+        raise _lib.DlwpError(f"conv3x3_weight_grad: no HIP kernel for {c0}+{c1} -> {cout} channels on {n} x {h} x {w}")
+    dw = torch.empty(cout, c0 + c1, 3, 3, device=x0.device, dtype=torch.float32)
+    db = torch.empty(cout, device=x0.device, dtype=torch.float32) if need_bias else None
+    with torch.cuda.device(x0.device):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x0.device)
+        _lib.check(lib.dlwp_conv3x3_wgrad_f32(x0.data_ptr(), c0, x1.data_ptr() if x1 is not None else None, c1, dz.data_ptr(),
+                                              dw.data_ptr(), db.data_ptr() if db is not None else None, n, h, w, cout,
+                                              int(pre_act), table.data_ptr() if table is not None else None, ws.data_ptr(),
+                                              nbytes, _lib.stream_ptr()), "dlwp_conv3x3_wgrad_f32")
+    return dw, db
+
+
 def convlstm_gates(gates: torch.Tensor, c_prev: torch.Tensor):
     _lib.require_cuda_tensor(gates, "gates")
     _lib.require_cuda_tensor(c_prev, "c_prev")

@@ -498,6 +498,59 @@ def conv3x3_torch(x0, x1, weight, bias, resid, pre_act: int, act: int, hpx_table
     return _ACT_FNS[act](y)
 
 
+def conv3x3_weight_grad_torch(x0, x1, gz, pre_act: int, hpx_table=None, need_weight: bool = True, need_bias: bool = True):
+    """(dW, db) of conv3x3_torch from gz, the gradient of the convolution's output, as the composition of library operators:
+    torch.cat, the pre-activation, the padded copy, torch.nn.grad.conv2d_weight (MIOpen on the GPU) and gz.sum.  On any device:
+    the DLWP_CONV_WGRAD=torch path of _Conv3x3Fn.backward, the CPU reference of dlwp_conv3x3_wgrad_f32 and the torch form
+    tools/bench_conv_wgrad.py times.  hpx_table: the pad-1 table of healpix.device_table (HEALPixPadding), None = CylinderPad."""
+    dw = db = None
+    if need_weight:
+        xcat = x0 if x1 is None else torch.cat([x0, x1], dim=1)
+        xa = _ACT_FNS[pre_act](xcat)
+        if hpx_table is None:
+            xp = F.pad(F.pad(xa, (1, 1, 0, 0), mode="circular"), (0, 0, 1, 1))
+        elif xa.is_cuda:
+            from . import ops
+
+            xp = ops.healpix_pad(xa, 1)
+        else:
+            xp = _hpx_pad_torch(xa, hpx_table)
+        dw = torch.nn.grad.conv2d_weight(xp, (gz.shape[1], xcat.shape[1], 3, 3), gz)
+    if need_bias:
+        db = gz.sum(dim=(0, 2, 3))
+    return dw, db
+
+
+CONV_WGRAD_MODES = ("auto", "hip", "torch")
+# DLWP_CONV_WGRAD=auto: layers of fewer FLOPs than this (2 N H W cin cout 9) keep the torch form.  Value from the per-layer
+# table of profiles/conv_wgrad.jsonl (tools/bench_conv_wgrad.py, DESIGN.md section 23): of the 14 measured layers above it 12
+# run 0.97-1.35 x MIOpen's composition on dlwp_conv3x3_wgrad_f32 and two lose (68 -> 272 on 32 x 32 faces 0.72 x, 12 -> 136
+# on 64 x 64 faces 0.58 x: narrow sides fill little of a 64 x 64 channel block); of the 53 below it 51 run 0.34-0.93 x, the
+# other two 1.26 and 1.12 x.  Whole steps under auto are not slower than torch on any of the seven measured networks
+CONV_WGRAD_AUTO_MIN_FLOPS = 40e9
+
+
+def conv_wgrad_mode() -> str:
+    """DLWP_CONV_WGRAD: "hip" every supported 3x3 weight gradient on dlwp_conv3x3_wgrad_f32, "torch" the library composition
+    conv3x3_weight_grad_torch, "auto" (default) HIP where it is supported and measured not slower.  Read at every backward."""
+    import os
+
+    mode = os.environ.get("DLWP_CONV_WGRAD", "auto")
+    if mode not in CONV_WGRAD_MODES:
+        raise _lib.DlwpError(f"DLWP_CONV_WGRAD={mode!r}: one of {CONV_WGRAD_MODES}")
+    return mode
+
+
+def conv_wgrad_uses_hip(batch: int, c0: int, c1: int, cout: int, h: int, w: int, hpx: bool) -> bool:
+    """whether _Conv3x3Fn.backward takes the HIP weight gradient for a layer under the current DLWP_CONV_WGRAD"""
+    from . import ops
+
+    mode = conv_wgrad_mode()
+    if mode == "torch" or (mode == "auto" and 18.0 * batch * h * w * (c0 + c1) * cout < CONV_WGRAD_AUTO_MIN_FLOPS):
+        return False                                     # decided without a library call
+    return ops.conv3x3_weight_grad_supported(batch, c0, c1, cout, h, w, hpx)
+
+
 # output channels up to which the HEALPix input gradient runs dlwp_conv3x3_hpx_bwd_data_f32; wider layers take the two-step
 # form (MIOpen transposed conv + dlwp_healpix_pad_bwd_f32), which measured faster there (DESIGN.md section 13)
 HPX_DX_DIRECT_MAX_COUT = 48
@@ -524,14 +577,21 @@ class _Conv3x3Fn(torch.autograd.Function):
         if not _TORCH_BACKWARD():
             # CylinderPad (circular in longitude, zeros in latitude) + 3x3: the input gradient is the SAME operator with the weights
             # transposed and flipped -- dlwp_conv3x3_ex_f32 again (reference backward: train.py:271 through unet.py:429-555,
-            # convlstm.py:82-111); pre- / post-activation derivatives are pointwise torch operators, the weight gradient is one
-            # correlation of the padded input with the output gradient (MIOpen through torch, like the other weight gradients).
+            # convlstm.py:82-111); pre- / post-activation derivatives are pointwise torch operators, the weight and bias gradients
+            # are one dlwp_conv3x3_wgrad_f32 call on the unpadded segments (DLWP_CONV_WGRAD: or conv3x3_weight_grad_torch, the
+            # correlation of a padded copy with the output gradient through MIOpen).
             # HEALPixPadding(1) + 3x3 (healpix.py:69-114): the input gradient is dlwp_conv3x3_hpx_bwd_data_f32 (the transposed
-            # 3x3 folded through the adjoint of the padding table) and the padded input of the weight gradient is
-            # dlwp_healpix_pad_f32; everything else is the cylinder path's
+            # 3x3 folded through the adjoint of the padding table); everything else is the cylinder path's
             x0, x1, weight, bias, resid = saved
             with torch.no_grad():
-                xcat = x0 if x1 is None else torch.cat([x0, x1], dim=1)
+                cat = []        # cat([x0, x1], 1), made once and only where a step below reads it
+
+                def xcat():
+                    if not cat:
+                        cat.append(x0 if x1 is None else torch.cat([x0, x1], dim=1))
+                    return cat[0]
+
+                c0, c1 = x0.shape[1], (x1.shape[1] if x1 is not None else 0)
                 gz = grad_out.contiguous()
                 if act != 0:
                     z = ops.conv3x3(x0, weight, bias, act=0, x1=x1, pre_act=pre_act, resid=resid, hpx=hpx)
@@ -542,7 +602,7 @@ class _Conv3x3Fn(torch.autograd.Function):
                 res = [None] * 5
                 if ctx.needs_input_grad[0] or (x1 is not None and ctx.needs_input_grad[1]):
                     if hpx and weight.shape[0] <= HPX_DX_DIRECT_MAX_COUT:
-                        dxa = ops.conv3x3_hpx_backward_data(gz, weight, xcat.shape[1])
+                        dxa = ops.conv3x3_hpx_backward_data(gz, weight, c0 + c1)
                     elif hpx:
                         # wide layers: the full transposed 3x3 (MIOpen) onto the padded face, folded by the padding's adjoint
                         dxa = ops.healpix_pad_backward(F.conv_transpose2d(gz, weight), 1)
@@ -551,20 +611,20 @@ class _Conv3x3Fn(torch.autograd.Function):
                         dxa = ops.conv3x3(gz, wt, None)
                     if pre_act != 0:
                         with torch.enable_grad():
-                            xc_ = xcat.detach().requires_grad_(True)
+                            xc_ = xcat().detach().requires_grad_(True)
                             dxa, = torch.autograd.grad(_ACT_FNS[pre_act](xc_), xc_, dxa)
-                    c0 = x0.shape[1]
                     res[0] = dxa[:, :c0].contiguous() if ctx.needs_input_grad[0] else None
                     res[1] = dxa[:, c0:].contiguous() if (x1 is not None and ctx.needs_input_grad[1]) else None
-                if ctx.needs_input_grad[2]:
-                    xa = _ACT_FNS[pre_act](xcat)
-                    if hpx:
-                        xp = ops.healpix_pad(xa, 1)
+                need_w, need_b = ctx.needs_input_grad[2], bias is not None and ctx.needs_input_grad[3]
+                if need_w or need_b:
+                    n_, _, h_, w_ = x0.shape
+                    if conv_wgrad_uses_hip(n_, c0, c1, weight.shape[0], h_, w_, hpx):
+                        dw, db = ops.conv3x3_weight_grad(x0, x1, gz, pre_act=pre_act, hpx=hpx, need_bias=need_b)
                     else:
-                        xp = F.pad(F.pad(xa, (1, 1, 0, 0), mode="circular"), (0, 0, 1, 1))
-                    res[2] = torch.nn.grad.conv2d_weight(xp, weight.shape, gz)
-                if bias is not None and ctx.needs_input_grad[3]:
-                    res[3] = gz.sum(dim=(0, 2, 3))
+                        table = _hpx.device_table(h_, w_, 1, x0.device) if hpx else None
+                        dw, db = conv3x3_weight_grad_torch(xcat(), None, gz, pre_act, table, need_weight=need_w, need_bias=need_b)
+                    res[2] = dw if need_w else None
+                    res[3] = db if need_b else None
                 if resid is not None and ctx.needs_input_grad[4]:
                     res[4] = gz
             return (*res, None, None, None)

@@ -541,6 +541,29 @@ int32_t dlwp_conv3x3_hpx_bwd_data_f32(const float* dy_dev, const float* weight_d
                                       const float* adj_weight_dev, void* workspace, size_t workspace_bytes,
                                       void* stream);
 
+/* Weight and bias gradient of pad(1) + Conv2d(3x3, padding 0) on cat([x0, x1], 1), either padding rule (csrc/conv3x3_wgrad.hip;
+ * the reference lines differentiated: scripts/train.py:271 through models/unet/unet.py:456-470, :512-525, :886,
+ * models/convlstm/convlstm.py:94, :148-157, utils/healpix.py:69-114):
+ *   dw[co][ci][ky][kx] = sum_{b,y,x} dz[b][co][y][x] * P(act_pre(xcat))[b][ci][y+ky][x+kx],   db[co] = sum_{b,y,x} dz[b][co][y][x]
+ * x0_dev, c0, x1_dev, c1, pre_act and ring_table as dlwp_conv3x3_ex_f32 (ring_table NULL: CylinderPad, else the HEALPix halo
+ * table with batch = 12 * samples faces): the padded, pre-activated input is read the way the forward reads it, no cat, activated
+ * or padded copy is made.  dz_dev [batch, cout, H, W] is the gradient of the convolution's output (after the post-activation
+ * derivative); dw_dev [cout, c0+c1, 3, 3]; db_dev [cout] or NULL.  Exact-fp32 matrix instructions (an fmaf chain per element).
+ * Two launches on `stream`: partial sums of the K-slices (runs of consecutive 8 x 8 pixel tiles) into the workspace, then their
+ * sum in slice order.  One writer per element, no atomics, a slice count that depends on the shape arguments only: results are
+ * bit-identical from run to run.  No pointer needs more than 4-byte alignment.
+ * Envelope: c0 >= 1, c1 >= 0, cout >= 1, c0 + c1 and cout up to 1024, any H, W >= 1, per-sample offsets (channels * H * W)
+ * within 32 bits, HEALPix batches a multiple of 12; anything else returns DLWP_ERR_UNSUPPORTED before any launch.
+ *   dlwp_conv3x3_wgrad_workspace_bytes: slices * (cout * cin * 9 + cout) floats, cin = c0 + c1 (0 = unsupported shape); a
+ *   smaller workspace returns DLWP_ERR_WORKSPACE.
+ *   dlwp_conv3x3_wgrad_slices: the K-slices the launcher takes (0 = unsupported shape).  For tests and tools. */
+size_t dlwp_conv3x3_wgrad_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t cin, int32_t cout);
+int32_t dlwp_conv3x3_wgrad_slices(int32_t batch, int32_t height, int32_t width, int32_t cin, int32_t cout);
+int32_t dlwp_conv3x3_wgrad_f32(const float* x0_dev, int32_t c0, const float* x1_dev, int32_t c1, const float* dz_dev,
+                               float* dw_dev, float* db_dev, int32_t batch, int32_t height, int32_t width, int32_t cout,
+                               int32_t pre_act, const int32_t* ring_table, void* workspace, size_t workspace_bytes,
+                               void* stream);
+
 /* ConvLSTM cell gate math (models/convlstm/convlstm.py:96-109): gates_dev [B, 4*hidden, H, W] in the
  * order (netin, igate, fgate, ogate), c_prev_dev [B, hidden, H, W] -> h_out_dev, c_out_dev. */
 int32_t dlwp_convlstm_gates_f32(const float* gates_dev, const float* c_prev_dev, float* h_out_dev,

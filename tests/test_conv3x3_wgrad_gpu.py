@@ -1,0 +1,229 @@
+"""dlwp_conv3x3_wgrad_f32 (csrc/conv3x3_wgrad.hip) on the GPU: the weight / bias gradient of the 3x3 convolutions of the U-Net
+and ConvLSTM families, and its wiring into training._Conv3x3Fn.backward under DLWP_CONV_WGRAD.
+
+  * every case of test_conv3x3_wgrad_cpu.CASES against fp64 autograd of training.conv3x3_torch: relative L2 of dW and of db
+    <= 1e-5 (the project's fp32 bound; a sequential fp32 chain over normal data deviates 6e-7 at K = 1024 and 1.2e-6 at
+    K = 4096, the largest K here is 1536);
+  * whole-number inputs, every sum exact in fp32: torch.equal to the fp64 reference (a swapped row / column, tap or pixel
+    order cannot pass);
+  * reruns bitwise identical; need_bias=False; bad arguments; a workspace one byte short;
+  * ops.conv3x3 under autograd with DLWP_CONV_WGRAD=hip against fp64 autograd, all five inputs, need_bias following
+    needs_input_grad;
+  * the rollout-MSE step of the U-Net / ConvLSTM fixtures of both grids with torch.nn.grad.conv2d_weight patched to raise, at
+    the bounds of test_training_gpu.py / test_hpx_train_gpu.py (they run those tests' own drivers);
+  * hip and torch paths agree to 1e-5 per parameter on munethpx_h16_8_norm."""
+import ctypes
+
+import pytest
+import torch
+
+from helpers import rel_l2
+from test_conv3x3_wgrad_cpu import CASES, deviation, inputs, make_inputs, reference, reference_of
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def _dev(t, offset):
+    """t on the GPU, contiguous; offset: as a view that starts one float into its storage (4-byte-aligned pointer)"""
+    if t is None:
+        return None
+    if not offset:
+        return t.to(DEV)
+    store = torch.empty(t.numel() + 1, device=DEV, dtype=torch.float32)
+    view = store[1:].view(t.shape)
+    view.copy_(t)
+    assert view.is_contiguous() and view.data_ptr() % 16 == 4
+    return view
+
+
+def _run(tag, tensors=None, pre_act=None, need_bias=True):
+    from dlwp_benchmark_amd import ops
+
+    x0, x1, dz = tensors if tensors is not None else inputs(tag)
+    offset = CASES[tag][8]
+    dw, db = ops.conv3x3_weight_grad(_dev(x0, offset), _dev(x1, offset), _dev(dz, offset),
+                                     pre_act=CASES[tag][6] if pre_act is None else pre_act, hpx=CASES[tag][7],
+                                     need_bias=need_bias)
+    torch.cuda.synchronize()
+    return dw, db
+
+
+def _slices(tag):
+    from dlwp_benchmark_amd import lib
+
+    b, c0, c1, cout, h, w = CASES[tag][:6]
+    return int(lib.load().dlwp_conv3x3_wgrad_slices(b, h, w, c0 + c1, cout))
+
+
+@pytest.mark.parametrize("tag", list(CASES))
+def test_matches_fp64_reference(tag):
+    dw, db = _run(tag)
+    want_w, want_b = reference(tag)
+    assert tuple(dw.shape) == tuple(want_w.shape) and tuple(db.shape) == tuple(want_b.shape)
+    ew, eb = deviation(dw, want_w), deviation(db, want_b)
+    print(tag, "slices %d, dW %.2e db %.2e" % (_slices(tag), ew, eb))
+    assert ew <= 1e-5 and eb <= 1e-5
+
+
+def test_slice_counts():
+    """multi_slice is the smallest cylinder shape that takes two slices with a shorter last one: 5 tiles (five 1 x 1 maps), runs
+    of one length with the remainder last, at least 4 tiles per run -- two slices cannot split 5 tiles evenly, and 4 tiles are
+    one slice; tiny takes one"""
+    from dlwp_benchmark_amd import lib
+
+    q = lib.load().dlwp_conv3x3_wgrad_slices
+    b, c0, c1, cout, h, w = CASES["multi_slice"][:6]
+    tiles = b * -(-h // 8) * -(-w // 8)
+    assert _slices("tiny") == 1
+    assert tiles == 5 and _slices("multi_slice") == 2 and tiles % 2 == 1
+    assert q(4, h, w, c0 + c1, cout) == 1              # 4 tiles: one full slice, so every smaller shape has one slice
+    assert q(8, h, w, c0 + c1, cout) == 2              # 8 tiles: two full slices of 4, so at 5 the last one holds 1
+    assert q(9, h, w, c0 + c1, cout) == 3
+    assert q(1, 3, 33, 2, 3) == 2 and q(1, 3, 32, 2, 3) == 1       # the same counts from the width of one map
+    assert q(1, 1, 1, 1025, 1) == 0 and q(1, 1, 1, 1, 1025) == 0 and q(0, 1, 1, 1, 1) == 0
+    assert q(1, 1, 1, 1024, 1024) == 1
+
+
+@pytest.mark.parametrize("tag", ["segments", "tiles", "hpx_two"])
+@pytest.mark.parametrize("act", [0, 3], ids=["none", "relu"])
+def test_whole_number_inputs_are_exact(tag, act):
+    tensors = make_inputs(tag, integer=True)
+    dw, db = _run(tag, tensors, pre_act=act)
+    want_w, want_b = reference_of(*tensors, act, CASES[tag][7])
+    assert float(want_w.abs().max()) > 0 and float(want_w.abs().max()) < 2 ** 24
+    assert torch.equal(dw.cpu(), want_w.float()) and torch.equal(db.cpu(), want_b.float())
+
+
+@pytest.mark.parametrize("tag", ["multi_slice", "tiles", "hpx_two"])
+def test_reruns_are_bitwise_identical(tag):
+    a = _run(tag)
+    b = _run(tag)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+
+
+@pytest.mark.parametrize("tag", ["segments", "hpx_small"])
+def test_without_bias(tag):
+    dw, db = _run(tag)
+    dw2, none = _run(tag, need_bias=False)
+    assert none is None and torch.equal(dw, dw2)
+
+
+def test_bad_arguments():
+    from dlwp_benchmark_amd import lib, ops
+
+    z = lambda *s: torch.zeros(*s, device=DEV)
+    with pytest.raises(lib.DlwpError):
+        ops.conv3x3_weight_grad(z(13, 2, 4, 4), None, z(13, 3, 4, 4), hpx=True)        # faces not a multiple of 12
+    with pytest.raises(lib.DlwpError):
+        ops.conv3x3_weight_grad(z(2, 2, 4, 4), None, z(2, 3, 4, 5))                    # dz of another map
+    with pytest.raises(lib.DlwpError):
+        ops.conv3x3_weight_grad(z(2, 2, 4, 4), z(2, 1, 4, 5), z(2, 3, 4, 4))           # x1 of another map
+    with pytest.raises(lib.DlwpError):
+        ops.conv3x3_weight_grad(z(1, 1025, 1, 1), None, z(1, 1, 1, 1))                 # cin over the envelope
+    with pytest.raises(lib.DlwpError):
+        ops.conv3x3_weight_grad(z(1, 1000, 1, 1), z(1, 25, 1, 1), z(1, 1, 1, 1))       # c0 + c1 over the envelope
+    with pytest.raises(lib.DlwpError):
+        ops.conv3x3_weight_grad(z(1, 1, 1, 1), None, z(1, 1025, 1, 1))                 # cout over the envelope
+    assert not ops.conv3x3_weight_grad_supported(1, 1025, 0, 1, 1, 1)
+    assert ops.conv3x3_weight_grad_supported(1, 1024, 0, 1024, 1, 1)
+    with pytest.raises(lib.DlwpError):
+        ops.conv3x3_weight_grad(torch.zeros(1, 1, 4, 4), None, z(1, 1, 4, 4))          # a CPU tensor
+
+
+def test_short_workspace_is_refused():
+    from dlwp_benchmark_amd import lib
+
+    l = lib.load()
+    x, dz = torch.ones(1, 2, 4, 4, device=DEV), torch.ones(1, 3, 4, 4, device=DEV)
+    dw, db = torch.full((3, 2, 3, 3), 7.0, device=DEV), torch.full((3,), 7.0, device=DEV)
+    need = int(l.dlwp_conv3x3_wgrad_workspace_bytes(1, 4, 4, 2, 3))
+    assert need == 4 * (3 * 2 * 9 + 3)
+    ws = torch.empty(need, dtype=torch.uint8, device=DEV)
+    args = lambda nbytes: (x.data_ptr(), 2, None, 0, dz.data_ptr(), dw.data_ptr(), db.data_ptr(), 1, 4, 4, 3, 0, None,
+                           ws.data_ptr(), nbytes, lib.stream_ptr())
+    assert l.dlwp_conv3x3_wgrad_f32(*args(need - 1)) == -4          # DLWP_ERR_WORKSPACE, nothing launched
+    torch.cuda.synchronize()
+    assert float(dw.min()) == 7.0 and float(db.min()) == 7.0
+    assert l.dlwp_conv3x3_wgrad_f32(*args(need)) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(db, torch.full((3,), 16.0, device=DEV))
+    assert l.dlwp_conv3x3_wgrad_f32(x.data_ptr(), 2, None, 0, dz.data_ptr(), dw.data_ptr(), db.data_ptr(), 1, 4, 4, 1025, 0,
+                                    None, ws.data_ptr(), ctypes.c_size_t(need), lib.stream_ptr()) == -2   # DLWP_ERR_UNSUPPORTED
+
+
+@pytest.mark.parametrize("tag", ["segments", "hpx_two"])
+@pytest.mark.parametrize("bias_grad", [True, False], ids=["bias_grad", "bias_fixed"])
+def test_autograd_wiring(tag, bias_grad, monkeypatch):
+    from dlwp_benchmark_amd import ops, training, weights
+
+    monkeypatch.setenv("DLWP_CONV_WGRAD", "hip")
+    b, c0, c1, cout, h, w, pre_act, hpx, _ = CASES[tag]
+    act = ops.ACTS["gelu"]
+    x0, x1, gy = inputs(tag)
+    wgt = weights.normal(f"conv3x3_wgrad/{tag}/w", (cout, c0 + c1, 3, 3), std=(9 * (c0 + c1)) ** -0.5)
+    bias = weights.normal(f"conv3x3_wgrad/{tag}/b", (cout,), std=0.5)
+    resid = weights.normal(f"conv3x3_wgrad/{tag}/r", (b, cout, h, w))
+    needs = [True, True, True, bias_grad, True]
+
+    seen = []
+    real = ops.conv3x3_weight_grad
+
+    def spy(*a, **kw):
+        seen.append(kw["need_bias"])
+        return real(*a, **kw)
+
+    monkeypatch.setattr(ops, "conv3x3_weight_grad", spy)
+    ins = [t.to(DEV).requires_grad_(n) for t, n in zip((x0, x1, wgt, bias, resid), needs)]
+    y = ops.conv3x3(ins[0], ins[2], ins[3], act=act, x1=ins[1], pre_act=pre_act, resid=ins[4], hpx=hpx)
+    y.backward(gy.to(DEV))
+    torch.cuda.synchronize()
+    assert seen == [bias_grad]
+
+    from dlwp_benchmark_amd import healpix
+    ref = [t.double().requires_grad_(n) for t, n in zip((x0, x1, wgt, bias, resid), needs)]
+    table = healpix.device_table(h, w, 1, "cpu") if hpx else None
+    yr = training.conv3x3_torch(ref[0], ref[1], ref[2], ref[3], ref[4], pre_act, act, table)
+    yr.backward(gy.double())
+    assert rel_l2(y, yr) <= 1e-5
+    for name, got, want, need in zip(("x0", "x1", "weight", "bias", "resid"), ins, ref, needs):
+        if not need:
+            assert got.grad is None, name
+            continue
+        print(tag, name, "%.2e" % rel_l2(got.grad, want.grad))
+        assert rel_l2(got.grad, want.grad) <= 1e-5, name
+
+
+def _no_library_weight_grad(monkeypatch):
+    def refuse(*a, **kw):
+        raise AssertionError("torch.nn.grad.conv2d_weight called under DLWP_CONV_WGRAD=hip")
+
+    monkeypatch.setattr(torch.nn.grad, "conv2d_weight", refuse)
+    monkeypatch.setenv("DLWP_CONV_WGRAD", "hip")
+
+
+@pytest.mark.parametrize("tag", ["unet_h4_32x64", "convlstm_h8_32x64"])
+def test_cylinder_networks_train_without_the_library_weight_grad(tag, monkeypatch):
+    import test_training_gpu as driver
+
+    _no_library_weight_grad(monkeypatch)
+    driver.test_training_gradients_match_reference(tag)          # loss within 1e-5, worst gradient deviation within 1e-4
+
+
+@pytest.mark.parametrize("tag", ["unethpx_h4_8x8", "munethpx_h16_8_norm", "convlstmhpx_h8_8x8"])
+def test_healpix_networks_train_without_the_library_weight_grad(tag, monkeypatch):
+    import test_hpx_train_gpu as driver
+
+    _no_library_weight_grad(monkeypatch)
+    driver.test_hpx_gradients_match_reference(tag)               # loss within 1e-5, worst gradient deviation within 1e-4
+
+
+def test_hip_and_torch_paths_agree(monkeypatch):
+    import test_hpx_train_gpu as driver
+
+    monkeypatch.setenv("DLWP_CONV_WGRAD", "hip")
+    _, hip, _ = driver._step("munethpx_h16_8_norm")
+    monkeypatch.setenv("DLWP_CONV_WGRAD", "torch")
+    _, ref, _ = driver._step("munethpx_h16_8_norm")
+    for (name, a), (_, b) in zip(hip.named_parameters(), ref.named_parameters()):
+        assert rel_l2(a.grad, b.grad) <= 1e-5, name

@@ -20,10 +20,11 @@
 // tap), each reading the input operand at the tap's halo offset.  Pixels outside the map carry dz = 0; channels outside the
 // layer are zero-filled, and a wave whose quarter lies wholly outside skips its MFMAs.  The bias gradient is summed from the
 // staged dz tile by the workgroups of the first cin block.  Partial dW / db of every slice go to the workspace; a second
-// kernel adds the slices in index order.  One writer per element, no atomics, and the slice count depends on the shape
-// arguments only: reruns are bit-identical.
+// kernel (wgrad_reduce.hpp) adds the slices in index order.  One writer per element, no atomics, and the slice count depends
+// on the shape arguments only: reruns are bit-identical.
 #include "act_common.hpp"
 #include "conv3x3_load.hpp"
+#include "wgrad_reduce.hpp"
 
 namespace dlwp {
 namespace wgrad {
@@ -36,8 +37,6 @@ constexpr int NT = 256;
 constexpr int MAX_CH = 1024;      // envelope: c0 + c1 and cout
 constexpr int TARGET_WGS = 512;   // workgroups a launch aims at (2 per CU on 256 CUs)
 constexpr int MIN_SLICE_TILES = 4;   // tiles per slice from which the accumulator write-out stops mattering
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct Params {
   const float* x0; int c0;   // first input segment [B][c0][H][W]
@@ -162,23 +161,6 @@ __global__ __launch_bounds__(NT) void wgrad_kernel(const Params p) {
     }
   }
   if (bias_owner && co0 + tid < p.Cout) p.part_b[(long long)slice * p.Cout + co0 + tid] = bsum;
-}
-
-// dw[i] = sum over the slices, in index order, of part_w[s][i]; db likewise behind it (n_b = 0: no bias gradient)
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ part_w, const float* __restrict__ part_b,
-                                                           float* __restrict__ dw, float* __restrict__ db, long long n_w,
-                                                           int n_b, int slices) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i < n_w) {
-    float v = 0.f;
-    for (int s = 0; s < slices; ++s) v += part_w[(long long)s * n_w + i];
-    dw[i] = v;
-  } else if (i < n_w + n_b) {
-    const int c = (int)(i - n_w);
-    float v = 0.f;
-    for (int s = 0; s < slices; ++s) v += part_b[(long long)s * n_b + c];
-    db[c] = v;
-  }
 }
 
 static size_t workspace_bytes(const Plan& pl, int cin, int cout) {

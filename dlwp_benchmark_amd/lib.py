@@ -170,6 +170,9 @@ SIGNATURES = {
     "dlwp_conv3x3_wgrad_slices": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     "dlwp_conv3x3_wgrad_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                          c_int32, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dlwp_conv2d_wgrad_workspace_bytes": (c_size_t, [c_int32] * 9),
+    "dlwp_conv2d_wgrad_slices": (c_int32, [c_int32] * 9),
+    "dlwp_conv2d_wgrad_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int32] * 10 + [c_void_p, c_size_t, c_void_p]),
     "dlwp_convlstm_gates_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                           c_void_p]),
     "dlwp_layernorm_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int32, c_float, c_void_p]),

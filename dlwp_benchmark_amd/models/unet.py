@@ -8,7 +8,9 @@ Every `CylinderPad(1) -> Conv2d(3x3) -> activation` triple is ONE HIP kernel (`d
 halo staged in LDS with the wrap/zero rule applied at load time, bias + activation in the epilogue); the
 skip-connection `torch.cat` (unet.py:553) and the ConvLSTM `cat((x, h_prev))` (convlstm.py:94) are folded
 into the kernel's two-segment input; the LSTM gate math (convlstm.py:96-109) is one fused kernel.
-AvgPool / ConvTranspose2d(2x2, s2) / the 1x1 head go through torch on the GPU.
+AvgPool / ConvTranspose2d(2x2, s2) / the 1x1 head run their own HIP kernels through `ops.small_module`; under
+autograd the two convolutions run the library's forward and input gradient and `dlwp_conv2d_wgrad_f32` for the
+weight and bias gradients (`DLWP_CONV_WGRAD`).
 
 Reference defect NOT reproduced: the shipped UNet encoder pads twice (CylinderPad(1) AND padding=1,
 unet.py:456-462) and crashes on the first skip concat; this mirror uses the consistent `padding=0`

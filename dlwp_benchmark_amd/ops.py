@@ -441,14 +441,14 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], 
            pre_act: int = 0, act: int = 0, resid: Optional[torch.Tensor] = None, form: str = "direct") -> torch.Tensor:
     """zero-padded Conv2d (square kernel / stride / padding): the strided and 1x1 convolutions of unet.py:583-584, :879, :450.
     `form` (CONV_FORMS): "direct" the one-thread-per-output kernel; "bf16x6" / "bf16" dlwp_conv2d_mfma_f32 (k <= 4, stride 1 or 2,
-    padding < k; anything else raises.  Inference only: with gradients wanted every form runs the differentiable torch path)."""
+    padding < k; anything else raises.  Inference only: with gradients wanted every form runs training.conv2d -- the library's
+    forward and input gradient, the weight and bias gradient on dlwp_conv2d_wgrad_f32 under DLWP_CONV_WGRAD)."""
     _conv_form(form)
     for t, n in ((x, "x"), (weight, "weight"), (resid, "resid")):
         _lib.require_cuda_tensor(t, n)
     from . import training as _T
-    if _T.wants_grad(x, weight, bias, resid):
-        y = torch.nn.functional.conv2d(_T._ACT_FNS[int(pre_act)](x), weight, bias, stride=stride, padding=padding)
-        return _T._ACT_FNS[int(act)](y if resid is None else y + resid)
+    if _T.wants_grad(x, weight, bias, resid):       # library forward and input gradient, dlwp_conv2d_wgrad_f32 (training.py)
+        return _T.conv2d(x, weight, bias, resid, int(stride), int(padding), int(pre_act), int(act))
     owner = weight          # the pack belongs to the caller's tensor, not to a contiguous copy made below
     x, weight = x.contiguous(), weight.contiguous()
     n, cin, h, w = x.shape
@@ -480,13 +480,13 @@ def conv_transpose2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch
                      act: int = 0, form: str = "direct") -> torch.Tensor:
     """ConvTranspose2d (weight [cin, cout, k, k]; unet.py:523 2x2 s2, :719 4x4 s2 p1).  `form` (CONV_FORMS): "direct" the
     one-thread-per-output kernel; "bf16x6" / "bf16" dlwp_conv_transpose2d_mfma_f32 (exactly those two geometries; anything else
-    raises.  Inference only: with gradients wanted every form runs the differentiable torch path)."""
+    raises.  Inference only: with gradients wanted every form runs training.conv_transpose2d, as conv2d does)."""
     _conv_form(form)
     _lib.require_cuda_tensor(x, "x")
     _lib.require_cuda_tensor(weight, "weight")
     from . import training as _T
-    if _T.wants_grad(x, weight, bias):
-        return _T._ACT_FNS[int(act)](torch.nn.functional.conv_transpose2d(x, weight, bias, stride=stride, padding=padding))
+    if _T.wants_grad(x, weight, bias):              # library forward and input gradient, dlwp_conv2d_wgrad_f32 (training.py)
+        return _T.conv_transpose2d(x, weight, bias, int(stride), int(padding), int(act))
     owner = weight
     x, weight = x.contiguous(), weight.contiguous()
     n, cin, h, w = x.shape
@@ -672,6 +672,64 @@ def conv3x3_weight_grad(x0: torch.Tensor, x1: Optional[torch.Tensor], dz: torch.
                                               dw.data_ptr(), db.data_ptr() if db is not None else None, n, h, w, cout,
                                               int(pre_act), table.data_ptr() if table is not None else None, ws.data_ptr(),
                                               nbytes, _lib.stream_ptr()), "dlwp_conv3x3_wgrad_f32")
+    return dw, db
+
+
+def _conv2d_out_hw(h: int, w: int, k: int, stride: int, padding: int, transposed: bool):
+    if transposed:
+        return (h - 1) * stride - 2 * padding + k, (w - 1) * stride - 2 * padding + k
+    return (h + 2 * padding - k) // stride + 1, (w + 2 * padding - k) // stride + 1
+
+
+def conv2d_weight_grad_supported(batch: int, cin: int, cout: int, h: int, w: int, k: int, stride: int, padding: int,
+                                 transposed: bool = False) -> bool:
+    """whether dlwp_conv2d_wgrad_f32 takes the layer (its envelope: include/dlwp_hip.h); needs the library, not a GPU"""
+    args = [int(v) for v in (batch, cin, h, w, cout, k, stride, padding)]
+    if min(args[:7]) < 1 or args[7] < 0 or max(args) >= 1 << 31:
+        return False
+    return _lib.load().dlwp_conv2d_wgrad_workspace_bytes(*args, int(bool(transposed))) > 0
+
+
+def conv2d_weight_grad(x: torch.Tensor, grad_z: torch.Tensor, k: int, stride: int, padding: int, pre_act: int = 0,
+                       transposed: bool = False, need_weight: bool = True, need_bias: bool = True):
+    """Weight and bias gradient of conv2d (transposed: of conv_transpose2d) with a k x k kernel from the layer's input
+    x [N, cin, H, W] and grad_z [N, cout, OH, OW], the gradient of the layer's output before its activation:
+    (dw [cout, cin, k, k] -- transposed [cin, cout, k, k] --, db [cout]), None where not wanted, on dlwp_conv2d_wgrad_f32.
+    Both maps are read where they lie, `pre_act` applied to x at load (the transposed layer has none); no copies.  Runs on
+    the current stream without a host synchronisation; reruns are bitwise identical."""
+    for t, name in ((x, "x"), (grad_z, "grad_z")):
+        _lib.require_cuda_tensor(t, name)
+    x, dz = x.contiguous(), grad_z.contiguous()
+    k, stride, padding, transposed = int(k), int(stride), int(padding), bool(transposed)
+    if x.dim() != 4 or dz.dim() != 4:
+        raise _lib.DlwpError(f"conv2d_weight_grad: x {tuple(x.shape)} and grad_z {tuple(dz.shape)} must be [N, C, H, W]")
+    if transposed and int(pre_act) != 0:
+        raise _lib.DlwpError("conv2d_weight_grad: the transposed layer has no pre-activation")
+    n, cin, h, w = x.shape
+    cout = dz.shape[1]
+    lib = _lib.load()
+    nbytes = 0
+    if min(n, cin, cout, h, w, k, stride) >= 1 and padding >= 0 and max(n, cin, cout, h, w, k, stride, padding) < 1 << 31:
+        nbytes = int(lib.dlwp_conv2d_wgrad_workspace_bytes(n, cin, h, w, cout, k, stride, padding, int(transposed)))
+    if nbytes == 0:                 # the one query gives the envelope (conv2d_weight_grad_supported) and the size
+        raise _lib.DlwpError(f"conv2d_weight_grad: no HIP kernel for {cin} -> {cout} channels on {n} x {h} x {w}, k={k} "
+                             f"stride={stride} padding={padding} transposed={transposed}")
+    if tuple(dz.shape) != (n, cout, *_conv2d_out_hw(h, w, k, stride, padding, transposed)):
+        raise _lib.DlwpError(f"conv2d_weight_grad: grad_z {tuple(dz.shape)} is not the output map of x {tuple(x.shape)} under "
+                             f"k={k} stride={stride} padding={padding} transposed={transposed}")
+    dw = db = None
+    if need_weight:
+        dw = torch.empty((cin, cout, k, k) if transposed else (cout, cin, k, k), device=x.device, dtype=torch.float32)
+    if need_bias:
+        db = torch.empty(cout, device=x.device, dtype=torch.float32)
+    if dw is None and db is None:
+        return None, None
+    with torch.cuda.device(x.device):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        _lib.check(lib.dlwp_conv2d_wgrad_f32(x.data_ptr(), dz.data_ptr(), dw.data_ptr() if dw is not None else None,
+                                             db.data_ptr() if db is not None else None, n, cin, h, w, cout, k, stride, padding,
+                                             int(pre_act), int(transposed), ws.data_ptr(), nbytes, _lib.stream_ptr()),
+                   "dlwp_conv2d_wgrad_f32")
     return dw, db
 
 

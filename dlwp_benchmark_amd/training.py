@@ -531,8 +531,9 @@ CONV_WGRAD_AUTO_MIN_FLOPS = 40e9
 
 
 def conv_wgrad_mode() -> str:
-    """DLWP_CONV_WGRAD: "hip" every supported 3x3 weight gradient on dlwp_conv3x3_wgrad_f32, "torch" the library composition
-    conv3x3_weight_grad_torch, "auto" (default) HIP where it is supported and measured not slower.  Read at every backward."""
+    """DLWP_CONV_WGRAD, the one switch of the U-Net family's convolution weight gradients: "hip" every supported one on
+    dlwp_conv3x3_wgrad_f32 / dlwp_conv2d_wgrad_f32, "torch" the library compositions conv3x3_weight_grad_torch /
+    conv2d_weight_grad_torch, "auto" (default) HIP where it is supported and measured not slower.  Read at every backward."""
     import os
 
     mode = os.environ.get("DLWP_CONV_WGRAD", "auto")
@@ -640,6 +641,158 @@ class _Conv3x3Fn(torch.autograd.Function):
 
 def conv3x3(x0, weight, bias, act=0, x1=None, pre_act=0, resid=None, hpx=False):
     return _Conv3x3Fn.apply(x0, x1, weight, bias, resid, pre_act, act, hpx)
+
+
+def conv2d_torch(x, weight, bias, resid, stride: int, padding: int, pre_act: int, act: int):
+    """act(Conv2d(pre_act(x)) + resid), zero padding, with torch operators (reference unet.py:450, :583-584, :879)"""
+    y = F.conv2d(_ACT_FNS[int(pre_act)](x), weight, bias, stride=stride, padding=padding)
+    return _ACT_FNS[int(act)](y if resid is None else y + resid)
+
+
+def conv_transpose2d_torch(x, weight, bias, stride: int, padding: int, act: int):
+    """act(ConvTranspose2d(x)) with torch operators (reference unet.py:523, :719)"""
+    return _ACT_FNS[int(act)](F.conv_transpose2d(x, weight, bias, stride=stride, padding=padding))
+
+
+def conv2d_weight_grad_torch(x, gz, k: int, stride: int, padding: int, pre_act: int = 0, transposed: bool = False,
+                             need_weight: bool = True, need_bias: bool = True):
+    """(dW, db) of conv2d_torch (transposed: of conv_transpose2d_torch) from the layer's input x and gz, the gradient of the
+    convolution's output, as the composition of library operators: the pre-activated copy of x, the library's convolution
+    weight gradient (MIOpen on the GPU) and gz.sum.  On any device: the DLWP_CONV_WGRAD=torch path of _Conv2dFn /
+    _ConvTranspose2dFn, the CPU reference of dlwp_conv2d_wgrad_f32 and the torch form tools/bench_conv2_wgrad.py times."""
+    dw = db = None
+    if need_weight:
+        cin, cout = x.shape[1], gz.shape[1]
+        shape = (cin, cout, k, k) if transposed else (cout, cin, k, k)
+        dw = torch.ops.aten.convolution_backward(gz, _ACT_FNS[int(pre_act)](x), x.new_empty(shape), None, [stride, stride],
+                                                 [padding, padding], [1, 1], bool(transposed), [0, 0], 1,
+                                                 [False, True, False])[1]
+    if need_bias:
+        db = gz.sum(dim=(0, 2, 3))
+    return dw, db
+
+
+# DLWP_CONV_WGRAD=auto for the non-3x3 convolutions: layers of fewer FLOPs than this (2 N SH SW cin cout k^2 over the smaller
+# map: Conv2d's output, ConvTranspose2d's input) keep the library form.  Infinite: auto takes no layer.  In the per-layer table
+# of profiles/conv2_wgrad.jsonl (tools/bench_conv2_wgrad.py, DESIGN.md section 24) every one of the 12 measured layers of 8
+# GFLOP and more runs 0.51-0.99 x MIOpen's composition on dlwp_conv2d_wgrad_f32 (staging-bound: 0.12-0.26 of the fp32 matrix
+# peak), and the 10 of the 46 smaller ones that win (1.09-1.57 x) lie between losers of the same size, so no FLOP threshold
+# admits winners only; with every layer on the kernel the MUNetHPX steps are 0.6-0.75 % slower than under auto, beyond the
+# spread of their repeats.  DLWP_CONV_WGRAD=hip takes every supported layer (bit-reproducible gradients, 4 % less peak memory)
+CONV2_WGRAD_AUTO_MIN_FLOPS = float("inf")
+
+
+def conv2_wgrad_flops(batch: int, cin: int, cout: int, h: int, w: int, k: int, stride: int, padding: int,
+                      transposed: bool) -> float:
+    """the multiply-adds (times 2) of the weight gradient of a layer on input [batch, cin, h, w]"""
+    sh, sw = (h, w) if transposed else ((h + 2 * padding - k) // stride + 1, (w + 2 * padding - k) // stride + 1)
+    return 2.0 * batch * sh * sw * cin * cout * k * k
+
+
+def conv2_wgrad_uses_hip(batch: int, cin: int, cout: int, h: int, w: int, k: int, stride: int, padding: int,
+                         transposed: bool) -> bool:
+    """whether _Conv2dFn / _ConvTranspose2dFn take dlwp_conv2d_wgrad_f32 for a layer under the current DLWP_CONV_WGRAD"""
+    from . import ops
+
+    mode = conv_wgrad_mode()
+    if mode == "torch" or (mode == "auto" and conv2_wgrad_flops(batch, cin, cout, h, w, k, stride, padding, transposed)
+                           < CONV2_WGRAD_AUTO_MIN_FLOPS):
+        return False                                     # decided without a library call
+    return ops.conv2d_weight_grad_supported(batch, cin, cout, h, w, k, stride, padding, transposed)
+
+
+def _act_backward(v, grad, act: int):
+    """grad * act'(v) by autograd of the torch activation (the kernel the plain composition's backward runs)"""
+    if act == 0:
+        return grad
+    with torch.enable_grad():
+        v_ = v.detach().requires_grad_(True)
+        g, = torch.autograd.grad(_ACT_FNS[act](v_), v_, grad)
+    return g
+
+
+def _conv2_backward(ctx, grad_out, transposed: bool):
+    """(dx, dw, db, dresid) of _Conv2dFn / _ConvTranspose2dFn: the post-activation derivative from the saved z, the input
+    gradient by the library call autograd makes for the plain composition (aten.convolution_backward, input alone) followed by
+    the pre-activation derivative, the weight and bias gradients in one dlwp_conv2d_wgrad_f32 call on x as it lies
+    (DLWP_CONV_WGRAD: or conv2d_weight_grad_torch), the residual's gradient gz itself."""
+    from . import ops
+
+    stride, padding, pre_act, act = ctx.cfg
+    x, weight, bias, resid, z = ctx.saved_tensors
+    need_x, need_w, need_b = ctx.needs_input_grad[:3]
+    need_b = need_b and bias is not None
+    need_r = not transposed and resid is not None and ctx.needs_input_grad[3]
+    k = weight.shape[2]
+    dx = dw = db = None
+    with torch.no_grad():
+        gz = _act_backward(z, grad_out.contiguous(), act).contiguous()
+        if need_x:
+            dxa = torch.ops.aten.convolution_backward(gz, x, weight, None, [stride, stride], [padding, padding], [1, 1],
+                                                      transposed, [0, 0], 1, [True, False, False])[0]
+            dx = _act_backward(x, dxa, pre_act)
+        if need_w or need_b:
+            n, cin, h, w = x.shape
+            cout = weight.shape[1] if transposed else weight.shape[0]
+            if conv2_wgrad_uses_hip(n, cin, cout, h, w, k, stride, padding, transposed):
+                dw, db = ops.conv2d_weight_grad(x, gz, k, stride, padding, pre_act=pre_act, transposed=transposed,
+                                                need_weight=need_w, need_bias=need_b)
+            else:
+                dw, db = conv2d_weight_grad_torch(x, gz, k, stride, padding, pre_act, transposed, need_weight=need_w,
+                                                  need_bias=need_b)
+    return dx, dw, db, (gz if need_r else None)
+
+
+class _Conv2dFn(torch.autograd.Function):
+    """ops.conv2d under autograd: the forward is conv2d_torch's operators (values bit for bit the plain composition's); saved
+    are x, weight, bias, resid and -- only with a post-activation -- the convolution's output z.  Backward: _conv2_backward."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, resid, stride, padding, pre_act, act):
+        ctx.cfg = (stride, padding, pre_act, act)
+        with torch.no_grad():
+            z = F.conv2d(_ACT_FNS[pre_act](x), weight, bias, stride=stride, padding=padding)
+            if resid is not None:
+                z = z + resid
+            ctx.save_for_backward(x, weight, bias, resid, z if act != 0 else None)
+            return _ACT_FNS[act](z)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return (*_conv2_backward(ctx, grad_out, False), None, None, None, None)
+
+
+class _ConvTranspose2dFn(torch.autograd.Function):
+    """ops.conv_transpose2d under autograd, as _Conv2dFn (no pre-activation, no residual)"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, padding, act):
+        ctx.cfg = (stride, padding, 0, act)
+        with torch.no_grad():
+            z = F.conv_transpose2d(x, weight, bias, stride=stride, padding=padding)
+            ctx.save_for_backward(x, weight, bias, None, z if act != 0 else None)
+            return _ACT_FNS[act](z)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return (*_conv2_backward(ctx, grad_out, True)[:3], None, None, None)
+
+
+def _plain_conv2(weight) -> bool:
+    """the cases that keep the plain composition under autograd: the cross-check setting and kernels that are not square"""
+    return _TORCH_BACKWARD() or weight.dim() != 4 or weight.shape[2] != weight.shape[3]
+
+
+def conv2d(x, weight, bias, resid, stride: int, padding: int, pre_act: int, act: int):
+    if _plain_conv2(weight):
+        return conv2d_torch(x, weight, bias, resid, stride, padding, pre_act, act)
+    return _Conv2dFn.apply(x, weight, bias, resid, stride, padding, pre_act, act)
+
+
+def conv_transpose2d(x, weight, bias, stride: int, padding: int, act: int):
+    if _plain_conv2(weight):
+        return conv_transpose2d_torch(x, weight, bias, stride, padding, act)
+    return _ConvTranspose2dFn.apply(x, weight, bias, stride, padding, act)
 
 
 def _act_grad_torch(v: torch.Tensor, act: int) -> torch.Tensor:

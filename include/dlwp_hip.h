@@ -564,6 +564,34 @@ int32_t dlwp_conv3x3_wgrad_f32(const float* x0_dev, int32_t c0, const float* x1_
                                int32_t pre_act, const int32_t* ring_table, void* workspace, size_t workspace_bytes,
                                void* stream);
 
+/* Weight and bias gradient of the zero-padded Conv2d (dlwp_conv2d_f32's layer) and of ConvTranspose2d (dlwp_conv_transpose2d_f32's,
+ * output_padding 0) with a square k x k kernel (csrc/conv2_wgrad.hip; the reference lines differentiated: scripts/train.py:271
+ * through models/unet/unet.py:450, :583-584, :879 (Conv2d 1x1, 3x3 stride 2) and :523, :719 (ConvTranspose2d 2x2 s2, 4x4 s2 p1)):
+ *   transposed == 0: dw[co][ci][ky][kx] = sum_{b,i,j} dz[b][co][i][j] * act_pre(x)[b][ci][i s - p + ky][j s - p + kx]
+ *   transposed != 0: dw[ci][co][ky][kx] = sum_{b,i,j} x[b][ci][i][j] * dz[b][co][i s - p + ky][j s - p + kx]
+ *   db[co] = sum_{b,y,x} dz[b][co][y][x]
+ * with the map under the taps zero outside its bounds: one kernel, the two maps exchanging roles.  x_dev [batch, cin, H, W] is
+ * the layer's input, read where it lies with pre_act (the codes of dlwp_conv2d_f32; 0 for the transposed layer) applied at
+ * load; dz_dev [batch, cout, OH, OW] the gradient of the layer's output before its activation, OH = (H + 2p - k) / s + 1
+ * (Conv2d, rounded down: trailing rows / columns of x that no output reads are skipped) or (H - 1) s - 2p + k (transposed).
+ * dw_dev in torch's layout ([cout, cin, k, k], transposed [cin, cout, k, k]) or NULL; db_dev [cout] or NULL.  No padded,
+ * activated, unfolded or zero-stuffed copy is made.  Exact-fp32 matrix instructions (an fmaf chain per element).  Two launches
+ * on `stream`: partial sums of the K-slices (runs of consecutive pixel tiles of the smaller map) into the workspace, then their
+ * sum in slice order.  One writer per element, no atomics, a slice count that depends on the shape arguments only: results are
+ * bit-identical from run to run.  No pointer needs more than 4-byte alignment.
+ * Envelope: k 1..4, stride 1 or 2, 0 <= pad < k, cin and cout 1..1024, any H, W >= 1 that leave OH, OW >= 1, per-sample offsets
+ * (channels * map) within 32 bits; anything else returns DLWP_ERR_UNSUPPORTED before any launch.
+ *   dlwp_conv2d_wgrad_workspace_bytes: slices * (cout * cin * k * k + cout) floats (0 = unsupported shape); a smaller workspace
+ *   returns DLWP_ERR_WORKSPACE.
+ *   dlwp_conv2d_wgrad_slices: the K-slices the launcher takes (0 = unsupported shape).  For tests and tools. */
+size_t dlwp_conv2d_wgrad_workspace_bytes(int32_t batch, int32_t cin, int32_t height, int32_t width, int32_t cout, int32_t k,
+                                         int32_t stride, int32_t pad, int32_t transposed);
+int32_t dlwp_conv2d_wgrad_slices(int32_t batch, int32_t cin, int32_t height, int32_t width, int32_t cout, int32_t k,
+                                 int32_t stride, int32_t pad, int32_t transposed);
+int32_t dlwp_conv2d_wgrad_f32(const float* x_dev, const float* dz_dev, float* dw_dev, float* db_dev, int32_t batch, int32_t cin,
+                              int32_t height, int32_t width, int32_t cout, int32_t k, int32_t stride, int32_t pad,
+                              int32_t pre_act, int32_t transposed, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ConvLSTM cell gate math (models/convlstm/convlstm.py:96-109): gates_dev [B, 4*hidden, H, W] in the
  * order (netin, igate, fgate, ogate), c_prev_dev [B, hidden, H, W] -> h_out_dev, c_out_dev. */
 int32_t dlwp_convlstm_gates_f32(const float* gates_dev, const float* c_prev_dev, float* h_out_dev,

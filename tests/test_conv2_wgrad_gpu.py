@@ -1,0 +1,311 @@
+"""dlwp_conv2d_wgrad_f32 (csrc/conv2_wgrad.hip) on the GPU: the weight / bias gradient of the strided, 1x1 and transposed
+convolutions of the U-Net family, and its wiring into training._Conv2dFn / _ConvTranspose2dFn under DLWP_CONV_WGRAD.
+
+  * every case of test_conv2_wgrad_cpu.CASES against fp64 autograd of training.conv2d_torch / conv_transpose2d_torch: relative
+    L2 of dW and of db <= 1e-5 (the project's fp32 bound; the largest K here is 256, where a sequential fp32 chain over
+    normal data deviates well under 1e-6);
+  * whole-number inputs, every sum exact in fp32: torch.equal to the fp64 reference (a swapped row / column, tap, tap group or
+    pixel order cannot pass);
+  * reruns bitwise identical; the slice rule on each side of its boundaries; need_bias / need_weight False; bad arguments; a
+    workspace one byte short;
+  * ops.conv2d (pre_act, GELU, resid) and ops.conv_transpose2d (GELU) under autograd with DLWP_CONV_WGRAD=hip against fp64
+    autograd of the compositions, every input, need_bias following needs_input_grad;
+  * the rollout-MSE step of U-Net fixtures of both grids under hip at the bounds of test_training_gpu.py /
+    test_hpx_train_gpu.py (their own drivers), the new op called once per gradient-carrying ops.conv2d / ops.conv_transpose2d;
+  * hip and torch paths agree to 1e-5 per parameter on munethpx_h16_8_norm;
+  * under the default auto the fixtures never call the new op: CONV2_WGRAD_AUTO_MIN_FLOPS is infinite,
+    so every layer lies below it."""
+import ctypes
+
+import pytest
+import torch
+
+from helpers import rel_l2
+from test_conv2_wgrad_cpu import CASES, deviation, inputs, make_inputs, reference, reference_of
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def _dev(t, offset):
+    """t on the GPU, contiguous; offset: as a view that starts one float into its storage (4-byte-aligned pointer)"""
+    if not offset:
+        return t.to(DEV)
+    store = torch.empty(t.numel() + 1, device=DEV, dtype=torch.float32)
+    view = store[1:].view(t.shape)
+    view.copy_(t)
+    assert view.is_contiguous() and view.data_ptr() % 16 == 4
+    return view
+
+
+def _run(tag, tensors=None, pre_act=None, need_weight=True, need_bias=True):
+    from dlwp_benchmark_amd import ops
+
+    x, dz = tensors if tensors is not None else inputs(tag)
+    k, s, p, act, transposed, offset = CASES[tag][5:]
+    dw, db = ops.conv2d_weight_grad(_dev(x, offset), _dev(dz, offset), k, s, p, pre_act=act if pre_act is None else pre_act,
+                                    transposed=transposed, need_weight=need_weight, need_bias=need_bias)
+    torch.cuda.synchronize()
+    return dw, db
+
+
+def _query(b, cin, cout, h, w, k, s, p, transposed=False):
+    from dlwp_benchmark_amd import lib
+
+    return int(lib.load().dlwp_conv2d_wgrad_slices(b, cin, h, w, cout, k, s, p, int(transposed)))
+
+
+def _slices(tag):
+    return _query(*CASES[tag][:8], CASES[tag][9])
+
+
+@pytest.mark.parametrize("tag", list(CASES))
+def test_matches_fp64_reference(tag):
+    dw, db = _run(tag)
+    want_w, want_b = reference(tag)
+    assert tuple(dw.shape) == tuple(want_w.shape) and tuple(db.shape) == tuple(want_b.shape)
+    ew, eb = deviation(dw, want_w), deviation(db, want_b)
+    print(tag, "slices %d, dW %.2e db %.2e" % (_slices(tag), ew, eb))
+    assert ew <= 1e-5 and eb <= 1e-5
+
+
+def test_slice_counts():
+    """a slice holds at least 256 pixels of the smaller map: 4 tiles of 8 x 8 at stride 1, 8 tiles of 4 x 8 at stride 2; runs
+    of one length with the remainder last.  multi_slice (5 stride-1 tiles) and multi_slice_s2 (9 stride-2 tiles) are the smallest
+    shapes with two slices and a shorter last one; above 512 workgroups the run length grows instead of the count."""
+    assert _slices("pointwise") == 1 and _slices("up4") == 1
+    assert _slices("multi_slice") == 2 and _slices("multi_slice_s2") == 2
+    pw = lambda b: _query(b, 1, 1, 1, 1, 1, 1, 0)                      # b tiles of one pixel, stride 1
+    assert [pw(b) for b in (4, 5, 8, 9)] == [1, 2, 2, 3]
+    up = lambda b: _query(b, 2, 3, 1, 1, 2, 2, 0, True)                # b tiles, stride 2
+    assert [up(b) for b in (8, 9, 16, 17)] == [1, 2, 2, 3]
+    assert _query(1, 2, 3, 3, 33, 1, 1, 0) == 2 and _query(1, 2, 3, 3, 32, 1, 1, 0) == 1      # the same from one map's width
+    assert _query(1, 2, 3, 8, 130, 3, 2, 1) == 2 and _query(1, 2, 3, 8, 128, 3, 2, 1) == 1    # output 4 x 65 / 4 x 64
+    # 512 workgroups: one block -> up to 512 slices; k = 4 has two tap groups per block -> 256
+    assert pw(4 * 512) == 512 and pw(4 * 512 + 1) == 410                # 2049 tiles in runs of 5
+    assert _query(8 * 512, 2, 3, 1, 1, 4, 2, 1, True) == 256
+    assert _query(1, 65, 1, 1, 1, 1, 1, 0) == 1 and _query(2048, 65, 1, 1, 1, 1, 1, 0) == 256   # two channel blocks
+    # the envelope
+    assert _query(1, 1024, 1024, 1, 1, 4, 2, 1, True) == 1 and _query(1, 1024, 1024, 4, 4, 4, 1, 3) == 1
+    for bad in ((1, 1025, 1, 4, 4, 1, 1, 0), (1, 1, 1025, 4, 4, 1, 1, 0), (0, 1, 1, 4, 4, 1, 1, 0), (1, 1, 1, 4, 4, 5, 1, 0),
+                (1, 1, 1, 4, 4, 0, 1, 0), (1, 1, 1, 4, 4, 3, 3, 0), (1, 1, 1, 4, 4, 3, 0, 0), (1, 1, 1, 4, 4, 3, 1, 3),
+                (1, 1, 1, 4, 4, 3, 1, -1), (1, 1, 1, 2, 2, 3, 1, 0), (1, 1, 1, 0, 4, 1, 1, 0),
+                (1, 1024, 1, 2048, 1024, 1, 1, 0)):                      # the last: a per-sample offset of 2^31
+        assert _query(*bad) == 0, bad
+    assert _query(1, 1, 1, 1, 1, 2, 2, 1, True) == 0                     # ConvTranspose2d with an empty output
+    assert _query(1, 1, 1024, 1024, 512, 2, 2, 0, True) == 0             # ... with an output map of 2^31 values
+
+
+@pytest.mark.parametrize("tag,act", [("blocks_down", 0), ("blocks_down", 3), ("down_tiles", 0), ("down_tiles", 3),
+                                     ("blocks_up", 0), ("up4_tiles", 0)])       # ReLU at load where the layer has one
+def test_whole_number_inputs_are_exact(tag, act):
+    tensors = make_inputs(tag, integer=True)
+    k, s, p, _, transposed = CASES[tag][5:10]
+    dw, db = _run(tag, tensors, pre_act=act)
+    want_w, want_b = reference_of(*tensors, k, s, p, act, transposed)
+    assert float(want_w.abs().max()) > 0 and float(want_w.abs().max()) < 2 ** 24
+    assert torch.equal(dw.cpu(), want_w.float()) and torch.equal(db.cpu(), want_b.float())
+
+
+@pytest.mark.parametrize("tag", ["multi_slice", "multi_slice_s2", "blocks_down", "up4"])
+def test_reruns_are_bitwise_identical(tag):
+    a = _run(tag)
+    b = _run(tag)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+
+
+@pytest.mark.parametrize("tag", ["down_even", "blocks_down", "up4", "blocks_up"])
+def test_need_flags(tag):
+    dw, db = _run(tag)
+    dw2, none = _run(tag, need_bias=False)
+    assert none is None and torch.equal(dw, dw2)
+    none, db2 = _run(tag, need_weight=False)
+    assert none is None and torch.equal(db, db2)
+
+
+def test_bad_arguments():
+    from dlwp_benchmark_amd import lib, ops
+
+    z = lambda *s: torch.zeros(*s, device=DEV)
+    with pytest.raises(lib.DlwpError):
+        ops.conv2d_weight_grad(z(2, 2, 8, 8), z(2, 3, 4, 5), 3, 2, 1)                         # grad_z of another map
+    with pytest.raises(lib.DlwpError):
+        ops.conv2d_weight_grad(z(2, 2, 4, 4), z(2, 3, 8, 8), 4, 2, 1)                         # ... the transposed layer's map
+    with pytest.raises(lib.DlwpError):
+        ops.conv2d_weight_grad(z(2, 2, 4, 4), z(1, 3, 8, 8), 4, 2, 1, transposed=True)        # ... another batch
+    with pytest.raises(lib.DlwpError):
+        ops.conv2d_weight_grad(z(1, 1025, 1, 1), z(1, 1, 1, 1), 1, 1, 0)                      # cin over the envelope
+    with pytest.raises(lib.DlwpError):
+        ops.conv2d_weight_grad(z(1, 1, 1, 1), z(1, 1025, 1, 1), 1, 1, 0)                      # cout over the envelope
+    with pytest.raises(lib.DlwpError):
+        ops.conv2d_weight_grad(z(1, 1, 8, 8), z(1, 1, 4, 4), 5, 1, 0)                         # k over the envelope
+    with pytest.raises(lib.DlwpError):
+        ops.conv2d_weight_grad(z(1, 1, 9, 9), z(1, 1, 3, 3), 3, 3, 0)                         # stride 3
+    with pytest.raises(lib.DlwpError):
+        ops.conv2d_weight_grad(z(1, 1, 4, 4), z(1, 1, 8, 8), 3, 1, 3)                         # padding >= k
+    with pytest.raises(lib.DlwpError):
+        ops.conv2d_weight_grad(z(1, 1, 4, 4), z(1, 1, 8, 8), 2, 2, 0, pre_act=1, transposed=True)   # no pre-activation there
+    with pytest.raises(lib.DlwpError):
+        ops.conv2d_weight_grad(z(4, 4), z(1, 1, 4, 4), 1, 1, 0)                               # not [N, C, H, W]
+    with pytest.raises(lib.DlwpError):
+        ops.conv2d_weight_grad(torch.zeros(1, 1, 4, 4), z(1, 1, 4, 4), 1, 1, 0)               # a CPU tensor
+    assert not ops.conv2d_weight_grad_supported(1, 1025, 1, 1, 1, 1, 1, 0)
+    assert ops.conv2d_weight_grad_supported(1, 1024, 1024, 1, 1, 1, 1, 0)
+
+
+def test_short_workspace_is_refused():
+    from dlwp_benchmark_amd import lib
+
+    l = lib.load()
+    x, dz = torch.ones(1, 2, 4, 4, device=DEV), torch.ones(1, 3, 2, 2, device=DEV)
+    dw, db = torch.full((3, 2, 3, 3), 7.0, device=DEV), torch.full((3,), 7.0, device=DEV)
+    shape = (1, 2, 4, 4, 3, 3, 2, 1)                                   # batch, cin, H, W, cout, k, stride, pad
+    need = int(l.dlwp_conv2d_wgrad_workspace_bytes(*shape, 0))
+    assert need == 4 * (3 * 2 * 9 + 3)
+    ws = torch.empty(need, dtype=torch.uint8, device=DEV)
+    args = lambda nbytes: (x.data_ptr(), dz.data_ptr(), dw.data_ptr(), db.data_ptr(), *shape, 0, 0, ws.data_ptr(), nbytes,
+                           lib.stream_ptr())
+    assert l.dlwp_conv2d_wgrad_f32(*args(need - 1)) == -4              # DLWP_ERR_WORKSPACE, nothing launched
+    torch.cuda.synchronize()
+    assert float(dw.min()) == 7.0 and float(db.min()) == 7.0
+    assert l.dlwp_conv2d_wgrad_f32(*args(need)) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(db, torch.full((3,), 4.0, device=DEV))
+    assert float(dw[0, 0, 1, 1]) == 4.0 and float(dw[0, 0, 0, 0]) == 1.0     # the centre tap sees all four outputs
+    assert l.dlwp_conv2d_wgrad_f32(x.data_ptr(), dz.data_ptr(), dw.data_ptr(), db.data_ptr(), 1, 2, 4, 4, 1025, 3, 2, 1, 0, 0,
+                                   ws.data_ptr(), ctypes.c_size_t(need), lib.stream_ptr()) == -2     # DLWP_ERR_UNSUPPORTED
+
+
+def _spy(monkeypatch, seen):
+    from dlwp_benchmark_amd import ops
+
+    real = ops.conv2d_weight_grad
+
+    def spy(*a, **kw):
+        seen.append((kw["need_weight"], kw["need_bias"]))
+        return real(*a, **kw)
+
+    monkeypatch.setattr(ops, "conv2d_weight_grad", spy)
+
+
+@pytest.mark.parametrize("tag", ["down_even", "down_s1", "pointwise", "up2", "up4_tiles"])
+@pytest.mark.parametrize("bias_grad", [True, False], ids=["bias_grad", "bias_fixed"])
+def test_autograd_wiring(tag, bias_grad, monkeypatch):
+    from dlwp_benchmark_amd import ops, training, weights
+
+    monkeypatch.setenv("DLWP_CONV_WGRAD", "hip")
+    b, cin, cout, h, w, k, s, p, pre_act, transposed, _ = CASES[tag]
+    act = ops.ACTS["gelu"]
+    x, gy = inputs(tag)
+    wgt = weights.normal(f"conv2_wgrad/{tag}/w", (cin, cout, k, k) if transposed else (cout, cin, k, k), std=(k * k * cin) ** -0.5)
+    bias = weights.normal(f"conv2_wgrad/{tag}/b", (cout,), std=0.5)
+    resid = None if transposed else weights.normal(f"conv2_wgrad/{tag}/r", tuple(gy.shape))
+    tensors = [t for t in (x, wgt, bias, resid) if t is not None]
+    needs = [True, True, bias_grad, True][:len(tensors)]
+    seen = []
+    _spy(monkeypatch, seen)
+
+    def run(ins, fn_conv, fn_up):
+        if transposed:
+            return fn_up(ins[0], ins[1], ins[2])
+        return fn_conv(ins[0], ins[1], ins[2], ins[3])
+
+    ins = [t.to(DEV).requires_grad_(n) for t, n in zip(tensors, needs)]
+    y = run(ins, lambda x_, w_, b_, r_: ops.conv2d(x_, w_, b_, stride=s, padding=p, pre_act=pre_act, act=act, resid=r_),
+            lambda x_, w_, b_: ops.conv_transpose2d(x_, w_, b_, stride=s, padding=p, act=act))
+    y.backward(gy.to(DEV))
+    torch.cuda.synchronize()
+    assert seen == [(True, bias_grad)]
+
+    ref = [t.double().requires_grad_(n) for t, n in zip(tensors, needs)]
+    yr = run(ref, lambda x_, w_, b_, r_: training.conv2d_torch(x_, w_, b_, r_, s, p, pre_act, act),
+             lambda x_, w_, b_: training.conv_transpose2d_torch(x_, w_, b_, s, p, act))
+    yr.backward(gy.double())
+    assert rel_l2(y, yr) <= 1e-5
+    for name, got, want, need in zip(("x", "weight", "bias", "resid"), ins, ref, needs):
+        if not need:
+            assert got.grad is None, name
+            continue
+        print(tag, name, "%.2e" % rel_l2(got.grad, want.grad))
+        assert rel_l2(got.grad, want.grad) <= 1e-5, name
+
+
+def test_frozen_weight_asks_for_the_bias_alone(monkeypatch):
+    from dlwp_benchmark_amd import ops
+
+    monkeypatch.setenv("DLWP_CONV_WGRAD", "hip")
+    seen = []
+    _spy(monkeypatch, seen)
+    x, gy = inputs("down_even")
+    wgt = torch.zeros(4, 6, 3, 3, device=DEV)
+    bias = torch.zeros(4, device=DEV, requires_grad=True)
+    ops.conv2d(x.to(DEV), wgt, bias, stride=2, padding=1).backward(gy.to(DEV))
+    assert seen == [(False, True)] and wgt.grad is None
+    assert deviation(bias.grad, reference("down_even")[1]) <= 1e-5
+
+
+def _count_layers(monkeypatch):
+    """spies: the gradient-carrying calls of ops.conv2d / ops.conv_transpose2d, and the calls of ops.conv2d_weight_grad"""
+    from dlwp_benchmark_amd import ops, training
+
+    layers, grads = [], []
+    conv, up = ops.conv2d, ops.conv_transpose2d
+
+    def conv_spy(x, weight, bias, *a, **kw):
+        if training.wants_grad(weight, bias):
+            layers.append(tuple(weight.shape))
+        return conv(x, weight, bias, *a, **kw)
+
+    def up_spy(x, weight, bias, *a, **kw):
+        if training.wants_grad(weight, bias):
+            layers.append(tuple(weight.shape))
+        return up(x, weight, bias, *a, **kw)
+
+    monkeypatch.setattr(ops, "conv2d", conv_spy)
+    monkeypatch.setattr(ops, "conv_transpose2d", up_spy)
+    _spy(monkeypatch, grads)
+    return layers, grads
+
+
+def test_cylinder_network_trains_on_the_kernel(monkeypatch):
+    import test_training_gpu as driver
+
+    monkeypatch.setenv("DLWP_CONV_WGRAD", "hip")
+    layers, grads = _count_layers(monkeypatch)
+    driver.test_training_gradients_match_reference("unet_h4_32x64")     # loss within 1e-5, worst gradient deviation within 1e-4
+    print("unet_h4_32x64: %d layers" % len(layers), sorted(set(layers)))
+    assert len(layers) > 0 and len(grads) == len(layers)
+
+
+@pytest.mark.parametrize("tag", ["unethpx_h4_8x8", "munethpx_h16_8_norm"])
+def test_healpix_networks_train_on_the_kernel(tag, monkeypatch):
+    import test_hpx_train_gpu as driver
+
+    monkeypatch.setenv("DLWP_CONV_WGRAD", "hip")
+    layers, grads = _count_layers(monkeypatch)
+    driver.test_hpx_gradients_match_reference(tag)                      # loss within 1e-5, worst gradient deviation within 1e-4
+    print("%s: %d layers" % (tag, len(layers)), sorted(set(layers)))
+    assert len(layers) > 0 and len(grads) == len(layers)
+
+
+def test_hip_and_torch_paths_agree(monkeypatch):
+    import test_hpx_train_gpu as driver
+
+    monkeypatch.setenv("DLWP_CONV_WGRAD", "hip")
+    _, hip, _ = driver._step("munethpx_h16_8_norm")
+    monkeypatch.setenv("DLWP_CONV_WGRAD", "torch")
+    _, ref, _ = driver._step("munethpx_h16_8_norm")
+    for (name, a), (_, b) in zip(hip.named_parameters(), ref.named_parameters()):
+        assert rel_l2(a.grad, b.grad) <= 1e-5, name
+
+
+def test_auto_leaves_the_fixtures_on_the_library(monkeypatch):
+    """CONV2_WGRAD_AUTO_MIN_FLOPS is infinite: under the default setting no layer takes the new kernel"""
+    import test_hpx_train_gpu as driver
+    from dlwp_benchmark_amd import training
+
+    monkeypatch.delenv("DLWP_CONV_WGRAD", raising=False)
+    assert training.CONV2_WGRAD_AUTO_MIN_FLOPS == float("inf")
+    layers, grads = _count_layers(monkeypatch)
+    driver._step("munethpx_h16_8_norm")
+    assert len(layers) > 0 and grads == []

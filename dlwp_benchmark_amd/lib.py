@@ -249,8 +249,15 @@ SIGNATURES = {
 _lib = None
 
 
+ERR_UNSUPPORTED = -2      # DLWP_ERR_UNSUPPORTED (include/dlwp_hip.h): the shape lies outside the kernel's envelope
+
+
 class DlwpError(RuntimeError):
-    pass
+    """`status`: the library's status where check() raised the error, None where Python code did."""
+
+    def __init__(self, *args, status=None):
+        super().__init__(*args)
+        self.status = status
 
 
 def load():
@@ -277,7 +284,7 @@ def load():
 def check(rc: int, what: str = ""):
     if rc != 0:
         msg = load().dlwp_last_error().decode(errors="replace")
-        raise DlwpError(f"{what or 'libdlwp_hip'} failed with status {rc}: {msg}")
+        raise DlwpError(f"{what or 'libdlwp_hip'} failed with status {rc}: {msg}", status=int(rc))
 
 
 def require_cuda_tensor(t, name: str):

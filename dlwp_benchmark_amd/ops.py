@@ -10,6 +10,8 @@ import torch
 
 from . import lib as _lib
 from .derived import Derived, bump_pack_epoch, derived_for, live_holders, pack_epoch, source_key  # noqa: F401 (re-exported)
+# training.py imports this module at its top, so the other direction of the cycle stays lazy: the wrappers below import
+# training (as _T) inside the function, where a gradient may be wanted
 
 BIG = 1 << 30
 
@@ -372,8 +374,6 @@ def groupnorm_act(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optiona
     _lib.require_cuda_tensor(x, "x")
     from . import training as _T
     if _T.wants_grad(x, weight, bias):
-        if _T._TORCH_BACKWARD():
-            return _T._ACT_FNS[int(act)](torch.nn.functional.group_norm(x, int(groups), weight, bias, eps))
         return _T.groupnorm_act(x, weight, bias, groups, eps, act)           # HIP forward and backward (training.py)
     x = x.contiguous()
     n, c = x.shape[0], x.shape[1]

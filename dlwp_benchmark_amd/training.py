@@ -1,8 +1,17 @@
-"""Training-side use of the spectral kernels (first slice).
+"""The hot kernels under autograd (reference scripts/train.py:263-271 runs `loss.backward()` through the
+backbone): one autograd Function per kernel family, each with a HIP forward and a HIP backward, and the entry points the
+ops call when a gradient is wanted (`wants_grad`).  First the spectral convolution, then window and global attention,
+the AFNO filter, HEALPix padding, the cylinder / HEALPix 3x3 convolution, Conv2d and ConvTranspose2d, GroupNorm, Linear,
+MeshGraphNet and GraphCastNet.
 
-Reference: scripts/train.py:263-271 runs `loss.backward()` through the backbone; for the spectral
-convolutions (models/unet/unet.py:46-69 `SpectralConv2d`, and neuralop's SpectralConv inside
-`FNO2DModule`, fno.py:38-47) autograd differentiates rfft2 / einsum / irfft2.  Here
+Every family but the spectral one also has a torch form: the same operator in plain torch operators (a restatement of
+the reference arithmetic that imports nothing from the oracle).  Autograd of that form is the cross-check of the HIP
+backward (`DLWP_TRAIN_TORCH_BACKWARD=1`, tests/test_training_gpu.py and the per-kernel tests) and the fallback for shapes
+outside a backward kernel's envelope: a Function's backward differentiates it through `_grad_of_torch_form`; Conv2d,
+ConvTranspose2d, GroupNorm and Linear leave the plain composition in the graph instead of their Function.
+
+The spectral convolutions (models/unet/unet.py:46-69 `SpectralConv2d`, and neuralop's SpectralConv inside
+`FNO2DModule`, fno.py:38-47): the reference's autograd differentiates rfft2 / einsum / irfft2.  Here
 
   forward        y  = S_W(x)                           dlwp_spectral_conv2d_f32 (pruned-DFT MFMA kernels)
   backward-data  dx = S_{W^H}(dy)                      the SAME kernels: rows_in/rows_out swapped, weights
@@ -19,15 +28,19 @@ is the same formula in plain torch on any device: the checker of the kernel and 
 path calls.
 
 Everything pointwise around the spectral operator (1x1 convolutions, GELU, residuals) stays in torch ops on
-the GPU in training mode.  The other hot kernels' training paths (window and global attention, Linear, the AFNO
-filter, the cylinder and HEALPix convolutions, GroupNorm, MeshGraphNet, GraphCastNet) follow below, each with its HIP backward.
+the GPU in training mode.
 """
 import ctypes
-from typing import List, Optional, Sequence
+import functools
+import os
+from typing import Optional, Sequence
 
 import torch
+import torch.nn.functional as F
 
+from . import healpix as _hpx
 from . import lib as _lib
+from . import ops       # called as ops.name(...), the attribute tests and tools replace; ops imports this module lazily
 
 
 def spectral_weight_grad(x, grad_y, rows_in, rows_out, n_cols: int, fwd_scale: float, inv_scale: float):
@@ -181,19 +194,69 @@ def pde_arena_rows(height: int, modes1: int):
 # =====================================================================================================================
 # Training through the other hot kernels (reference scripts/train.py:263-271 `loss.backward()`)
 #
-# The boundary requires a differentiable forward ("wrap kernels in autograd.Function with a PyTorch-op
-# backward").  For window attention, the AFNO filter and the padded 3x3 convolution the FORWARD of a training step runs
-# the same HIP kernels as inference; the BACKWARD recomputes the operator from the saved inputs with torch operators on
-# the GPU (a plain restatement of the reference arithmetic, below) and lets autograd differentiate that.  Nothing here
-# imports the oracle: these restatements are part of the product and double as an independent cross-check of the
-# kernels (tests/test_training_gpu.py).  Hand-written backward kernels are the next step; the spectral convolution
-# already has one (above).
+# Each Function below runs the inference kernels forward (Conv2d / ConvTranspose2d: the library's) and a HIP kernel
+# backward.  Beside each stands its torch form (`*_torch`), the operator restated in torch operators, which
+# `_grad_of_torch_form` differentiates where the backward kernel answers "unsupported" and everywhere under
+# DLWP_TRAIN_TORCH_BACKWARD=1.  What the Functions share comes first.
 # =====================================================================================================================
-import functools
+_ACT_FNS = {0: lambda t: t, 1: F.gelu, 2: torch.tanh, 3: F.relu, 4: F.silu}     # the activation codes of ops.ACTS
 
-import torch.nn.functional as F
 
-_ACT_FNS = {0: lambda t: t, 1: F.gelu, 2: torch.tanh, 3: F.relu, 4: F.silu}
+def _torch_backward_selected() -> bool:
+    """DLWP_TRAIN_TORCH_BACKWARD=1: every operator's gradient comes from autograd of its torch form, none from a HIP
+    backward (the cross-check the tests and benches use).  Read at every call."""
+    return os.environ.get("DLWP_TRAIN_TORCH_BACKWARD", "0") == "1"
+
+
+def _grad_of_torch_form(fn, inputs, needs, grad_outs, params=(), zero_fill: bool = False):
+    """The backward of a Function by autograd of its torch form.  fn is called under enable_grad on detached `inputs`
+    (tensors or None) that require a gradient where the matching flag of `needs` is set; its output -- a tensor, or a tuple
+    of which the entries whose `grad_outs` is None are left out -- is differentiated in one torch.autograd.grad call with
+    respect to the needed inputs and to `params`, the live Parameters fn closes over.  Returns a list: one gradient per input
+    (None for a None or unneeded one), then one per parameter.  A tensor the outputs do not depend on gets None, or zeros
+    under zero_fill (a Parameter's .grad is then a tensor whether or not this layer reached it)."""
+    with torch.enable_grad():
+        ins = [t.detach().requires_grad_(bool(need)) if t is not None else None for t, need in zip(inputs, needs)]
+        outs = fn(*ins)
+        if isinstance(outs, torch.Tensor):
+            outs, grad_outs = (outs,), (grad_outs,)
+        pairs = [(o, g.reshape(o.shape).contiguous()) for o, g in zip(outs, grad_outs) if g is not None]
+        wrt = [t for t in ins if t is not None and t.requires_grad] + list(params)
+        grads = torch.autograd.grad([o for o, _ in pairs], wrt, [g for _, g in pairs], allow_unused=True) if wrt else ()
+    if zero_fill:
+        grads = [torch.zeros_like(t) if g is None else g for g, t in zip(grads, wrt)]
+    grads = iter(grads)
+    return [next(grads) if t is not None and t.requires_grad else None for t in ins] + list(grads)
+
+
+# Two activation derivatives, because two things must be reproduced.  _act_backward runs torch's own backward kernel of the
+# activation, so the convolution Functions return the bits autograd gives for the plain composition.  _act_grad_torch is the
+# closed form dlwp_groupnorm_act_bwd_f32 evaluates: the term-by-term reference of that kernel's arithmetic
+# (groupnorm_act_backward_torch).
+def _act_backward(v, grad, act: int):
+    """grad * act'(v) by autograd of the torch activation (the kernel the plain composition's backward runs)"""
+    if act == 0:
+        return grad
+    with torch.enable_grad():
+        v_ = v.detach().requires_grad_(True)
+        g, = torch.autograd.grad(_ACT_FNS[act](v_), v_, grad)
+    return g
+
+
+def _act_grad_torch(v: torch.Tensor, act: int) -> torch.Tensor:
+    """act'(v) for the activation codes of ops.ACTS (0 identity, 1 exact-erf GELU, 2 tanh, 3 ReLU, 4 SiLU)"""
+    if act == 1:
+        return 0.5 * (1.0 + torch.erf(v * 0.7071067811865476)) + v * torch.exp(-0.5 * v * v) * 0.3989422804014327
+    if act == 2:
+        return 1.0 - torch.tanh(v) ** 2
+    if act == 3:
+        return (v > 0).to(v.dtype)
+    if act == 4:
+        s = torch.sigmoid(v)
+        return s * (1.0 + v * (1.0 - s))
+    if act != 0:
+        raise _lib.DlwpError(f"unknown activation {act}")
+    return torch.ones_like(v)
 
 
 @functools.lru_cache(maxsize=64)
@@ -274,8 +337,6 @@ def window_attention_torch(qkv: torch.Tensor, qkv_bias, table: torch.Tensor, spe
 class _WindowAttentionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, qkv_bias, table, spec, precision):
-        from . import ops
-
         ctx.spec = spec
         ctx.save_for_backward(qkv, qkv_bias, table)
         with torch.no_grad():
@@ -286,42 +347,24 @@ class _WindowAttentionFn(torch.autograd.Function):
     def backward(ctx, grad_out):
         """HIP backward (dlwp_window_attn_bwd_f32): scores recomputed tile by tile, no [B, heads, N, N] tensor.  Descriptors the
         kernel does not cover (a bias column that does not fit LDS) and DLWP_TRAIN_TORCH_BACKWARD=1 (the cross-check the tests
-        use) take the torch recomputation below."""
-        from . import ops
-
+        use) differentiate window_attention_torch; any other error raises."""
         qkv, qkv_bias, table = ctx.saved_tensors
-        if not _TORCH_BACKWARD():
+        needs = ctx.needs_input_grad[:3]
+        if not _torch_backward_selected():
             try:
                 gq, gb, gt = ops.window_attention_backward(qkv, qkv_bias, table, ctx.spec, grad_out)
                 if qkv_bias is not None and gb is None:
-                    gb = torch.zeros_like(qkv_bias) if ctx.needs_input_grad[1] else None
-                return (gq if ctx.needs_input_grad[0] else None, gb if ctx.needs_input_grad[1] else None,
-                        gt if ctx.needs_input_grad[2] else None, None, None)
+                    gb = torch.zeros_like(qkv_bias) if needs[1] else None
+                return (gq if needs[0] else None, gb if needs[1] else None, gt if needs[2] else None, None, None)
             except _lib.DlwpError as e:
-                if "status -2:" not in str(e):       # DLWP_ERR_UNSUPPORTED only
+                if e.status != _lib.ERR_UNSUPPORTED:
                     raise
-        with torch.enable_grad():
-            q_ = qkv.detach().requires_grad_(ctx.needs_input_grad[0])
-            b_ = qkv_bias.detach().requires_grad_(ctx.needs_input_grad[1]) if qkv_bias is not None else None
-            t_ = table.detach().requires_grad_(ctx.needs_input_grad[2])
-            out = window_attention_torch(q_, b_, t_, ctx.spec)
-            wrt = [t for t, need in ((q_, ctx.needs_input_grad[0]), (b_, ctx.needs_input_grad[1]), (t_, ctx.needs_input_grad[2]))
-                   if need and t is not None]
-            grads = list(torch.autograd.grad(out, wrt, grad_out.contiguous(), allow_unused=True)) if wrt else []
-        res = []
-        for t, need in ((q_, ctx.needs_input_grad[0]), (b_, ctx.needs_input_grad[1]), (t_, ctx.needs_input_grad[2])):
-            res.append(grads.pop(0) if (need and t is not None) else None)
-        return res[0], res[1], res[2], None, None
-
-
-def _TORCH_BACKWARD() -> bool:
-    import os
-
-    return os.environ.get("DLWP_TRAIN_TORCH_BACKWARD", "0") == "1"
+        return (*_grad_of_torch_form(lambda q, b, t: window_attention_torch(q, b, t, ctx.spec), (qkv, qkv_bias, table), needs,
+                                     grad_out), None, None)
 
 
 def window_attention(qkv, qkv_bias, table, spec, precision="fp32"):
-    """differentiable window attention: HIP forward, recomputed torch backward"""
+    """differentiable window attention: HIP forward and HIP backward"""
     return _WindowAttentionFn.apply(qkv, qkv_bias, table, spec, precision)
 
 
@@ -337,8 +380,6 @@ def global_attention_torch(qkv: torch.Tensor, heads: int, d_k: int, scale: float
 class _GlobalAttentionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, heads, d_k, scale):
-        from . import ops
-
         with torch.no_grad():
             out, stats = ops.global_attention(qkv.detach(), heads, d_k, scale, return_stats=True)
         ctx.cfg = (heads, d_k, scale)
@@ -348,24 +389,19 @@ class _GlobalAttentionFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         """HIP backward (dlwp_global_attn_bwd_f32) from the forward's per-key statistics: no N x N tensor.  DLWP_ERR_UNSUPPORTED
-        (head_dim above 1024) and DLWP_TRAIN_TORCH_BACKWARD=1 (the cross-check the tests use) take the torch recomputation
-        below; any other error raises."""
-        from . import ops
-
+        (head_dim above 1024) and DLWP_TRAIN_TORCH_BACKWARD=1 (the cross-check the tests use) differentiate
+        global_attention_torch; any other error raises."""
         qkv, stats = ctx.saved_tensors
         heads, d_k, scale = ctx.cfg
         if not ctx.needs_input_grad[0]:
             return None, None, None, None
-        if not _TORCH_BACKWARD():
+        if not _torch_backward_selected():
             try:
                 return ops.global_attention_backward(qkv, stats, grad_out, heads, d_k, scale), None, None, None
             except _lib.DlwpError as e:
-                if "status -2:" not in str(e):       # DLWP_ERR_UNSUPPORTED only
+                if e.status != _lib.ERR_UNSUPPORTED:
                     raise
-        with torch.enable_grad():
-            q_ = qkv.detach().requires_grad_(True)
-            out = global_attention_torch(q_, heads, d_k, scale)
-            g, = torch.autograd.grad(out, q_, grad_out.contiguous())
+        g, = _grad_of_torch_form(lambda q: global_attention_torch(q, heads, d_k, scale), (qkv,), (True,), grad_out)
         return g, None, None, None
 
 
@@ -405,8 +441,6 @@ def _put(full, rows, kept, z):
 class _AfnoFilterFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x_cf, w1, b1, w2, b2, num_blocks, lam, frac):
-        from . import ops
-
         ctx.cfg = (num_blocks, lam, frac)
         ctx.save_for_backward(x_cf, w1, b1, w2, b2)
         with torch.no_grad():
@@ -415,21 +449,14 @@ class _AfnoFilterFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         """HIP backward (ops.afno2d_filter_backward: the hand-written transforms around dlwp_afno2d_mix_bwd_f32); grids / block
-        sizes it does not take and DLWP_TRAIN_TORCH_BACKWARD=1 differentiate the torch form below."""
-        from . import ops
-
+        sizes it does not take and DLWP_TRAIN_TORCH_BACKWARD=1 differentiate afno_filter_torch."""
         saved = ctx.saved_tensors
-        if not _TORCH_BACKWARD():
+        needs = ctx.needs_input_grad[:5]
+        if not _torch_backward_selected():
             res = ops.afno2d_filter_backward(saved[0], grad_out, saved[1], saved[2], saved[3], saved[4], *ctx.cfg)
             if res is not None:
-                return (*[g if need else None for g, need in zip(res, ctx.needs_input_grad[:5])], None, None, None)
-        with torch.enable_grad():
-            ins = [t.detach().requires_grad_(need) for t, need in zip(saved, ctx.needs_input_grad[:5])]
-            out = afno_filter_torch(*ins, *ctx.cfg)
-            wrt = [t for t, need in zip(ins, ctx.needs_input_grad[:5]) if need]
-            grads = list(torch.autograd.grad(out, wrt, grad_out.contiguous(), allow_unused=True)) if wrt else []
-        res = [grads.pop(0) if need else None for need in ctx.needs_input_grad[:5]]
-        return (*res, None, None, None)
+                return (*[g if need else None for g, need in zip(res, needs)], None, None, None)
+        return (*_grad_of_torch_form(lambda *a: afno_filter_torch(*a, *ctx.cfg), saved, needs, grad_out), None, None, None)
 
 
 def afno_filter(x_cf, w1, b1, w2, b2, num_blocks, lam, frac):
@@ -457,8 +484,6 @@ class _HpxPadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, padding):
-        from . import ops
-
         ctx.padding = padding
         ctx.save_for_backward(x)
         with torch.no_grad():
@@ -466,17 +491,12 @@ class _HpxPadFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from . import healpix as _hpx
-        from . import ops
-
-        if not _TORCH_BACKWARD():
+        if not _torch_backward_selected():
             with torch.no_grad():
                 return ops.healpix_pad_backward(grad_out, ctx.padding), None
         x, = ctx.saved_tensors
-        with torch.enable_grad():
-            x_ = x.detach().requires_grad_(True)
-            table = _hpx.device_table(x.shape[2], x.shape[3], ctx.padding, x.device)
-            gx, = torch.autograd.grad(_hpx_pad_torch(x_, table), x_, grad_out.contiguous())
+        table = _hpx.device_table(x.shape[2], x.shape[3], ctx.padding, x.device)
+        gx, = _grad_of_torch_form(lambda t: _hpx_pad_torch(t, table), (x,), (True,), grad_out)
         return gx, None
 
 
@@ -510,8 +530,6 @@ def conv3x3_weight_grad_torch(x0, x1, gz, pre_act: int, hpx_table=None, need_wei
         if hpx_table is None:
             xp = F.pad(F.pad(xa, (1, 1, 0, 0), mode="circular"), (0, 0, 1, 1))
         elif xa.is_cuda:
-            from . import ops
-
             xp = ops.healpix_pad(xa, 1)
         else:
             xp = _hpx_pad_torch(xa, hpx_table)
@@ -534,8 +552,6 @@ def conv_wgrad_mode() -> str:
     """DLWP_CONV_WGRAD, the one switch of the U-Net family's convolution weight gradients: "hip" every supported one on
     dlwp_conv3x3_wgrad_f32 / dlwp_conv2d_wgrad_f32, "torch" the library compositions conv3x3_weight_grad_torch /
     conv2d_weight_grad_torch, "auto" (default) HIP where it is supported and measured not slower.  Read at every backward."""
-    import os
-
     mode = os.environ.get("DLWP_CONV_WGRAD", "auto")
     if mode not in CONV_WGRAD_MODES:
         raise _lib.DlwpError(f"DLWP_CONV_WGRAD={mode!r}: one of {CONV_WGRAD_MODES}")
@@ -544,8 +560,6 @@ def conv_wgrad_mode() -> str:
 
 def conv_wgrad_uses_hip(batch: int, c0: int, c1: int, cout: int, h: int, w: int, hpx: bool) -> bool:
     """whether _Conv3x3Fn.backward takes the HIP weight gradient for a layer under the current DLWP_CONV_WGRAD"""
-    from . import ops
-
     mode = conv_wgrad_mode()
     if mode == "torch" or (mode == "auto" and 18.0 * batch * h * w * (c0 + c1) * cout < CONV_WGRAD_AUTO_MIN_FLOPS):
         return False                                     # decided without a library call
@@ -558,10 +572,11 @@ HPX_DX_DIRECT_MAX_COUT = 48
 
 
 class _Conv3x3Fn(torch.autograd.Function):
+    """pad(1) + Conv2d(3x3) with its fusions (CylinderPad, or HEALPixPadding with hpx): dlwp_conv3x3_ex_f32 forward, the
+    kernels of _conv3x3_backward backward.  DLWP_TRAIN_TORCH_BACKWARD=1 differentiates conv3x3_torch instead."""
+
     @staticmethod
     def forward(ctx, x0, x1, weight, bias, resid, pre_act, act, hpx):
-        from . import ops
-
         ctx.cfg = (pre_act, act, hpx)
         ctx.save_for_backward(x0, x1, weight, bias, resid)
         with torch.no_grad():
@@ -570,73 +585,13 @@ class _Conv3x3Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from . import healpix as _hpx
-        from . import ops
-
+        if not _torch_backward_selected():
+            return (*_conv3x3_backward(ctx, grad_out), None, None, None)
         pre_act, act, hpx = ctx.cfg
-        saved = ctx.saved_tensors
-        if not _TORCH_BACKWARD():
-            # CylinderPad (circular in longitude, zeros in latitude) + 3x3: the input gradient is the SAME operator with the weights
-            # transposed and flipped -- dlwp_conv3x3_ex_f32 again (reference backward: train.py:271 through unet.py:429-555,
-            # convlstm.py:82-111); pre- / post-activation derivatives are pointwise torch operators, the weight and bias gradients
-            # are one dlwp_conv3x3_wgrad_f32 call on the unpadded segments (DLWP_CONV_WGRAD: or conv3x3_weight_grad_torch, the
-            # correlation of a padded copy with the output gradient through MIOpen).
-            # HEALPixPadding(1) + 3x3 (healpix.py:69-114): the input gradient is dlwp_conv3x3_hpx_bwd_data_f32 (the transposed
-            # 3x3 folded through the adjoint of the padding table); everything else is the cylinder path's
-            x0, x1, weight, bias, resid = saved
-            with torch.no_grad():
-                cat = []        # cat([x0, x1], 1), made once and only where a step below reads it
-
-                def xcat():
-                    if not cat:
-                        cat.append(x0 if x1 is None else torch.cat([x0, x1], dim=1))
-                    return cat[0]
-
-                c0, c1 = x0.shape[1], (x1.shape[1] if x1 is not None else 0)
-                gz = grad_out.contiguous()
-                if act != 0:
-                    z = ops.conv3x3(x0, weight, bias, act=0, x1=x1, pre_act=pre_act, resid=resid, hpx=hpx)
-                    with torch.enable_grad():
-                        z_ = z.detach().requires_grad_(True)
-                        gz, = torch.autograd.grad(_ACT_FNS[act](z_), z_, gz)
-                    gz = gz.contiguous()
-                res = [None] * 5
-                if ctx.needs_input_grad[0] or (x1 is not None and ctx.needs_input_grad[1]):
-                    if hpx and weight.shape[0] <= HPX_DX_DIRECT_MAX_COUT:
-                        dxa = ops.conv3x3_hpx_backward_data(gz, weight, c0 + c1)
-                    elif hpx:
-                        # wide layers: the full transposed 3x3 (MIOpen) onto the padded face, folded by the padding's adjoint
-                        dxa = ops.healpix_pad_backward(F.conv_transpose2d(gz, weight), 1)
-                    else:
-                        wt = weight.flip(2, 3).transpose(0, 1).contiguous()
-                        dxa = ops.conv3x3(gz, wt, None)
-                    if pre_act != 0:
-                        with torch.enable_grad():
-                            xc_ = xcat().detach().requires_grad_(True)
-                            dxa, = torch.autograd.grad(_ACT_FNS[pre_act](xc_), xc_, dxa)
-                    res[0] = dxa[:, :c0].contiguous() if ctx.needs_input_grad[0] else None
-                    res[1] = dxa[:, c0:].contiguous() if (x1 is not None and ctx.needs_input_grad[1]) else None
-                need_w, need_b = ctx.needs_input_grad[2], bias is not None and ctx.needs_input_grad[3]
-                if need_w or need_b:
-                    n_, _, h_, w_ = x0.shape
-                    if conv_wgrad_uses_hip(n_, c0, c1, weight.shape[0], h_, w_, hpx):
-                        dw, db = ops.conv3x3_weight_grad(x0, x1, gz, pre_act=pre_act, hpx=hpx, need_bias=need_b)
-                    else:
-                        table = _hpx.device_table(h_, w_, 1, x0.device) if hpx else None
-                        dw, db = conv3x3_weight_grad_torch(xcat(), None, gz, pre_act, table, need_weight=need_w, need_bias=need_b)
-                    res[2] = dw if need_w else None
-                    res[3] = db if need_b else None
-                if resid is not None and ctx.needs_input_grad[4]:
-                    res[4] = gz
-            return (*res, None, None, None)
-        with torch.enable_grad():
-            ins = [t.detach().requires_grad_(need) if t is not None else None for t, need in zip(saved, ctx.needs_input_grad[:5])]
-            table = _hpx.device_table(ins[0].shape[2], ins[0].shape[3], 1, ins[0].device) if hpx else None
-            out = conv3x3_torch(ins[0], ins[1], ins[2], ins[3], ins[4], pre_act, act, table)
-            wrt = [t for t, need in zip(ins, ctx.needs_input_grad[:5]) if need and t is not None]
-            grads = list(torch.autograd.grad(out, wrt, grad_out.contiguous(), allow_unused=True)) if wrt else []
-        res = [grads.pop(0) if (need and t is not None) else None for t, need in zip(ins, ctx.needs_input_grad[:5])]
-        return (*res, None, None, None)
+        x0 = ctx.saved_tensors[0]
+        table = _hpx.device_table(x0.shape[2], x0.shape[3], 1, x0.device) if hpx else None
+        return (*_grad_of_torch_form(lambda *a: conv3x3_torch(*a, pre_act, act, table), ctx.saved_tensors,
+                                     ctx.needs_input_grad[:5], grad_out), None, None, None)
 
 
 def conv3x3(x0, weight, bias, act=0, x1=None, pre_act=0, resid=None, hpx=False):
@@ -692,8 +647,6 @@ def conv2_wgrad_flops(batch: int, cin: int, cout: int, h: int, w: int, k: int, s
 def conv2_wgrad_uses_hip(batch: int, cin: int, cout: int, h: int, w: int, k: int, stride: int, padding: int,
                          transposed: bool) -> bool:
     """whether _Conv2dFn / _ConvTranspose2dFn take dlwp_conv2d_wgrad_f32 for a layer under the current DLWP_CONV_WGRAD"""
-    from . import ops
-
     mode = conv_wgrad_mode()
     if mode == "torch" or (mode == "auto" and conv2_wgrad_flops(batch, cin, cout, h, w, k, stride, padding, transposed)
                            < CONV2_WGRAD_AUTO_MIN_FLOPS):
@@ -701,14 +654,48 @@ def conv2_wgrad_uses_hip(batch: int, cin: int, cout: int, h: int, w: int, k: int
     return ops.conv2d_weight_grad_supported(batch, cin, cout, h, w, k, stride, padding, transposed)
 
 
-def _act_backward(v, grad, act: int):
-    """grad * act'(v) by autograd of the torch activation (the kernel the plain composition's backward runs)"""
-    if act == 0:
-        return grad
-    with torch.enable_grad():
-        v_ = v.detach().requires_grad_(True)
-        g, = torch.autograd.grad(_ACT_FNS[act](v_), v_, grad)
-    return g
+def _conv3x3_backward(ctx, grad_out):
+    """(dx0, dx1, dw, db, dresid) of _Conv3x3Fn (reference backward: train.py:271 through unet.py:429-555, convlstm.py:82-111).
+    The post-activation derivative from z, recomputed by the forward kernel.  The input gradient: under CylinderPad (circular
+    in longitude, zeros in latitude) the SAME operator with the weights transposed and flipped, dlwp_conv3x3_ex_f32 again;
+    under HEALPixPadding(1) (healpix.py:69-114) dlwp_conv3x3_hpx_bwd_data_f32, the transposed 3x3 folded through the adjoint
+    of the padding table, or for wide layers the library's transposed convolution onto the padded face folded by
+    dlwp_healpix_pad_bwd_f32; then the pre-activation derivative.  The weight and bias gradients in one
+    dlwp_conv3x3_wgrad_f32 call on the unpadded segments (DLWP_CONV_WGRAD: or conv3x3_weight_grad_torch, the correlation of a
+    padded copy with the output gradient through MIOpen), the residual's gradient gz itself."""
+    pre_act, act, hpx = ctx.cfg
+    x0, x1, weight, bias, resid = ctx.saved_tensors
+    need_x0, need_x1, need_w, need_b, need_r = ctx.needs_input_grad[:5]
+    need_x1, need_b, need_r = need_x1 and x1 is not None, need_b and bias is not None, need_r and resid is not None
+    n, c0, h, w = x0.shape
+    c1 = x1.shape[1] if x1 is not None else 0
+    dx0 = dx1 = dw = db = None
+    xcat = None             # cat([x0, x1], 1): made at most once, by the first step below that reads it
+    with torch.no_grad():
+        gz = grad_out.contiguous()
+        if act != 0:
+            z = ops.conv3x3(x0, weight, bias, act=0, x1=x1, pre_act=pre_act, resid=resid, hpx=hpx)
+            gz = _act_backward(z, gz, act).contiguous()
+        if need_x0 or need_x1:
+            if hpx and weight.shape[0] <= HPX_DX_DIRECT_MAX_COUT:
+                dxa = ops.conv3x3_hpx_backward_data(gz, weight, c0 + c1)
+            elif hpx:
+                dxa = ops.healpix_pad_backward(F.conv_transpose2d(gz, weight), 1)
+            else:
+                dxa = ops.conv3x3(gz, weight.flip(2, 3).transpose(0, 1).contiguous(), None)
+            if pre_act != 0:
+                xcat = x0 if x1 is None else torch.cat([x0, x1], dim=1)
+                dxa = _act_backward(xcat, dxa, pre_act)
+            dx0 = dxa[:, :c0].contiguous() if need_x0 else None
+            dx1 = dxa[:, c0:].contiguous() if need_x1 else None
+        if need_w or need_b:
+            if conv_wgrad_uses_hip(n, c0, c1, weight.shape[0], h, w, hpx):
+                dw, db = ops.conv3x3_weight_grad(x0, x1, gz, pre_act=pre_act, hpx=hpx, need_bias=need_b)
+            else:
+                table = _hpx.device_table(h, w, 1, x0.device) if hpx else None
+                segments = (x0, x1) if xcat is None else (xcat, None)       # two segments it joins itself, where it reads them
+                dw, db = conv3x3_weight_grad_torch(*segments, gz, pre_act, table, need_weight=need_w, need_bias=need_b)
+    return dx0, dx1, (dw if need_w else None), (db if need_b else None), (gz if need_r else None)
 
 
 def _conv2_backward(ctx, grad_out, transposed: bool):
@@ -716,8 +703,6 @@ def _conv2_backward(ctx, grad_out, transposed: bool):
     gradient by the library call autograd makes for the plain composition (aten.convolution_backward, input alone) followed by
     the pre-activation derivative, the weight and bias gradients in one dlwp_conv2d_wgrad_f32 call on x as it lies
     (DLWP_CONV_WGRAD: or conv2d_weight_grad_torch), the residual's gradient gz itself."""
-    from . import ops
-
     stride, padding, pre_act, act = ctx.cfg
     x, weight, bias, resid, z = ctx.saved_tensors
     need_x, need_w, need_b = ctx.needs_input_grad[:3]
@@ -780,7 +765,7 @@ class _ConvTranspose2dFn(torch.autograd.Function):
 
 def _plain_conv2(weight) -> bool:
     """the cases that keep the plain composition under autograd: the cross-check setting and kernels that are not square"""
-    return _TORCH_BACKWARD() or weight.dim() != 4 or weight.shape[2] != weight.shape[3]
+    return _torch_backward_selected() or weight.dim() != 4 or weight.shape[2] != weight.shape[3]
 
 
 def conv2d(x, weight, bias, resid, stride: int, padding: int, pre_act: int, act: int):
@@ -793,22 +778,6 @@ def conv_transpose2d(x, weight, bias, stride: int, padding: int, act: int):
     if _plain_conv2(weight):
         return conv_transpose2d_torch(x, weight, bias, stride, padding, act)
     return _ConvTranspose2dFn.apply(x, weight, bias, stride, padding, act)
-
-
-def _act_grad_torch(v: torch.Tensor, act: int) -> torch.Tensor:
-    """act'(v) for the activation codes of ops.ACTS (0 identity, 1 exact-erf GELU, 2 tanh, 3 ReLU, 4 SiLU)"""
-    if act == 1:
-        return 0.5 * (1.0 + torch.erf(v * 0.7071067811865476)) + v * torch.exp(-0.5 * v * v) * 0.3989422804014327
-    if act == 2:
-        return 1.0 - torch.tanh(v) ** 2
-    if act == 3:
-        return (v > 0).to(v.dtype)
-    if act == 4:
-        s = torch.sigmoid(v)
-        return s * (1.0 + v * (1.0 - s))
-    if act != 0:
-        raise _lib.DlwpError(f"unknown activation {act}")
-    return torch.ones_like(v)
 
 
 def groupnorm_act_backward_torch(x, mean, rstd, gamma, beta, gy, groups: int, act: int):
@@ -846,8 +815,6 @@ class _GroupNormActFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, groups, eps, act):
-        from . import ops
-
         x = x.contiguous()
         d = lambda t: t.detach() if t is not None else None
         with torch.no_grad():
@@ -858,8 +825,6 @@ class _GroupNormActFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from . import ops
-
         groups, act, has_w, has_b = ctx.cfg
         x, stats, *wb = ctx.saved_tensors
         weight = wb.pop(0) if has_w else None
@@ -874,7 +839,10 @@ class _GroupNormActFn(torch.autograd.Function):
 
 
 def groupnorm_act(x, weight, bias, groups: int, eps: float = 1e-5, act: int = 0):
-    """differentiable act(GroupNorm(groups)(x)) for x [N, C, *]: HIP forward and HIP backward"""
+    """differentiable act(GroupNorm(groups)(x)) for x [N, C, *]: HIP forward and HIP backward; under
+    DLWP_TRAIN_TORCH_BACKWARD=1 the library's group_norm and activation, left to autograd"""
+    if _torch_backward_selected():
+        return _ACT_FNS[int(act)](F.group_norm(x, int(groups), weight, bias, eps))
     return _GroupNormActFn.apply(x, weight, bias, int(groups), float(eps), int(act))
 
 
@@ -888,15 +856,11 @@ class _LinearFn(torch.autograd.Function):
 
     @staticmethod
     def supported(rows: int, k: int, n: int) -> bool:
-        from . import ops
-
         return (ops.linear_supported(k, n) and ops.linear_supported(n, k) and ops.linear_supported(rows, k) and
-                not _TORCH_BACKWARD())
+                not _torch_backward_selected())
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        from . import ops
-
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         with torch.no_grad():
@@ -904,8 +868,6 @@ class _LinearFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from . import ops
-
         x, weight = ctx.saved_tensors
         n, k = weight.shape
         gy2 = gy.reshape(-1, n).contiguous()
@@ -942,16 +904,12 @@ def mgn_mlp_backward_torch(seq, x, grad_out, batch: int, rows: int, channels_fir
                            need_input_grad: bool):
     """the backward of one MeshGraphMLP by autograd of the torch composition (DLWP_TRAIN_TORCH_BACKWARD=1): (grad_x or None,
     [gradients in the order of seq.parameters()])"""
-    from . import ops
-
-    params = list(seq.parameters())
-    with torch.enable_grad():
-        x_ = x.detach().requires_grad_(need_input_grad)
+    def form(x_):
         y = ops.mgn_mlp_torch(seq, _mgn_rows(x_, batch, rows, channels_first_in))
-        if channels_first_out:
-            y = y.view(batch, rows, -1).permute(0, 2, 1)
-        grads = torch.autograd.grad(y, ([x_] if need_input_grad else []) + params, grad_out.reshape(y.shape))
-    return (grads[0] if need_input_grad else None), list(grads[int(need_input_grad):])
+        return y.view(batch, rows, -1).permute(0, 2, 1) if channels_first_out else y
+
+    gx, *gp = _grad_of_torch_form(form, (x,), (need_input_grad,), grad_out, params=list(seq.parameters()))
+    return gx, gp
 
 
 class _MgnMlpFn(torch.autograd.Function):
@@ -960,8 +918,6 @@ class _MgnMlpFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, seq, packed, batch, rows, channels_first_in, channels_first_out, *params):
-        from . import ops
-
         with torch.no_grad():
             y = ops.mgn_mlp(packed, seq, x.detach(), batch, rows, channels_first_in, channels_first_out)
         ctx.save_for_backward(x, *params)         # the parameters too: autograd's version check sees in-place edits
@@ -970,12 +926,10 @@ class _MgnMlpFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from . import ops
-
         x = ctx.saved_tensors[0]
         seq, packed, batch, rows, cf_in, cf_out = ctx.cfg
         need_x = ctx.needs_input_grad[0]
-        if _TORCH_BACKWARD():
+        if _torch_backward_selected():
             gx, gp = mgn_mlp_backward_torch(seq, x, grad_out, batch, rows, cf_in, cf_out, need_x)
         else:
             gx, gp = ops.mgn_mlp_backward(packed, seq, x, grad_out, batch, rows, cf_in, cf_out, need_x)
@@ -992,20 +946,11 @@ def mgn_mlp(seq, packed, x, batch: int, rows: int, channels_first_in: bool = Fal
 def mgn_layer_backward_torch(edge_seq, node_seq, aggregation, graph, batch: int, x, e, dx_out, de_out):
     """the backward of one processor layer by autograd of ops.mgn_layer_torch (DLWP_TRAIN_TORCH_BACKWARD=1): (dx, de,
     [edge MLP gradients], [node MLP gradients])"""
-    from . import ops
-
     _, src, dst, deg = graph[:4]
     pe, pn = list(edge_seq.parameters()), list(node_seq.parameters())
-    with torch.enable_grad():
-        x_, e_ = x.detach().requires_grad_(True), e.detach().requires_grad_(True)
-        xo, eo = ops.mgn_layer_torch(edge_seq, node_seq, aggregation, src, dst, deg, batch, x_, e_)
-        outs, gouts = [xo], [dx_out if dx_out is not None else torch.zeros_like(xo)]
-        if de_out is not None:
-            outs.append(eo)
-            gouts.append(de_out)
-        grads = torch.autograd.grad(outs, [x_, e_] + pe + pn, gouts, allow_unused=True)
-    grads = [g if g is not None else torch.zeros_like(t) for g, t in zip(grads, [x_, e_] + pe + pn)]
-    return grads[0], grads[1], grads[2:2 + len(pe)], grads[2 + len(pe):]
+    form = lambda x_, e_: ops.mgn_layer_torch(edge_seq, node_seq, aggregation, src, dst, deg, batch, x_, e_)
+    dx, de, *gp = _grad_of_torch_form(form, (x, e), (True, True), (dx_out, de_out), params=pe + pn, zero_fill=True)
+    return dx, de, gp[:len(pe)], gp[len(pe):]
 
 
 class _MgnLayerFn(torch.autograd.Function):
@@ -1015,8 +960,6 @@ class _MgnLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, e, e_shared, cfg, *params):
-        from . import ops
-
         edge_seq, edge_packed, node_seq, node_packed, aggregation, graph, batch = cfg
         row_ptr, src, dst = graph[0], graph[1], graph[2]
         d = x.shape[1]
@@ -1032,11 +975,9 @@ class _MgnLayerFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dx_out, de_out):
-        from . import ops
-
         x, e = ctx.saved_tensors[:2]
         edge_seq, edge_packed, node_seq, node_packed, aggregation, graph, batch = ctx.cfg
-        if _TORCH_BACKWARD():
+        if _torch_backward_selected():
             dx, de, ge, gn = mgn_layer_backward_torch(edge_seq, node_seq, aggregation, graph, batch, x, e, dx_out, de_out)
         else:
             if dx_out is None:
@@ -1061,8 +1002,6 @@ def _gc_tail_backward(seq, batch: int, rows: int, zs, gy, out_cf: bool, ln_gathe
                       want_total: bool = False):
     """the backward of a MeshGraphMLP above its first Linear from the saved pre-activations zs: (dZ_0 [batch * rows, H],
     the LayerNorm's total output gradient or None, [gradients in the order of seq.parameters(), the first Linear's None])"""
-    from . import ops
-
     lins, ln = ops.mgn_parts(seq)
     act = ops.GC_ACT[type(seq[1])]
     n = len(lins)
@@ -1085,8 +1024,6 @@ def _gc_tail_backward(seq, batch: int, rows: int, zs, gy, out_cf: bool, ln_gathe
 
 def _gc_batch_sum(t: torch.Tensor, batch: int) -> torch.Tensor:
     """the fixed-order sum over the batch of [batch * rows, D] (the gradient of a table the batch shares)"""
-    from . import ops
-
     if batch == 1:
         return t
     return ops.gc_segment_sum(t, batch, None, None, t.shape[0] // batch, batch_sum=True)
@@ -1118,8 +1055,6 @@ class _GcMlpFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, cfg, *params):
-        from . import ops
-
         seq, pk, batch, rows, mode, x_bs, residual, out_cf, col_order = cfg
         with torch.no_grad():
             xd = x.detach()
@@ -1131,19 +1066,14 @@ class _GcMlpFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from . import ops
-
         seq, pk, batch, rows, mode, x_bs, residual, out_cf, col_order = ctx.cfg
         saved = ctx.saved_tensors
         x, zs = saved[0], saved[1:1 + ctx.n_z]
-        params = list(seq.parameters())
         need_x = ctx.needs_input_grad[0]
-        if _TORCH_BACKWARD():
-            with torch.enable_grad():
-                x_ = x.detach().requires_grad_(need_x)
-                y = gc_mlp_torch(seq, x_, batch, rows, mode, x_bs, residual, out_cf, col_order)
-                grads = torch.autograd.grad(y, ([x_] if need_x else []) + params, gy.reshape(y.shape))
-            return ((grads[0] if need_x else None), None, *grads[int(need_x):])
+        if _torch_backward_selected():
+            form = lambda x_: gc_mlp_torch(seq, x_, batch, rows, mode, x_bs, residual, out_cf, col_order)
+            gx, *gp = _grad_of_torch_form(form, (x,), (need_x,), gy, params=list(seq.parameters()))
+            return (gx, None, *gp)
         gy = gy.contiguous()
         lins, _ = ops.mgn_parts(seq)
         g0, _, grads = _gc_tail_backward(seq, batch, rows, zs, gy, out_cf)
@@ -1200,8 +1130,6 @@ class _GcLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, e, xs, xd, cfg, *params):
-        from . import ops
-
         edge_seq, epk, node_seq, npk, aggregation, graph, batch, residual = cfg
         # batch strides: 0 for one [rows, D] table the batch shares (at batch 1 every operand counts as per sample)
         bs = tuple(rows * t.shape[-1] if t.shape[0] == batch * rows else 0
@@ -1216,28 +1144,19 @@ class _GcLayerFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gx_out, ge_out):
-        from . import ops
-
         edge_seq, epk, node_seq, npk, aggregation, graph, batch, residual = ctx.cfg
         sv = ctx.saved_tensors
         e, xs, xd, e_new = sv[:4]
         ze, zn = sv[4:4 + ctx.n_ze], sv[4 + ctx.n_ze:4 + ctx.n_ze + ctx.n_zn]
         e_bs, xs_bs, xd_bs = ctx.bs
         n_src, n_dst, ne = graph["n_src"], graph["n_dst"], graph["src"].numel()
-        pe, pn = list(edge_seq.parameters()), list(node_seq.parameters())
+        if _torch_backward_selected():
+            form = lambda e_, xs_, xd_: gc_layer_torch(edge_seq, node_seq, aggregation, graph, batch, e_, xs_, xd_, residual)
+            grads = _grad_of_torch_form(form, (e, xs, xd), ctx.needs_input_grad[:3], (gx_out, ge_out),
+                                        params=[*edge_seq.parameters(), *node_seq.parameters()], zero_fill=True)
+            return (*grads[:3], None, *grads[3:])
         if gx_out is None:
             gx_out = torch.zeros(batch * n_dst, xd.shape[-1], device=xd.device, dtype=torch.float32)
-        if _TORCH_BACKWARD():
-            with torch.enable_grad():
-                e_, xs_, xd_ = (t.detach().requires_grad_(True) for t in (e, xs, xd))
-                xo, eo = gc_layer_torch(edge_seq, node_seq, aggregation, graph, batch, e_, xs_, xd_, residual)
-                outs, gouts = [xo], [gx_out]
-                if ge_out is not None:
-                    outs.append(eo)
-                    gouts.append(ge_out)
-                grads = torch.autograd.grad(outs, [e_, xs_, xd_] + pe + pn, gouts, allow_unused=True)
-            grads = [g if g is not None else torch.zeros_like(t) for g, t in zip(grads, [e_, xs_, xd_] + pe + pn)]
-            return (*grads[:3], None, *grads[3:])
         gx_out = gx_out.contiguous()
         ge_out = ge_out.contiguous() if ge_out is not None else None
         d = e_new.shape[-1]

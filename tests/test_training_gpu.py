@@ -140,12 +140,30 @@ def test_training_gradients_match_reference(tag):
 def test_differentiable_restatements_match_the_kernels():
     """The torch forms the backward passes differentiate (training.py) are the same operators as the HIP kernels."""
     from dlwp_benchmark_amd import ops, training as T
-    from test_window_attn_gpu import _inputs, _spec
+    from test_window_attn_bwd_gpu import _pangu_spec
+    from test_window_attn_gpu import _inputs, _spec, _sub_window_spec
 
     for shifted in (False, True):
         spec, rows = _spec(16, 32, 2, 8, shifted)
         qkv, bias, table = _inputs(2, 16, 32, 2, 8, rows)
         a = ops.window_attention(qkv, bias, table, spec, precision="fp32_mfma")
+        b = T.window_attention_torch(qkv, bias, table, spec)
+        assert float((a - b).norm() / b.norm()) <= 2e-6
+    # a shifted Swin block with four windows per map, and a rolled Pangu block padded on every axis (every geometry, against
+    # float64: tests/test_window_attn_ref_cpu.py for the torch form, tests/test_window_attn_fp64_gpu.py for the kernels)
+    spec, rows = _sub_window_spec(16, 64, 8, 32, 2, 16, True)
+    qkv, bias, table = _inputs(2, 16, 64, 2, 16, rows, seed=1)
+    a = ops.window_attention(qkv, bias, table, spec, precision="fp32_mfma")
+    b = T.window_attention_torch(qkv, bias, table, spec)
+    assert float((a - b).norm() / b.norm()) <= 2e-6
+    spec, tshape = _pangu_spec(16, 32, 2, 32, True)
+    assert all(p > g for p, g in zip(spec.padded, spec.grid)) and any(spec.shift_fwd)
+    gen = torch.Generator().manual_seed(2)
+    qkv = torch.randn(2, 16 * 32, 3 * 2 * 32, generator=gen).cuda()
+    bias = (0.3 * torch.randn(3 * 2 * 32, generator=gen)).cuda()
+    table = (0.5 * torch.randn(*tshape, generator=gen)).cuda()
+    for precision in ("fp32_mfma", "bf16x6"):       # the generic kernel and the earth-window kernel
+        a = ops.window_attention(qkv, bias, table, spec, precision=precision)
         b = T.window_attention_torch(qkv, bias, table, spec)
         assert float((a - b).norm() / b.norm()) <= 2e-6
     gen = torch.Generator().manual_seed(3)

@@ -1,6 +1,8 @@
 """Backward of the window attention (csrc/window_attn_bwd.hip, dlwp_window_attn_bwd_f32) against autograd of the torch
-restatement of the operator (training.window_attention_torch, itself checked against the forward kernels and -- through the
-model-level gradient fixtures of tests/test_training_gpu.py -- against gradients the REAL reference classes produced).
+restatement of the operator (training.window_attention_torch: equal in float64 to the independent reference of
+tests/window_attn_ref.py at every geometry of tests/test_window_attn_ref_cpu.py, the reference the forward kernels are held to
+in tests/test_window_attn_fp64_gpu.py; and -- through the model-level gradient fixtures of tests/test_training_gpu.py --
+checked against gradients the REAL reference classes produced).
 Reference backward: scripts/train.py:271 through swin_transformer.py:122-154 / panguweather.py:176-211."""
 import pytest
 import torch

@@ -1,6 +1,12 @@
-"""Op-level tests of the second-generation 2-D window attention (csrc/window_attn2.hip) against the first-generation
-kernel's fp32-MFMA form (an independent implementation: running maximum, per-score bias gather and mask, no tile
-skipping) -- itself pinned by the model goldens of the real reference classes (tests/test_backbones_gpu.py)."""
+"""Op-level tests of the second-generation 2-D window attention (csrc/window_attn2.hip) and the earth-window kernel
+(csrc/window_attn3.hip) against the first-generation kernel's fp32-MFMA form (another implementation of the softmax:
+running maximum, per-score bias gather and mask, no tile skipping), and the bit-identity of the bfloat16-tensor forms.
+
+Kernel against kernel: the three kernels share csrc/window_attn_desc.hpp (token_coord, token_dest, bias_index, the region
+arithmetic), so nothing here can see an error in that header or in the host's reading of the descriptor.  What anchors the
+forward kernels -- the generic one included -- is tests/test_window_attn_fp64_gpu.py: every kernel, variant and plan against
+an independent float64 reference (tests/window_attn_ref.py), beside the model goldens of the real reference classes
+(tests/test_backbones_gpu.py), which run one geometry each."""
 import pytest
 import torch
 
@@ -155,14 +161,30 @@ def test_earth_window_kernel_large_logits():
     assert torch.isfinite(got).all() and rel_l2(got, want) <= 2e-4      # fp32 rounding of logits of several hundred
 
 
-@pytest.mark.parametrize("kind", ["swin", "swin_shifted", "pangu", "pangu_rolled"])
+# the nine (RP, PP, PB) plans of the earth-window kernel (tests/test_window_attn_ref_cpu.py asserts which grid reaches which),
+# rolled wherever a roll exists (every component of window // 2 non-zero): each has an IO16 instance of its own
+_EARTH_PLANS = [((1, 16, 32), (2, 6, 12)), ((1, 10, 17), (2, 5, 7)), ((1, 9, 30), (2, 3, 10)),        # (1,1,5) (1,1,3) (1,1,2)
+                ((2, 12, 24), (2, 6, 12)), ((2, 11, 13), (2, 5, 7)), ((4, 8, 16), (2, 4, 8)),         # (2,0,5) (2,0,3) (2,0,2)
+                ((2, 12, 24), (1, 6, 12)), ((1, 10, 16), (1, 5, 8)), ((1, 8, 16), (1, 4, 8))]         # (1,0,5) (1,0,3) (1,0,2)
+_EARTH_KINDS = [(g, w, s) for g, w in _EARTH_PLANS for s in ((False, True) if all(v // 2 for v in w) else (False,))]
+
+
+@pytest.mark.parametrize("kind", ["swin", "swin_shifted", "pangu", "pangu_rolled"] + _EARTH_KINDS,
+                         ids=lambda k: k if isinstance(k, str) else "earth-" + "x".join(map(str, k[0] + k[1])) + ("-rolled" if k[2] else ""))
 def test_bf16_tensor_handover_is_bit_identical(kind):
     """dlwp_window_attn_bf16_io (bf16 qkv in, bf16 out: the hand-over of a block in the all-bf16 form) computes exactly what
     dlwp_window_attn_bf16 computes on the same bf16-representable values, rounded once more to bf16 on the way out."""
     from dlwp_benchmark_amd import ops
     from test_window_attn_bwd_gpu import _pangu_spec
 
-    if kind.startswith("swin"):
+    if not isinstance(kind, str):
+        grid, window, rolled = kind
+        spec, rows, types = _earth_spec(grid, window, 3, rolled)
+        g = torch.Generator().manual_seed(9)
+        qkv = torch.randn(2, grid[0] * grid[1] * grid[2], 3 * 3 * 32, generator=g).cuda()
+        bias = (0.3 * torch.randn(3 * 3 * 32, generator=g)).cuda()
+        table = (0.5 * torch.randn(rows, types, 3, generator=g)).cuda()
+    elif kind.startswith("swin"):
         spec, rows = _spec(32, 64, 4, 24, kind.endswith("shifted"))
         qkv, bias, table = _inputs(2, 32, 64, 4, 24, rows, seed=5)
     else:

@@ -436,6 +436,63 @@ __device__ __forceinline__ void lift_segment(const f32x4 (&xs)[CIN_STEPS], const
 }
 
 // ---------------------------------------------------------------------------------------------
+// Lifting MLP of ONE input channel from a table.  With one input channel
+//   lift(x)[o] = b2[o] + sum_c W2[o][c] gelu(w1[c] x + b1[c])
+// is 32 smooth functions of one scalar.  The plan tabulates them once: per interval of width h = 2^-log2_inv_h over
+// [-range, range) and output channel a quintic Hermite interpolant (f, f', f'' matched at both ends, fp64 with erfc),
+// written in the coordinate v in [0, 1) measured from the interval's end NEARER zero -- so c0 = lift(knot) and the
+// polynomial keeps its RELATIVE accuracy as x -> 0 (zero biases make lift(x) proportional to x there).
+// Layout: fp32 [interval][coef 0..5][32 channels]; a lane's channels 4g.. and 16+4g.. are two 16-byte loads per coefficient.
+// ---------------------------------------------------------------------------------------------
+constexpr int kLiftTabRange = 32, kLiftTabLog2 = 4;   // the plans' table: 1024 intervals, 768 KB
+constexpr int kLiftTabCoefs = 6;
+constexpr int kLiftTabStride = kLiftTabCoefs * kC;    // floats per interval
+
+// Interval of x and its coordinate v.  n_side = intervals per sign, scale = 1 / h (a power of two): |x| scale, its floor
+// and their difference are all exact in fp32.  The caller has checked |x| < range; the index is clamped regardless.
+__host__ __device__ __forceinline__ int lift_tab_locate(float x, int n_side, float scale, float& v) {
+  const float a = fabsf(x) * scale;
+  const float fl = floorf(a);
+  v = a - fl;
+  int k = (int)fl;
+  k = k < 0 ? 0 : (k > n_side - 1 ? n_side - 1 : k);
+  return x < 0.f ? n_side - 1 - k : n_side + k;
+}
+
+// Lifting output from the table: xbc = four pixel values, g = channel group; vv[ot][r][q] = channel 16 ot + 4 g + r of pixel q
+// (the trunk's resident layout for the lane that holds these pixels).  Two pixels at a time: 24 loads in flight, then 2 x 8
+// Horner chains.
+__device__ __forceinline__ void lift_from_table(const float* __restrict__ tab, const f32x4& xbc, int g, f32x4 (&vv)[2][4]) {
+#pragma unroll
+  for (int qp = 0; qp < 2; ++qp) {
+    f32x4 c[2][kLiftTabCoefs][2];
+    float v[2];
+#pragma unroll
+    for (int qq = 0; qq < 2; ++qq) {
+      const int idx = lift_tab_locate(xbc[2 * qp + qq], kLiftTabRange << kLiftTabLog2, (float)(1 << kLiftTabLog2), v[qq]);
+      const f32x4* src = reinterpret_cast<const f32x4*>(tab + (size_t)idx * kLiftTabStride + 4 * g);
+#pragma unroll
+      for (int k = kLiftTabCoefs - 1; k >= 0; --k) {
+        c[qq][k][0] = src[k * (kC / 4)];
+        c[qq][k][1] = src[k * (kC / 4) + 4];
+      }
+    }
+#pragma unroll
+    for (int qq = 0; qq < 2; ++qq)
+#pragma unroll
+      for (int ot = 0; ot < 2; ++ot) {
+        f32x4 acc = c[qq][kLiftTabCoefs - 1][ot];
+#pragma unroll
+        for (int k = kLiftTabCoefs - 2; k >= 0; --k)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) acc[r] = __builtin_fmaf(acc[r], v[qq], c[qq][k][ot][r]);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) vv[ot][r][2 * qp + qq] = acc[r];
+      }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // lifting, bf16x6 variant: out[32] = W2 * gelu(W1 * x + b1) + b2, plus the W-direction DFT of out.
 // Layer 1 (Cin <= 32 -> hid) stays on fp32 MFMA (K is tiny); layer 2 (hid -> 32, K = hid) runs on the
 // bf16 matrix pipe.  Hidden tiles are processed in PAIRS: the GELU outputs of tiles (2u, 2u+1) are
@@ -1212,6 +1269,7 @@ struct TrunkParams {
   const float* lift_b1;    // [hid]
   const u32x4* lift_w2b;   // [hid/32][3][2][64]
   const float* lift_b2;    // [32]
+  const float* lift_tab;   // one input channel: the lifting MLP tabulated (lift_from_table), or null = evaluate it (lift_segment)
   float lift_up, lift_down, proj_up, proj_down;   // f16x3 form: 2^(11+s) of the lifting W2 / projection W1 images and its inverse
   int proj_hid, proj_co, cout;   // projection width (<= 256), outputs the FMA layer 2 is built for (1, 2, 4), real outputs
   const u32x4* proj_w1b;   // [hid/16][3][64], k order of the resident activation
@@ -1521,13 +1579,44 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
     bias2[1] = *reinterpret_cast<const f32x4*>(p.lift_b2 + 16 + 4 * g);
     lds_barrier();
     if (p.trace && tid == p.trace_tid && n_stamp < 64) p.trace[blockIdx.x * 64 + n_stamp++] = __builtin_amdgcn_s_memrealtime();
-    f32x4 acc2[2][4];
-    lift_segment<4, F16>(xs, l_w1, l_b1, l_w2, npair, lane, bias2, acc2, p.lift_ns, p.lift_cin1 != 0, p.lift_up, p.lift_down);
+    // One input channel and a table from the plan: the wave reads lift(x) from it when EVERY pixel of its row lies inside the
+    // table's domain (one ballot; NaN and +-inf fail the test) and evaluates the MLP as before otherwise -- the decision
+    // depends on the row's own data only, and no load address is formed from an unchecked x.
+    bool from_table = false;
+    f32x4 xp = {0.f, 0.f, 0.f, 0.f};
+#ifndef DLWP_NO_LIFT_TABLE   // A/B switch (tools/ab_build.sh): the kernel without the table path
+    if (p.lift_tab) {
+      // The gather runs in a PERMUTED lane order: lane 4 j' + g' reads what resident lane (j', g') needs, so the four lanes
+      // of a pixel are neighbours and their 16-byte loads cover 64 contiguous bytes of one line (one tag look-up instead of
+      // four: in the resident order every lane of a 16-lane pass touched a line of its own and the phase ran at the L1's
+      // look-up rate, 11 us instead of the 2.6 us its bytes need).  The channel's pixels sit in lane group g = 0.
+      bool inside = true;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        xp[q] = __shfl(xs[0][q], lane >> 2);
+        inside = inside && (fabsf(xp[q]) < (float)kLiftTabRange);
+      }
+      from_table = __all(inside) != 0;
+    }
+#endif
+    if (from_table) {
+      f32x4 vp[2][4];
+      lift_from_table(p.lift_tab, xp, lane & 3, vp);
+#pragma unroll
+      for (int ot = 0; ot < 2; ++ot)   // back to the resident order: lane (j, g) takes its values from lane 4 j + g
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) vv[ot][r][q] = __shfl(vp[ot][r][q], 4 * j + g);
+    } else {
+      f32x4 acc2[2][4];
+      lift_segment<4, F16>(xs, l_w1, l_b1, l_w2, npair, lane, bias2, acc2, p.lift_ns, p.lift_cin1 != 0, p.lift_up, p.lift_down);
+#pragma unroll
+      for (int ot = 0; ot < 2; ++ot)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) vv[ot][r] = f32x4{acc2[ot][0][r], acc2[ot][1][r], acc2[ot][2][r], acc2[ot][3][r]};
+    }
     if (p.trace && tid == p.trace_tid && n_stamp < 64) p.trace[blockIdx.x * 64 + n_stamp++] = __builtin_amdgcn_s_memrealtime();
-#pragma unroll
-    for (int ot = 0; ot < 2; ++ot)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) vv[ot][r] = f32x4{acc2[ot][0][r], acc2[ot][1][r], acc2[ot][2][r], acc2[ot][3][r]};
     lds_barrier();   // every wave is done with the lifting weights: the region turns into transpose tiles
     if (p.trace && tid == p.trace_tid && n_stamp < 64) p.trace[blockIdx.x * 64 + n_stamp++] = __builtin_amdgcn_s_memrealtime();
 #pragma unroll
@@ -2348,6 +2437,7 @@ struct FnoKnobs {
   bool fp32_mfma = false;     // plain fp32-MFMA kernels + unfused spectral path (cross-check form)
   bool feed_regs = true;      // persistent rollout: a step's input / residual stays in registers when it is the previous output (debug: DLWP_FNO_FEED_REGS=0)
   bool f16x3 = false;         // precision_form 2: the fused step kernel takes its big products as f16x3 (common.hpp)
+  bool lift_table = true;     // one input channel: the fused step kernel reads the lifting MLP from a plan-time table (desc.lift_table = 1 or DLWP_FNO_LIFT_TABLE=0: off)
   bool trunk = true;          // fused trunk kernel (DLWP_FNO_TRUNK=0 disables)
   int trunk_rows_forced = 0;  // DLWP_TRUNK_ROWS
   bool step = true;           // whole step in one launch (DLWP_FNO_STEP=0 disables)
@@ -2366,6 +2456,148 @@ static int env_int(const char* name, int dflt) {
   return e ? atoi(e) : dflt;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Table of the one-input-channel lifting MLP (see lift_from_table): builder, host evaluation, guard
+// ---------------------------------------------------------------------------------------------
+namespace {
+constexpr double kLiftTabBound = 1.0 / 4194304.0;   // 2^-22: the operand precision the f16x3 form documents and accepts
+
+struct LiftFn {   // lift(x) and its first two derivatives, fp64 (weights as given, fp32)
+  const float *w1, *b1, *w2, *b2;
+  int hid;
+  mutable std::vector<double> g0, g1, g2;
+  void operator()(double x, double* f, double* d1, double* d2) const {
+    g0.resize(hid); g1.resize(hid); g2.resize(hid);
+    for (int c = 0; c < hid; ++c) {
+      const double w = w1[c], z = w * x + (double)b1[c];
+      const double cdf = 0.5 * std::erfc(-z * 0.70710678118654752440);          // no cancellation in the lower tail
+      const double pdf = 0.39894228040143267794 * std::exp(-0.5 * z * z);
+      g0[c] = z * cdf;                           // gelu
+      g1[c] = (cdf + z * pdf) * w;               // d/dx
+      g2[c] = (2.0 - z * z) * pdf * w * w;       // d2/dx2
+    }
+    for (int o = 0; o < kC; ++o) {
+      const float* wr = w2 + (size_t)o * hid;
+      double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+      for (int c = 0; c < hid; ++c) {
+        const double w = wr[c];
+        s0 += w * g0[c];
+        if (d1) { s1 += w * g1[c]; s2 += w * g2[c]; }
+      }
+      f[o] = (double)b2[o] + s0;
+      if (d1) { d1[o] = s1; d2[o] = s2; }
+    }
+  }
+};
+
+// The table at x, with the device's arithmetic (lift_tab_locate + fp32 fmaf Horner); false outside the domain.
+bool lift_table_eval1(const float* tab, int range, int log2_inv_h, float x, float* out, float* v_out, int* idx_out) {
+  if (!(std::fabs(x) < (float)range)) return false;
+  float v;
+  const int idx = lift_tab_locate(x, range << log2_inv_h, (float)(1 << log2_inv_h), v);
+  const float* c = tab + (size_t)idx * kLiftTabStride;
+  for (int o = 0; o < kC; ++o) {
+    float acc = c[(kLiftTabCoefs - 1) * kC + o];
+    for (int k = kLiftTabCoefs - 2; k >= 0; --k) acc = std::fmaf(acc, v, c[k * kC + o]);
+    out[o] = acc;
+  }
+  if (v_out) *v_out = v;
+  if (idx_out) *idx_out = idx;
+  return true;
+}
+
+// Fills tab [2 range 2^log2_inv_h][6][32] and returns the guard's figure: the largest ||p(x) - lift(x)||_2 / ||lift(x)||_2 over four
+// interior points of every interval and, in the two intervals touching zero, v = 2^-k, k = 1..20 (points whose ||lift|| is
+// below 1e-30 count with their absolute error over the largest ||lift|| seen).  NaN if anything is not finite.
+double lift_table_fill(const LiftFn& fn, int range, int log2_inv_h, float* tab) {
+  const int n_side = range << log2_inv_h, n = 2 * n_side;
+  const double h = std::ldexp(1.0, -log2_inv_h);
+  std::vector<double> F((size_t)(n + 1) * kC), D(F.size()), E(F.size());
+  double fmax = 0.0;
+  for (int k = 0; k <= n; ++k) {
+    double* f = &F[(size_t)k * kC];
+    fn((k - n_side) * h, f, &D[(size_t)k * kC], &E[(size_t)k * kC]);
+    double nn = 0.0;
+    for (int o = 0; o < kC; ++o) nn += f[o] * f[o];
+    fmax = std::fmax(fmax, std::sqrt(nn));
+  }
+  for (int t = 0; t < n; ++t) {
+    // anchor = the end nearer zero; v runs from it towards the far end, so odd derivatives change sign for x < 0
+    const bool neg = t < n_side;
+    const int a = neg ? t + 1 : t, b = neg ? t : t + 1;
+    const double sg = neg ? -h : h;
+    for (int o = 0; o < kC; ++o) {
+      const double f0 = F[(size_t)a * kC + o], d0 = sg * D[(size_t)a * kC + o], e0 = h * h * E[(size_t)a * kC + o];
+      const double f1 = F[(size_t)b * kC + o], d1 = sg * D[(size_t)b * kC + o], e1 = h * h * E[(size_t)b * kC + o];
+      const double c0 = f0, c1 = d0, c2 = 0.5 * e0;
+      const double ra = f1 - c0 - c1 - c2, rb = d1 - c1 - 2.0 * c2, rc = e1 - 2.0 * c2;
+      const double co[kLiftTabCoefs] = {c0, c1, c2, 10.0 * ra - 4.0 * rb + 0.5 * rc, -15.0 * ra + 7.0 * rb - rc,
+                                        6.0 * ra - 3.0 * rb + 0.5 * rc};
+      for (int k = 0; k < kLiftTabCoefs; ++k) tab[((size_t)t * kLiftTabCoefs + k) * kC + o] = (float)co[k];
+    }
+  }
+  double worst = 0.0;
+  bool finite = std::isfinite(fmax);
+  double want[kC];
+  float got[kC];
+  auto probe = [&](float x) {
+    if (!lift_table_eval1(tab, range, log2_inv_h, x, got, nullptr, nullptr)) { finite = false; return; }
+    fn((double)x, want, nullptr, nullptr);
+    double en = 0.0, fnorm = 0.0;
+    for (int o = 0; o < kC; ++o) {
+      const double e = (double)got[o] - want[o];
+      en += e * e;
+      fnorm += want[o] * want[o];
+    }
+    en = std::sqrt(en); fnorm = std::sqrt(fnorm);
+    const double rel = fnorm < 1e-30 ? (fmax > 0.0 ? en / fmax : en) : en / fnorm;
+    if (!std::isfinite(rel)) finite = false;
+    worst = std::fmax(worst, rel);
+  };
+  for (int t = 0; t < n; ++t) {
+    const bool neg = t < n_side;
+    const double anchor = ((neg ? t + 1 : t) - n_side) * h;
+    for (int m = 0; m < 4; ++m) probe((float)(anchor + (neg ? -h : h) * (2 * m + 1) / 8.0));
+  }
+  for (int k = 1; k <= 20; ++k) {
+    probe((float)std::ldexp(h, -k));
+    probe((float)-std::ldexp(h, -k));
+  }
+  return finite ? worst : std::nan("");
+}
+}  // namespace
+
+extern "C" int32_t dlwp_fno2d_lift_table_build(const float* lift_w1, const float* lift_b1, const float* lift_w2,
+                                               const float* lift_b2, int32_t lifting, int32_t range, int32_t log2_inv_h,
+                                               float* table, size_t table_floats, double* guard_err, int32_t* accepted) {
+  DLWP_REQUIRE(lift_w1 && lift_b1 && lift_w2 && lift_b2 && table, DLWP_ERR_INVALID_ARGUMENT, "null argument");
+  DLWP_REQUIRE(lifting >= 1 && range >= 1 && range <= 1024 && log2_inv_h >= 0 && log2_inv_h <= 8, DLWP_ERR_INVALID_ARGUMENT,
+               "need lifting >= 1, range in [1, 1024], log2_inv_h in [0, 8] (got %d, %d, %d)", lifting, range, log2_inv_h);
+  const size_t need = (size_t)2 * ((size_t)range << log2_inv_h) * kLiftTabStride;
+  DLWP_REQUIRE(table_floats >= need, DLWP_ERR_INVALID_ARGUMENT, "table holds %zu floats, %zu needed", table_floats, need);
+  const LiftFn fn{lift_w1, lift_b1, lift_w2, lift_b2, lifting, {}, {}, {}};
+  const double err = lift_table_fill(fn, range, log2_inv_h, table);
+  if (guard_err) *guard_err = err;
+  if (accepted) *accepted = err <= kLiftTabBound ? 1 : 0;   // NaN fails
+  return DLWP_OK;
+}
+
+extern "C" int32_t dlwp_fno2d_lift_table_eval_host(const float* table, int32_t range, int32_t log2_inv_h, const float* x,
+                                                   int64_t n, float* out, float* v_out, int32_t* interval_out) {
+  DLWP_REQUIRE(table && x && out && n >= 0, DLWP_ERR_INVALID_ARGUMENT, "null argument");
+  DLWP_REQUIRE(range >= 1 && range <= 1024 && log2_inv_h >= 0 && log2_inv_h <= 8, DLWP_ERR_INVALID_ARGUMENT,
+               "need range in [1, 1024], log2_inv_h in [0, 8] (got %d, %d)", range, log2_inv_h);
+  for (int64_t i = 0; i < n; ++i) {
+    float v = std::nanf("");
+    int idx = -1;
+    if (!lift_table_eval1(table, range, log2_inv_h, x[i], out + i * kC, &v, &idx))   // outside the domain: the kernel evaluates the MLP
+      for (int o = 0; o < kC; ++o) out[i * kC + o] = std::nanf("");
+    if (v_out) v_out[i] = v;
+    if (interval_out) interval_out[i] = idx;
+  }
+  return DLWP_OK;
+}
+
 struct dlwp_fno2d_plan {
   FnoKnobs k;
   mutable std::atomic<unsigned> timeouts{0};   // statistics only: fused launches that timed out (re-run or reported)
@@ -2376,6 +2608,9 @@ struct dlwp_fno2d_plan {
   SpectralCore sc;
   DevBuf lift_w1p, lift_b1, lift_w2p, lift_b2, lift_w2b;
   DevBuf lift_w2h, proj_w1hp;      // f16x3 operands of the fused step kernel (precision_form 2)
+  DevBuf lift_tab;                 // fused step kernel, one input channel: table of the lifting MLP (lift_from_table)
+  int lift_tab_state = 0;          // dlwp_fno2d_lift_table_state
+  double lift_tab_err = 0.0;       // the guard's figure for this plan's weights
   int lift_shift = 0, proj_shift = 0;   // the shift s those two matrices were packed with (common.hpp f16x3_weight_shift)
   std::vector<DevBuf> wshp;        // likewise the skip weights, trunk k order
   DevBuf proj_w1p, proj_b1, proj_w2p, proj_b2, proj_w2v, proj_w1b, proj_w1bp;   // w1bp: k order of the trunk's resident activation
@@ -2460,7 +2695,7 @@ static void pack_w2(std::vector<float>& dst, const float* w2, int hid, int cout,
         }
 }
 
-namespace { int fused_resident_per_cu(int G); }
+namespace { int fused_resident_per_cu(int G); bool step_eligible(const dlwp_fno2d_plan* p); }
 
 extern "C" int32_t dlwp_fno2d_plan_create(dlwp_fno2d_plan** out, const dlwp_fno2d_desc* d, void* stream) {
   DLWP_REQUIRE(out && d, DLWP_ERR_INVALID_ARGUMENT, "null plan/desc");
@@ -2494,12 +2729,14 @@ extern "C" int32_t dlwp_fno2d_plan_create(dlwp_fno2d_plan** out, const dlwp_fno2
                d->precision_form);
   DLWP_REQUIRE(d->on_timeout == 0 || d->on_timeout == 1, DLWP_ERR_INVALID_ARGUMENT, "on_timeout %d not in {0, 1}", d->on_timeout);
   DLWP_REQUIRE(d->debug_spin_limit >= 0, DLWP_ERR_INVALID_ARGUMENT, "debug_spin_limit must be >= 0");
+  DLWP_REQUIRE(d->lift_table == 0 || d->lift_table == 1, DLWP_ERR_INVALID_ARGUMENT, "lift_table %d not in {0, 1}", d->lift_table);
   auto* p = new dlwp_fno2d_plan();
   {
     FnoKnobs& k = p->k;
     // descriptor first; the environment only supplies debug defaults, read HERE and never again
     k.fp32_mfma = d->precision_form == 1 || env_int("DLWP_FP32_MFMA", 0) != 0;
     k.feed_regs = env_int("DLWP_FNO_FEED_REGS", 1) != 0;
+    k.lift_table = d->lift_table == 0 && env_int("DLWP_FNO_LIFT_TABLE", 1) != 0;
     k.f16x3 = !k.fp32_mfma && (d->precision_form == 2 || env_int("DLWP_FNO_F16X3", 0) != 0);
     k.trunk = env_int("DLWP_FNO_TRUNK", 1) != 0 && d->launch_form != 3;
     k.trunk_rows_forced = env_int("DLWP_TRUNK_ROWS", 0);
@@ -2656,9 +2893,28 @@ extern "C" int32_t dlwp_fno2d_plan_create(dlwp_fno2d_plan** out, const dlwp_fno2
     p->k.resident_per_cu = fused_resident_per_cu(p->H / 8);
     if (p->k.resident_per_cu == 0) p->k.trunk = false;
   }
+  // One input channel on the fused step kernel: tabulate the lifting MLP (fixed for the life of the plan) and keep the table
+  // only if the guard accepts it for THESE weights; otherwise the kernel evaluates the MLP as it does for wider inputs.
+  if (step_eligible(p) && p->cin == 1) {
+    if (!p->k.lift_table) {
+      p->lift_tab_state = 3;
+    } else {
+      std::vector<float> tab((size_t)2 * (kLiftTabRange << kLiftTabLog2) * kLiftTabStride);
+      const LiftFn fn{d->lift_w1, d->lift_b1, d->lift_w2, d->lift_b2, p->hid_l, {}, {}, {}};
+      p->lift_tab_err = lift_table_fill(fn, kLiftTabRange, kLiftTabLog2, tab.data());
+      p->lift_tab_state = p->lift_tab_err <= kLiftTabBound ? 1 : 2;
+      if (p->lift_tab_state == 1) {
+        hipError_t te = p->lift_tab.upload(tab.data(), tab.size() * 4, s);
+        if (te == hipSuccess) te = hipStreamSynchronize(s);
+        if (te != hipSuccess) { delete p; return fail(DLWP_ERR_HIP, "plan upload failed: %s", hipGetErrorString(te)); }
+      }
+    }
+  }
   *out = p;
   return DLWP_OK;
 }
+
+extern "C" int32_t dlwp_fno2d_lift_table_state(const dlwp_fno2d_plan* plan) { return plan ? plan->lift_tab_state : 0; }
 
 extern "C" uint32_t dlwp_fno2d_timeouts(const dlwp_fno2d_plan* plan) { return plan ? plan->timeouts.load() : 0u; }
 extern "C" uint32_t dlwp_fno2d_range_reruns(const dlwp_fno2d_plan* plan) { return plan ? plan->range_reruns.load() : 0u; }
@@ -2939,6 +3195,7 @@ int32_t launch_trunk(const dlwp_fno2d_plan* p, const FnoWorkspace& ws, int B, co
 #endif
       tp.lift_w1p = p->lift_w1p.as<float>(); tp.lift_b1 = p->lift_b1.as<float>();
       tp.lift_w2b = p->lift_w2b.as<u32x4>(); tp.lift_b2 = p->lift_b2.as<float>();
+      tp.lift_tab = p->lift_tab_state == 1 ? p->lift_tab.as<float>() : nullptr;
       tp.proj_hid = p->hid_p; tp.proj_co = p->proj_co; tp.cout = p->cout;
       if (io->lift_only) { tp.proj_hid = 0; tp.y = hout; }   // diagnostics: the projection stays a launch of its own
       tp.proj_w1b = p->proj_w1bp.as<u32x4>(); tp.proj_b1 = p->proj_b1.as<float>();

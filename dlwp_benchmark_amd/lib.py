@@ -27,7 +27,7 @@ class FNO2dDesc(ctypes.Structure):
         ("spec_w", POINTER(c_void_p)), ("spec_b", c_void_p), ("skip_w", POINTER(c_void_p)),
         ("proj_w1", c_void_p), ("proj_b1", c_void_p), ("proj_w2", c_void_p), ("proj_b2", c_void_p),
         ("precision_form", c_int32), ("launch_form", c_int32), ("on_timeout", c_int32), ("unchecked", c_int32),
-        ("debug_spin_limit", c_int32),
+        ("debug_spin_limit", c_int32), ("lift_table", c_int32),
     ]
 
 
@@ -74,6 +74,11 @@ SIGNATURES = {
     "dlwp_fno2d_status": (c_int32, [c_void_p, c_void_p]),
     "dlwp_fno2d_timeouts": (ctypes.c_uint32, [c_void_p]),
     "dlwp_fno2d_range_reruns": (ctypes.c_uint32, [c_void_p]),
+    "dlwp_fno2d_lift_table_state": (c_int32, [c_void_p]),
+    "dlwp_fno2d_lift_table_build": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p,
+                                              c_size_t, POINTER(ctypes.c_double), c_int32_p]),
+    "dlwp_fno2d_lift_table_eval_host": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, ctypes.c_int64, c_void_p, c_void_p,
+                                                  c_void_p]),
     "dlwp_fno2d_forward_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_size_t, c_void_p]),
     "dlwp_fno2d_rollout_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32,
                                          c_int32, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),

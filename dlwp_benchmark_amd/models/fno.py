@@ -177,10 +177,12 @@ class FNO2DModule(HipBackbone):
         self.launch_form = 0             # 0 fewest launches, 1 one per step, 2 three per step, 3 unfused kernels
         self.on_timeout = "rerun"        # or "raise": DLWP_ERR_TIMEOUT instead of the automatic re-run on the unfused kernels
         self.check = "per_call"          # or "deferred": asynchronous calls, the caller verifies with .check() (see there)
+        self.lift_table = True           # one input channel: the fused step kernel reads the lifting MLP from a plan-time table
         self._debug_spin_limit = 0       # test hook: tiny hand-off spin bound to force the timeout path
 
     def set_execution_form(self, precision_form: Optional[str] = None, launch_form: Optional[int] = None,
-                           on_timeout: Optional[str] = None, check: Optional[str] = None):
+                           on_timeout: Optional[str] = None, check: Optional[str] = None,
+                           lift_table: Optional[bool] = None):
         if precision_form is not None:
             if precision_form not in ("f16x3", "bf16x6", "fp32_mfma"):
                 raise _lib.DlwpError(f"unknown precision_form {precision_form!r}")
@@ -197,6 +199,8 @@ class FNO2DModule(HipBackbone):
             if check not in ("per_call", "deferred"):
                 raise _lib.DlwpError(f"unknown check mode {check!r}")
             self.check = check
+        if lift_table is not None:
+            self.lift_table = bool(lift_table)
         return self
 
     def verify(self):
@@ -216,6 +220,11 @@ class FNO2DModule(HipBackbone):
     def fused_timeouts(self) -> int:
         """fused launches of the current plan whose hand-off spin ran out (re-run on the unfused kernels or raised)"""
         return int(_lib.load().dlwp_fno2d_timeouts(self._plan)) if self._plan is not None else 0
+
+    def lift_table_state(self) -> int:
+        """the current plan's lifting table: 0 not applicable (or no plan yet), 1 in use, 2 rejected by the guard for these
+        weights, 3 switched off (dlwp_fno2d_lift_table_state)"""
+        return int(_lib.load().dlwp_fno2d_lift_table_state(self._plan)) if self._plan is not None else 0
 
     def range_reruns(self) -> int:
         """f16x3 step ranges of the current plan that were repeated on the bf16x6 kernels (non-finite output)"""
@@ -238,7 +247,7 @@ class FNO2DModule(HipBackbone):
 
     def _get_plan(self, h: int, w: int, device):
         key = (h, w, str(device), self._param_key(), self.precision_form, self.launch_form, self.on_timeout,
-               self._debug_spin_limit, self.check)
+               self._debug_spin_limit, self.check, self.lift_table)
         if self._plan is not None and key == self._plan_key:
             return self._plan
         if self._plan is not None and getattr(self, "_plan_check", None) == "deferred":
@@ -297,6 +306,7 @@ class FNO2DModule(HipBackbone):
         d.on_timeout = 1 if self.on_timeout == "raise" else 0
         d.unchecked = 1 if self.check == "deferred" else 0
         d.debug_spin_limit = int(self._debug_spin_limit)
+        d.lift_table = 0 if self.lift_table else 1
         plan = ctypes.c_void_p()
         with torch.cuda.device(device):
             _lib.check(lib.dlwp_fno2d_plan_create(ctypes.byref(plan), ctypes.byref(d), _lib.stream_ptr()),

@@ -103,6 +103,11 @@ typedef struct dlwp_fno2d_desc {
   int32_t unchecked;           /* 0 (default): every call that used fused kernels synchronises `stream` once and reads
                                   their fail word; 1: fully asynchronous calls, the caller polls dlwp_fno2d_status */
   int32_t debug_spin_limit;    /* 0: default bound (~0.1 s); > 0: spin bound of the hand-offs (test hook) */
+  int32_t lift_table;          /* in_channels == 1 on the fused step kernel: 0 (default) the lifting MLP -- a function of one
+                                  scalar per grid point -- is read from a table built when the plan is created (quintic
+                                  Hermite, h = 1/16 over [-32, 32); kept only if a guard finds it within 2^-22 of the fp64
+                                  function for these weights; a row with a value outside the domain is evaluated as before);
+                                  1: off, the MLP is always evaluated.  See dlwp_fno2d_lift_table_state. */
 } dlwp_fno2d_desc;
 
 int32_t dlwp_fno2d_plan_create(dlwp_fno2d_plan** plan, const dlwp_fno2d_desc* desc, void* stream);
@@ -118,6 +123,23 @@ int32_t dlwp_fno2d_status(const dlwp_fno2d_plan* plan, void* stream);
 uint32_t dlwp_fno2d_timeouts(const dlwp_fno2d_plan* plan);
 /* statistics: f16x3 step ranges of this plan (precision_form 2) repeated on the bf16x6 kernels after a non-finite output */
 uint32_t dlwp_fno2d_range_reruns(const dlwp_fno2d_plan* plan);
+
+/* The one-input-channel lifting table of a plan: 0 not applicable (another shape or launch form, more input channels),
+ * 1 in use, 2 rejected by the guard for these weights (the MLP is evaluated), 3 switched off (desc.lift_table = 1 or
+ * DLWP_FNO_LIFT_TABLE=0 in the environment when the plan was created). */
+int32_t dlwp_fno2d_lift_table_state(const dlwp_fno2d_plan* plan);
+/* Host only, no device needed: the builder the plans use.  Fills table [2 * range * 2^log2_inv_h][6][32] (fp32) for
+ * lift(x)[o] = b2[o] + sum_c W2[o][c] gelu(w1[c] x + b1[c]) (weights in the descriptor's layouts, one input channel, 32 outputs)
+ * over [-range, range) with knots at multiples of 2^-log2_inv_h.  *guard_err (may be NULL): the largest relative vector error
+ * the guard found (NaN if anything was not finite); *accepted (may be NULL): 1 if it is <= 2^-22, else 0. */
+int32_t dlwp_fno2d_lift_table_build(const float* lift_w1, const float* lift_b1, const float* lift_w2,
+                                    const float* lift_b2, int32_t lifting, int32_t range, int32_t log2_inv_h,
+                                    float* table, size_t table_floats, double* guard_err, int32_t* accepted);
+/* Host only: evaluates such a table at x[0..n) with the arithmetic of the device (interval and coordinate exact in fp32,
+ * fp32 fmaf Horner).  out [n][32]; v_out [n] (may be NULL) the coordinate in [0, 1) from the interval's end nearer zero;
+ * interval_out [n] (may be NULL) the interval index.  An x outside the domain (|x| >= range, NaN) gives NaN and -1. */
+int32_t dlwp_fno2d_lift_table_eval_host(const float* table, int32_t range, int32_t log2_inv_h, const float* x,
+                                        int64_t n, float* out, float* v_out, int32_t* interval_out);
 
 /* One backbone step WITHOUT the residual: y = fno(x).  Replaces `self.fno(x_t)` at fno.py:103.
  * x_dev [B, in, H, W], y_dev [B, out, H, W], both contiguous fp32. */

@@ -4,7 +4,7 @@
 // the 268 MB of one FourCastNet LayerNorm at 128x256x32); rows here are register resident: 16 / 32 / 64
 // lanes per row with one or more 16-byte vectors each, mean and variance by xor-shuffles inside the
 // lane group, two-pass (mean, then sum of squared deviations) like torch's CPU kernel.
-#include "common.hpp"
+#include "layernorm_row.hpp"
 
 namespace dlwp {
 namespace norm {
@@ -35,31 +35,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     const long long row = r0 + lane / LPR;
     const bool live = row < rows;
     f32x4 xv[NV];
-    float s = 0.f;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-      const int iv = sub + v * LPR;
-      xv[v] = (live && iv < nvec) ? *reinterpret_cast<const f32x4*>(x + row * C + 4 * iv) + pb[v] : f32x4{0.f, 0.f, 0.f, 0.f};
-      s += (xv[v][0] + xv[v][1]) + (xv[v][2] + xv[v][3]);
-    }
-#pragma unroll
-    for (int m = LPR / 2; m >= 1; m >>= 1) s += __shfl_xor(s, m);
-    const float mean = s * inv_c;
-    float q = 0.f;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-      const int iv = sub + v * LPR;
-      if (iv < nvec) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float dlt = xv[v][k] - mean;
-          q = fmaf(dlt, dlt, q);
-        }
-      }
-    }
-#pragma unroll
-    for (int m = LPR / 2; m >= 1; m >>= 1) q += __shfl_xor(q, m);
-    const float rstd = rsqrtf(q * inv_c + eps);
+    float mean, rstd;
+    load_row_stats<LPR, NV>(x, row, live, sub, nvec, C, pb, inv_c, eps, xv, mean, rstd);
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       const int iv = sub + v * LPR;
@@ -102,18 +79,9 @@ static int32_t layernorm_prebias(const float* x, const float* pre, const float* 
   DLWP_REQUIRE(channels % 4 == 0 && channels <= 2048, DLWP_ERR_UNSUPPORTED,
                "channels %d: must be a multiple of 4 and <= 2048", channels);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int nvec = channels / 4;
-  if (nvec <= 16) return norm::launch<16, 1>(x, pre, gamma, beta, y, rows, channels, eps, s, ob16);
-  if (nvec <= 32) return norm::launch<32, 1>(x, pre, gamma, beta, y, rows, channels, eps, s, ob16);
-  const int nv = (nvec + 63) / 64;
-  switch (nv) {
-    case 1: return norm::launch<64, 1>(x, pre, gamma, beta, y, rows, channels, eps, s, ob16);
-    case 2: return norm::launch<64, 2>(x, pre, gamma, beta, y, rows, channels, eps, s, ob16);
-    case 3: return norm::launch<64, 3>(x, pre, gamma, beta, y, rows, channels, eps, s, ob16);
-    case 4: return norm::launch<64, 4>(x, pre, gamma, beta, y, rows, channels, eps, s, ob16);
-    case 5: case 6: return norm::launch<64, 6>(x, pre, gamma, beta, y, rows, channels, eps, s, ob16);
-    default: return norm::launch<64, 8>(x, pre, gamma, beta, y, rows, channels, eps, s, ob16);
-  }
+  return norm::dispatch_row(channels / 4, [&](auto lpr, auto nv) {
+    return norm::launch<decltype(lpr)::value, decltype(nv)::value>(x, pre, gamma, beta, y, rows, channels, eps, s, ob16);
+  });
 }
 
 extern "C" int32_t dlwp_layernorm_prebias_f32(const float* x, const float* pre, const float* gamma, const float* beta,

@@ -158,6 +158,14 @@ SIGNATURES = {
     "dlwp_groupnorm_act_bwd_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "dlwp_groupnorm_act_bwd_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "dlwp_layernorm_bwd_partials": (c_int32, [ctypes.c_int64, c_int32]),
+    "dlwp_layernorm_bwd_workspace_bytes": (c_size_t, [ctypes.c_int64, c_int32]),
+    "dlwp_layernorm_bwd_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                         ctypes.c_int64, c_int32, c_float, c_void_p]),
+    "dlwp_act_f32": (c_int32, [c_void_p, c_void_p, ctypes.c_int64, c_int32, c_void_p]),
+    "dlwp_bias_act_bwd_workspace_bytes": (c_size_t, [ctypes.c_int64, c_int32]),
+    "dlwp_bias_act_bwd_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, ctypes.c_int64, c_int32,
+                                        c_int32, c_void_p]),
     "dlwp_conv2d_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                   c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "dlwp_conv_transpose2d_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,

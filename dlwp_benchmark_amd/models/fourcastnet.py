@@ -72,10 +72,11 @@ class _Block(nn.Module):
         if self.training and torch.is_grad_enabled():
             # training (train.py:263-271): the block as the reference composes it (fourcastnet.py:180-193); the filter runs
             # its HIP kernels forward AND backward inside an autograd Function (training._AfnoFilterFn), so do the MLP's two Linears
-            # (ops.linear_any -> training._LinearFn); LayerNorm / GELU / adds are torch operators
+            # (ops.linear_any -> training._LinearFn, with bias / GELU / the second skip in its forward and backward) and the
+            # LayerNorms (training._LayerNormFn); the first skip is a torch add
             residual = x
             x = self.filter(self.norm1(x)) + residual
-            return x + ops.linear_any(ops.linear_any(self.norm2(x), self.mlp.fc1, act=1), self.mlp.fc2), None
+            return ops.linear_any(ops.linear_any(self.norm2(x), self.mlp.fc1, act=1), self.mlp.fc2, resid=x), None
         if l_cf is None:
             l_cf = ops.layernorm_nhwc_to_nchw(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)
         f_cf = self.filter.filter_cf(l_cf)

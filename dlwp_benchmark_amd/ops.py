@@ -1136,7 +1136,10 @@ def layer_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: f
     would round it the same way itself."""
     _lib.require_cuda_tensor(x, "x")
     from . import training as _T
-    if _T.wants_grad(x, weight, bias, pre_bias):     # training: the pointwise layers are torch operators (training.py)
+    if _T.wants_grad(x, weight, bias, pre_bias):
+        if pre_bias is None and weight is not None and bias is not None and layernorm_backward_supported(x.shape[-1]):
+            return _T.layer_norm(x, weight, bias, eps)           # HIP forward and backward (training._LayerNormFn)
+        # the deferred-bias form is inference only; widths outside the kernels' envelope: the torch operator
         return torch.nn.functional.layer_norm(x if pre_bias is None else x + pre_bias, (x.shape[-1],), weight, bias, eps)
     x = x.contiguous()
     c = x.shape[-1]
@@ -1150,6 +1153,74 @@ def layer_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: f
                                       weight.contiguous().data_ptr(), bias.contiguous().data_ptr(),
                                       y.data_ptr(), rows, c, float(eps), _lib.stream_ptr()), name)
     return y
+
+
+def layernorm_backward_supported(channels: int) -> bool:
+    """True inside the envelope of dlwp_layernorm_bwd_f32 (the forward's: channels % 4 == 0 and <= 2048)."""
+    return int(channels) > 0 and int(channels) % 4 == 0 and int(channels) <= 2048
+
+
+def layernorm_backward(x: torch.Tensor, weight: torch.Tensor, grad_out: torch.Tensor, eps: float = 1e-5, need_x: bool = True,
+                       need_weight: bool = True, need_bias: bool = True):
+    """The gradients of layer_norm on dlwp_layernorm_bwd_f32 from x, gamma and grad_out alone (both contiguous, [..., C];
+    mean and rstd are recomputed): (dx, dgamma, dbeta), None where not wanted.  Runs on the current stream without a host
+    synchronisation; reruns are bitwise identical.  A width or an alignment outside the envelope raises a DlwpError whose
+    status is ERR_UNSUPPORTED."""
+    for t, name in ((x, "x"), (weight, "weight"), (grad_out, "grad_out")):
+        _lib.require_cuda_tensor(t, name)
+    c = x.shape[-1]
+    rows = x.numel() // max(c, 1)
+    if grad_out.shape != x.shape or not x.is_contiguous() or not grad_out.is_contiguous() or weight.numel() != c:
+        raise _lib.DlwpError(f"layernorm_backward: x {tuple(x.shape)} and grad_out {tuple(grad_out.shape)} must be contiguous "
+                             f"and of one shape, weight [{c}]")
+    lib = _lib.load()
+    gm = weight.contiguous()
+    dx = torch.empty_like(x) if need_x else None
+    dw = torch.empty(c, device=x.device, dtype=torch.float32) if need_weight else None
+    db = torch.empty(c, device=x.device, dtype=torch.float32) if need_bias else None
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(x.device):
+        nbytes = max(int(lib.dlwp_layernorm_bwd_workspace_bytes(rows, c)), 16) if (need_weight or need_bias) else 0
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+        _lib.check(lib.dlwp_layernorm_bwd_f32(x.data_ptr(), gm.data_ptr(), grad_out.data_ptr(), ptr(dx), ptr(dw), ptr(db), ptr(ws),
+                                              nbytes, rows, c, float(eps), _lib.stream_ptr()), "dlwp_layernorm_bwd_f32")
+    return dx, dw, db
+
+
+def activation(z: torch.Tensor, act: int) -> torch.Tensor:
+    """act(z) elementwise on dlwp_act_f32 (codes of ACTS): for GELU the arithmetic of the dlwp_linear_f32 epilogue, so the
+    result is bit for bit what linear(..., act=1) stores.  z contiguous with a multiple of 4 values."""
+    _lib.require_cuda_tensor(z, "z")
+    if not z.is_contiguous():
+        raise _lib.DlwpError("activation: z must be contiguous")
+    h = torch.empty_like(z)
+    with torch.cuda.device(z.device):
+        _lib.check(_lib.load().dlwp_act_f32(z.data_ptr(), h.data_ptr(), z.numel(), int(act), _lib.stream_ptr()), "dlwp_act_f32")
+    return h
+
+
+def bias_act_backward(grad_out: torch.Tensor, z: Optional[torch.Tensor], act: int = 0, need_bias: bool = True):
+    """The pointwise part of a Linear's backward on dlwp_bias_act_bwd_f32: (gz, db) with gz = grad_out * act'(z) and
+    db = gz summed over the rows ([N]; None unless need_bias).  grad_out and z contiguous [..., N]; act 0 needs no z and
+    returns grad_out itself as gz.  Runs on the current stream without a host synchronisation; reruns are bitwise
+    identical.  A width or an alignment outside the envelope raises a DlwpError whose status is ERR_UNSUPPORTED."""
+    _lib.require_cuda_tensor(grad_out, "grad_out")
+    _lib.require_cuda_tensor(z, "z")
+    act = int(act)
+    n = grad_out.shape[-1]
+    rows = grad_out.numel() // max(n, 1)
+    if not grad_out.is_contiguous() or (act != 0 and (z is None or z.shape != grad_out.shape or not z.is_contiguous())):
+        raise _lib.DlwpError("bias_act_backward: grad_out and z must be contiguous and of one shape")
+    lib = _lib.load()
+    gz = torch.empty_like(grad_out) if act != 0 else grad_out
+    db = torch.empty(n, device=grad_out.device, dtype=torch.float32) if need_bias else None
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(grad_out.device):
+        nbytes = max(int(lib.dlwp_bias_act_bwd_workspace_bytes(rows, n)), 16) if need_bias else 0
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=grad_out.device) if nbytes else None
+        _lib.check(lib.dlwp_bias_act_bwd_f32(grad_out.data_ptr(), ptr(z) if act != 0 else None, gz.data_ptr() if act != 0 else None,
+                                             ptr(db), ptr(ws), nbytes, rows, n, act, _lib.stream_ptr()), "dlwp_bias_act_bwd_f32")
+    return gz, db
 
 
 @functools.lru_cache(maxsize=None)
@@ -1183,9 +1254,11 @@ class LinearWeights:
         return self._derived[f16].get(source_key(weight), build)
 
 
-def linear_raw(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
-    """x [..., K] @ weight[N, K]^T + bias through dlwp_linear_f32 (fp32-accurate) for a weight that is a plain tensor -- the
-    three GEMMs of a Linear's training step (training._LinearFn); the weight is split on the device per call."""
+def linear_raw(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
+               resid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [..., K] @ weight[N, K]^T + bias + resid through dlwp_linear_f32 (fp32-accurate) for a weight that is a plain tensor --
+    the three GEMMs of a Linear's training step (training._LinearFn); the weight is split on the device per call.  resid
+    (contiguous, shaped like the output) is added in the GEMM's epilogue, as linear() does at inference."""
     _lib.require_cuda_tensor(x, "x")
     _lib.require_cuda_tensor(weight, "weight")
     _lib.require_cuda_tensor(bias, "bias")
@@ -1198,11 +1271,16 @@ def linear_raw(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
     if nbytes == 0:
         raise _lib.DlwpError(f"linear: unsupported shape out={n} in={k} (need in % 32 == 0 and out % 4 == 0)")
     out = torch.empty((*x.shape[:-1], n), device=x.device, dtype=torch.float32)
+    if resid is not None:
+        _lib.require_cuda_tensor(resid, "resid")
+        if resid.shape != out.shape or not resid.is_contiguous():
+            raise _lib.DlwpError("linear: resid must be contiguous and shaped like the output")
     with torch.cuda.device(x.device):
         packed = torch.empty(nbytes // 4, dtype=torch.int32, device=x.device)
         _lib.check(lib.dlwp_linear_pack_f32(weight.data_ptr(), n, k, packed.data_ptr(), _lib.stream_ptr()), "dlwp_linear_pack_f32")
         _lib.check(lib.dlwp_linear_f32(x.data_ptr(), packed.data_ptr(), bias.contiguous().data_ptr() if bias is not None else None,
-                                       None, out.data_ptr(), x.numel() // k, k, n, 0, _lib.stream_ptr()), "dlwp_linear_f32")
+                                       resid.data_ptr() if resid is not None else None, out.data_ptr(), x.numel() // k, k, n, 0,
+                                       _lib.stream_ptr()), "dlwp_linear_f32")
     return out
 
 
@@ -1214,21 +1292,24 @@ def linear(x: torch.Tensor, m: torch.nn.Linear, act: int = 0, resid: Optional[to
     precision "fp32": dlwp_linear_f32, fp32-accurate GEMM on the bf16 matrix pipe (six products of exact three-way splits);
     "bf16": dlwp_linear_bf16, bf16 operands and fp32 accumulation (what autocast(bfloat16) makes of nn.Linear);
     "f16x3": dlwp_linear_f16x3, fp32-GEMM accuracy from exact two-part f16 splits (three products; |x| < 65504).
-    `out` may be `resid` (in-place residual add).  With gradients wanted the torch operators run instead (training.py's
-    convention)."""
+    `out` may be `resid` (in-place residual add).  With gradients wanted the differentiable form runs (training._LinearFn:
+    the same kernels forward, HIP backward; `out`, `precision` and `out_dtype` are inference only), or the torch operators for
+    a shape the GEMM kernel does not take."""
     if precision not in ("fp32", "bf16", "f16x3"):
         raise _lib.DlwpError(f"linear: unknown precision {precision!r}")
     from . import training as _T
     if _T.wants_grad(x, m.weight, m.bias, resid):
         rows = x.numel() // max(x.shape[-1], 1)
-        if x.is_cuda and x.dtype == torch.float32 and _T._LinearFn.supported(rows, m.in_features, m.out_features):
-            y = _T.linear_fn(x, m.weight, m.bias)         # HIP GEMMs forward and backward (training._LinearFn)
-        else:
-            y = torch.nn.functional.linear(x, m.weight, m.bias)
-        if act == 1:
-            y = torch.nn.functional.gelu(y)
-        elif act != 0:
+        if act not in (0, 1):
             raise _lib.DlwpError(f"linear: activation {act} not supported")
+        resid_ok = resid is None or (resid.is_cuda and resid.dtype == torch.float32 and
+                                     tuple(resid.shape) == (*x.shape[:-1], m.out_features))
+        if x.is_cuda and x.dtype == torch.float32 and resid_ok and _T._LinearFn.supported(rows, m.in_features, m.out_features):
+            # HIP GEMMs forward and backward, bias / GELU / residual and their gradients on HIP too (training._LinearFn)
+            return _T.linear_fn(x, m.weight, m.bias, act=act, resid=resid)
+        y = torch.nn.functional.linear(x, m.weight, m.bias)
+        if act == 1:
+            y = _T.activation(y, 1)         # HIP in both directions on a GPU (training._ActFn); the GEMMs stay torch's
         return y if resid is None else y + resid
     x_bf16 = x.dtype == torch.bfloat16
     o_bf16 = out_dtype == torch.bfloat16 or (out is not None and out.dtype == torch.bfloat16)
@@ -1277,14 +1358,16 @@ def linear(x: torch.Tensor, m: torch.nn.Linear, act: int = 0, resid: Optional[to
     return out
 
 
-def linear_any(x: torch.Tensor, m: torch.nn.Linear, act: int = 0) -> torch.Tensor:
-    """act(m(x)) for any Linear: through linear() (HIP kernel; with gradients wanted its differentiable form) on a GPU, the
-    module itself elsewhere (CPU construction / registry tests) or when the kernel does not take the shape."""
+def linear_any(x: torch.Tensor, m: torch.nn.Linear, act: int = 0, resid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """act(m(x)) + resid for any Linear: through linear() (HIP kernel; with gradients wanted its differentiable form) on a
+    GPU, the module itself elsewhere (CPU construction / registry tests) or when the kernel does not take the shape."""
     from . import training as _T
-    if x.is_cuda and x.dtype == torch.float32 and (_T.wants_grad(x, m.weight, m.bias) or linear_supported(m.in_features, m.out_features)):
-        return linear(x, m, act=act)
+    if x.is_cuda and x.dtype == torch.float32 and (_T.wants_grad(x, m.weight, m.bias, resid) or
+                                                   linear_supported(m.in_features, m.out_features)):
+        return linear(x, m, act=act, resid=resid.contiguous() if resid is not None else None)
     y = m(x)
-    return torch.nn.functional.gelu(y) if act == 1 else y
+    y = torch.nn.functional.gelu(y) if act == 1 else y
+    return y if resid is None else y + resid
 
 
 LINEAR_FORMS = ("bf16x6", "f16x3", "bf16", "rocblas")

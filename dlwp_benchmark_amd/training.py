@@ -846,13 +846,123 @@ def groupnorm_act(x, weight, bias, groups: int, eps: float = 1e-5, act: int = 0)
     return _GroupNormActFn.apply(x, weight, bias, int(groups), float(eps), int(act))
 
 
+def layernorm_backward_torch(x, gamma, gy, eps: float):
+    """The backward of y = LayerNorm(x) gamma + beta over the last dimension (reference fourcastnet.py:180-193,
+    swin_transformer.py:213,262, panguweather.py:281,321 under train.py:271) from x and gamma alone, as plain torch operators on
+    any device: what dlwp_layernorm_bwd_f32 computes (csrc/layernorm_bwd.hip), term by term.  x, gy [..., C]; gamma [C].
+
+        mean, rstd: two-pass, biased variance      xh = (x - mean) rstd      g = gy gamma
+        a = mean_C(g)      b = mean_C(g xh)        dx = rstd (g - a - xh b)
+        dgamma_c = sum_rows gy xh                  dbeta_c = sum_rows gy
+
+    Returns (dx, dgamma, dbeta)."""
+    c = x.shape[-1]
+    x2, gy2 = x.reshape(-1, c), gy.reshape(-1, c)
+    mean = x2.mean(dim=1, keepdim=True)
+    rstd = torch.rsqrt(((x2 - mean) ** 2).mean(dim=1, keepdim=True) + eps)
+    xh = (x2 - mean) * rstd
+    g = gy2 * gamma.reshape(1, c)
+    a = g.mean(dim=1, keepdim=True)
+    b = (g * xh).mean(dim=1, keepdim=True)
+    dx = rstd * (g - a - xh * b)
+    return dx.reshape(x.shape), (gy2 * xh).sum(dim=0), gy2.sum(dim=0)
+
+
+class _LayerNormFn(torch.autograd.Function):
+    """y = LayerNorm(x) gamma + beta over the last dimension on HIP in both directions: dlwp_layernorm_prebias_f32 (the
+    inference kernel, y bit for bit) and dlwp_layernorm_bwd_f32.  Saved for the backward: x and gamma -- no statistics, no
+    normalised copy of x (the kernel recomputes mean and rstd with the forward's arithmetic)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps):
+        x = x.contiguous()
+        with torch.no_grad():
+            y = ops.layer_norm(x.detach(), weight.detach(), bias.detach(), eps)
+        ctx.eps = eps
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        """HIP backward; DLWP_ERR_UNSUPPORTED (a tensor that is not 16-byte aligned) and DLWP_TRAIN_TORCH_BACKWARD=1
+        evaluate layernorm_backward_torch; any other error raises."""
+        x, weight = ctx.saved_tensors
+        needs = ctx.needs_input_grad[:3]
+        if not any(needs):
+            return None, None, None, None
+        with torch.no_grad():
+            gy = grad_out.contiguous()
+            grads = None
+            if not _torch_backward_selected():
+                try:
+                    grads = ops.layernorm_backward(x, weight, gy, ctx.eps, *needs)
+                except _lib.DlwpError as e:
+                    if e.status != _lib.ERR_UNSUPPORTED:
+                        raise
+            if grads is None:
+                grads = layernorm_backward_torch(x, weight, gy, ctx.eps)
+        return (*[g if need else None for g, need in zip(grads, needs)], None)
+
+
+def layer_norm(x, weight, bias, eps: float = 1e-5):
+    """differentiable LayerNorm over the last dimension: HIP forward and HIP backward; under DLWP_TRAIN_TORCH_BACKWARD=1 the
+    library's layer_norm, left to autograd"""
+    if _torch_backward_selected():
+        return F.layer_norm(x, (x.shape[-1],), weight, bias, eps)
+    return _LayerNormFn.apply(x, weight, bias, float(eps))
+
+
+def bias_act_backward_torch(gy, z, act: int):
+    """The pointwise part of the backward of y = act(z) + resid, z = x W^T + b, as plain torch operators on any device: what
+    dlwp_bias_act_bwd_f32 computes (csrc/bias_act.hip), term by term.  gy, z [..., N] (z unused for act 0).
+    Returns (gz, db): gz = gy act'(z) in the closed form of _act_grad_torch, db_n = sum_rows gz."""
+    gz = gy * _act_grad_torch(z, int(act)) if int(act) != 0 else gy
+    return gz, gz.reshape(-1, gz.shape[-1]).sum(dim=0)
+
+
+class _ActFn(torch.autograd.Function):
+    """h = act(z) on dlwp_act_f32 forward and dlwp_bias_act_bwd_f32 backward (saved: z): the activation of a Linear whose
+    GEMMs the HIP kernel does not take, so that its GELU is still the one inference evaluates."""
+
+    @staticmethod
+    def forward(ctx, z, act):
+        z = z.contiguous()
+        ctx.act = int(act)
+        ctx.save_for_backward(z)
+        with torch.no_grad():
+            return ops.activation(z.detach(), ctx.act)
+
+    @staticmethod
+    def backward(ctx, gy):
+        z, = ctx.saved_tensors
+        with torch.no_grad():
+            gy = gy.contiguous()
+            try:
+                return ops.bias_act_backward(gy, z, ctx.act, False)[0], None
+            except _lib.DlwpError as e:
+                if e.status != _lib.ERR_UNSUPPORTED:
+                    raise
+            return bias_act_backward_torch(gy, z, ctx.act)[0], None
+
+
+def activation(z, act: int):
+    """differentiable act(z) for a fp32 GPU tensor of a multiple of 4 values: HIP forward and HIP backward; anything else,
+    and everything under DLWP_TRAIN_TORCH_BACKWARD=1, the library's activation, left to autograd"""
+    if _torch_backward_selected() or not z.is_cuda or z.dtype != torch.float32 or z.numel() % 4 or z.numel() == 0:
+        return _ACT_FNS[int(act)](z)
+    return _ActFn.apply(z, int(act))
+
+
 class _LinearFn(torch.autograd.Function):
-    """y = x W^T + b with the HIP Linear kernel in BOTH directions (reference backward: scripts/train.py:271 through the
-    nn.Linear layers of swin_transformer.py:21-39, :107-120 and panguweather.py:176-211): the fp32-accurate GEMM of
-    csrc/linear.hip (bf16x6) computes the output, the input gradient dX = dY W (the same kernel on the transposed weight) and
-    the weight gradient dW = dY^T X (the same kernel with dY^T as the activation and X^T as the "weight"; the reduction runs
-    over the tokens).  The bias gradient is a column sum.  Shapes the kernel does not take (in / out features not multiples
-    of 32 / 4 in the roles they play in the three products) use the torch operator."""
+    """y = act(x W^T + b) + resid with the HIP Linear kernel in BOTH directions (reference backward: scripts/train.py:271
+    through the nn.Linear layers of swin_transformer.py:21-39, :107-120 and panguweather.py:176-211): the fp32-accurate GEMM of
+    csrc/linear.hip (bf16x6) computes the output, the input gradient dX = dZ W (the same kernel on the transposed weight) and
+    the weight gradient dW = dZ^T X (the same kernel with dZ^T as the activation and X^T as the "weight"; the reduction runs
+    over the tokens).  Without an activation the bias and the residual ride in the GEMM epilogue, one launch, bit-equal to
+    inference; with one the GEMM stores z = x W^T + b, which the backward needs, and dlwp_act_f32 applies the epilogue's own
+    activation to it (saved: x, W and z).  The backward first takes dZ = dY act'(z) and the bias gradient, the column sum of
+    dZ, in one pass (dlwp_bias_act_bwd_f32); the gradient of resid is dY itself.  Shapes the kernel does not take (in / out
+    features not multiples of 32 / 4 in the roles they play in the three products) use the torch operator."""
 
     @staticmethod
     def supported(rows: int, k: int, n: int) -> bool:
@@ -860,31 +970,46 @@ class _LinearFn(torch.autograd.Function):
                 not _torch_backward_selected())
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
-        ctx.save_for_backward(x, weight)
-        ctx.has_bias = bias is not None
+    def forward(ctx, x, weight, bias, act=0, resid=None):
+        d = lambda t: t.detach() if t is not None else None
+        ctx.has_bias, ctx.act = bias is not None, int(act)
         with torch.no_grad():
-            return ops.linear_raw(x.detach(), weight.detach(), bias.detach() if bias is not None else None)
+            if ctx.act == 0:
+                ctx.save_for_backward(x, weight)
+                return ops.linear_raw(d(x), d(weight), d(bias), resid=d(resid).contiguous() if resid is not None else None)
+            z = ops.linear_raw(d(x), d(weight), d(bias))
+            ctx.save_for_backward(x, weight, z)
+            y = ops.activation(z, ctx.act)
+            return y if resid is None else y.add_(d(resid))
 
     @staticmethod
     def backward(ctx, gy):
-        x, weight = ctx.saved_tensors
+        x, weight, *z = ctx.saved_tensors
         n, k = weight.shape
         gy2 = gy.reshape(-1, n).contiguous()
         x2 = x.reshape(-1, k)
         gx = gw = gb = None
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
         with torch.no_grad():
+            gz = gy2
+            if ctx.act != 0 or need_b:
+                z2 = z[0].reshape(-1, n) if z else None
+                try:
+                    gz, gb = ops.bias_act_backward(gy2, z2, ctx.act, need_b)
+                except _lib.DlwpError as e:
+                    if e.status != _lib.ERR_UNSUPPORTED:      # a grad_out that is not 16-byte aligned: the torch form
+                        raise
+                    gz, gb = bias_act_backward_torch(gy2, z2, ctx.act)
+                    gb = gb if need_b else None
             if ctx.needs_input_grad[0]:
-                gx = ops.linear_raw(gy2, weight.t().contiguous(), None).view(x.shape)          # [M, N] x [K, N]^T
+                gx = ops.linear_raw(gz, weight.t().contiguous(), None).view(x.shape)          # [M, N] x [K, N]^T
             if ctx.needs_input_grad[1]:
-                gw = ops.linear_raw(gy2.t().contiguous(), x2.t().contiguous(), None)             # [N, M] x [K, M]^T -> [N, K]
-            if ctx.has_bias and ctx.needs_input_grad[2]:
-                gb = gy2.sum(dim=0)
-        return gx, gw, gb
+                gw = ops.linear_raw(gz.t().contiguous(), x2.t().contiguous(), None)             # [N, M] x [K, M]^T -> [N, K]
+        return gx, gw, gb, None, gy if ctx.needs_input_grad[4] else None
 
 
-def linear_fn(x, weight, bias):
-    return _LinearFn.apply(x, weight, bias)
+def linear_fn(x, weight, bias, act: int = 0, resid=None):
+    return _LinearFn.apply(x, weight, bias, int(act), resid)
 
 
 def wants_grad(*tensors) -> bool:

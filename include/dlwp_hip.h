@@ -639,6 +639,41 @@ int32_t dlwp_layernorm_prebias_bf16out(const float* x_dev, const float* pre_bias
                                        const float* beta_dev, void* y_bf16_dev, int64_t rows, int32_t channels, float eps,
                                        void* stream);
 
+/* LayerNorm for training (csrc/layernorm_bwd.hip): the `loss.backward()` of scripts/train.py:271 through the nn.LayerNorm
+ * layers above (fourcastnet.py:180-193, swin_transformer.py:213,262, panguweather.py:281,321).  For y = LayerNorm(x) gamma + beta
+ * over the last dimension, x_dev and gy_dev [rows, channels], with xh = (x - mean) rstd and g = gy gamma:
+ *   dx = rstd (g - mean_C(g) - xh mean_C(g xh)),  dgamma_c = sum_rows gy xh,  dbeta_c = sum_rows gy.
+ * mean and rstd are recomputed from x with the forward's own arithmetic: a training step keeps x and gamma only, and one
+ * pass reads x and gy once and writes dx once.  dx_dev, dgamma_dev, dbeta_dev may each be NULL (not wanted, not computed;
+ * without dgamma / dbeta there is one launch and no workspace).  The row sums run in a fixed order with one writer per
+ * element (no atomics): reruns are bitwise identical.  The envelope is the forward's (channels % 4 == 0, <= 2048, 64-bit row
+ * offsets) with x_dev, gamma_dev, gy_dev, dx_dev and workspace_dev 16-byte aligned; anything else returns
+ * DLWP_ERR_UNSUPPORTED before any launch, a smaller workspace DLWP_ERR_WORKSPACE.  No pre_bias form (inference only).
+ *   dlwp_layernorm_bwd_partials: the number of partial sums per channel the first launch leaves for the fixed-order sum
+ *     (one launch up to 32 partials, two above), a function of (rows, channels) alone, at most 2048 (0 outside the envelope).
+ *   dlwp_layernorm_bwd_workspace_bytes: 2 * (partials + 32 above 32 partials) * channels floats, at most 4.5 MB (0 outside the
+ *     envelope). */
+int32_t dlwp_layernorm_bwd_partials(int64_t rows, int32_t channels);
+size_t dlwp_layernorm_bwd_workspace_bytes(int64_t rows, int32_t channels);
+int32_t dlwp_layernorm_bwd_f32(const float* x_dev, const float* gamma_dev, const float* gy_dev, float* dx_dev, float* dgamma_dev,
+                               float* dbeta_dev, void* workspace_dev, size_t workspace_bytes, int64_t rows, int32_t channels,
+                               float eps, void* stream);
+
+/* The pointwise part of a Linear's training step (csrc/bias_act.hip): bias, activation and their gradients around the GEMMs of
+ * dlwp_linear_f32, for the nn.Linear layers of swin_transformer.py:21-39, :107-120, panguweather.py:176-211 and
+ * fourcastnet.py:40-53 under scripts/train.py:271.  Activation codes as for the convolutions (0 none, 1 exact-erf GELU,
+ * 2 tanh, 3 ReLU, 4 SiLU); sizes multiples of 4 and 16-byte aligned tensors, otherwise DLWP_ERR_UNSUPPORTED.
+ *   dlwp_act_f32: h = act(z) over n values, with the arithmetic of the dlwp_linear_f32 epilogue (h is bit for bit what the
+ *     fused inference call stores).
+ *   dlwp_bias_act_bwd_f32: gz = gy act'(z) and db_n = sum_rows gz in one pass over gy_dev, z_dev [rows, n].  act == 0 reads
+ *     neither z_dev nor gz_dev (both may be NULL) and only sums; gz_dev may be gy_dev; db_dev may be NULL (then no
+ *     workspace).  The column sum has a fixed order and one writer: reruns are bitwise identical.
+ *   dlwp_bias_act_bwd_workspace_bytes: the partial column sums (at most 272 * n floats; 0 for a size outside the envelope). */
+int32_t dlwp_act_f32(const float* z_dev, float* h_dev, int64_t n, int32_t act, void* stream);
+size_t dlwp_bias_act_bwd_workspace_bytes(int64_t rows, int32_t n);
+int32_t dlwp_bias_act_bwd_f32(const float* gy_dev, const float* z_dev, float* gz_dev, float* db_dev, void* workspace_dev,
+                              size_t workspace_bytes, int64_t rows, int32_t n, int32_t act, void* stream);
+
 /* FourCastNet block glue fused with the layout change the FFT needs (models/fourcastnet/fourcastnet.py
  * :180-193 around AFNO2D :78-127).  x is token-major [B, tokens, C] ("NHWC"), y / f / l channel-major
  * [B, C, tokens] ("NCHW"); C % 4 == 0, C <= 256.

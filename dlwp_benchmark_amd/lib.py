@@ -319,6 +319,60 @@ def stream_ptr():
     return c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+_CTYPES_VALUE = (ctypes._SimpleCData, ctypes.Array, ctypes._Pointer, type(ctypes.byref(ctypes.c_int())))
+
+
+def marshal(args):
+    """The C arguments of a call from its Python ones: a tensor gives its data_ptr(), None stays None (a null pointer), a
+    ctypes.Structure goes by reference, numbers and ctypes values stay as they are.  Layout is the caller's business: nothing
+    here makes a tensor contiguous or checks that it is (some callers pass strided blocks with their leading dimension)."""
+    import torch
+
+    Tensor, Parameter = torch.Tensor, torch.nn.Parameter
+    out = []
+    for a in args:
+        t = type(a)
+        if t is int or a is None or t is float or t is bool:           # exact types first: this loop runs at every launch
+            out.append(a)
+        elif t is Tensor or t is Parameter or isinstance(a, Tensor):
+            out.append(a.data_ptr())
+        elif isinstance(a, ctypes.Structure):
+            out.append(ctypes.byref(a))
+        elif isinstance(a, (int, float)) or isinstance(a, _CTYPES_VALUE):
+            out.append(a)
+        else:
+            raise DlwpError(f"argument {len(out)} of a library call is a {type(a).__name__}: "
+                            "a tensor, None, a ctypes structure or value, or a number is needed")
+    return out
+
+
+def workspace(nbytes: int, device):
+    """A uint8 workspace tensor of `nbytes` on `device` from torch's caching allocator, or None for 0 bytes (a null workspace
+    means something to several entry points; a wrapper that needs a floor asks for max(n, FLOOR))."""
+    import torch
+
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=device) if nbytes else None
+
+
+def launch(name: str, device, *args, accept=()):
+    """The one way Python reaches an entry point whose last parameter is the stream: calls `name` with marshal(args) and
+    the current stream of `device`, with `device` current (the guard is entered only when it is not).  Returns the status;
+    one that is neither 0 nor in `accept` raises DlwpError labelled with `name`.  The entry point is looked up on the library
+    object at every call, which is where KernelTimer puts its wrappers."""
+    import torch
+
+    fn = getattr(load(), name)
+    argv = marshal(args)
+    if getattr(device, "index", None) == torch.cuda.current_device():      # the usual case: no guard to pay for
+        rc = fn(*argv, torch.cuda.current_stream().cuda_stream)
+    else:
+        with torch.cuda.device(device):
+            rc = fn(*argv, torch.cuda.current_stream().cuda_stream)
+    if rc != 0 and rc not in accept:
+        check(rc, name)
+    return rc
+
+
 class KernelTimer:
     """Measurement aid (bench.py): brackets every call of the chosen C-ABI entry points with HIP events on the stream
     the call launches on (torch's current stream = the `stream` argument every wrapper passes) and sums the elapsed

@@ -59,12 +59,8 @@ class RolloutMetrics:
             if tuple(into.shape) != (4, k, c) or into.dtype != torch.float64 or not into.is_contiguous() or into.device != dev:
                 raise _lib.DlwpError(f"running sums must be a contiguous double [4, {k}, {c}] tensor on {dev}")
         sums = into if into is not None else torch.empty(4, k, c, dtype=torch.float64, device=dev)
-        lib = _lib.load()
-        fn = lib.dlwp_weighted_error_sums_acc_f32 if into is not None else lib.dlwp_weighted_error_sums_f32
-        with torch.cuda.device(dev):
-            _lib.check(fn(out.data_ptr(), target.data_ptr(), clim.data_ptr() if clim is not None else None, latw.data_ptr(),
-                          std.data_ptr() if std is not None else None, sums.data_ptr(), b, k, c, h, w, _lib.stream_ptr()),
-                       "dlwp_weighted_error_sums_f32")
+        _lib.launch("dlwp_weighted_error_sums_acc_f32" if into is not None else "dlwp_weighted_error_sums_f32", dev, out, target,
+                    clim, latw, std, sums, b, k, c, h, w)
         return sums
 
     def __call__(self, out: torch.Tensor, target: torch.Tensor, world_size: int = 1):
@@ -165,11 +161,8 @@ class ZonalSpectrumMetrics:
         circ = self._on(dev)
         ws = self._workspace(dev, (b, k, c, h, w))
         sums = into if into is not None else torch.empty(2, k, c, nb, dtype=torch.float64, device=dev)
-        lib = _lib.load()
-        fn = lib.dlwp_zonal_power_sums_acc_f32 if into is not None else lib.dlwp_zonal_power_sums_f32
-        with torch.cuda.device(dev):
-            _lib.check(fn(out.data_ptr(), target.data_ptr(), circ.data_ptr(), sums.data_ptr(), b, k, c, h, w, ws.data_ptr(),
-                          ws.numel(), _lib.stream_ptr()), "dlwp_zonal_power_sums_f32")
+        _lib.launch("dlwp_zonal_power_sums_acc_f32" if into is not None else "dlwp_zonal_power_sums_f32", dev, out, target, circ,
+                    sums, b, k, c, h, w, ws, ws.numel())
         return sums
 
     def __call__(self, out: torch.Tensor, target: torch.Tensor, world_size: int = 1):

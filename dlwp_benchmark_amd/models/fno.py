@@ -213,8 +213,7 @@ class FNO2DModule(HipBackbone):
         cannot synchronise a capturing stream, so replays of a captured rollout are verified here, whatever `check` says.
         With the default `check="per_call"` outside graphs every call verifies (and repairs) itself and this passes."""
         if self._plan is not None:
-            with torch.cuda.device(next(self.parameters()).device):
-                _lib.check(_lib.load().dlwp_fno2d_status(self._plan, _lib.stream_ptr()), "dlwp_fno2d_status")
+            _lib.launch("dlwp_fno2d_status", next(self.parameters()).device, self._plan)
         return self
 
     def fused_timeouts(self) -> int:
@@ -255,7 +254,6 @@ class FNO2DModule(HipBackbone):
             # verified now (raises DLWP_ERR_TIMEOUT / DLWP_ERR_RANGE here), before a rebuild would drop them
             self.verify()
         self._destroy_plan()
-        lib = _lib.load()
         f = self.fno
         host = lambda t: t.detach().to("cpu", torch.float32).contiguous()
         keep = []  # keep host tensors alive across the call
@@ -308,9 +306,7 @@ class FNO2DModule(HipBackbone):
         d.debug_spin_limit = int(self._debug_spin_limit)
         d.lift_table = 0 if self.lift_table else 1
         plan = ctypes.c_void_p()
-        with torch.cuda.device(device):
-            _lib.check(lib.dlwp_fno2d_plan_create(ctypes.byref(plan), ctypes.byref(d), _lib.stream_ptr()),
-                       "dlwp_fno2d_plan_create")
+        _lib.launch("dlwp_fno2d_plan_create", device, ctypes.byref(plan), d)
         self._plan, self._plan_key, self._plan_check = plan, key, self.check
         return plan
 
@@ -323,14 +319,11 @@ class FNO2DModule(HipBackbone):
         b, c, h, w = x_t.shape
         if c != self.in_channels:
             raise _lib.DlwpError(f"x_t has {c} channels, model expects {self.in_channels}")
-        lib = _lib.load()
         plan = self._get_plan(h, w, x_t.device)
         y = torch.empty(b, self.prognostic_channels, h, w, device=x_t.device, dtype=torch.float32)
-        nbytes = lib.dlwp_fno2d_workspace_bytes(plan, b)
+        nbytes = _lib.load().dlwp_fno2d_workspace_bytes(plan, b)
         ws = self._workspace(nbytes, x_t.device)
-        with torch.cuda.device(x_t.device):
-            _lib.check(lib.dlwp_fno2d_forward_f32(plan, x_t.data_ptr(), y.data_ptr(), b, ws.data_ptr(), nbytes,
-                                                  _lib.stream_ptr()), "dlwp_fno2d_forward_f32")
+        _lib.launch("dlwp_fno2d_forward_f32", x_t.device, plan, x_t, y, b, ws, nbytes)
         return y
 
     def rollout_into(self, out: torch.Tensor, constants, prescribed, prognostic, step_begin: int = 0,
@@ -345,7 +338,7 @@ class FNO2DModule(HipBackbone):
         plan = self._get_plan(h, w, prognostic.device)
         nbytes = lib.dlwp_fno2d_workspace_bytes(plan, b)
         ws = self._workspace(nbytes, prognostic.device)
-        with torch.cuda.device(prognostic.device):
+        with torch.cuda.device(prognostic.device):      # spelled out: the stream is not this entry point's last parameter
             _lib.check(lib.dlwp_fno2d_rollout_range_f32(
                 plan, constants.data_ptr() if constants is not None else None, cc,
                 prescribed.data_ptr() if prescribed is not None else None, cp,

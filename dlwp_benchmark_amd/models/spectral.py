@@ -46,14 +46,11 @@ class SpectralConv2d(nn.Module):
         if self._plan is not None and key == self._plan_key:
             return self._plan
         self._destroy_plan()
-        lib = _lib.load()
         w1 = self.weights1.detach().to("cpu", torch.float32).contiguous()
         w2 = self.weights2.detach().to("cpu", torch.float32).contiguous()
         plan = ctypes.c_void_p()
-        with torch.cuda.device(device):
-            _lib.check(lib.dlwp_spectral_conv2d_plan_create(
-                ctypes.byref(plan), self.in_channels, self.out_channels, h, w, self.modes1, self.modes2,
-                w1.data_ptr(), w2.data_ptr(), _lib.stream_ptr()), "dlwp_spectral_conv2d_plan_create")
+        _lib.launch("dlwp_spectral_conv2d_plan_create", device, ctypes.byref(plan), self.in_channels, self.out_channels, h, w,
+                    self.modes1, self.modes2, w1, w2)
         self._plan, self._plan_key = plan, key
         return plan
 
@@ -82,13 +79,10 @@ class SpectralConv2d(nn.Module):
         b, c, h, w = x.shape
         if c != self.in_channels:
             raise _lib.DlwpError(f"x has {c} channels, layer expects {self.in_channels}")
-        lib = _lib.load()
         plan = self._get_plan(h, w, x.device)
-        nbytes = lib.dlwp_spectral_conv2d_workspace_bytes(plan, b)
+        nbytes = _lib.load().dlwp_spectral_conv2d_workspace_bytes(plan, b)
         if self._ws is None or self._ws.numel() < nbytes or self._ws.device != x.device:
             self._ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=x.device)
         y = torch.empty(b, self.out_channels, h, w, device=x.device, dtype=torch.float32)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.dlwp_spectral_conv2d_f32(plan, x.data_ptr(), y.data_ptr(), b, self._ws.data_ptr(), nbytes,
-                                                    _lib.stream_ptr()), "dlwp_spectral_conv2d_f32")
+        _lib.launch("dlwp_spectral_conv2d_f32", x.device, plan, x, y, b, self._ws, nbytes)
         return y

@@ -1,6 +1,7 @@
 """Thin Python wrappers over the C ABI (include/dlwp_hip.h) for ops used by several backbones.
-Every wrapper takes CUDA tensors, passes raw pointers + the current HIP stream, and raises
-`DlwpError` on a non-zero status.  No wrapper has a CPU path."""
+Every wrapper takes CUDA tensors, validates them, and reaches a stream-taking entry point only through `lib.launch`,
+which owns the device guard, the stream, pointer marshalling and the status check (`DlwpError` on a non-zero status).
+No wrapper has a CPU path."""
 import ctypes
 import functools
 from dataclasses import dataclass
@@ -14,6 +15,10 @@ from .derived import Derived, bump_pack_epoch, derived_for, live_holders, pack_e
 # training (as _T) inside the function, where a gradient may be wanted
 
 BIG = 1 << 30
+
+
+def _contig(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    return None if t is None else t.contiguous()
 
 
 @dataclass
@@ -79,23 +84,19 @@ def window_attention(qkv: torch.Tensor, qkv_bias: Optional[torch.Tensor], table:
     lib = _lib.load()
     d = spec.to_c()
     d.form = forms[precision]
-    with torch.cuda.device(qkv.device):
-        bf16 = precision == "bf16"
-        fn = lib.dlwp_window_attn_bf16 if bf16 else lib.dlwp_window_attn_f32
-        # the caller (torch's caching allocator) owns the workspace of the fast path; 0 bytes = generic kernel
-        nbytes = int(lib.dlwp_window_attn_workspace_bytes(ctypes.byref(d), b, 1 if bf16 else 0))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=qkv.device) if nbytes else None
-        _lib.check(fn(ctypes.byref(d), qkv.data_ptr(),
-                      qkv_bias.contiguous().data_ptr() if qkv_bias is not None else None,
-                      table.data_ptr(), out.data_ptr(), b, ws.data_ptr() if ws is not None else None, nbytes,
-                      _lib.stream_ptr()),
-                   "dlwp_window_attn_" + ("bf16" if precision == "bf16" else "f32"))
-        if count_fallbacks:
-            n = ctypes.c_int32(0)
-            if ws is not None:
+    bf16 = precision == "bf16"
+    # the caller (torch's caching allocator) owns the workspace of the fast path; 0 bytes = generic kernel
+    nbytes = int(lib.dlwp_window_attn_workspace_bytes(ctypes.byref(d), b, 1 if bf16 else 0))
+    ws = _lib.workspace(nbytes, qkv.device)
+    _lib.launch("dlwp_window_attn_bf16" if bf16 else "dlwp_window_attn_f32", qkv.device, d, qkv, _contig(qkv_bias), table, out,
+                b, ws, nbytes)
+    if count_fallbacks:
+        n = ctypes.c_int32(0)
+        if ws is not None:
+            with torch.cuda.device(qkv.device):     # spelled out: the stream is not this entry point's last parameter
                 _lib.check(lib.dlwp_window_attn_fallbacks(ctypes.byref(d), b, 1 if bf16 else 0, ws.data_ptr(),
                                                           _lib.stream_ptr(), ctypes.byref(n)), "dlwp_window_attn_fallbacks")
-            return out, int(n.value)
+        return out, int(n.value)
     return out
 
 
@@ -123,17 +124,14 @@ def _window_attention_bf16_io(qkv: torch.Tensor, qkv_bias: Optional[torch.Tensor
         raise _lib.DlwpError(f"qkv shape {tuple(qkv.shape)} does not match grid {tuple(spec.grid)} x 3*{c}")
     bias16 = _bias_bf16(qkv_bias) if qkv_bias is not None else None
     out = torch.empty(b, l, c, device=qkv.device, dtype=torch.bfloat16)
-    lib = _lib.load()
     d = spec.to_c()
     d.form = -1
-    with torch.cuda.device(qkv.device):
-        nbytes = int(lib.dlwp_window_attn_workspace_bytes(ctypes.byref(d), b, 1))
-        ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=qkv.device)
-        rc = lib.dlwp_window_attn_bf16_io(ctypes.byref(d), qkv.data_ptr(), bias16.data_ptr() if bias16 is not None else None,
-                                          table.data_ptr(), out.data_ptr(), b, ws.data_ptr(), nbytes, _lib.stream_ptr())
-    if rc == -2:     # DLWP_ERR_UNSUPPORTED: a descriptor only the generic kernel takes -- the same arithmetic on fp32 tensors
+    nbytes = int(_lib.load().dlwp_window_attn_workspace_bytes(ctypes.byref(d), b, 1))
+    ws = _lib.workspace(max(nbytes, 256), qkv.device)
+    rc = _lib.launch("dlwp_window_attn_bf16_io", qkv.device, d, qkv, bias16, table, out, b, ws, nbytes,
+                     accept=(_lib.ERR_UNSUPPORTED,))
+    if rc == _lib.ERR_UNSUPPORTED:     # a descriptor only the generic kernel takes -- the same arithmetic on fp32 tensors
         return window_attention(qkv.float(), qkv_bias, table, spec, precision="bf16").to(torch.bfloat16)
-    _lib.check(rc, "dlwp_window_attn_bf16_io")
     return out
 
 
@@ -156,16 +154,11 @@ def window_attention_backward(qkv: torch.Tensor, qkv_bias: Optional[torch.Tensor
     gqkv = torch.empty_like(qkv)
     gtab = torch.empty_like(table)
     gbias = torch.empty(3 * c, device=qkv.device, dtype=torch.float32) if (padded and qkv_bias is not None) else None
-    lib = _lib.load()
     d = spec.to_c()
-    with torch.cuda.device(qkv.device):
-        nbytes = int(lib.dlwp_window_attn_bwd_workspace_bytes(ctypes.byref(d), b))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=qkv.device)
-        _lib.check(lib.dlwp_window_attn_bwd_f32(ctypes.byref(d), qkv.data_ptr(),
-                                                qkv_bias.contiguous().data_ptr() if qkv_bias is not None else None,
-                                                table.data_ptr(), grad_out.data_ptr(), gqkv.data_ptr(),
-                                                gbias.data_ptr() if gbias is not None else None, gtab.data_ptr(), b,
-                                                ws.data_ptr(), nbytes, _lib.stream_ptr()), "dlwp_window_attn_bwd_f32")
+    nbytes = int(_lib.load().dlwp_window_attn_bwd_workspace_bytes(ctypes.byref(d), b))
+    ws = _lib.workspace(nbytes, qkv.device)
+    _lib.launch("dlwp_window_attn_bwd_f32", qkv.device, d, qkv, _contig(qkv_bias), table, grad_out, gqkv, gbias, gtab, b, ws,
+                nbytes)
     return gqkv, gbias, gtab
 
 
@@ -208,9 +201,7 @@ class Conv3x3Weights:
             if nbytes == 0:
                 raise _lib.DlwpError(f"conv3x3: unsupported shape cout={cout} cin={cin} for the matrix-pipe forms")
             buf = torch.empty(nbytes // 4, dtype=torch.int32, device=weight.device)
-            with torch.cuda.device(weight.device):
-                _lib.check(lib.dlwp_conv3x3_mfma_pack_f32(weight.detach().contiguous().data_ptr(), cout, cin, buf.data_ptr(),
-                                                          _lib.stream_ptr()), "dlwp_conv3x3_mfma_pack_f32")
+            _lib.launch("dlwp_conv3x3_mfma_pack_f32", weight.device, weight.detach().contiguous(), cout, cin, buf)
             return buf
 
         return self._derived.get(source_key(weight), build)
@@ -238,10 +229,8 @@ class Conv2dWeights:
             if nbytes == 0:
                 raise _lib.DlwpError(f"conv2d: unsupported shape cout={cout} cin={cin} k={k} for the matrix-pipe forms")
             buf = torch.empty(nbytes // 4, dtype=torch.int32, device=weight.device)
-            with torch.cuda.device(weight.device):
-                _lib.check(lib.dlwp_conv2d_mfma_pack_f32(weight.detach().contiguous().data_ptr(), cout, cin, k,
-                                                         int(self._transposed), buf.data_ptr(), _lib.stream_ptr()),
-                           "dlwp_conv2d_mfma_pack_f32")
+            _lib.launch("dlwp_conv2d_mfma_pack_f32", weight.device, weight.detach().contiguous(), cout, cin, k,
+                        int(self._transposed), buf)
             return buf
 
         return self._derived.get(source_key(weight), build)
@@ -277,11 +266,7 @@ def conv3x3_cyl(x0: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Ten
     if tuple(weight.shape[1:]) != (c0 + c1, 3, 3):
         raise _lib.DlwpError(f"weight {tuple(weight.shape)} does not match {c0}+{c1} input channels, 3x3")
     y = torch.empty(b, cout, h, w, device=x0.device, dtype=torch.float32)
-    lib = _lib.load()
-    with torch.cuda.device(x0.device):
-        _lib.check(lib.dlwp_conv3x3_cyl_f32(x0.data_ptr(), c0, x1.data_ptr() if x1 is not None else None, c1,
-                                            weight.data_ptr(), bias.contiguous().data_ptr() if bias is not None else None,
-                                            y.data_ptr(), b, h, w, cout, act, _lib.stream_ptr()), "dlwp_conv3x3_cyl_f32")
+    _lib.launch("dlwp_conv3x3_cyl_f32", x0.device, x0, c0, x1, c1, weight, _contig(bias), y, b, h, w, cout, act)
     return y
 
 
@@ -308,12 +293,7 @@ def conv3x3_hpx(x0: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Ten
         raise _lib.DlwpError(f"weight {tuple(weight.shape)} does not match {c0}+{c1} input channels, 3x3")
     table = _hpx.device_table(h, w, 1, x0.device)
     y = torch.empty(n, cout, h, w, device=x0.device, dtype=torch.float32)
-    lib = _lib.load()
-    with torch.cuda.device(x0.device):
-        _lib.check(lib.dlwp_conv3x3_hpx_f32(x0.data_ptr(), c0, x1.data_ptr() if x1 is not None else None, c1,
-                                            weight.data_ptr(), bias.contiguous().data_ptr() if bias is not None else None,
-                                            y.data_ptr(), n, h, w, cout, act, table.data_ptr(), _lib.stream_ptr()),
-                   "dlwp_conv3x3_hpx_f32")
+    _lib.launch("dlwp_conv3x3_hpx_f32", x0.device, x0, c0, x1, c1, weight, _contig(bias), y, n, h, w, cout, act, table)
     return y
 
 
@@ -349,22 +329,13 @@ def conv3x3(x0: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]
             raise _lib.DlwpError(f"leading dimension {n} is not (batch * 12 faces)")
         table = _hpx.device_table(h, w, 1, x0.device)
     y = torch.empty(n, cout, h, w, device=x0.device, dtype=torch.float32)
-    lib = _lib.load()
     if form != "direct":
         packed = conv3x3_weights(owner).get(owner)
-        with torch.cuda.device(x0.device):
-            _lib.check(lib.dlwp_conv3x3_mfma_f32(x0.data_ptr(), c0, x1.data_ptr() if x1 is not None else None, c1,
-                                                 packed.data_ptr(), bias.contiguous().data_ptr() if bias is not None else None,
-                                                 resid.data_ptr() if resid is not None else None, y.data_ptr(), n, h, w, cout,
-                                                 int(pre_act), int(act), table.data_ptr() if table is not None else None,
-                                                 CONV_FORMS.index(form) - 1, _lib.stream_ptr()), "dlwp_conv3x3_mfma_f32")
+        _lib.launch("dlwp_conv3x3_mfma_f32", x0.device, x0, c0, x1, c1, packed, _contig(bias), resid, y, n, h, w, cout,
+                    int(pre_act), int(act), table, CONV_FORMS.index(form) - 1)
         return y
-    with torch.cuda.device(x0.device):
-        _lib.check(lib.dlwp_conv3x3_ex_f32(x0.data_ptr(), c0, x1.data_ptr() if x1 is not None else None, c1, weight.data_ptr(),
-                                           bias.contiguous().data_ptr() if bias is not None else None,
-                                           resid.data_ptr() if resid is not None else None, y.data_ptr(), n, h, w, cout,
-                                           int(pre_act), int(act), table.data_ptr() if table is not None else None,
-                                           _lib.stream_ptr()), "dlwp_conv3x3_ex_f32")
+    _lib.launch("dlwp_conv3x3_ex_f32", x0.device, x0, c0, x1, c1, weight, _contig(bias), resid, y, n, h, w, cout, int(pre_act),
+                int(act), table)
     return y
 
 
@@ -379,12 +350,8 @@ def groupnorm_act(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optiona
     n, c = x.shape[0], x.shape[1]
     hw = x.numel() // (n * c)
     y = torch.empty_like(x)
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        _lib.check(lib.dlwp_groupnorm_act_f32(x.data_ptr(), weight.contiguous().data_ptr() if weight is not None else None,
-                                              bias.contiguous().data_ptr() if bias is not None else None, y.data_ptr(), n, c,
-                                              hw, int(groups), float(eps), int(act), _lib.stream_ptr()),
-                   "dlwp_groupnorm_act_f32")
+    _lib.launch("dlwp_groupnorm_act_f32", x.device, x, _contig(weight), _contig(bias), y, n, c, hw, int(groups), float(eps),
+                int(act))
     return y
 
 
@@ -398,12 +365,8 @@ def groupnorm_act_fwd_stats(x: torch.Tensor, weight: Optional[torch.Tensor], bia
     hw = x.numel() // (n * c)
     y = torch.empty_like(x)
     stats = torch.empty(n, max(int(groups), 1), 2, device=x.device, dtype=torch.float32)
-    gm = weight.contiguous() if weight is not None else None
-    bt = bias.contiguous() if bias is not None else None
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().dlwp_groupnorm_act_fwd_stats_f32(
-            x.data_ptr(), gm.data_ptr() if gm is not None else None, bt.data_ptr() if bt is not None else None, y.data_ptr(),
-            stats.data_ptr(), n, c, hw, int(groups), float(eps), int(act), _lib.stream_ptr()), "dlwp_groupnorm_act_fwd_stats_f32")
+    _lib.launch("dlwp_groupnorm_act_fwd_stats_f32", x.device, x, _contig(weight), _contig(bias), y, stats, n, c, hw, int(groups),
+                float(eps), int(act))
     return y, stats
 
 
@@ -422,18 +385,12 @@ def groupnorm_act_backward(x: torch.Tensor, stats: torch.Tensor, weight: Optiona
                              "contiguous and of one shape")
     if int(groups) <= 0 or stats.numel() != 2 * n * int(groups) or not stats.is_contiguous():
         raise _lib.DlwpError(f"groupnorm_act_backward: stats of {stats.numel()} values, 2 * {n} * {groups} needed")
-    lib = _lib.load()
-    gm = weight.contiguous() if weight is not None else None
-    bt = bias.contiguous() if bias is not None else None
     dx = torch.empty_like(x) if need_x else None
     dw = torch.empty(c, device=x.device, dtype=torch.float32) if need_weight else None
     db = torch.empty(c, device=x.device, dtype=torch.float32) if need_bias else None
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    with torch.cuda.device(x.device):
-        ws = torch.empty(max(int(lib.dlwp_groupnorm_act_bwd_workspace_bytes(n, c)), 4), dtype=torch.uint8, device=x.device)
-        _lib.check(lib.dlwp_groupnorm_act_bwd_f32(x.data_ptr(), stats.data_ptr(), ptr(gm), ptr(bt), grad_out.data_ptr(), ptr(dx),
-                                                  ptr(dw), ptr(db), ws.data_ptr(), n, c, hw, int(groups), int(act),
-                                                  _lib.stream_ptr()), "dlwp_groupnorm_act_bwd_f32")
+    ws = _lib.workspace(max(int(_lib.load().dlwp_groupnorm_act_bwd_workspace_bytes(n, c)), 4), x.device)
+    _lib.launch("dlwp_groupnorm_act_bwd_f32", x.device, x, stats, _contig(weight), _contig(bias), grad_out, dx, dw, db, ws, n, c,
+                hw, int(groups), int(act))
     return dx, dw, db
 
 
@@ -459,20 +416,13 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], 
     if resid is not None and (tuple(resid.shape) != (n, cout, oh, ow) or not resid.is_contiguous()):
         raise _lib.DlwpError("conv2d: resid must be contiguous and shaped like the output")
     y = torch.empty(n, cout, oh, ow, device=x.device, dtype=torch.float32)
-    lib = _lib.load()
     if form != "direct":
         packed = conv2d_weights(owner).get(owner)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.dlwp_conv2d_mfma_f32(x.data_ptr(), packed.data_ptr(),
-                                                bias.contiguous().data_ptr() if bias is not None else None,
-                                                resid.data_ptr() if resid is not None else None, y.data_ptr(), n, cin, h, w, cout,
-                                                k, int(stride), int(padding), int(pre_act), int(act),
-                                                CONV_FORMS.index(form) - 1, _lib.stream_ptr()), "dlwp_conv2d_mfma_f32")
+        _lib.launch("dlwp_conv2d_mfma_f32", x.device, x, packed, _contig(bias), resid, y, n, cin, h, w, cout, k, int(stride),
+                    int(padding), int(pre_act), int(act), CONV_FORMS.index(form) - 1)
         return y
-    with torch.cuda.device(x.device):
-        _lib.check(lib.dlwp_conv2d_f32(x.data_ptr(), weight.data_ptr(), bias.contiguous().data_ptr() if bias is not None else None,
-                                       resid.data_ptr() if resid is not None else None, y.data_ptr(), n, cin, h, w, cout, k,
-                                       int(stride), int(padding), int(pre_act), int(act), _lib.stream_ptr()), "dlwp_conv2d_f32")
+    _lib.launch("dlwp_conv2d_f32", x.device, x, weight, _contig(bias), resid, y, n, cin, h, w, cout, k, int(stride), int(padding),
+                int(pre_act), int(act))
     return y
 
 
@@ -495,21 +445,13 @@ def conv_transpose2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch
         raise _lib.DlwpError(f"conv_transpose2d: weight {tuple(weight.shape)} does not match input {tuple(x.shape)}")
     oh, ow = (h - 1) * stride - 2 * padding + k, (w - 1) * stride - 2 * padding + k
     y = torch.empty(n, cout, oh, ow, device=x.device, dtype=torch.float32)
-    lib = _lib.load()
     if form != "direct":
         packed = conv2d_weights(owner, transposed=True).get(owner)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.dlwp_conv_transpose2d_mfma_f32(x.data_ptr(), packed.data_ptr(),
-                                                          bias.contiguous().data_ptr() if bias is not None else None,
-                                                          y.data_ptr(), n, cin, h, w, cout, k, int(stride), int(padding),
-                                                          int(act), CONV_FORMS.index(form) - 1, _lib.stream_ptr()),
-                       "dlwp_conv_transpose2d_mfma_f32")
+        _lib.launch("dlwp_conv_transpose2d_mfma_f32", x.device, x, packed, _contig(bias), y, n, cin, h, w, cout, k, int(stride),
+                    int(padding), int(act), CONV_FORMS.index(form) - 1)
         return y
-    with torch.cuda.device(x.device):
-        _lib.check(lib.dlwp_conv_transpose2d_f32(x.data_ptr(), weight.data_ptr(),
-                                                 bias.contiguous().data_ptr() if bias is not None else None, y.data_ptr(), n,
-                                                 cin, h, w, cout, k, int(stride), int(padding), int(act), _lib.stream_ptr()),
-                   "dlwp_conv_transpose2d_f32")
+    _lib.launch("dlwp_conv_transpose2d_f32", x.device, x, weight, _contig(bias), y, n, cin, h, w, cout, k, int(stride),
+                int(padding), int(act))
     return y
 
 
@@ -521,9 +463,7 @@ def avgpool2x2(x: torch.Tensor) -> torch.Tensor:
     x = x.contiguous()
     n, c, h, w = x.shape
     y = torch.empty(n, c, h // 2, w // 2, device=x.device, dtype=torch.float32)
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        _lib.check(lib.dlwp_avgpool2x2_f32(x.data_ptr(), y.data_ptr(), n * c, h, w, _lib.stream_ptr()), "dlwp_avgpool2x2_f32")
+    _lib.launch("dlwp_avgpool2x2_f32", x.device, x, y, n * c, h, w)
     return y
 
 
@@ -566,10 +506,7 @@ def healpix_pad(x: torch.Tensor, padding: int) -> torch.Tensor:
         return _T.healpix_pad(x, int(padding))          # HIP forward, backward through the adjoint kernel
     table = _hpx.device_table(h, w, int(padding), x.device)
     y = torch.empty(n, c, h + 2 * padding, w + 2 * padding, device=x.device, dtype=torch.float32)
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        _lib.check(lib.dlwp_healpix_pad_f32(x.data_ptr(), y.data_ptr(), table.data_ptr(), n, c, h, w, int(padding),
-                                            _lib.stream_ptr()), "dlwp_healpix_pad_f32")
+    _lib.launch("dlwp_healpix_pad_f32", x.device, x, y, table, n, c, h, w, int(padding))
     return y
 
 
@@ -589,11 +526,7 @@ def healpix_pad_backward(dy: torch.Tensor, padding: int) -> torch.Tensor:
         raise _lib.DlwpError(f"padded face {ph}x{pw} does not hold a square face with padding {p}")
     adj = _hpx.device_adjoint_table(h, w, p, dy.device)
     dx = torch.empty(n, c, h, w, device=dy.device, dtype=torch.float32)
-    lib = _lib.load()
-    with torch.cuda.device(dy.device):
-        _lib.check(lib.dlwp_healpix_pad_bwd_f32(dy.data_ptr(), dx.data_ptr(), adj.indptr.data_ptr(), adj.index.data_ptr(),
-                                                adj.weight.data_ptr(), n, c, h, w, p, _lib.stream_ptr()),
-                   "dlwp_healpix_pad_bwd_f32")
+    _lib.launch("dlwp_healpix_pad_bwd_f32", dy.device, dy, dx, adj.indptr, adj.index, adj.weight, n, c, h, w, p)
     return dx
 
 
@@ -614,13 +547,10 @@ def conv3x3_hpx_backward_data(dy: torch.Tensor, weight: torch.Tensor, cin: int) 
         raise _lib.DlwpError(f"weight {tuple(weight.shape)} does not match {cout} output, {cin} input channels, 3x3")
     adj = _hpx.device_adjoint_table(h, w, 1, dy.device)
     dx = torch.empty(n, int(cin), h, w, device=dy.device, dtype=torch.float32)
-    lib = _lib.load()
-    nbytes = lib.dlwp_conv3x3_hpx_bwd_data_workspace_bytes(n, h, w, int(cin))
-    ring = torch.empty(max(nbytes, 4) // 4, device=dy.device, dtype=torch.float32)
-    with torch.cuda.device(dy.device):
-        _lib.check(lib.dlwp_conv3x3_hpx_bwd_data_f32(dy.data_ptr(), weight.data_ptr(), dx.data_ptr(), n, h, w, int(cin), cout,
-                                                     adj.indptr.data_ptr(), adj.index.data_ptr(), adj.weight.data_ptr(),
-                                                     ring.data_ptr(), nbytes, _lib.stream_ptr()), "dlwp_conv3x3_hpx_bwd_data_f32")
+    nbytes = _lib.load().dlwp_conv3x3_hpx_bwd_data_workspace_bytes(n, h, w, int(cin))
+    ring = _lib.workspace(max(nbytes, 4), dy.device)
+    _lib.launch("dlwp_conv3x3_hpx_bwd_data_f32", dy.device, dy, weight, dx, n, h, w, int(cin), cout, adj.indptr, adj.index,
+                adj.weight, ring, nbytes)
     return dx
 
 
@@ -666,12 +596,8 @@ def conv3x3_weight_grad(x0: torch.Tensor, x1: Optional[torch.Tensor], dz: torch.
         raise _lib.DlwpError(f"conv3x3_weight_grad: no HIP kernel for {c0}+{c1} -> {cout} channels on {n} x {h} x {w}")
     dw = torch.empty(cout, c0 + c1, 3, 3, device=x0.device, dtype=torch.float32)
     db = torch.empty(cout, device=x0.device, dtype=torch.float32) if need_bias else None
-    with torch.cuda.device(x0.device):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x0.device)
-        _lib.check(lib.dlwp_conv3x3_wgrad_f32(x0.data_ptr(), c0, x1.data_ptr() if x1 is not None else None, c1, dz.data_ptr(),
-                                              dw.data_ptr(), db.data_ptr() if db is not None else None, n, h, w, cout,
-                                              int(pre_act), table.data_ptr() if table is not None else None, ws.data_ptr(),
-                                              nbytes, _lib.stream_ptr()), "dlwp_conv3x3_wgrad_f32")
+    ws = _lib.workspace(nbytes, x0.device)
+    _lib.launch("dlwp_conv3x3_wgrad_f32", x0.device, x0, c0, x1, c1, dz, dw, db, n, h, w, cout, int(pre_act), table, ws, nbytes)
     return dw, db
 
 
@@ -724,12 +650,9 @@ def conv2d_weight_grad(x: torch.Tensor, grad_z: torch.Tensor, k: int, stride: in
         db = torch.empty(cout, device=x.device, dtype=torch.float32)
     if dw is None and db is None:
         return None, None
-    with torch.cuda.device(x.device):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        _lib.check(lib.dlwp_conv2d_wgrad_f32(x.data_ptr(), dz.data_ptr(), dw.data_ptr() if dw is not None else None,
-                                             db.data_ptr() if db is not None else None, n, cin, h, w, cout, k, stride, padding,
-                                             int(pre_act), int(transposed), ws.data_ptr(), nbytes, _lib.stream_ptr()),
-                   "dlwp_conv2d_wgrad_f32")
+    ws = _lib.workspace(nbytes, x.device)
+    _lib.launch("dlwp_conv2d_wgrad_f32", x.device, x, dz, dw, db, n, cin, h, w, cout, k, stride, padding, int(pre_act),
+                int(transposed), ws, nbytes)
     return dw, db
 
 
@@ -744,10 +667,7 @@ def convlstm_gates(gates: torch.Tensor, c_prev: torch.Tensor):
     b, c4, h, w = gates.shape
     hid = c4 // 4
     h_out, c_out = torch.empty_like(c_prev), torch.empty_like(c_prev)
-    lib = _lib.load()
-    with torch.cuda.device(gates.device):
-        _lib.check(lib.dlwp_convlstm_gates_f32(gates.data_ptr(), c_prev.data_ptr(), h_out.data_ptr(), c_out.data_ptr(),
-                                               b, hid, h, w, _lib.stream_ptr()), "dlwp_convlstm_gates_f32")
+    _lib.launch("dlwp_convlstm_gates_f32", gates.device, gates, c_prev, h_out, c_out, b, hid, h, w)
     return h_out, c_out
 
 
@@ -761,13 +681,8 @@ def afno2d_mix(xf_cf: torch.Tensor, w1, b1, w2, b2, num_blocks: int, sparsity_th
     b, c, h, wf = xc.shape
     xr = torch.view_as_real(xc)
     yr = torch.empty_like(xr)
-    lib = _lib.load()
-    with torch.cuda.device(xc.device):
-        _lib.check(lib.dlwp_afno2d_mix_f32(xr.data_ptr(), yr.data_ptr(), w1.contiguous().data_ptr(),
-                                           b1.contiguous().data_ptr(), w2.contiguous().data_ptr(),
-                                           b2.contiguous().data_ptr(), b, h, wf, c, num_blocks,
-                                           float(sparsity_threshold), float(hard_thresholding_fraction),
-                                           _lib.stream_ptr()), "dlwp_afno2d_mix_f32")
+    _lib.launch("dlwp_afno2d_mix_f32", xc.device, xr, yr, w1.contiguous(), b1.contiguous(), w2.contiguous(), b2.contiguous(), b,
+                h, wf, c, num_blocks, float(sparsity_threshold), float(hard_thresholding_fraction))
     return torch.view_as_complex(yr)
 
 
@@ -800,11 +715,8 @@ class _AfnoFftPlans:
     def get(self, device, h: int, w: int, kc: int):
         key = (str(device), h, w, kc)
         if key not in self._plans:
-            lib = _lib.load()
             handle = ctypes.c_void_p()
-            with torch.cuda.device(device):
-                _lib.check(lib.dlwp_afno_fft_plan_create(ctypes.byref(handle), h, w, kc, _lib.stream_ptr()),
-                           "dlwp_afno_fft_plan_create")
+            _lib.launch("dlwp_afno_fft_plan_create", device, ctypes.byref(handle), h, w, kc)
             self._plans[key] = handle
         return self._plans[key]
 
@@ -835,20 +747,16 @@ def afno2d_filter_backward(x_cf: torch.Tensor, grad_y: torch.Tensor, w1, b1, w2,
     if kc < 1 or not lib.dlwp_afno_fft_supported(h, w, kc) or bs not in (4, 8, 16):
         return None
     scale = 1.0 / float(h * w) ** 0.5
-    with torch.cuda.device(x_cf.device):
-        st = _lib.stream_ptr()
-        plan = _afno_fft_plans.get(x_cf.device, h, w, kc)
-        mk = lambda: torch.empty(b, c, h, kc, 2, device=x_cf.device, dtype=torch.float32)
-        xf, gf, gxf, xin, o1, d1, d2 = mk(), mk(), mk(), mk(), mk(), mk(), mk()
-        _lib.check(lib.dlwp_afno_rfft2_kept_f32(plan, x_cf.data_ptr(), xf.data_ptr(), b * c, st), "dlwp_afno_rfft2_kept_f32")
-        _lib.check(lib.dlwp_afno_rfft2_kept_f32(plan, grad_y.data_ptr(), gf.data_ptr(), b * c, st), "dlwp_afno_rfft2_kept_f32")
-        ptr = lambda t: t.detach().contiguous().data_ptr()
-        _lib.check(lib.dlwp_afno2d_mix_bwd_f32(xf.data_ptr(), gf.data_ptr(), gxf.data_ptr(), xin.data_ptr(), o1.data_ptr(),
-                                               d1.data_ptr(), d2.data_ptr(), ptr(w1), ptr(b1), ptr(w2), ptr(b2), b, h, kc, c,
-                                               num_blocks, w, float(sparsity_threshold), float(hard_thresholding_fraction),
-                                               scale, scale, st), "dlwp_afno2d_mix_bwd_f32")
-        gx = torch.empty_like(x_cf)
-        _lib.check(lib.dlwp_afno_irfft2_kept_f32(plan, gxf.data_ptr(), gx.data_ptr(), b * c, st), "dlwp_afno_irfft2_kept_f32")
+    dev = x_cf.device
+    plan = _afno_fft_plans.get(dev, h, w, kc)
+    mk = lambda: torch.empty(b, c, h, kc, 2, device=dev, dtype=torch.float32)
+    xf, gf, gxf, xin, o1, d1, d2 = mk(), mk(), mk(), mk(), mk(), mk(), mk()
+    _lib.launch("dlwp_afno_rfft2_kept_f32", dev, plan, x_cf, xf, b * c)
+    _lib.launch("dlwp_afno_rfft2_kept_f32", dev, plan, grad_y, gf, b * c)
+    _lib.launch("dlwp_afno2d_mix_bwd_f32", dev, xf, gf, gxf, xin, o1, d1, d2, *(t.detach().contiguous() for t in (w1, b1, w2, b2)),
+                b, h, kc, c, num_blocks, w, float(sparsity_threshold), float(hard_thresholding_fraction), scale, scale)
+    gx = torch.empty_like(x_cf)
+    _lib.launch("dlwp_afno_irfft2_kept_f32", dev, plan, gxf, gx, b * c)
     cv = lambda t: torch.view_as_complex(t).view(b, num_blocks, bs, h, kc)
     gw1 = torch.einsum("bnihk,bnohk->nio", cv(xin).conj(), cv(d1))
     gw2 = torch.einsum("bnihk,bnohk->nio", cv(o1).conj(), cv(d2))
@@ -875,29 +783,22 @@ def afno2d_filter_cf(x_cf: torch.Tensor, w1, b1, w2, b2, num_blocks: int, sparsi
     scale = 1.0 / float(h * w) ** 0.5
     kc = afno_kept_cols(h, w, hard_thresholding_fraction)
     y = torch.empty_like(x_cf)
-    with torch.cuda.device(x_cf.device):
-        st = _lib.stream_ptr()
-        if not use_rocfft and kc >= 1 and lib.dlwp_afno_fft_supported(h, w, kc):
-            plan = _afno_fft_plans.get(x_cf.device, h, w, kc)
-            spec = torch.empty(b, c, h, kc, 2, device=x_cf.device, dtype=torch.float32)
-            _lib.check(lib.dlwp_afno_rfft2_kept_f32(plan, x_cf.data_ptr(), spec.data_ptr(), b * c, st), "dlwp_afno_rfft2_kept_f32")
-            _lib.check(lib.dlwp_afno2d_mix_scaled_f32(spec.data_ptr(), spec.data_ptr(), w1.contiguous().data_ptr(),
-                                                      b1.contiguous().data_ptr(), w2.contiguous().data_ptr(),
-                                                      b2.contiguous().data_ptr(), b, h, kc, c, num_blocks,
-                                                      float(sparsity_threshold), float(hard_thresholding_fraction),
-                                                      scale, scale, st), "dlwp_afno2d_mix_scaled_f32")
-            _lib.check(lib.dlwp_afno_irfft2_kept_f32(plan, spec.data_ptr(), y.data_ptr(), b * c, st), "dlwp_afno_irfft2_kept_f32")
-            return y
-        wf = w // 2 + 1
-        spec = torch.empty(b, c, h, wf, 2, device=x_cf.device, dtype=torch.float32)
-        plan = _fft2_plans.get(x_cf.device, b * c, h, w)
-        _lib.check(lib.dlwp_rfft2_f32(plan, x_cf.data_ptr(), spec.data_ptr(), st), "dlwp_rfft2_f32")
-        _lib.check(lib.dlwp_afno2d_mix_scaled_f32(spec.data_ptr(), spec.data_ptr(), w1.contiguous().data_ptr(),
-                                                  b1.contiguous().data_ptr(), w2.contiguous().data_ptr(),
-                                                  b2.contiguous().data_ptr(), b, h, wf, c, num_blocks,
-                                                  float(sparsity_threshold), float(hard_thresholding_fraction),
-                                                  scale, scale, st), "dlwp_afno2d_mix_scaled_f32")
-        _lib.check(lib.dlwp_irfft2_f32(plan, spec.data_ptr(), y.data_ptr(), st), "dlwp_irfft2_f32")
+    dev = x_cf.device
+    kept = not use_rocfft and kc >= 1 and lib.dlwp_afno_fft_supported(h, w, kc)
+    cols = kc if kept else w // 2 + 1           # the kept columns, or hipFFT's full half spectrum
+    spec = torch.empty(b, c, h, cols, 2, device=dev, dtype=torch.float32)
+    if kept:
+        plan = _afno_fft_plans.get(dev, h, w, kc)
+        _lib.launch("dlwp_afno_rfft2_kept_f32", dev, plan, x_cf, spec, b * c)
+    else:
+        plan = _fft2_plans.get(dev, b * c, h, w)
+        _lib.launch("dlwp_rfft2_f32", dev, plan, x_cf, spec)
+    _lib.launch("dlwp_afno2d_mix_scaled_f32", dev, spec, spec, w1.contiguous(), b1.contiguous(), w2.contiguous(), b2.contiguous(),
+                b, h, cols, c, num_blocks, float(sparsity_threshold), float(hard_thresholding_fraction), scale, scale)
+    if kept:
+        _lib.launch("dlwp_afno_irfft2_kept_f32", dev, plan, spec, y, b * c)
+    else:
+        _lib.launch("dlwp_irfft2_f32", dev, plan, spec, y)
     return y
 
 
@@ -907,11 +808,7 @@ def layernorm_nhwc_to_nchw(x: torch.Tensor, weight, bias, eps: float) -> torch.T
     x = x.contiguous()
     b, h, w, c = x.shape
     y = torch.empty(b, c, h, w, device=x.device, dtype=torch.float32)
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        _lib.check(lib.dlwp_layernorm_nhwc_to_nchw_f32(x.data_ptr(), weight.contiguous().data_ptr(),
-                                                       bias.contiguous().data_ptr(), y.data_ptr(), b, h * w, c,
-                                                       float(eps), _lib.stream_ptr()), "dlwp_layernorm_nhwc_to_nchw_f32")
+    _lib.launch("dlwp_layernorm_nhwc_to_nchw_f32", x.device, x, weight.contiguous(), bias.contiguous(), y, b, h * w, c, float(eps))
     return y
 
 
@@ -925,15 +822,9 @@ def afno_merge(f_nchw: torch.Tensor, l_nchw: torch.Tensor, x_nhwc: torch.Tensor,
     b, h, w, c = x_nhwc.shape
     s = torch.empty_like(x_nhwc)
     n = torch.empty_like(x_nhwc) if want_norm else None
-    lib = _lib.load()
-    with torch.cuda.device(x_nhwc.device):
-        _lib.check(lib.dlwp_afno_merge_f32(f_nchw.data_ptr(), l_nchw.data_ptr(), x_nhwc.data_ptr(),
-                                           weight.contiguous().data_ptr() if want_norm else None,
-                                           bias.contiguous().data_ptr() if want_norm else None,
-                                           sum_bias.contiguous().data_ptr() if sum_bias is not None else None,
-                                           s.data_ptr(), n.data_ptr() if want_norm else None, b, h * w, c, float(eps),
-                                           _lib.stream_ptr()),
-                   "dlwp_afno_merge_f32")
+    gamma, beta = (weight.contiguous(), bias.contiguous()) if want_norm else (None, None)
+    _lib.launch("dlwp_afno_merge_f32", x_nhwc.device, f_nchw, l_nchw, x_nhwc, gamma, beta, _contig(sum_bias), s, n, b, h * w, c,
+                float(eps))
     return s, n
 
 
@@ -952,12 +843,7 @@ def patch_embed_1x1(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.
     if pos is not None and (tuple(pos.shape) != (h * w, c) or not pos.is_contiguous()):
         raise _lib.DlwpError(f"patch embed: pos must be contiguous [{h * w}, {c}], got {tuple(pos.shape)}")
     out = torch.empty(b, h * w, c, device=x.device, dtype=torch.float32)
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        _lib.check(lib.dlwp_patch_embed_1x1_f32(x.data_ptr(), weight.contiguous().data_ptr(),
-                                                bias.contiguous().data_ptr() if bias is not None else None,
-                                                pos.data_ptr() if pos is not None else None, out.data_ptr(), b, cin,
-                                                h * w, c, _lib.stream_ptr()), "dlwp_patch_embed_1x1_f32")
+    _lib.launch("dlwp_patch_embed_1x1_f32", x.device, x, weight.contiguous(), _contig(bias), pos, out, b, cin, h * w, c)
     return out
 
 
@@ -982,10 +868,7 @@ def concat_channels(parts: Sequence[torch.Tensor]) -> torch.Tensor:
     ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in parts])
     chans = (ctypes.c_int32 * n)(*[int(t.shape[1]) for t in parts])
     strides = (ctypes.c_int64 * n)(*[int(t.stride(0)) for t in parts])
-    lib = _lib.load()
-    with torch.cuda.device(p0.device):
-        _lib.check(lib.dlwp_concat_channels_f32(ptrs, chans, strides, n, out.data_ptr(), b, plane, _lib.stream_ptr()),
-                   "dlwp_concat_channels_f32")
+    _lib.launch("dlwp_concat_channels_f32", p0.device, ptrs, chans, strides, n, out, b, plane)
     return out
 
 
@@ -1003,12 +886,8 @@ def patch_recover_1x1(tokens: torch.Tensor, weight: torch.Tensor, bias: Optional
     if tokens.numel() != b * h * w * c:
         raise _lib.DlwpError(f"patch recover: tokens {tuple(tokens.shape)} do not hold {h} x {w} tokens per sample")
     out = torch.empty(b, cout, h, w, device=tokens.device, dtype=torch.float32)
-    lib = _lib.load()
-    with torch.cuda.device(tokens.device):
-        _lib.check(lib.dlwp_patch_recover_1x1_f32(tokens.data_ptr(), weight.detach().contiguous().data_ptr(),
-                                                  bias.detach().contiguous().data_ptr() if bias is not None else None,
-                                                  out.data_ptr(), b, h * w, c, cout, _lib.stream_ptr()),
-                   "dlwp_patch_recover_1x1_f32")
+    _lib.launch("dlwp_patch_recover_1x1_f32", tokens.device, tokens, weight.detach().contiguous(), _contig(bias), out, b, h * w, c,
+                cout)
     return out
 
 
@@ -1041,14 +920,8 @@ class TokenMlpWeights:
             if nbytes == 0:
                 raise _lib.DlwpError(f"token MLP: unsupported shape channels={c} hidden={hid}")
             buf = torch.empty(nbytes // 4, dtype=torch.int32, device=w1.device)
-
-            def ptr(t):
-                return t.detach().contiguous().data_ptr() if t is not None else None
-
-            with torch.cuda.device(w1.device):
-                packer = "dlwp_token_mlp_pack_f16x3" if f16x3 else "dlwp_token_mlp_pack_f32"
-                _lib.check(getattr(lib, packer)(ptr(w1), ptr(w2), ptr(ln_weight), ptr(ln_bias), ptr(b1), c, hid,
-                                                1 if merged else 0, buf.data_ptr(), _lib.stream_ptr()), packer)
+            _lib.launch("dlwp_token_mlp_pack_f16x3" if f16x3 else "dlwp_token_mlp_pack_f32", w1.device,
+                        *(_contig(t) for t in (w1, w2, ln_weight, ln_bias, b1)), c, hid, 1 if merged else 0, buf)
             return buf
 
         return self._derived.get(source_key(w1, w2, ln_weight, ln_bias, b1, extra=(merged, f16x3)), build)
@@ -1075,23 +948,17 @@ def token_mlp(n: torch.Tensor, resid: Optional[torch.Tensor], packed: torch.Tens
         out = torch.empty_like(n)
     elif out.shape != n.shape or not out.is_contiguous():
         raise _lib.DlwpError("token MLP: out must be contiguous and shaped like n")
-    lib = _lib.load()
-    common = (n.data_ptr(), resid.data_ptr() if resid is not None else None, packed.data_ptr(),
-              b1.contiguous().data_ptr() if b1 is not None else None,
-              b2.contiguous().data_ptr() if b2 is not None else None,
-              out.data_ptr(), n.numel() // c, c, int(hidden), float(ln_eps) if ln_eps is not None else -1.0)
-    with torch.cuda.device(n.device):
-        if emit_norm is None:
-            _lib.check(lib.dlwp_token_mlp_f32(*common, _lib.stream_ptr()), "dlwp_token_mlp_f32")
-            return out
-        if n.dim() != 4:
-            raise _lib.DlwpError("token MLP emit_norm: n must be [B, H, W, C]")
-        gamma, beta, eps = emit_norm
-        b, h, w, _ = n.shape
-        nxt = torch.empty(b, c, h, w, device=n.device, dtype=torch.float32)
-        _lib.check(lib.dlwp_token_mlp_emit_norm_f32(*common, gamma.contiguous().data_ptr(), beta.contiguous().data_ptr(),
-                                                    float(eps), nxt.data_ptr(), h * w, _lib.stream_ptr()),
-                   "dlwp_token_mlp_emit_norm_f32")
+    common = (n, resid, packed, _contig(b1), _contig(b2), out, n.numel() // c, c, int(hidden),
+              float(ln_eps) if ln_eps is not None else -1.0)
+    if emit_norm is None:
+        _lib.launch("dlwp_token_mlp_f32", n.device, *common)
+        return out
+    if n.dim() != 4:
+        raise _lib.DlwpError("token MLP emit_norm: n must be [B, H, W, C]")
+    gamma, beta, eps = emit_norm
+    b, h, w, _ = n.shape
+    nxt = torch.empty(b, c, h, w, device=n.device, dtype=torch.float32)
+    _lib.launch("dlwp_token_mlp_emit_norm_f32", n.device, *common, gamma.contiguous(), beta.contiguous(), float(eps), nxt, h * w)
     return out, nxt
 
 
@@ -1116,16 +983,9 @@ def afno_block_tail(f_cf: torch.Tensor, l_cf: torch.Tensor, x_nhwc: torch.Tensor
         out = torch.empty_like(x_nhwc)
     nxt = torch.empty(b, c, h, w, device=x_nhwc.device, dtype=torch.float32) if emit_norm is not None else None
     gamma, beta, eps = emit_norm if emit_norm is not None else (None, None, 0.0)
-    lib = _lib.load()
-    with torch.cuda.device(x_nhwc.device):
-        name = "dlwp_afno_block_tail_f16x3" if form == "f16x3" else "dlwp_afno_block_tail_f32"
-        _lib.check(getattr(lib, name)(f_cf.data_ptr(), l_cf.data_ptr(), x_nhwc.data_ptr(), packed.data_ptr(),
-                                                b2.contiguous().data_ptr() if b2 is not None else None, out.data_ptr(), b,
-                                                h * w, c, int(hidden), float(ln_eps),
-                                                gamma.contiguous().data_ptr() if gamma is not None else None,
-                                                beta.contiguous().data_ptr() if beta is not None else None, float(eps),
-                                                nxt.data_ptr() if nxt is not None else None, _lib.stream_ptr()),
-                   name)
+    _lib.launch("dlwp_afno_block_tail_f16x3" if form == "f16x3" else "dlwp_afno_block_tail_f32", x_nhwc.device, f_cf, l_cf,
+                x_nhwc, packed, _contig(b2), out, b, h * w, c, int(hidden), float(ln_eps), _contig(gamma), _contig(beta),
+                float(eps), nxt)
     return (out, nxt) if emit_norm is not None else out
 
 
@@ -1146,12 +1006,8 @@ def layer_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: f
     rows = x.numel() // c
     ob16 = out_dtype == torch.bfloat16
     y = torch.empty_like(x, dtype=torch.bfloat16) if ob16 else torch.empty_like(x)
-    lib = _lib.load()
-    name = "dlwp_layernorm_prebias_bf16out" if ob16 else "dlwp_layernorm_prebias_f32"
-    with torch.cuda.device(x.device):
-        _lib.check(getattr(lib, name)(x.data_ptr(), pre_bias.contiguous().data_ptr() if pre_bias is not None else None,
-                                      weight.contiguous().data_ptr(), bias.contiguous().data_ptr(),
-                                      y.data_ptr(), rows, c, float(eps), _lib.stream_ptr()), name)
+    _lib.launch("dlwp_layernorm_prebias_bf16out" if ob16 else "dlwp_layernorm_prebias_f32", x.device, x, _contig(pre_bias),
+                weight.contiguous(), bias.contiguous(), y, rows, c, float(eps))
     return y
 
 
@@ -1173,17 +1029,12 @@ def layernorm_backward(x: torch.Tensor, weight: torch.Tensor, grad_out: torch.Te
     if grad_out.shape != x.shape or not x.is_contiguous() or not grad_out.is_contiguous() or weight.numel() != c:
         raise _lib.DlwpError(f"layernorm_backward: x {tuple(x.shape)} and grad_out {tuple(grad_out.shape)} must be contiguous "
                              f"and of one shape, weight [{c}]")
-    lib = _lib.load()
-    gm = weight.contiguous()
     dx = torch.empty_like(x) if need_x else None
     dw = torch.empty(c, device=x.device, dtype=torch.float32) if need_weight else None
     db = torch.empty(c, device=x.device, dtype=torch.float32) if need_bias else None
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    with torch.cuda.device(x.device):
-        nbytes = max(int(lib.dlwp_layernorm_bwd_workspace_bytes(rows, c)), 16) if (need_weight or need_bias) else 0
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
-        _lib.check(lib.dlwp_layernorm_bwd_f32(x.data_ptr(), gm.data_ptr(), grad_out.data_ptr(), ptr(dx), ptr(dw), ptr(db), ptr(ws),
-                                              nbytes, rows, c, float(eps), _lib.stream_ptr()), "dlwp_layernorm_bwd_f32")
+    nbytes = max(int(_lib.load().dlwp_layernorm_bwd_workspace_bytes(rows, c)), 16) if (need_weight or need_bias) else 0
+    ws = _lib.workspace(nbytes, x.device)
+    _lib.launch("dlwp_layernorm_bwd_f32", x.device, x, weight.contiguous(), grad_out, dx, dw, db, ws, nbytes, rows, c, float(eps))
     return dx, dw, db
 
 
@@ -1194,8 +1045,7 @@ def activation(z: torch.Tensor, act: int) -> torch.Tensor:
     if not z.is_contiguous():
         raise _lib.DlwpError("activation: z must be contiguous")
     h = torch.empty_like(z)
-    with torch.cuda.device(z.device):
-        _lib.check(_lib.load().dlwp_act_f32(z.data_ptr(), h.data_ptr(), z.numel(), int(act), _lib.stream_ptr()), "dlwp_act_f32")
+    _lib.launch("dlwp_act_f32", z.device, z, h, z.numel(), int(act))
     return h
 
 
@@ -1211,15 +1061,12 @@ def bias_act_backward(grad_out: torch.Tensor, z: Optional[torch.Tensor], act: in
     rows = grad_out.numel() // max(n, 1)
     if not grad_out.is_contiguous() or (act != 0 and (z is None or z.shape != grad_out.shape or not z.is_contiguous())):
         raise _lib.DlwpError("bias_act_backward: grad_out and z must be contiguous and of one shape")
-    lib = _lib.load()
     gz = torch.empty_like(grad_out) if act != 0 else grad_out
     db = torch.empty(n, device=grad_out.device, dtype=torch.float32) if need_bias else None
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    with torch.cuda.device(grad_out.device):
-        nbytes = max(int(lib.dlwp_bias_act_bwd_workspace_bytes(rows, n)), 16) if need_bias else 0
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=grad_out.device) if nbytes else None
-        _lib.check(lib.dlwp_bias_act_bwd_f32(grad_out.data_ptr(), ptr(z) if act != 0 else None, gz.data_ptr() if act != 0 else None,
-                                             ptr(db), ptr(ws), nbytes, rows, n, act, _lib.stream_ptr()), "dlwp_bias_act_bwd_f32")
+    nbytes = max(int(_lib.load().dlwp_bias_act_bwd_workspace_bytes(rows, n)), 16) if need_bias else 0
+    ws = _lib.workspace(nbytes, grad_out.device)
+    z_in, gz_out = (z, gz) if act != 0 else (None, None)        # act 0: nothing to read or write but the bias sum
+    _lib.launch("dlwp_bias_act_bwd_f32", grad_out.device, grad_out, z_in, gz_out, db, ws, nbytes, rows, n, act)
     return gz, db
 
 
@@ -1246,9 +1093,7 @@ class LinearWeights:
             if nbytes == 0:
                 raise _lib.DlwpError(f"linear: unsupported shape out={n} in={k} (need in % 32 == 0 and out % 4 == 0)")
             buf = torch.empty(nbytes // 4, dtype=torch.int32, device=weight.device)
-            with torch.cuda.device(weight.device):
-                _lib.check(getattr(lib, packer)(weight.detach().contiguous().data_ptr(), n, k, buf.data_ptr(),
-                                                _lib.stream_ptr()), packer)
+            _lib.launch(packer, weight.device, weight.detach().contiguous(), n, k, buf)
             return buf
 
         return self._derived[f16].get(source_key(weight), build)
@@ -1275,12 +1120,9 @@ def linear_raw(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
         _lib.require_cuda_tensor(resid, "resid")
         if resid.shape != out.shape or not resid.is_contiguous():
             raise _lib.DlwpError("linear: resid must be contiguous and shaped like the output")
-    with torch.cuda.device(x.device):
-        packed = torch.empty(nbytes // 4, dtype=torch.int32, device=x.device)
-        _lib.check(lib.dlwp_linear_pack_f32(weight.data_ptr(), n, k, packed.data_ptr(), _lib.stream_ptr()), "dlwp_linear_pack_f32")
-        _lib.check(lib.dlwp_linear_f32(x.data_ptr(), packed.data_ptr(), bias.contiguous().data_ptr() if bias is not None else None,
-                                       resid.data_ptr() if resid is not None else None, out.data_ptr(), x.numel() // k, k, n, 0,
-                                       _lib.stream_ptr()), "dlwp_linear_f32")
+    packed = torch.empty(nbytes // 4, dtype=torch.int32, device=x.device)
+    _lib.launch("dlwp_linear_pack_f32", x.device, weight, n, k, packed)
+    _lib.launch("dlwp_linear_f32", x.device, x, packed, _contig(bias), resid, out, x.numel() // k, k, n, 0)
     return out
 
 
@@ -1342,19 +1184,12 @@ def linear(x: torch.Tensor, m: torch.nn.Linear, act: int = 0, resid: Optional[to
         raise _lib.DlwpError("linear: out must be contiguous and shaped like the output")
     if out.data_ptr() == x.data_ptr():
         raise _lib.DlwpError("linear: out must not alias x")
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        if x_bf16 or o_bf16:
-            _lib.check(lib.dlwp_linear_bf16_io(x.data_ptr(), packed.data_ptr(),
-                                               m.bias.contiguous().data_ptr() if m.bias is not None else None,
-                                               resid.data_ptr() if resid is not None else None, out.data_ptr(), x.numel() // k,
-                                               k, n, int(act), int(x_bf16), int(o_bf16), _lib.stream_ptr()), "dlwp_linear_bf16_io")
-            return out
-        name = {"fp32": "dlwp_linear_f32", "bf16": "dlwp_linear_bf16", "f16x3": "dlwp_linear_f16x3"}[precision]
-        _lib.check(getattr(lib, name)(x.data_ptr(), packed.data_ptr(),
-                                      m.bias.contiguous().data_ptr() if m.bias is not None else None,
-                                      resid.data_ptr() if resid is not None else None, out.data_ptr(), x.numel() // k, k, n,
-                                      int(act), _lib.stream_ptr()), name)
+    if x_bf16 or o_bf16:
+        _lib.launch("dlwp_linear_bf16_io", x.device, x, packed, _contig(m.bias), resid, out, x.numel() // k, k, n, int(act),
+                    int(x_bf16), int(o_bf16))
+        return out
+    name = {"fp32": "dlwp_linear_f32", "bf16": "dlwp_linear_bf16", "f16x3": "dlwp_linear_f16x3"}[precision]
+    _lib.launch(name, x.device, x, packed, _contig(m.bias), resid, out, x.numel() // k, k, n, int(act))
     return out
 
 
@@ -1513,12 +1348,10 @@ def global_attention(qkv: torch.Tensor, heads: int, d_k: int, scale: Optional[fl
         raise _lib.DlwpError(f"global_attention: batch {bt} and tokens {n} must be in [1, 2^31)")
     scale = d_k ** -0.5 if scale is None else float(scale)
     qkv = qkv.contiguous()
-    lib = _lib.load()
-    ws = torch.empty(int(lib.dlwp_global_attn_workspace_bytes(bt, heads, n)) // 4, device=qkv.device, dtype=torch.float32)
+    # the workspace IS the statistics tensor a caller may ask for, so it is typed: [Bt, heads, N] fp32
+    ws = torch.empty(int(_lib.load().dlwp_global_attn_workspace_bytes(bt, heads, n)) // 4, device=qkv.device, dtype=torch.float32)
     out = torch.empty((bt, n, heads * d_k), device=qkv.device, dtype=torch.float32)
-    with torch.cuda.device(qkv.device):
-        _lib.check(lib.dlwp_global_attn_f32(qkv.data_ptr(), out.data_ptr(), bt, n, heads, d_k, scale, ws.data_ptr(),
-                                            ws.numel() * 4, _lib.stream_ptr()), "dlwp_global_attn_f32")
+    _lib.launch("dlwp_global_attn_f32", qkv.device, qkv, out, bt, n, heads, d_k, scale, ws, ws.numel() * 4)
     return (out, ws.view(bt, heads, n)) if return_stats else out
 
 
@@ -1552,13 +1385,10 @@ def global_attention_backward(qkv: torch.Tensor, stats: torch.Tensor, grad_out: 
         raise _lib.DlwpError("global_attention_backward: qkv, stats and grad_out must be on one device")
     scale = d_k ** -0.5 if scale is None else float(scale)
     qkv, grad_out, stats = qkv.contiguous(), grad_out.contiguous(), stats.contiguous()
-    lib = _lib.load()
-    ws = torch.empty(int(lib.dlwp_global_attn_bwd_workspace_bytes(bt, heads, n)) // 4, device=qkv.device, dtype=torch.float32)
+    nbytes = int(_lib.load().dlwp_global_attn_bwd_workspace_bytes(bt, heads, n))
+    ws = _lib.workspace(nbytes, qkv.device)
     dqkv = torch.empty_like(qkv)
-    with torch.cuda.device(qkv.device):
-        _lib.check(lib.dlwp_global_attn_bwd_f32(qkv.data_ptr(), grad_out.data_ptr(), stats.data_ptr(), dqkv.data_ptr(), bt, n,
-                                                heads, d_k, scale, ws.data_ptr(), ws.numel() * 4, _lib.stream_ptr()),
-                   "dlwp_global_attn_bwd_f32")
+    _lib.launch("dlwp_global_attn_bwd_f32", qkv.device, qkv, grad_out, stats, dqkv, bt, n, heads, d_k, scale, ws, nbytes)
     return dqkv.view(shape)
 
 
@@ -1653,9 +1483,8 @@ def mgn_mlp(packed: MgnMlpWeights, seq: torch.nn.Sequential, x: torch.Tensor, ba
         raise _lib.DlwpError(f"mgn mlp: input of shape {tuple(x.shape)} for {batch} x {rows} rows of width {cin}")
     x = x.contiguous()                  # the kernel indexes a dense [B, C, rows] / [rows, C] block
     out = torch.empty((batch, cout, rows) if channels_first_out else (batch * rows, cout), device=x.device, dtype=torch.float32)
-    d = packed.get(seq)
-    _lib.check(_lib.load().dlwp_mgn_mlp_f32(ctypes.byref(d), x.data_ptr(), out.data_ptr(), batch, rows,
-                                            int(channels_first_in), int(channels_first_out), _lib.stream_ptr()), "mgn mlp")
+    _lib.launch("dlwp_mgn_mlp_f32", x.device, packed.get(seq), x, out, batch, rows, int(channels_first_in),
+                int(channels_first_out))
     return out
 
 
@@ -1666,10 +1495,9 @@ def mgn_processor_layer(edge_packed: MgnMlpWeights, edge_seq, node_packed: MgnMl
     e_shared: e_in is one [E, D] table for the whole batch (stride 0), else [batch, E, D]."""
     n_nodes, n_edges = row_ptr.numel() - 1, src.numel()
     d = edge_seq[-1].normalized_shape[0]
-    _lib.check(_lib.load().dlwp_mgn_processor_layer_f32(
-        ctypes.byref(edge_packed.get(edge_seq)), ctypes.byref(node_packed.get(node_seq)), 0 if aggregation == "sum" else 1,
-        row_ptr.data_ptr(), src.data_ptr(), dst.data_ptr(), n_nodes, n_edges, batch, x_in.data_ptr(), x_out.data_ptr(), e_in.data_ptr(),
-        0 if e_shared else n_edges * d, e_out.data_ptr(), _lib.stream_ptr()), "mgn processor layer")
+    _lib.launch("dlwp_mgn_processor_layer_f32", x_in.device, edge_packed.get(edge_seq), node_packed.get(node_seq),
+                0 if aggregation == "sum" else 1, row_ptr, src, dst, n_nodes, n_edges, batch, x_in, x_out, e_in,
+                0 if e_shared else n_edges * d, e_out)
 
 
 MGN_BWD_MAX_WIDTH = 64      # hidden / output widths of the backward kernels (csrc/mgn_bwd.hip)
@@ -1720,17 +1548,14 @@ def mgn_mlp_backward(packed: MgnMlpWeights, seq: torch.nn.Sequential, x: torch.T
     _lib.require_cuda_tensor(grad_out, "grad_out")
     x, grad_out = x.contiguous(), grad_out.contiguous()
     d = packed.get(seq)
-    lib = _lib.load()
-    ws_bytes = lib.dlwp_mgn_mlp_bwd_workspace_bytes(ctypes.byref(d), batch, rows)
+    ws_bytes = _lib.load().dlwp_mgn_mlp_bwd_workspace_bytes(ctypes.byref(d), batch, rows)
     if ws_bytes == 0:
         raise _lib.DlwpError("mgn mlp backward: shape outside the backward envelope (ops.mgn_mlp_backward_supported)")
-    ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8)
+    ws = _lib.workspace(ws_bytes, x.device)
     gx = torch.empty_like(x) if need_input_grad else None
     flat = torch.empty(_mgn_param_count(seq), device=x.device, dtype=torch.float32)
-    _lib.check(lib.dlwp_mgn_mlp_bwd_f32(ctypes.byref(d), x.data_ptr(), grad_out.data_ptr(),
-                                        gx.data_ptr() if gx is not None else None, flat.data_ptr(), batch, rows,
-                                        int(channels_first_in), int(channels_first_out), ws.data_ptr(), ws_bytes,
-                                        _lib.stream_ptr()), "mgn mlp backward")
+    _lib.launch("dlwp_mgn_mlp_bwd_f32", x.device, d, x, grad_out, gx, flat, batch, rows, int(channels_first_in),
+                int(channels_first_out), ws, ws_bytes)
     return gx, _mgn_param_grads(seq, flat)
 
 
@@ -1751,25 +1576,21 @@ def mgn_processor_layer_backward(edge_packed: MgnMlpWeights, edge_seq, node_pack
     n_nodes, n_edges = row_ptr.numel() - 1, src.numel()
     d = edge_seq[-1].normalized_shape[0]
     dx_out = dx_out.contiguous()
-    de_out = de_out.contiguous() if de_out is not None else None
+    de_out = _contig(de_out)
     ed, nd = edge_packed.get(edge_seq), node_packed.get(node_seq)
-    lib = _lib.load()
-    ws_bytes = lib.dlwp_mgn_processor_layer_bwd_workspace_bytes(ctypes.byref(ed), ctypes.byref(nd), n_nodes, n_edges, batch,
-                                                                int(e_shared))
+    ws_bytes = _lib.load().dlwp_mgn_processor_layer_bwd_workspace_bytes(ctypes.byref(ed), ctypes.byref(nd), n_nodes, n_edges,
+                                                                        batch, int(e_shared))
     if ws_bytes == 0:
         raise _lib.DlwpError("mgn processor layer backward: shape outside the backward envelope "
                              "(ops.mgn_layer_backward_supported)")
-    ws = torch.empty(ws_bytes, device=x_in.device, dtype=torch.uint8)
+    ws = _lib.workspace(ws_bytes, x_in.device)
     dx_in = torch.empty_like(x_in)
     de_in = torch.empty(e_in.shape, device=e_in.device, dtype=torch.float32)
     ge = torch.empty(_mgn_param_count(edge_seq), device=x_in.device, dtype=torch.float32)
     gn = torch.empty(_mgn_param_count(node_seq), device=x_in.device, dtype=torch.float32)
-    _lib.check(lib.dlwp_mgn_processor_layer_bwd_f32(
-        ctypes.byref(ed), ctypes.byref(nd), 0 if aggregation == "sum" else 1, row_ptr.data_ptr(), src.data_ptr(),
-        dst.data_ptr(), src_row_ptr.data_ptr(), src_perm.data_ptr(), n_nodes, n_edges, batch, x_in.data_ptr(),
-        e_in.data_ptr(), 0 if e_shared else n_edges * d, dx_out.data_ptr(), de_out.data_ptr() if de_out is not None else None,
-        dx_in.data_ptr(), de_in.data_ptr(), ge.data_ptr(), gn.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr()),
-        "mgn processor layer backward")
+    _lib.launch("dlwp_mgn_processor_layer_bwd_f32", x_in.device, ed, nd, 0 if aggregation == "sum" else 1, row_ptr, src, dst,
+                src_row_ptr, src_perm, n_nodes, n_edges, batch, x_in, e_in, 0 if e_shared else n_edges * d, dx_out, de_out, dx_in,
+                de_in, ge, gn, ws, ws_bytes)
     return dx_in, de_in, _mgn_param_grads(edge_seq, ge), _mgn_param_grads(node_seq, gn)
 
 
@@ -1859,17 +1680,15 @@ def _gc_args(**kw) -> "_lib.GcLinearArgs":
     return a
 
 
-def gc_linear(args: "_lib.GcLinearArgs") -> None:
-    _lib.check(_lib.load().dlwp_gc_linear_f32(ctypes.byref(args), _lib.stream_ptr()), "gc linear")
+def gc_linear(args: "_lib.GcLinearArgs", device) -> None:
+    _lib.launch("dlwp_gc_linear_f32", device, args)
 
 
 def gc_layernorm(x: torch.Tensor, batch: int, rows: int, ln: torch.nn.LayerNorm, res: Optional[torch.Tensor] = None,
                  res_bs: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     out = x if out is None else out
     d = ln.normalized_shape[0]
-    _lib.check(_lib.load().dlwp_gc_layernorm_f32(x.data_ptr(), out.data_ptr(), batch, rows, d, ln.weight.data_ptr(),
-                                                 ln.bias.data_ptr(), float(ln.eps), res.data_ptr() if res is not None else None,
-                                                 res_bs, _lib.stream_ptr()), "gc layernorm")
+    _lib.launch("dlwp_gc_layernorm_f32", x.device, x, out, batch, rows, d, ln.weight, ln.bias, float(ln.eps), res, res_bs)
     return out
 
 
@@ -1916,7 +1735,7 @@ def gc_mlp(pk: GcMlpWeights, seq: torch.nn.Sequential, batch: int, rows: int, fi
                 kw["a_act"] = act
         if last and ln is None and res is not None:
             kw.update(res=res, res_batch_stride=res_bs)
-        gc_linear(_gc_args(**kw))
+        gc_linear(_gc_args(**kw), dev)
         cur = out
         if save:
             zs.append(out)
@@ -1931,7 +1750,7 @@ def gc_node_products(pk: GcMlpWeights, part: int, x: torch.Tensor, batch: int, r
     k, h = w.shape
     out = torch.empty(batch * rows, h, device=x.device, dtype=torch.float32)
     gc_linear(_gc_args(a_mode=0, a=x, a_batch_stride=x_bs, lda=k, wt=w, bias=pk.zero, k=k, n=h, batch=batch, rows=rows,
-                       act=0, out=out, out_layout=0, ldo=h))
+                       act=0, out=out, out_layout=0, ldo=h), x.device)
     return out
 
 
@@ -1966,12 +1785,11 @@ def gc_weight_grad(a_fields: dict, k: int, n: int, batch: int, rows: int, dz: to
     """dlwp_gc_weight_grad_f32: (dW [n, k] = A^T dZ in torch's layout, db = column sums of dZ or None).  a_fields: the A
     operand as dlwp_gc_linear_args fields (a_mode, a, a_batch_stride, lda, agg_*, row_ptr, a_act).  dw may be a column
     block of a wider weight gradient (a view with unit column stride)."""
-    lib = _lib.load()
-    ws_bytes = lib.dlwp_gc_weight_grad_workspace_bytes(k, n, batch, rows)
+    ws_bytes = _lib.load().dlwp_gc_weight_grad_workspace_bytes(k, n, batch, rows)
     if ws_bytes == 0:
         raise _lib.DlwpError(f"gc weight grad: {k} -> {n} is outside the envelope")
     dev = dz.device
-    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    ws = _lib.workspace(ws_bytes, dev)
     if dw is None:
         dw = torch.empty(n, k, device=dev, dtype=torch.float32)
     if dw.stride(1) != 1 or dw.shape != (n, k):
@@ -1979,9 +1797,8 @@ def gc_weight_grad(a_fields: dict, k: int, n: int, batch: int, rows: int, dz: to
     if db is None and bias:
         db = torch.empty(n, device=dev, dtype=torch.float32)
     args = _gc_args(k=k, n=n, batch=batch, rows=rows, **a_fields)
-    _lib.check(lib.dlwp_gc_weight_grad_f32(ctypes.byref(args), dz.data_ptr(), int(dz_cf), 0 if dz_cf else dz.stride(0),
-                                           dw.data_ptr(), dw.stride(0), db.data_ptr() if db is not None else None,
-                                           ws.data_ptr(), ws_bytes, _lib.stream_ptr()), "gc weight grad")
+    _lib.launch("dlwp_gc_weight_grad_f32", dev, args, dz, int(dz_cf), 0 if dz_cf else dz.stride(0), dw, dw.stride(0), db, ws,
+                ws_bytes)
     return dw, db
 
 
@@ -1999,7 +1816,7 @@ def gc_data_grad(dz: torch.Tensor, w: torch.Tensor, batch: int, rows: int, dz_cf
         kw.update(act_grad_z=z, act_grad=act, ld_act_grad_z=z.stride(0))
     if res is not None:
         kw.update(res=res, res_batch_stride=res_bs)
-    gc_linear(_gc_args(**kw))
+    gc_linear(_gc_args(**kw), dz.device)
     return out
 
 
@@ -2007,25 +1824,18 @@ def gc_layernorm_backward(z: torch.Tensor, ln: torch.nn.LayerNorm, batch: int, r
                           g_agg: Optional[torch.Tensor] = None, g_agg_bs: int = 0, idx: Optional[torch.Tensor] = None,
                           deg: Optional[torch.Tensor] = None, want_total: bool = False):
     """dlwp_gc_layernorm_bwd_f32: (g_total or None, dz, dgamma, dbeta) with g = gy + g_agg[idx] (/ deg[idx])"""
-    lib = _lib.load()
     d = ln.normalized_shape[0]
-    ws_bytes = lib.dlwp_gc_layernorm_bwd_workspace_bytes(batch, rows, d)
+    ws_bytes = _lib.load().dlwp_gc_layernorm_bwd_workspace_bytes(batch, rows, d)
     if ws_bytes == 0:
         raise _lib.DlwpError(f"gc layernorm backward: width {d} is outside the envelope")
     dev = z.device
-    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    ws = _lib.workspace(ws_bytes, dev)
     gx = torch.empty(batch * rows, d, device=dev, dtype=torch.float32)
     gt = torch.empty(batch * rows, d, device=dev, dtype=torch.float32) if want_total else None
     dg = torch.empty(d, device=dev, dtype=torch.float32)
     dbeta = torch.empty(d, device=dev, dtype=torch.float32)
-
-    def ptr(t):
-        return t.data_ptr() if t is not None else None
-
-    _lib.check(lib.dlwp_gc_layernorm_bwd_f32(z.data_ptr(), ln.weight.data_ptr(), float(ln.eps), ptr(gy), ptr(g_agg), g_agg_bs,
-                                             ptr(idx), ptr(deg), batch, rows, d, ptr(gt), gx.data_ptr(), dg.data_ptr(),
-                                             dbeta.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr()),
-               "gc layernorm backward")
+    _lib.launch("dlwp_gc_layernorm_bwd_f32", dev, z, ln.weight, float(ln.eps), gy, g_agg, g_agg_bs, idx, deg, batch, rows, d, gt, gx,
+                dg, dbeta, ws, ws_bytes)
     return gt, gx, dg, dbeta
 
 
@@ -2036,7 +1846,6 @@ def gc_segment_sum(x: torch.Tensor, batch: int, row_ptr: Optional[torch.Tensor],
     d = x.shape[-1]
     x = x.contiguous()
     out = torch.empty((1 if batch_sum else batch) * n_segments, d, device=x.device, dtype=torch.float32)
-    _lib.check(_lib.load().dlwp_gc_segment_sum_f32(x.data_ptr(), x.numel() // batch, row_ptr.data_ptr() if row_ptr is not None
-                                                   else None, perm.data_ptr() if perm is not None else None, n_segments, d,
-                                                   batch, int(batch_sum), out.data_ptr(), _lib.stream_ptr()), "gc segment sum")
+    _lib.launch("dlwp_gc_segment_sum_f32", x.device, x, x.numel() // batch, row_ptr, perm, n_segments, d, batch, int(batch_sum),
+                out)
     return out

@@ -81,19 +81,15 @@ class SpectralOperator:
         if self.device.type != "cuda":
             raise _lib.DlwpError(f"SpectralOperator runs HIP kernels on an MI355X device, got {self.device}: "
                                  "the HIP path has no CPU fallback")
-        lib = _lib.load()
         n = len(self.rows_in)
         ri = (ctypes.c_int32 * n)(*self.rows_in)
         ro = (ctypes.c_int32 * n)(*self.rows_out)
         ci, co = self.channels, self.out_channels
         self._fwd, self._adj = ctypes.c_void_p(), ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(lib.dlwp_spectral_conv2d_plan_create_ex(ctypes.byref(self._fwd), ci, co, height, width,
-                                                               n, self.n_cols, ri, ro, self.fwd_scale, self.inv_scale,
-                                                               _lib.stream_ptr()), "dlwp_spectral_conv2d_plan_create_ex")
-            _lib.check(lib.dlwp_spectral_conv2d_plan_create_ex(ctypes.byref(self._adj), co, ci, height, width,
-                                                               n, self.n_cols, ro, ri, self.fwd_scale, self.inv_scale,
-                                                               _lib.stream_ptr()), "dlwp_spectral_conv2d_plan_create_ex")
+        _lib.launch("dlwp_spectral_conv2d_plan_create_ex", self.device, ctypes.byref(self._fwd), ci, co, height, width, n,
+                    self.n_cols, ri, ro, self.fwd_scale, self.inv_scale)
+        _lib.launch("dlwp_spectral_conv2d_plan_create_ex", self.device, ctypes.byref(self._adj), co, ci, height, width, n,
+                    self.n_cols, ro, ri, self.fwd_scale, self.inv_scale)
         self._ws = None
 
     def __del__(self):
@@ -123,15 +119,11 @@ class SpectralOperator:
             raise _lib.DlwpError(f"spectral operator built for {ci}->{co} channels on {self.h}x{self.w}, "
                                  f"{n}x{self.n_cols} modes; got x {tuple(x.shape)}, weight {tuple(w.shape)}"
                                  + (" (adjoint)" if adjoint else ""))
-        lib = _lib.load()
-        nbytes = lib.dlwp_spectral_conv2d_workspace_bytes(plan, b)
+        nbytes = _lib.load().dlwp_spectral_conv2d_workspace_bytes(plan, b)
         ws = self._workspace(nbytes, x.device)
         y = torch.empty(b, c_out, h, wd, device=x.device, dtype=torch.float32)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.dlwp_spectral_conv2d_set_weights_dev(plan, w.data_ptr(), 1 if adjoint else 0, _lib.stream_ptr()),
-                       "dlwp_spectral_conv2d_set_weights_dev")
-            _lib.check(lib.dlwp_spectral_conv2d_f32(plan, x.data_ptr(), y.data_ptr(), b, ws.data_ptr(), nbytes,
-                                                    _lib.stream_ptr()), "dlwp_spectral_conv2d_f32")
+        _lib.launch("dlwp_spectral_conv2d_set_weights_dev", x.device, plan, w, 1 if adjoint else 0)
+        _lib.launch("dlwp_spectral_conv2d_f32", x.device, plan, x, y, b, ws, nbytes)
         return y
 
     def forward(self, x, weight_real):
@@ -152,14 +144,10 @@ class SpectralOperator:
         if tuple(x.shape) != (b, ci, self.h, self.w) or tuple(grad_y.shape) != (b, co, self.h, self.w):
             raise _lib.DlwpError(f"spectral operator built for {ci}->{co} channels on {self.h}x{self.w}; "
                                  f"got x {tuple(x.shape)}, grad_y {tuple(grad_y.shape)}")
-        lib = _lib.load()
-        nbytes = lib.dlwp_spectral_conv2d_wgrad_workspace_bytes(self._fwd, b)
+        nbytes = _lib.load().dlwp_spectral_conv2d_wgrad_workspace_bytes(self._fwd, b)
         ws = self._workspace(nbytes, x.device)
         gw = torch.empty(ci, co, len(self.rows_in), self.n_cols, 2, device=x.device, dtype=torch.float32)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.dlwp_spectral_conv2d_wgrad_f32(self._fwd, x.data_ptr(), grad_y.data_ptr(), gw.data_ptr(), b,
-                                                          ws.data_ptr(), nbytes, _lib.stream_ptr()),
-                       "dlwp_spectral_conv2d_wgrad_f32")
+        _lib.launch("dlwp_spectral_conv2d_wgrad_f32", x.device, self._fwd, x, grad_y, gw, b, ws, nbytes)
         return gw
 
 

@@ -1,5 +1,6 @@
 """CPU-side checks of the C-ABI library: it loads, exports every symbol include/dlwp_hip.h
 declares, and the product path fails loudly without a GPU (no CPU fallback)."""
+import ctypes
 import os
 import re
 
@@ -26,6 +27,83 @@ def test_library_loads_and_exports_every_declared_symbol():
     # the ctypes table covers the header exactly
     assert sorted(L.SIGNATURES) == declared
     assert lib.dlwp_version() >= 100
+
+
+_SCALARS = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32, "size_t": ctypes.c_size_t,
+            "float": ctypes.c_float, "double": ctypes.c_double}
+_STRUCTS = {"dlwp_fno2d_desc": "FNO2dDesc", "dlwp_wattn_desc": "WAttnDesc", "dlwp_mgn_mlp_desc": "MgnMlpDesc",
+            "dlwp_gc_linear_args": "GcLinearArgs"}
+_STRUCT_RE = r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\1\s*;"
+
+
+def _header():
+    src = open(os.path.join(ROOT, "include", "dlwp_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    return re.sub(r"//[^\n]*|^\s*#.*$", "", src, flags=re.M)      # and the preprocessor lines
+
+
+def _c_class(decl: str):
+    """"ptr" for anything with a `*`, else the ctypes type of the exact scalar type a C declaration names"""
+    if "*" in decl:
+        return "ptr"
+    return _SCALARS[[w for w in decl.split() if w != "const"][0]]
+
+
+def _ctypes_class(t):
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return "ptr"
+    return t
+
+
+def _header_prototypes():
+    """{name: (class of the return type, [class of each parameter])}; an array parameter is a pointer"""
+    src = re.sub(_STRUCT_RE, "", _header(), flags=re.S)
+    src = re.sub(r"typedef\s+enum\s+\w+\s*\{.*?\}\s*\w+\s*;", "", src, flags=re.S)
+    out = {}
+    for ret, name, params in re.findall(r"([\w\s\*]+?)\b(dlwp_\w+)\s*\(([^()]*)\)\s*;", src):
+        assert name not in out, f"{name} is declared twice"
+        params = [p.strip() for p in params.split(",")]
+        params = [] if params == ["void"] else params
+        out[name] = (_c_class(ret), ["ptr" if "[" in p else _c_class(p) for p in params])
+    return out
+
+
+def _header_structs():
+    """{struct: [(field, class or (class, length) for an array field)]} with `int32_t a, b;` as two fields"""
+    out = {}
+    for name, body in re.findall(_STRUCT_RE, _header(), flags=re.S):
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            first, *more = [d.strip() for d in decl.split(",")]
+            base = re.match(r"(.*?)(\w+)\s*(\[\d+\])?$", first, flags=re.S).group(1)
+            for d in [first] + [base + m for m in more]:
+                typ, field, length = re.match(r"(.*?)(\w+)\s*(?:\[(\d+)\])?$", d, flags=re.S).groups()
+                fields.append((field, (_c_class(typ), int(length)) if length else _c_class(typ)))
+        out[name] = fields
+    return out
+
+
+def test_signatures_match_the_header_type_by_type():
+    """lib.SIGNATURES is a hand-kept mirror of include/dlwp_hip.h: a c_int32 where the header says int64_t, or a dropped
+    argument, would load cleanly and corrupt a launch.  Every prototype's return and parameter types, in arity and position."""
+    protos = _header_prototypes()
+    assert len(protos) == len(L.SIGNATURES) and len(protos) > 100
+    assert sorted(protos) == sorted(L.SIGNATURES)
+    for name, (ret, params) in protos.items():
+        res, args = L.SIGNATURES[name]
+        assert _ctypes_class(res) == ret, f"{name}: return type {res} against the header's {ret}"
+        assert [_ctypes_class(a) for a in args] == params, f"{name}: argument types differ from the header"
+
+
+def test_structure_mirrors_match_the_header_field_by_field():
+    """the four ctypes.Structure mirrors: the header's field names in its order, types classified like the prototypes'
+    (an array field by its element class and its length)"""
+    structs = _header_structs()
+    assert sorted(structs) == sorted(_STRUCTS)
+    for cname, pyname in _STRUCTS.items():
+        mirror = [(f, (_ctypes_class(t._type_), t._length_) if issubclass(t, ctypes.Array) else _ctypes_class(t))
+                  for f, t in getattr(L, pyname)._fields_]
+        assert mirror == structs[cname], f"{pyname} differs from struct {cname}"
 
 
 def test_error_reporting_without_gpu():

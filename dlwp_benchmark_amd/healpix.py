@@ -131,3 +131,190 @@ def device_adjoint_table(h: int, w: int, p: int, device) -> AdjointTable:
     if key not in _device_adjoints:
         _device_adjoints[key] = AdjointTable(*(t.to(device).contiguous() for t in pad_adjoint_table(h, w, p)))
     return _device_adjoints[key]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# HEALPix -> lat-lon remap (host side of dlwp_healpix_to_latlon_f32).  The reference remaps every rollout to lat-lon before
+# it scores it (scripts/evaluate.py:79-116,298-303, scripts/train.py:430-441) by calling HEALPixRemap.hpx2ll
+# (data/processing/healpix_mapping.py:372-404) once per plane on the host: a Python loop over the pixels, then reproject's
+# bilinear interpolation.  The map is linear and fixed -- every lat-lon cell is a convex combination of at most four HEALPix
+# cells -- so, like the padding, the geometry is evaluated ONCE, in float64, into a gather table.  Pixel centres and the
+# interpolation rule are those of the HEALPix paper (Gorski et al. 2005, ApJ 622:759) and library (`get_interpol`).
+# ---------------------------------------------------------------------------------------------------------------------
+_JRLL = np.array([2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4], dtype=np.int64)
+_JPLL = np.array([1, 3, 5, 7, 0, 2, 4, 6, 1, 3, 5, 7], dtype=np.int64)
+
+
+def _check_nside(nside) -> int:
+    n = int(nside)
+    if n != nside or n < 2 or n & (n - 1):
+        raise ValueError(f"nside must be a power of two >= 2 (the reference's bit interleave needs that), got {nside}")
+    return n
+
+
+@functools.lru_cache(maxsize=16)
+def _cell_geometry(n: int):
+    """(z, phi, ring index) of every cell [f, a, b], float64 / int64 [12, n, n].  Cell [f, a, b] of the reference's face
+    layout (healpix_mapping.py:406-459: nested pixel (f, ix, iy) lands in hpx3d[f, ix, iy], then both face axes are flipped)
+    is nested pixel (f, ix = n-1-a, iy = n-1-b)."""
+    f = np.arange(12, dtype=np.int64)[:, None, None]
+    ix = (n - 1 - np.arange(n, dtype=np.int64))[None, :, None]
+    iy = (n - 1 - np.arange(n, dtype=np.int64))[None, None, :]
+    jr = _JRLL[f] * n - ix - iy - 1                                # ring number, 1 .. 4n-1 from the north
+    north, south = jr < n, jr > 3 * n
+    nr = np.where(north, jr, np.where(south, 4 * n - jr, n))
+    nrf = nr.astype(np.float64)
+    z = np.where(north, 1.0 - nrf * nrf / (3.0 * n * n),
+                 np.where(south, nrf * nrf / (3.0 * n * n) - 1.0, (2 * n - jr) * 2.0 / (3.0 * n)))
+    kshift = np.where(north | south, 0, (jr - n) & 1)
+    jp = (_JPLL[f] * nr + ix - iy + 1 + kshift) // 2               # pixel in the ring, wrapped into 1 .. 4 nr
+    jp = np.where(jp > 4 * nr, jp - 4 * nr, jp)
+    jp = np.where(jp < 1, jp + 4 * nr, jp)
+    phi = (jp - (kshift + 1) * 0.5) * (0.5 * np.pi / nrf)
+    start = np.where(north, 2 * nr * (nr - 1),
+                     np.where(south, 12 * n * n - 2 * nr * (nr + 1), 2 * n * (n - 1) + (jr - n) * 4 * n))
+    ring = start + jp - 1
+    for a in (z, phi, ring):
+        a.setflags(write=False)
+    return z, phi, ring
+
+
+def ring_index(nside: int) -> np.ndarray:
+    """int64 [12, n, n]: the RING-scheme pixel number of cell [f, a, b] (a permutation of 0 .. 12 n^2 - 1)."""
+    return _cell_geometry(_check_nside(nside))[2]
+
+
+def cell_centres(nside: int):
+    """(lat_deg, lon_deg), float64 [12, n, n]: where cell [f, a, b] of the reference's face layout sits on the sphere;
+    [f, 0, 0] is the northern corner of face f."""
+    z, phi, _ = _cell_geometry(_check_nside(nside))
+    return np.degrees(np.arcsin(z)), np.degrees(phi)
+
+
+def _as_f64(a) -> np.ndarray:
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
+
+
+def _ring_info(n: int, ring: np.ndarray):
+    """(pixels in the ring, first RING index, theta of the ring, s) for ring numbers 1 .. 4n-1; pixel i of a ring is centred
+    at (i + s/2) 2 pi / N."""
+    north, south = ring < n, ring > 3 * n
+    nr = np.where(north, ring, np.where(south, 4 * n - ring, n))
+    nrf = nr.astype(np.float64)
+    z = np.where(north, 1.0 - nrf * nrf / (3.0 * n * n),
+                 np.where(south, nrf * nrf / (3.0 * n * n) - 1.0, (2 * n - ring) * 2.0 / (3.0 * n)))
+    start = np.where(north, 2 * nr * (nr - 1),
+                     np.where(south, 12 * n * n - 2 * nr * (nr + 1), 2 * n * (n - 1) + (ring - n) * 4 * n))
+    s = np.where(north | south, 1, 1 - ((ring - n) & 1))
+    return 4 * nr, start, np.arccos(z), s
+
+
+def interp_weights(nside: int, lats_deg, lons_deg):
+    """The HEALPix library's bilinear interpolation (`get_interpol`, healpy `get_interp_weights`: what reproject_from_healpix
+    applies at its default order) for the H x W grid of targets (lats_deg[j], lons_deg[i]), target q = j W + i:
+    (cell int64 [H W, 4], weight float64 [H W, 4]) with cell = face n^2 + a n + b in the layout of `cell_centres`.  Taps 0, 1
+    lie on the ring above the target, 2, 3 on the ring below; beyond the first and last ring the missing pair is the ring's
+    four pixels (the two listed taps, turned by half the ring) at a quarter of the remaining weight each."""
+    n = _check_nside(nside)
+    lats, lons = _as_f64(lats_deg), _as_f64(lons_deg)
+    if lats.size == 0 or lons.size == 0 or not (np.all(np.abs(lats) <= 90.0) and np.all(np.isfinite(lons))):
+        raise ValueError("latitudes must lie in [-90, 90] and longitudes be finite, at least one of each")
+    theta = np.repeat(np.radians(90.0 - lats), lons.size)
+    phi = np.tile(np.radians(np.mod(lons, 360.0)), lats.size)
+    z = np.cos(theta)
+    az = np.abs(z)
+    cap = np.floor(n * np.sqrt(3.0 * (1.0 - az))).astype(np.int64)
+    ir1 = np.where(az <= 2.0 / 3.0, np.floor(n * (2.0 - 1.5 * z)).astype(np.int64), np.where(z > 0, cap, 4 * n - cap - 1))
+    ir2 = ir1 + 1
+    npix = 12 * n * n
+    pix = np.zeros((theta.size, 4), dtype=np.int64)
+    wgt = np.zeros((theta.size, 4), dtype=np.float64)
+    th = [None, None]
+    for k, ir in enumerate((ir1, ir2)):
+        ok = (ir >= 1) & (ir <= 4 * n - 1)
+        cnt, start, th[k], s = _ring_info(n, np.clip(ir, 1, 4 * n - 1))
+        t = phi * cnt / (2.0 * np.pi) - 0.5 * s
+        i1 = np.floor(t).astype(np.int64)
+        w = t - i1
+        i2 = i1 + 1
+        i1 = np.where(i1 < 0, i1 + cnt, np.where(i1 >= cnt, i1 - cnt, i1))
+        i2 = np.where(i2 >= cnt, i2 - cnt, i2)
+        pix[:, 2 * k], pix[:, 2 * k + 1] = np.where(ok, start + i1, 0), np.where(ok, start + i2, 0)
+        wgt[:, 2 * k], wgt[:, 2 * k + 1] = np.where(ok, 1.0 - w, 0.0), np.where(ok, w, 0.0)
+    top, bottom = ir1 == 0, ir2 == 4 * n
+    mid = ~(top | bottom)
+    wt = np.where(mid, (theta - th[0]) / np.where(mid, th[1] - th[0], 1.0), 0.0)
+    wt = np.where(top, theta / th[1], wt)
+    wt = np.where(bottom, (theta - th[0]) / (np.pi - th[0]), wt)
+    wgt[:, :2] *= (1.0 - wt)[:, None]
+    wgt[:, 2:] *= wt[:, None]
+    fac = np.where(top, (1.0 - wt) * 0.25, 0.0)                    # above the first ring: the rest goes to its four pixels
+    wgt[:, 0] = np.where(top, fac, wgt[:, 0])
+    wgt[:, 1] = np.where(top, fac, wgt[:, 1])
+    wgt[:, 2] += fac
+    wgt[:, 3] += fac
+    pix[:, 0] = np.where(top, (pix[:, 2] + 2) & 3, pix[:, 0])
+    pix[:, 1] = np.where(top, (pix[:, 3] + 2) & 3, pix[:, 1])
+    fac = np.where(bottom, wt * 0.25, 0.0)                         # below the last ring: the mirror image
+    wgt[:, 0] += fac
+    wgt[:, 1] += fac
+    wgt[:, 2] = np.where(bottom, fac, wgt[:, 2])
+    wgt[:, 3] = np.where(bottom, fac, wgt[:, 3])
+    pix[:, 2] = np.where(bottom, ((pix[:, 0] + 2) & 3) + npix - 4, pix[:, 2])
+    pix[:, 3] = np.where(bottom, ((pix[:, 1] + 2) & 3) + npix - 4, pix[:, 3])
+    if pix.min() < 0 or pix.max() >= npix:
+        raise ValueError("HEALPix interpolation produced a pixel outside the map")
+    cell_of_ring = np.empty(npix, dtype=np.int64)
+    cell_of_ring[ring_index(n).reshape(-1)] = np.arange(npix, dtype=np.int64)
+    return cell_of_ring[pix], wgt
+
+
+class LatLonTable(NamedTuple):
+    """Gather table of the HEALPix -> lat-lon remap: y[q] = sum_t weight[q, t] * x[index[q, t]] over the 12 n^2 cells of one
+    plane, q = j W + i (see `interp_weights`)."""
+    index: torch.Tensor      # int32 [H*W, 4], face*n*n + a*n + b
+    weight: torch.Tensor     # float32 [H*W, 4]
+
+
+_latlon_tables = {}
+
+
+def latlon_table(nside: int, lats_deg, lons_deg) -> LatLonTable:
+    """`interp_weights` as CPU tensors for the kernel: weights computed in float64 and rounded once to float32, every index
+    checked against 12 n^2 here (the kernel does not).  Cached per argument set."""
+    n = _check_nside(nside)
+    lats, lons = _as_f64(lats_deg), _as_f64(lons_deg)
+    key = (n, lats.tobytes(), lons.tobytes())
+    if key not in _latlon_tables:
+        cell, wgt = interp_weights(n, lats, lons)
+        if cell.min() < 0 or cell.max() >= 12 * n * n:
+            raise ValueError("remap table index outside the 12 n^2 cells of a plane")
+        if len(_latlon_tables) >= 32:
+            _latlon_tables.pop(next(iter(_latlon_tables)))
+        _latlon_tables[key] = LatLonTable(torch.from_numpy(cell.astype(np.int32)), torch.from_numpy(wgt.astype(np.float32)))
+    return _latlon_tables[key]
+
+
+def reference_grid(latitudes: int, longitudes: int):
+    """(lats_deg, lons_deg), float64: the target grid HEALPixRemap.hpx2ll produces, read from its WCS header
+    (healpix_mapping.py:109-123: CRVAL1 = 179 at CRPIX1 = longitudes / 2, CDELT = 360 / longitudes on both axes), north
+    first.  At 180 x 360 that is lon 0 .. 359 and lat 89.5 .. -89.5; at 32 x 64 the header's 179 puts lon_0 at 4.625 -- a
+    quirk of the reference that belongs here and nowhere else (the metric classes take explicit arrays)."""
+    latitudes, longitudes = int(latitudes), int(longitudes)
+    res = 360.0 / longitudes
+    lons = np.mod(179.0 + res * (np.arange(longitudes, dtype=np.float64) + 1.0 - longitudes / 2.0), 360.0)
+    lats = res * ((latitudes - 1) / 2.0 - np.arange(latitudes, dtype=np.float64))
+    return lats, lons
+
+
+_device_latlon_tables = {}
+
+
+def device_latlon_table(nside: int, lats_deg, lons_deg, device) -> LatLonTable:
+    lats, lons = _as_f64(lats_deg), _as_f64(lons_deg)
+    key = (int(nside), lats.tobytes(), lons.tobytes(), str(device))
+    if key not in _device_latlon_tables:
+        _device_latlon_tables[key] = LatLonTable(*(t.to(device).contiguous() for t in latlon_table(nside, lats, lons)))
+    return _device_latlon_tables[key]

@@ -179,6 +179,7 @@ SIGNATURES = {
     "dlwp_conv3x3_hpx_bwd_data_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "dlwp_conv3x3_hpx_bwd_data_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dlwp_healpix_to_latlon_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int32, c_int32, c_void_p]),
     "dlwp_conv3x3_wgrad_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     "dlwp_conv3x3_wgrad_slices": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     "dlwp_conv3x3_wgrad_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32,

@@ -9,6 +9,11 @@ trajectories.
 
 `ZonalSpectrumMetrics` reduces the same tensors to zonal energy spectra and the mean energy log ratio (MELR) of
 reference scripts/losses.py:16-152, the spectral-blurring score scripts/train.py:434-445 takes of validation rollouts.
+
+Both classes also take HEALPix rollouts [B, K, C, 12, n, n] when they are given the longitudes of the lat-lon grid beside its
+latitudes: the reference remaps inits, outputs and targets to lat-lon before every metric (scripts/evaluate.py:298-303,
+scripts/train.py:430-441), on the host; here `ops.healpix_to_latlon` does it on the device, a chunk of samples at a time into one
+reused workspace, and the sums accumulate through the `*_acc` entry points.
 """
 import math
 from typing import Optional
@@ -24,9 +29,63 @@ def latitude_weights(lats_deg: torch.Tensor) -> torch.Tensor:
     return (w / w.mean()).float()
 
 
-class RolloutMetrics:
+DEFAULT_WORKSPACE_BYTES = 256 << 20
+
+
+class _HealpixInput:
+    """What the two metric classes share for HEALPix rollouts [B, K, C, 12, n, n]: the target grid and one workspace per device
+    that holds a chunk of samples of `out` and of `target` remapped to lat-lon, within `max_workspace_bytes`."""
+
+    def _init_remap(self, lats_deg, lons_deg, max_workspace_bytes):
+        self._lats = torch.as_tensor(lats_deg).detach().double().cpu().reshape(-1).numpy()
+        self._lons = None if lons_deg is None else torch.as_tensor(lons_deg).detach().double().cpu().reshape(-1).numpy()
+        self.max_workspace_bytes = int(max_workspace_bytes)
+        self._remap_ws = {}   # device -> float32 workspace, grown when a shape needs more
+
+    def _require_remap(self, out, target):
+        if self._lons is None:
+            raise _lib.DlwpError(f"got a {out.dim()}-D rollout {tuple(out.shape)}: a HEALPix rollout [B, K, C, 12, n, n] is remapped "
+                                 "to lat-lon only when the metric is built with `lons_deg` (the longitudes of the lat-lon grid)")
+        _lib.require_cuda_tensor(out, "out")
+        _lib.require_cuda_tensor(target, "target")
+        if target.shape != out.shape:
+            raise _lib.DlwpError(f"target shape {tuple(target.shape)} != output shape {tuple(out.shape)}")
+        if target.device != out.device:
+            raise _lib.DlwpError(f"target is on {target.device}, output on {out.device}: both must be on one device")
+
+    def _remapped_chunks(self, out, target):
+        """Yields (out, target) as lat-lon [m, K, C, H, W] views of the workspace, m samples at a time, in sample order.  A
+        pair is valid until the next one is asked for."""
+        from . import ops as _ops
+
+        b, k, c = out.shape[:3]
+        h, w = len(self._lats), len(self._lons)
+        per = k * c * h * w                                    # floats of one sample of one tensor
+        chunk = min(b, self.max_workspace_bytes // (8 * per)) if per else b
+        if chunk < 1:
+            raise _lib.DlwpError(f"max_workspace_bytes = {self.max_workspace_bytes} does not hold one sample of the rollout and "
+                                 f"of the target on the {h}x{w} grid ({8 * per} bytes)")
+        key = str(out.device)
+        buf = self._remap_ws.get(key)
+        if buf is None or buf.numel() < 2 * chunk * per:
+            buf = self._remap_ws[key] = torch.empty(2 * chunk * per, dtype=torch.float32, device=out.device)
+        for b0 in range(0, b, chunk):
+            m = min(chunk, b - b0)
+            o = buf[:m * per].view(m, k, c, h, w)
+            t = buf[chunk * per:chunk * per + m * per].view(m, k, c, h, w)
+            _ops.healpix_to_latlon(out[b0:b0 + m], self._lats, self._lons, out=o)
+            _ops.healpix_to_latlon(target[b0:b0 + m], self._lats, self._lons, out=t)
+            yield o, t
+
+
+class RolloutMetrics(_HealpixInput):
     def __init__(self, lats_deg: torch.Tensor, std: Optional[torch.Tensor] = None,
-                 climatology: Optional[torch.Tensor] = None, group=None):
+                 climatology: Optional[torch.Tensor] = None, group=None, lons_deg=None,
+                 max_workspace_bytes: int = DEFAULT_WORKSPACE_BYTES):
+        """`lons_deg`: the longitudes of the lat-lon grid; with them `sums` and `__call__` also take HEALPix rollouts
+        [B, K, C, 12, n, n], remapped to (lats_deg, lons_deg) on the device in chunks of samples whose lat-lon copies stay within
+        `max_workspace_bytes`.  Climatology and latitude weights are lat-lon either way."""
+        self._init_remap(lats_deg, lons_deg, max_workspace_bytes)
         self.latw = latitude_weights(lats_deg)
         self.std = std.float() if std is not None else None
         self.clim = climatology.float() if climatology is not None else None
@@ -44,7 +103,14 @@ class RolloutMetrics:
     def sums(self, out: torch.Tensor, target: torch.Tensor, into: Optional[torch.Tensor] = None) -> torch.Tensor:
         """double [4, K, C] sums of this rank's samples (see dlwp_weighted_error_sums_f32).  `into`: a [4, K, C] double tensor
         of running sums the new ones are ADDED to (dlwp_weighted_error_sums_acc_f32: one launch per batch, no zero-fill, no add
-        kernel); it is returned."""
+        kernel); it is returned.  A HEALPix rollout [B, K, C, 12, n, n] (see `lons_deg`) is remapped chunk by chunk and summed
+        into zero-initialised (or `into`) sums."""
+        if isinstance(out, torch.Tensor) and out.dim() == 6:
+            self._require_remap(out, target)
+            sums = into if into is not None else torch.zeros(4, out.shape[1], out.shape[2], dtype=torch.float64, device=out.device)
+            for o, t in self._remapped_chunks(out, target):
+                self.sums(o, t, into=sums)
+            return sums
         _lib.require_cuda_tensor(out, "out")
         _lib.require_cuda_tensor(target, "target")
         out, target = out.contiguous(), target.contiguous()
@@ -65,7 +131,8 @@ class RolloutMetrics:
 
     def __call__(self, out: torch.Tensor, target: torch.Tensor, world_size: int = 1):
         """Returns {"rmse": [K, C], "acc": [K, C] or None} over ALL ranks' samples."""
-        return self.finalize(self.sums(out, target), float(out.shape[0]), out.shape[-2] * out.shape[-1], world_size)
+        cells = len(self._lats) * len(self._lons) if out.dim() == 6 and self._lons is not None else out.shape[-2] * out.shape[-1]
+        return self.finalize(self.sums(out, target), float(out.shape[0]), cells, world_size)
 
     def finalize(self, s: torch.Tensor, n_samples: float, cells: int, world_size: int = 1):
         """Scores from accumulated sums: `s` = this rank's [4, K, C] sums (of one batch, or ADDED UP over many -- the
@@ -100,7 +167,7 @@ def circumference_weights(lats_deg: torch.Tensor) -> torch.Tensor:
     return torch.cos(lats_deg.double() * (math.pi / 180)) * (2 * math.pi * EARTH_RADIUS_M)
 
 
-class ZonalSpectrumMetrics:
+class ZonalSpectrumMetrics(_HealpixInput):
     """Zonal energy spectra of a rollout [B, K, C, H, W] and its targets, and their mean energy log ratio (reference
     scripts/losses.py:16-152, `ZonalSpectrum` + `MELRCalculator`), reduced on the device (dlwp_zonal_power_sums_f32).
 
@@ -108,10 +175,13 @@ class ZonalSpectrumMetrics:
     W longitudes with every m > 0 doubled; log_ratio = ln((E_pred + 1e-10) / (E_true + 1e-10)); MELR = its mean over
     m = 0 .. W/2.  The reference places its latitudes at np.linspace(-90, 90, H) (losses.py:88): pass
     `torch.linspace(-90, 90, H)` as `lats_deg` to reproduce scripts/train.py:434-445, or the grid's own cell centres.
-    Fields are scored as given (the reference scores normalised fields).  W must be a power of two from 32 to 512;
-    HEALPix [B, K, F, C, H, W] rollouts are not remapped to lat-lon and are refused."""
+    Fields are scored as given (the reference scores normalised fields).  W must be a power of two from 32 to 512.
+    With `lons_deg` (the W longitudes of the lat-lon grid) HEALPix rollouts [B, K, C, 12, n, n] are taken too: they are remapped
+    to (lats_deg, lons_deg) on the device as scripts/train.py:430-441 remaps them on the host, in chunks of samples whose lat-lon
+    copies stay within `max_workspace_bytes`; without it they are refused."""
 
-    def __init__(self, lats_deg: torch.Tensor, group=None):
+    def __init__(self, lats_deg: torch.Tensor, group=None, lons_deg=None, max_workspace_bytes: int = DEFAULT_WORKSPACE_BYTES):
+        self._init_remap(lats_deg, lons_deg, max_workspace_bytes)
         self.circ = circumference_weights(torch.as_tensor(lats_deg))
         self.height = int(self.circ.numel())
         self.group = group
@@ -137,12 +207,21 @@ class ZonalSpectrumMetrics:
     def sums(self, out: torch.Tensor, target: torch.Tensor, into: Optional[torch.Tensor] = None) -> torch.Tensor:
         """double [2, K, C, W//2 + 1]: 0 = sum over this rank's samples and latitudes of circ_h P(out), 1 = of P(target)
         (dlwp_zonal_power_sums_f32).  `into`: a [2, K, C, W//2 + 1] double tensor of running sums the new ones are ADDED to
-        (dlwp_zonal_power_sums_acc_f32); it is returned."""
+        (dlwp_zonal_power_sums_acc_f32); it is returned.  A HEALPix rollout [B, K, C, 12, n, n] (see `lons_deg`) is remapped chunk
+        by chunk and summed into zero-initialised (or `into`) sums."""
         _lib.require_cuda_tensor(out, "out")
         _lib.require_cuda_tensor(target, "target")
+        if out.dim() == 6 and self._lons is not None:
+            self._require_remap(out, target)
+            sums = into if into is not None else torch.zeros(2, out.shape[1], out.shape[2], len(self._lons) // 2 + 1,
+                                                             dtype=torch.float64, device=out.device)
+            for o, t in self._remapped_chunks(out, target):
+                self.sums(o, t, into=sums)
+            return sums
         if out.dim() != 5:
             raise _lib.DlwpError(f"zonal spectrum: expected a lat-lon rollout [B, K, C, H, W], got {out.dim()}-D shape "
-                                 f"{tuple(out.shape)} (HEALPix rollouts are not remapped to lat-lon)")
+                                 f"{tuple(out.shape)} (a HEALPix rollout [B, K, C, 12, n, n] is remapped to lat-lon only when the "
+                                 "metric is built with `lons_deg`)")
         if target.shape != out.shape:
             raise _lib.DlwpError(f"target shape {tuple(target.shape)} != output shape {tuple(out.shape)}")
         if target.device != out.device:

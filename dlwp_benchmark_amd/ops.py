@@ -4,6 +4,7 @@ which owns the device guard, the stream, pointer marshalling and the status chec
 No wrapper has a CPU path."""
 import ctypes
 import functools
+import math
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
@@ -528,6 +529,37 @@ def healpix_pad_backward(dy: torch.Tensor, padding: int) -> torch.Tensor:
     dx = torch.empty(n, c, h, w, device=dy.device, dtype=torch.float32)
     _lib.launch("dlwp_healpix_pad_bwd_f32", dy.device, dy, dx, adj.indptr, adj.index, adj.weight, n, c, h, w, p)
     return dx
+
+
+def healpix_to_latlon(x: torch.Tensor, lats_deg, lons_deg, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """HEALPix fields [..., 12, n, n] -> lat-lon fields [..., H, W] at (lats_deg[j], lons_deg[i]) by the HEALPix library's
+    bilinear interpolation (dlwp_healpix_to_latlon_f32; the reference: HEALPixRemap.hpx2ll, healpix_mapping.py:372-404, per plane
+    on the host).  `healpix.reference_grid(H, W)` gives the grid hpx2ll itself produces.  `out`: a contiguous float32
+    [..., H, W] tensor on the same device to write into (the metric classes' reused workspace); it is returned."""
+    from . import healpix as _hpx
+
+    _lib.require_cuda_tensor(x, "x")
+    if x.dim() < 3 or x.shape[-3] != 12:
+        raise _lib.DlwpError(f"expected HEALPix fields [..., 12, n, n], got shape {tuple(x.shape)}")
+    n = int(x.shape[-1])
+    if x.shape[-2] != n:
+        raise _lib.DlwpError(f"HEALPix faces are square, got {x.shape[-2]}x{n}")
+    if n < 2 or n & (n - 1):
+        raise _lib.DlwpError(f"nside must be a power of two >= 2, got {n}")
+    table = _hpx.device_latlon_table(n, lats_deg, lons_deg, x.device)
+    lead = tuple(x.shape[:-3])
+    planes = math.prod(lead)
+    h = len(lats_deg)
+    cells = int(table.index.shape[0])
+    shape = lead + (h, cells // h)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    elif (not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != x.device
+          or not out.is_contiguous()):
+        raise _lib.DlwpError(f"out must be a contiguous float32 {shape} tensor on {x.device}")
+    if planes:
+        _lib.launch("dlwp_healpix_to_latlon_f32", x.device, x.contiguous(), table.index, table.weight, out, planes, n, cells)
+    return out
 
 
 def conv3x3_hpx_backward_data(dy: torch.Tensor, weight: torch.Tensor, cin: int) -> torch.Tensor:

@@ -563,6 +563,20 @@ int32_t dlwp_conv3x3_hpx_bwd_data_f32(const float* dy_dev, const float* weight_d
                                       const float* adj_weight_dev, void* workspace, size_t workspace_bytes,
                                       void* stream);
 
+/* HEALPix -> lat-lon remap of rollouts for scoring (csrc/healpix_remap.hip).  Replaces reference scripts/evaluate.py:79-116
+ * (`HEALPixRemap.hpx2ll`, data/processing/healpix_mapping.py:372-404, once per (sample, step, variable) plane in a pool of host
+ * processes: a Python loop over the pixels plus reproject's bilinear interpolation), as called at evaluate.py:298-303 and
+ * scripts/train.py:430-441.  The geometry is handed over as a table of four taps per lat-lon cell (healpix.latlon_table: the
+ * HEALPix library's bilinear interpolation in the reference's face layout, weights rounded once from float64):
+ *   x_dev [planes, 12 * nside^2] (a plane = one [12, nside, nside] field), index_dev int32 [cells, 4] with every entry in
+ *   0 .. 12 nside^2 - 1 (checked by the host builder, NOT here), weight_dev float [cells, 4], both 16-byte aligned,
+ *   y_dev [planes, cells]:  y[p][q] = ((w0 x[p][i0] + w1 x[p][i1]) + w2 x[p][i2]) + w3 x[p][i3] in fp32, in this order; a tap
+ *   of weight zero is still read (a NaN there gives NaN, as in numpy).
+ * Any planes >= 1 (64-bit; planes sit on the 31-bit grid axis, DLWP_ERR_UNSUPPORTED beyond it) and any cells >= 1.  One launch
+ * on `stream`, no host synchronisation, no atomics; y_dev may not alias x_dev. */
+int32_t dlwp_healpix_to_latlon_f32(const float* x_dev, const int32_t* index_dev, const float* weight_dev, float* y_dev,
+                                   int64_t planes, int32_t nside, int32_t cells, void* stream);
+
 /* Weight and bias gradient of pad(1) + Conv2d(3x3, padding 0) on cat([x0, x1], 1), either padding rule (csrc/conv3x3_wgrad.hip;
  * the reference lines differentiated: scripts/train.py:271 through models/unet/unet.py:456-470, :512-525, :886,
  * models/convlstm/convlstm.py:94, :148-157, utils/healpix.py:69-114):

@@ -1234,6 +1234,21 @@ constexpr bool kDftBf16 = DLWP_TRUNK_DFT_BF16 != 0;
 // checked when the plan is made -- a plan with larger ones takes the bf16x6 form), so everything sits at 2^14 times the true scale
 constexpr int kTrunkF16Shift = 3;
 constexpr float kTrunkF16Up = 16384.0f, kTrunkF16Down = 1.0f / 16384.0f;
+// Seam between two steps of the fused kernel when the lifting MLP is read from the plan's table:
+// the exact path's weights are staged only in a step in which some wave of the workgroup falls back to it (the "vote").
+// A/B switches (tools/ab_build.sh): -DDLWP_LIFT_STAGE_ALWAYS = the earlier seam (request before the end-of-step barrier, LDS
+// write and a second barrier behind it, a third one behind the lifting); -DDLWP_LIFT_GATHER_EARLY = a wave gathers its
+// next row from the table BEFORE the barrier of the seam (tried: 304 instead of 184 bytes of scratch per lane).
+#if defined(DLWP_LIFT_STAGE_ALWAYS) || defined(DLWP_NO_LIFT_TABLE)
+constexpr bool kLiftVote = false;
+#else
+constexpr bool kLiftVote = true;
+#endif
+#ifdef DLWP_LIFT_GATHER_EARLY
+constexpr bool kLiftGatherEarly = true;
+#else
+constexpr bool kLiftGatherEarly = false;
+#endif
 constexpr int kSyStride = 528;   // floats per Y row in LDS: 16 k' x 32 c + 16 (bank spread for the P1 B reads)
 
 struct TrunkParams {
@@ -1478,6 +1493,7 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
   float* s_tt = s_t + KP * W;                             // [64][16]      TT (forward W-DFT twiddles)
   int* s_fail = reinterpret_cast<int*>(s_tt + W * KP);
   int* s_fast = s_fail + 1;                               // LL: the sample's group shares one XCD (found in layer 0)
+  int* s_lflag = s_fail + 2;                              // STEP: [2] some wave evaluates the exact lifting MLP (by step parity)
   float2* s_ef = reinterpret_cast<float2*>(s_fail + 4);   // [16][ROWS]  EF rows of this workgroup's grid rows (0 beyond M1)
   float2* s_ei = s_ef + 16 * ROWS;                        // [16][ROWS]  EI likewise
   u32x4* s_tb = reinterpret_cast<u32x4*>(s_ei + 16 * ROWS);   // [4][3][64]  inverse W-DFT B operands (bf16x3)
@@ -1503,6 +1519,7 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
   if (tid == 0) {
     *s_fail = 0;
     *s_fast = 0;
+    s_lflag[0] = s_lflag[1] = 0;
     if (LL) {
       const unsigned xcc = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) & 0xFu;   // HW_REG_XCC_ID
       __hip_atomic_store(p.xcc_tab + sample * 32 + member, ((p.layer0 + 1u) << 4) | xcc, __ATOMIC_RELAXED,
@@ -1528,10 +1545,8 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
   int n_stamp = 0;
   const int n_steps = (STEP && p.n_steps > 1) ? p.n_steps : 1;
   f32x4 vfeed = {0.f, 0.f, 0.f, 0.f};   // feed_regs: the previous step's output of this lane (channel g, pixels 4j..4j+3)
-  // the lifting weights of the NEXT step are requested before the end-of-step barrier and written to LDS behind it
-  // (staged = they are already there when the step starts)
-  u32x4 pre_w2[6];
-  float pre_w1[8], pre_b1 = 0.f;
+  // no live table: the lifting weights of the NEXT step are requested before the end-of-step barrier and written to LDS
+  // behind it (staged = they are already there when the step starts)
   bool staged = false;
   for (int st = 0; st < n_steps; ++st) {
   // Everything lane-dependent is re-derived from an OPAQUE copy of the thread index inside the step loop: otherwise
@@ -1557,11 +1572,28 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
     u32x4* l_w2 = reinterpret_cast<u32x4*>(smem);                          // [npair][3][2][64]
     float* l_w1 = reinterpret_cast<float*>(l_w2 + npair * 6 * 64);         // [ntile][ns][64]
     float* l_b1 = l_w1 + ntile_l * p.lift_ns * 64;                         // [hid]
-    if (!staged) {
+    auto lift_stage = [&]() {
       for (int i = tid; i < npair * 6 * 64; i += NT) l_w2[i] = p.lift_w2b[i];
       for (int i = tid; i < ntile_l * p.lift_ns * 64; i += NT) l_w1[i] = p.lift_w1p[i];
       for (int i = tid; i < p.lift_hid; i += NT) l_b1[i] = p.lift_b1[i];
-    }
+    };
+    auto lift_stage_voted = [&]() {   // the same copy, rolled: rare, its latency is exposed anyway, and the step's input is live
+#pragma unroll 1
+      for (int i = tid; i < npair * 6 * 64; i += NT) l_w2[i] = p.lift_w2b[i];
+#pragma unroll 1
+      for (int i = tid; i < ntile_l * p.lift_ns * 64; i += NT) l_w1[i] = p.lift_w1p[i];
+#pragma unroll 1
+      for (int i = tid; i < p.lift_hid; i += NT) l_b1[i] = p.lift_b1[i];
+    };
+    // vote: with a live table the exact path's weights are staged only in a step in which some wave of the workgroup
+    // falls back to it.  Every wave knows its next input row BEFORE the barrier of the step seam (the one that ends the
+    // previous projection's reads of this LDS region), so a wave that will fall back raises a flag in front of that barrier
+    // and every wave reads it behind it.  No flag: no weight request, no LDS write, and this barrier is the only one
+    // between the projection and the transpose tiles.  Two flag words alternate by step: the word of step s is written
+    // before and read behind the seam barrier of step s, and cleared behind the seam barrier of step s - 1 -- the
+    // barriers of the spectral layers and of the projection lie between that clear and the next write.
+    const bool vote = kLiftVote && p.lift_tab != nullptr;
+    if (!vote && !staged) lift_stage();
     f32x4 xs[4];
     if (p.feed_regs && st > 0) {
       xs[0] = vfeed;
@@ -1577,15 +1609,12 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
     f32x4 bias2[2];
     bias2[0] = *reinterpret_cast<const f32x4*>(p.lift_b2 + 4 * g);
     bias2[1] = *reinterpret_cast<const f32x4*>(p.lift_b2 + 16 + 4 * g);
-    lds_barrier();
-    if (p.trace && tid == p.trace_tid && n_stamp < 64) p.trace[blockIdx.x * 64 + n_stamp++] = __builtin_amdgcn_s_memrealtime();
     // One input channel and a table from the plan: the wave reads lift(x) from it when EVERY pixel of its row lies inside the
     // table's domain (one ballot; NaN and +-inf fail the test) and evaluates the MLP as before otherwise -- the decision
     // depends on the row's own data only, and no load address is formed from an unchecked x.
     bool from_table = false;
     f32x4 xp = {0.f, 0.f, 0.f, 0.f};
-#ifndef DLWP_NO_LIFT_TABLE   // A/B switch (tools/ab_build.sh): the kernel without the table path
-    if (p.lift_tab) {
+    auto lift_pick = [&]() {
       // The gather runs in a PERMUTED lane order: lane 4 j' + g' reads what resident lane (j', g') needs, so the four lanes
       // of a pixel are neighbours and their 16-byte loads cover 64 contiguous bytes of one line (one tag look-up instead of
       // four: in the resident order every lane of a 16-lane pass touched a line of its own and the phase ran at the L1's
@@ -1597,9 +1626,8 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
         inside = inside && (fabsf(xp[q]) < (float)kLiftTabRange);
       }
       from_table = __all(inside) != 0;
-    }
-#endif
-    if (from_table) {
+    };
+    auto lift_gather = [&]() {
       f32x4 vp[2][4];
       lift_from_table(p.lift_tab, xp, lane & 3, vp);
 #pragma unroll
@@ -1608,17 +1636,59 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
         for (int r = 0; r < 4; ++r)
 #pragma unroll
           for (int q = 0; q < 4; ++q) vv[ot][r][q] = __shfl(vp[ot][r][q], 4 * j + g);
-    } else {
+    };
+    auto lift_exact = [&]() {
       f32x4 acc2[2][4];
       lift_segment<4, F16>(xs, l_w1, l_b1, l_w2, npair, lane, bias2, acc2, p.lift_ns, p.lift_cin1 != 0, p.lift_up, p.lift_down);
 #pragma unroll
       for (int ot = 0; ot < 2; ++ot)
 #pragma unroll
         for (int r = 0; r < 4; ++r) vv[ot][r] = f32x4{acc2[ot][0][r], acc2[ot][1][r], acc2[ot][2][r], acc2[ot][3][r]};
+    };
+#define DLWP_LIFT_STAMP()                                                                              \
+  do {                                                                                                 \
+    if (p.trace && tid == p.trace_tid && n_stamp < 64) p.trace[blockIdx.x * 64 + n_stamp++] = __builtin_amdgcn_s_memrealtime(); \
+  } while (0)
+    if (vote) {
+      lift_pick();
+      if (!from_table) s_lflag[st & 1] = 1;
     }
-    if (p.trace && tid == p.trace_tid && n_stamp < 64) p.trace[blockIdx.x * 64 + n_stamp++] = __builtin_amdgcn_s_memrealtime();
-    lds_barrier();   // every wave is done with the lifting weights: the region turns into transpose tiles
-    if (p.trace && tid == p.trace_tid && n_stamp < 64) p.trace[blockIdx.x * 64 + n_stamp++] = __builtin_amdgcn_s_memrealtime();
+    if (kLiftGatherEarly && vote && from_table) {
+      // The gather needs no LDS: a wave that is early runs it while the slower waves finish their projection.  (A branch
+      // of its own, with the same barriers as the other one: in a shared one vv would stay live across lift_exact.)
+      lift_gather();
+      DLWP_LIFT_STAMP();
+      lds_barrier();   // the seam: every wave is done with the projection weights, every flag of this step is up
+      DLWP_LIFT_STAMP();
+      const bool fallback = __builtin_amdgcn_readfirstlane(s_lflag[st & 1]) != 0;
+      if (tid == 0) s_lflag[(st + 1) & 1] = 0;
+      if (fallback) {   // other waves of the workgroup evaluate the MLP: help to stage its weights, wait until they are done
+        lift_stage_voted();
+        lds_barrier();
+        lds_barrier();
+      }
+      DLWP_LIFT_STAMP();
+    } else {
+      bool weights_used = true;   // the exact path's weights are in LDS (or on their way) and some wave may read them
+      if (vote) {
+        DLWP_LIFT_STAMP();
+        lds_barrier();   // the seam: every wave is done with the projection weights, every flag of this step is up
+        weights_used = __builtin_amdgcn_readfirstlane(s_lflag[st & 1]) != 0;
+        if (tid == 0) s_lflag[(st + 1) & 1] = 0;
+      }
+      if (vote && weights_used) lift_stage_voted();
+      if (weights_used) lds_barrier();
+      DLWP_LIFT_STAMP();
+#if defined(DLWP_LIFT_STAGE_ALWAYS) && !defined(DLWP_NO_LIFT_TABLE)
+      if (p.lift_tab) lift_pick();
+#endif
+      if (!from_table) lift_exact();
+      else if (!kLiftVote || !kLiftGatherEarly) lift_gather();
+      if (!vote) DLWP_LIFT_STAMP();
+      if (weights_used) lds_barrier();   // every wave is done with the lifting weights: the region turns into transpose tiles
+      DLWP_LIFT_STAMP();
+    }
+#undef DLWP_LIFT_STAMP
 #pragma unroll
     for (int ot = 0; ot < 2; ++ot)
 #pragma unroll
@@ -2102,6 +2172,8 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
     lds_barrier();
     // the lifting weights of the next step, requested into registers: DLWP_PREFETCH_EARLY = 1 before the projection (they
     // travel under its 16 us), 0 right before the end-of-step barrier (~2 us of L2 latency stay exposed behind it)
+    u32x4 pre_w2[6];
+    float pre_w1[8], pre_b1 = 0.f;
     auto lift_prefetch = [&]() {
       const int n_w2p = (p.lift_hid >> 5) * 6 * 64, n_w1p = (p.lift_hid >> 4) * p.lift_ns * 64;
 #pragma unroll
@@ -2117,7 +2189,7 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
       pre_b1 = p.lift_b1[tid < p.lift_hid ? tid : 0];
     };
 #if DLWP_PREFETCH_EARLY
-    if (st + 1 < n_steps) lift_prefetch();
+    if (st + 1 < n_steps && !(kLiftVote && p.lift_tab != nullptr)) lift_prefetch();
 #endif
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     auto run = [&](auto coc) {
@@ -2159,18 +2231,23 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
     if (p.trace && tid == p.trace_tid && n_stamp < 64) p.trace[blockIdx.x * 64 + n_stamp++] = __builtin_amdgcn_s_memrealtime();
     if (st + 1 < n_steps) {
       const int npair_n = p.lift_hid >> 5, n_w2 = npair_n * 6 * 64, n_w1 = (p.lift_hid >> 4) * p.lift_ns * 64;
-#if !DLWP_PREFETCH_EARLY
-      lift_prefetch();
-#endif
-      if (p.feed_regs) {
-        vfeed = (g < p.cout) ? v : f32x4{0.f, 0.f, 0.f, 0.f};   // next input + residual: no store -> load round trip, no drain
+      auto feed_next = [&]() {
+        if (p.feed_regs) {
+          vfeed = (g < p.cout) ? v : f32x4{0.f, 0.f, 0.f, 0.f};   // next input + residual: no store -> load round trip, no drain
+        } else {
+          // the next step's input rows are the ones this wave has just written: drain the stores, drop any L1 copy
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        }
+      };
+      if (kLiftVote && p.lift_tab != nullptr) {
+        feed_next();   // the next step votes: no weight request here, and the barrier of the seam is the one behind its vote
       } else {
-        // the next step's input rows are the ones this wave has just written: drain the stores, drop any L1 copy
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-      }
-      lds_barrier();   // every wave is done with the projection weights: the lifting weights may overwrite them
-      {
+#if !DLWP_PREFETCH_EARLY
+        lift_prefetch();
+#endif
+        feed_next();
+        lds_barrier();   // every wave is done with the projection weights: the lifting weights may overwrite them
         u32x4* l_w2n = reinterpret_cast<u32x4*>(smem);
         float* l_w1n = reinterpret_cast<float*>(l_w2n + n_w2);
         float* l_b1n = l_w1n + n_w1;
@@ -2185,8 +2262,8 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
           if (i < n_w1) l_w1n[i] = pre_w1[k];
         }
         if (tid < p.lift_hid) l_b1n[tid] = pre_b1;
+        staged = true;
       }
-      staged = true;
     }
     continue;
   }

@@ -1,10 +1,18 @@
 """Phase timeline of fno_trunk_kernel from a DLWP_TRUNK_TRACE dump (100 MHz s_memrealtime stamps).
-usage: DLWP_TRUNK_TRACE=gpurun_out/trunk_trace.txt python tools/trunk_trace.py gpurun_out/trunk_trace.txt"""
+usage: DLWP_TRUNK_TRACE=trunk_trace.txt python tools/trunk_trace.py trunk_trace.txt [--staged-seam]
+
+The first four stamps of a step depend on the seam the kernel ran.  With a live lifting table the
+workgroup votes: "step top" = previous projection done -> this step's top, "lift vote" = input row, domain test, flag,
+"seam barrier" = wait for the workgroup's slowest wave (plus, after a vote for it, staging the exact MLP's weights and the
+barrier behind that), "lift" = gather from the table or the exact MLP (and then the barrier that frees its weights).  --staged-seam names them for the seam that always stages the exact path's weights
+(no live table: DLWP_FNO_LIFT_TABLE=0, more input channels, a rejected table; or a -DDLWP_LIFT_STAGE_ALWAYS build):
+"step top" = end-of-step barrier + LDS write, "lift staged" = barrier, "lift seg" = gather or MLP, "lift all waves" = barrier."""
 import os
 import sys
 
 import numpy as np
 
+staged_seam = "--staged-seam" in sys.argv[2:] or os.environ.get("DLWP_FNO_LIFT_TABLE", "1") == "0"
 path = sys.argv[1]
 if not os.path.exists(path) or os.environ.get("DLWP_TRUNK_TRACE"):
     import torch
@@ -21,7 +29,9 @@ if not os.path.exists(path) or os.environ.get("DLWP_TRUNK_TRACE"):
 rows = [list(map(int, l.split())) for l in open(path)]
 names = ["start"]
 if os.environ.get("DLWP_FNO_STEP", "1") != "0":
-    names = ["step top", "lift staged", "lift seg", "lift all waves", "lift done", "trunk setup"]
+    names = ["step top", "lift vote", "seam barrier", "lift", "lift done", "trunk setup"]
+    if staged_seam:
+        names = ["step top", "lift staged", "lift seg", "lift all waves", "lift done", "trunk setup"]
 for l in range(4):
     names += [f"L{l} y-ready", f"L{l} P1 done", f"L{l} barrier1", f"L{l} P2 done", f"L{l} barrier2", f"L{l} P3+sync",
               f"L{l} skip+idft"]

@@ -258,6 +258,18 @@ SIGNATURES = {
                                                    c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                                    ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                    c_void_p, c_size_t, c_void_p]),
+    "dlwp_mt_chunk_elems": (c_int32, []),
+    "dlwp_mse_loss_partials": (c_int32, [ctypes.c_int64]),
+    "dlwp_mse_loss_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, ctypes.c_int64,
+                                    ctypes.c_int64, c_void_p]),
+    "dlwp_mse_loss_scale_grad_f32": (c_int32, [c_void_p, c_void_p, c_int32, ctypes.c_int64, c_void_p]),
+    "dlwp_mt_grad_norm_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_float, c_void_p, c_void_p]),
+    "dlwp_mt_scale_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "dlwp_mt_zero_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    "dlwp_mt_adamw_f32": (c_int32, [c_void_p] * 8 + [c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                    c_void_p]),
+    "dlwp_mt_ema_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_float, c_float,
+                                  c_void_p]),
 }
 
 _lib = None

@@ -1881,3 +1881,59 @@ def gc_segment_sum(x: torch.Tensor, batch: int, row_ptr: Optional[torch.Tensor],
     _lib.launch("dlwp_gc_segment_sum_f32", x.device, x, x.numel() // batch, row_ptr, perm, n_segments, d, batch, int(batch_sum),
                 out)
     return out
+
+
+def _mse_weight(weight: Optional[torch.Tensor], x: torch.Tensor):
+    """(the weight on x's device, contiguous, broadcast to the trailing dimensions of x it spans, or None; the element count of
+    that span)"""
+    if weight is None:
+        return None, max(int(x.shape[-1]), 1) if x.dim() else 1
+    if weight.dtype not in (torch.float32, torch.float64):
+        raise _lib.DlwpError(f"mse_loss: the weight must be float32 or float64 (got {weight.dtype})")
+    lead = x.dim() - weight.dim()
+    try:
+        weight = torch.broadcast_to(weight, x.shape[lead:]) if lead >= 0 else None
+    except RuntimeError:
+        weight = None
+    if weight is None or weight.numel() == 0:
+        raise _lib.DlwpError(f"mse_loss: the weight must broadcast to trailing dimensions of the input, {tuple(x.shape)}")
+    return weight.to(x.device).contiguous(), weight.numel()
+
+
+def mse_loss_forward(x: torch.Tensor, target: torch.Tensor, weight: Optional[torch.Tensor] = None, need_grad: bool = False):
+    """mean((target - x)^2 weight) on dlwp_mse_loss_f32 (reference scripts/losses.py:175-188): (loss, grad).  weight: None or
+    a float32 / float64 tensor whose shape is the trailing dimensions of x; a float64 weight is used as float64 and the loss
+    is then a float64 scalar, as the reference's promotion gives.  grad = d loss / d x = 2 (x - target) weight / N, written in
+    the same pass when need_grad, else None (nothing is allocated for it).  One pass and a single-workgroup finish, no host
+    synchronisation, bitwise identical reruns."""
+    _lib.require_cuda_tensor(x, "input")
+    _lib.require_cuda_tensor(target, "target")
+    if x.shape != target.shape or x.numel() == 0:
+        raise _lib.DlwpError(f"mse_loss: input {tuple(x.shape)} and target {tuple(target.shape)} must have one non-empty shape")
+    x, target = x.contiguous(), target.contiguous()
+    weight, inner = _mse_weight(weight, x)
+    n = x.numel()
+    grad = torch.empty_like(x) if need_grad else None
+    partials = torch.empty(int(_lib.load().dlwp_mse_loss_partials(n)), dtype=torch.float64, device=x.device)
+    out = torch.empty(2, dtype=torch.float64, device=x.device)
+    w64 = weight is not None and weight.dtype == torch.float64
+    _lib.launch("dlwp_mse_loss_f32", x.device, x, target, weight, int(w64), grad, partials, out, n // inner, inner)
+    return (out[0] if w64 else out.view(torch.float32)[2]), grad
+
+
+def mse_loss_scale_grad(grad: torch.Tensor, upstream: torch.Tensor) -> torch.Tensor:
+    """grad *= upstream in place on dlwp_mse_loss_scale_grad_f32: upstream is a one-element float32 / float64 device tensor
+    that is read on the device; when it is exactly 1 the kernel touches nothing."""
+    _lib.require_cuda_tensor(grad, "grad")
+    if not upstream.is_cuda or upstream.numel() != 1 or upstream.dtype not in (torch.float32, torch.float64):
+        raise _lib.DlwpError("mse_loss: the upstream gradient must be a float32 / float64 device scalar")
+    _lib.launch("dlwp_mse_loss_scale_grad_f32", grad.device, grad, upstream.contiguous(), int(upstream.dtype == torch.float64),
+                grad.numel())
+    return grad
+
+
+def mse_loss(x: torch.Tensor, target: torch.Tensor, weight: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The reference's CustomMSELoss with reduction 'mean' (scripts/losses.py:175-188), differentiable with respect to x:
+    training._MseLossFn (HIP forward that writes the gradient in the same pass)."""
+    from . import training as _T
+    return _T.mse_loss(x, target, weight)

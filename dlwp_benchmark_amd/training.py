@@ -1320,3 +1320,51 @@ def gc_layer(edge_seq, edge_packed, node_seq, node_packed, aggregation: str, gra
     destination), src_row_ptr, src_perm (ops.mgn_source_csr), n_src, n_dst."""
     cfg = (edge_seq, edge_packed, node_seq, node_packed, aggregation, graph, batch, residual)
     return _GcLayerFn.apply(e, xs, xd, cfg, *edge_seq.parameters(), *node_seq.parameters())
+
+
+def mse_loss_torch(x, target, weight=None):
+    """mean((target - x)^2 weight): the reference's CustomMSELoss.forward with reduction 'mean' (scripts/losses.py:175-188) as
+    plain torch operators on any device; a float64 weight promotes the product, as there."""
+    d = (target - x) ** 2
+    if weight is not None:
+        d = d * torch.as_tensor(weight, device=x.device)
+    return torch.mean(d)
+
+
+class _MseLossFn(torch.autograd.Function):
+    """loss = mean((target - x)^2 weight) on dlwp_mse_loss_f32.  When x needs a gradient the forward writes
+    d loss / d x = 2 (x - target) weight / N in the same pass (x and target are read once in the whole step); the backward only
+    multiplies it by the upstream scalar, on the device, and that kernel touches nothing when the scalar is exactly 1 (the
+    `loss.backward()` of train.py:271).  target and weight get no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, target, weight):
+        need = ctx.needs_input_grad[0]
+        with torch.no_grad():
+            loss, grad = ops.mse_loss_forward(x.detach(), target.detach(), weight, need_grad=need)
+        if need:
+            ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        (grad,) = ctx.saved_tensors
+        with torch.no_grad():
+            if getattr(ctx, "_used", False):        # the saved gradient was scaled in place: it serves one backward
+                raise _lib.DlwpError("mse_loss: a second backward through the same loss is not supported")
+            ctx._used = True
+            g = ops.mse_loss_scale_grad(grad, grad_out)
+        return g, None, None
+
+
+def mse_loss(x, target, weight=None):
+    """differentiable (in x) weighted mean squared error: HIP forward with the gradient written in the same pass; under
+    DLWP_TRAIN_TORCH_BACKWARD=1 mse_loss_torch, left to autograd.  A target or weight that requires a gradient is outside
+    the kernel's scope and raises."""
+    if _torch_backward_selected():
+        return mse_loss_torch(x, target, weight)
+    if target.requires_grad or (weight is not None and weight.requires_grad):
+        raise _lib.DlwpError("mse_loss: only the input can require a gradient")
+    return _MseLossFn.apply(x, target, weight)

@@ -1037,6 +1037,68 @@ int32_t dlwp_gc_segment_sum_f32(const float* in, int64_t in_batch_stride, const 
                                 int32_t n_segments, int32_t width, int32_t batch, int32_t batch_sum, float* out,
                                 void* stream);
 
+/* The tail of a training step (csrc/optim.hip): everything scripts/train.py:186-312 does once the gradients exist.  All
+ * arithmetic is fp32 unless stated; every reduction has a fixed order and one writer (no float atomics): reruns are bitwise
+ * identical.  No entry point reads a device value on the host, and no step-dependent value is an argument: a recorded step
+ * replays.
+ *
+ * The multi-tensor table (the dlwp_mt_* calls) is a set of device arrays, built once by the caller:
+ *   per tensor t   p_ptrs_dev[t], g_ptrs_dev[t]: the addresses of the parameter and of its gradient as int64 (g 0: no
+ *                  gradient this step, the tensor is skipped); numel_dev[t]; state_off_dev[t]: its element offset into the
+ *                  flat state arenas (exp_avg, exp_avg_sq, shadow), a multiple of 4; group_dev[t]: its parameter group;
+ *                  step_dev[t]: its step count; derived_dev[t][8]: scratch the AdamW header kernel fills
+ *   per group g    hyper_dev[g][5] doubles: lr, beta1, beta2, eps, weight_decay
+ *   per chunk c    chunk_tensor_dev[c], chunk_first_dev[c]: dlwp_mt_chunk_elems() consecutive elements of one tensor (fewer
+ *                  at its end), chunk_first a multiple of that number; the chunks cover every element exactly once
+ * A workgroup takes whole chunks; the grid is capped at 2048 workgroups and strided above.  16-byte accesses where the
+ * tensor's pointers are 16-byte aligned, 4-byte ones for a tensor that is not and for every ragged tail. */
+int32_t dlwp_mt_chunk_elems(void);
+/* criterion(output, target) of train.py:263 with CustomMSELoss (scripts/losses.py:175-188): mean((t - x)^2 w) over x_dev,
+ * t_dev viewed as [outer, inner] and w_dev [inner] (NULL: unweighted; w_is_f64: a float64 weight, used as float64 as the
+ * reference's promotion does).  One pass reads x and t once, leaves dlwp_mse_loss_partials(outer * inner) per-workgroup
+ * partial sums in partials_dev (doubles) and, when grad_dev is given, writes d loss / d x = 2 (x - t) w / N in the same pass;
+ * a single-workgroup finish adds the partials in a fixed order in double.  out_dev is a 16-byte block: the mean as a double
+ * in bytes 0-7 and as a float in bytes 8-11.  The per-element arithmetic is double.
+ *   dlwp_mse_loss_partials: min(ceil(n / 4096), 2048), 0 for n <= 0.
+ *   dlwp_mse_loss_scale_grad_f32: grad *= upstream (a device scalar, float or double): the backward under an upstream
+ *     gradient; reads and writes nothing when the scalar is exactly 1. */
+int32_t dlwp_mse_loss_partials(int64_t n);
+int32_t dlwp_mse_loss_f32(const float* x_dev, const float* t_dev, const void* w_dev, int32_t w_is_f64, float* grad_dev,
+                          double* partials_dev, double* out_dev, int64_t outer, int64_t inner, void* stream);
+int32_t dlwp_mse_loss_scale_grad_f32(float* grad_dev, const void* upstream_dev, int32_t upstream_is_f64, int64_t n,
+                                     void* stream);
+/* th.nn.utils.clip_grad_norm_(model.parameters(), max_norm) of train.py:299-305, norm type 2, with the arithmetic of
+ * torch/nn/utils/clip_grad.py:165-169 (torch 2.10):  dlwp_mt_grad_norm_f32 writes one sum of squares per chunk to partials_dev [n_chunks] and
+ * a finish kernel adds them in double, then writes scal_dev[0] = total_norm and scal_dev[1] = clip_coef =
+ * min(1, max_norm / (total_norm + 1e-6)) (a NaN stays NaN).  dlwp_mt_scale_f32: g *= scal_dev[1] in place, also when it
+ * is 1, as torch does. */
+int32_t dlwp_mt_grad_norm_f32(const int64_t* g_ptrs_dev, const int64_t* numel_dev, const int32_t* chunk_tensor_dev,
+                              const int64_t* chunk_first_dev, int32_t n_chunks, float* partials_dev, float max_norm,
+                              float* scal_dev, void* stream);
+int32_t dlwp_mt_scale_f32(const int64_t* g_ptrs_dev, const int64_t* numel_dev, const int32_t* chunk_tensor_dev,
+                          const int64_t* chunk_first_dev, int32_t n_chunks, const float* scal_dev, void* stream);
+/* optimizer.zero_grad() of train.py:186 with the gradient storage kept: every gradient of the table becomes 0. */
+int32_t dlwp_mt_zero_f32(const int64_t* g_ptrs_dev, const int64_t* numel_dev, const int32_t* chunk_tensor_dev,
+                         const int64_t* chunk_first_dev, int32_t n_chunks, void* stream);
+/* optimizer.step() of train.py:309 with th.optim.AdamW (train.py:59; torch 2.10's
+ * torch/optim/adam.py:347-547, _single_tensor_adam with decoupled weight decay), one pass
+ * over p, g, exp_avg, exp_avg_sq (16 bytes read, 12 written per element):
+ *   p *= 1 - lr wd;  m = lerp(m, g, 1 - beta1);  v = beta2 v + (1 - beta2) g g;  p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
+ * A header kernel (one thread per tensor) first advances step_dev[t] of every tensor with a gradient and derives lr / bc1
+ * and 1 / sqrt(bc2) from it in double into derived_dev; a tensor without a gradient is skipped and keeps its step.
+ * scal_dev non-NULL: the kernel consumes g * scal_dev[1] (the clip coefficient dlwp_mt_grad_norm_f32 left) without
+ * writing the gradient back -- the fused last clip, bit for bit dlwp_mt_scale_f32 followed by the plain call. */
+int32_t dlwp_mt_adamw_f32(const int64_t* p_ptrs_dev, const int64_t* g_ptrs_dev, const int64_t* numel_dev,
+                          const int64_t* state_off_dev, const int32_t* group_dev, int32_t* step_dev, float* derived_dev,
+                          const double* hyper_dev, int32_t n_tensors, const int32_t* chunk_tensor_dev,
+                          const int64_t* chunk_first_dev, int32_t n_chunks, float* exp_avg_dev, float* exp_avg_sq_dev,
+                          const float* scal_dev, void* stream);
+/* ema.update() of train.py:312: shadow = decay shadow + (1 - decay) p over every tensor of the table, shadow_dev the flat
+ * arena state_off_dev indexes. */
+int32_t dlwp_mt_ema_f32(const int64_t* p_ptrs_dev, const int64_t* numel_dev, const int64_t* state_off_dev,
+                        const int32_t* chunk_tensor_dev, const int64_t* chunk_first_dev, int32_t n_chunks, float* shadow_dev,
+                        float decay, float one_minus_decay, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

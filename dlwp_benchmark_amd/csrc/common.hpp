@@ -226,12 +226,10 @@ __device__ __forceinline__ void gelu_erf8(f32x4& u, f32x4& v) {
       "v_pk_fma_f32 %2, %2, %14, %21 op_sel:[0,0,1] op_sel_hi:[1,1,1]\n\t"
       "v_pk_fma_f32 %3, %3, %15, %21 op_sel:[0,0,1] op_sel_hi:[1,1,1]\n\t"
       "v_max_f32_e32 %6, 0, %18\n\t"
-#ifndef DLWP_KO_GELU_DEG4   /* TIMING EXPERIMENT ONLY (tools/ab_build2.sh): one Horner step less = what a degree-4 fit would cost */
       "v_pk_fma_f32 %0, %0, %12, %22 op_sel_hi:[1,1,0]\n\t"
       "v_pk_fma_f32 %1, %1, %13, %22 op_sel_hi:[1,1,0]\n\t"
       "v_pk_fma_f32 %2, %2, %14, %22 op_sel_hi:[1,1,0]\n\t"
       "v_pk_fma_f32 %3, %3, %15, %22 op_sel_hi:[1,1,0]\n\t"
-#endif
       "v_max_f32_e32 %7, 0, %19\n\t"
       "v_pk_fma_f32 %0, %0, %12, %22 op_sel:[0,0,1] op_sel_hi:[1,1,1]\n\t"
       "v_pk_fma_f32 %1, %1, %13, %22 op_sel:[0,0,1] op_sel_hi:[1,1,1]\n\t"
@@ -345,16 +343,6 @@ __device__ __forceinline__ void gelu_erf8_fma(f32x4& u, f32x4& v) {
   half(v);
 }
 
-// TIMING EXPERIMENTS ONLY (tools/ab_build.sh, never in the shipped library): a GELU that costs one instruction per
-// element, and (-DDLWP_KO_SPLIT) a "split" that keeps only the leading bf16 part with a single MFMA per product.
-__device__ __forceinline__ void gelu_ko8(f32x4& u, f32x4& v) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    u[i] = fmaxf(u[i], 0.f);
-    v[i] = fmaxf(v[i], 0.f);
-  }
-}
-
 // ---------------------------------------------------------------------------------------------
 // fp32 GEMM on the bf16 matrix pipe ("bf16x6")
 //   x = h + m + l with h = bf16(x), m = bf16(x - h), l = bf16(x - h - m)  (exact to 2^-24 |x|)
@@ -382,11 +370,6 @@ __device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {  // RNE, a i
 // three-way bf16 split of a pair of floats: 9 VALU issue slots (3 cvt_pk, 4 unpack, 2 packed subtract)
 __device__ __forceinline__ void split3_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
   h = cvt_pk_bf16(x0, x1);
-#ifdef DLWP_KO_SPLIT
-  m = h;
-  l = h;
-  return;
-#endif
   const float r0 = x0 - __uint_as_float(h << 16), r1 = x1 - __uint_as_float(h & 0xffff0000u);
   m = cvt_pk_bf16(r0, r1);
   const float s0 = r0 - __uint_as_float(m << 16), s1 = r1 - __uint_as_float(m & 0xffff0000u);
@@ -395,9 +378,6 @@ __device__ __forceinline__ void split3_pair(float x0, float x1, unsigned& h, uns
 
 // D += A*B with A = (ah, am, al), B = (bh, bm, bl), smallest terms first
 __device__ __forceinline__ f32x4 mfma_bf16x6(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x4 c) {
-#ifdef DLWP_KO_SPLIT
-  return mfma16x16x32_bf16(a[0], b[0], c);
-#endif
   c = mfma16x16x32_bf16(a[2], b[0], c);
   c = mfma16x16x32_bf16(a[0], b[2], c);
   c = mfma16x16x32_bf16(a[1], b[1], c);

@@ -45,9 +45,6 @@ constexpr int BM = 128, BK = 32;
 #ifndef DLWP_RING_STPOL
 #define DLWP_RING_STPOL " nt"     // cache policy of the output stores: streamed past the L2 -- the 200-600 MB an output tensor writes
 #endif                            // evicted the x slab / W panel the next tiles re-read from it (C5 l2 qkv 124 -> 97 us, A/B r03m)
-#ifndef DLWP_RING_PATCH
-#define DLWP_RING_PATCH 1         // 1: whole-line stores through a per-wave LDS patch; 0: straight from the accumulator layout
-#endif
 #ifndef DLWP_LIN_STPOL
 #define DLWP_LIN_STPOL " nt"      // the same for linear_kernel's fp32 stores (16 bytes per lane, 64-byte runs: f16x3 qkv 280 -> 253 us;
 #endif                            // NOT its 8-byte bf16 stores: partial lines streamed past the L2 cost 2-3x, A/B r03n)
@@ -87,7 +84,7 @@ struct Cursor {          // one (tile, k-step) position of this workgroup's flat
 // in the bf16 form hands its hidden activation from fc1 to fc2 this way: fc2 rounds its input to bf16 anyway, so the
 // result is bit-identical and the widest tensor of the block crosses HBM at half the bytes in both directions.
 #ifndef DLWP_LIN_WAVES_NP1
-#define DLWP_LIN_WAVES_NP1 2     // resident workgroups per CU the bf16-operand form is compiled for (A/B: tools/ab_build2.sh)
+#define DLWP_LIN_WAVES_NP1 2     // resident workgroups per CU the bf16-operand form is compiled for (A/B: tools/ab_build.sh)
 #endif
 template <int BN, int NP, bool F16 = false, bool XB16 = false, bool OB16 = false>
 __global__ __launch_bounds__(256, NP == 1 ? DLWP_LIN_WAVES_NP1 : 2) void linear_kernel(const Params p) {
@@ -501,11 +498,7 @@ __global__ __launch_bounds__(512, 1) void linear_ring_kernel(const Params p) {
   constexpr int XBYTES = BMR * ROWB, STAGE = XBYTES + BN * ROWB;
   constexpr int NFLY = GD * (S - 2);                 // DMAs that may stay in flight when stage t is needed
   constexpr int EL = TN + (RES ? 4 * TN : 0);        // epilogue loads of a wave and tile (bias, residual rows)
-#if DLWP_RING_PATCH
   constexpr int ES = OB16 ? 8 : 8 * ((TN + 1) / 2);  // output stores of a wave and tile (whole-line stores through the LDS patch)
-#else
-  constexpr int ES = 4 * TN;                         // output stores of a wave and tile
-#endif
   static_assert(S >= 3 && S <= 8 && NFLY + EL + ES <= 63, "ring depth / counted waits");
   extern __shared__ __align__(1024) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -634,8 +627,6 @@ __global__ __launch_bounds__(512, 1) void linear_ring_kernel(const Params p) {
   const unsigned long long out_bytes = (unsigned long long)p.M * p.N * (OB16 ? 2 : 4);
   const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (int)(out_bytes < 0xFFFFFFF0ull ? out_bytes : 0xFFFFFFF0ull), 0x00020000);
   auto epilogue = [&]() __attribute__((always_inline)) {
-    const long long mbase = row0(cc) + wm * 64 + j;
-    const int nbase = cc.nt * BN + wn * (BN / 2) + 4 * g;
     // the operands requested DL steps ago: younger in the queue are the DMAs of the steps since (this step's included)
     wait_vmcnt_dyn(GD * DL);
 #pragma unroll
@@ -646,41 +637,10 @@ __global__ __launch_bounds__(512, 1) void linear_ring_kernel(const Params p) {
 #pragma unroll
         for (int b = 0; b < TN; ++b) asm volatile("" : "+v"(rs[a][b]));
     }
-#if !DLWP_RING_PATCH
-    {
-      const long long mbase = row0(cc) + wm * 64 + j;
-      const int nbase = cc.nt * BN + wn * (BN / 2) + 4 * g;
-#pragma unroll
-      for (int a = 0; a < 4; a += 2) {
-        const long long m_u = mbase + 16 * a, m_v = m_u + 16;
-#pragma unroll
-        for (int b = 0; b < TN; ++b) {
-          f32x4 u = acc[a][b], v = acc[a + 1][b];
-          if (p.bias) { u += bv[b]; v += bv[b]; }
-          if (p.act) gelu_erf8_fma(u, v);
-          if constexpr (RES) {
-            u += rs[a][b];
-            v += rs[a + 1][b];
-          }
-          const int n = nbase + 16 * b;
-          const bool okn = n < p.N;
-          const unsigned off_u = (okn && m_u < p.M) ? (unsigned)((m_u * p.N + n) * (OB16 ? 2 : 4)) : 0xFFFFFFF0u;
-          const unsigned off_v = (okn && m_v < p.M) ? (unsigned)((m_v * p.N + n) * (OB16 ? 2 : 4)) : 0xFFFFFFF0u;
-          if constexpr (OB16) {
-            const uint2 pu = uint2{cvt_pk_bf16(u[0], u[1]), cvt_pk_bf16(u[2], u[3])}, pv = uint2{cvt_pk_bf16(v[0], v[1]), cvt_pk_bf16(v[2], v[3])};
-            asm volatile("buffer_store_dwordx2 %0, %1, %2, 0 offen" DLWP_RING_STPOL "\n\ts_nop 1" : : "v"(pu), "v"(off_u), "s"(orsrc) : "memory");
-            asm volatile("buffer_store_dwordx2 %0, %1, %2, 0 offen" DLWP_RING_STPOL "\n\ts_nop 1" : : "v"(pv), "v"(off_v), "s"(orsrc) : "memory");
-          } else {
-            asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen" DLWP_RING_STPOL "\n\ts_nop 1" : : "v"(u), "v"(off_u), "s"(orsrc) : "memory");
-            asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen" DLWP_RING_STPOL "\n\ts_nop 1" : : "v"(v), "v"(off_v), "s"(orsrc) : "memory");
-          }
-        }
-      }
-    }
-#else
     // Results leave through a 2 KB per-wave LDS patch that turns the accumulator layout (a lane: 4 columns of one row; an
     // instruction: 16 rows x 64 or 32 bytes) into whole 128-byte lines (an instruction: 8 rows x 128 bytes): a quarter (bf16) /
     // half (fp32) of the write requests for the same bytes -- requests, not bytes, are what the vector L1 runs out of.
+    // (Stores straight from the accumulator layout were the form this replaced.)
     unsigned char* patch = smem + S * STAGE + wave * 2048;
     const int rrow = lane >> 3, rchunk = lane & 7;             // read-back role: row (of 8), 16-byte chunk (of 8)
 
@@ -694,9 +654,7 @@ __global__ __launch_bounds__(512, 1) void linear_ring_kernel(const Params p) {
         u[b] = acc[a][b];
         v[b] = acc[a + 1][b];
         if (p.bias) { u[b] += bv[b]; v[b] += bv[b]; }
-#ifndef DLWP_KO_GELU
         if (p.act) gelu_erf8_fma(u[b], v[b]);
-#endif
         if constexpr (RES) {
           u[b] += rs[a][b];
           v[b] += rs[a + 1][b];
@@ -743,7 +701,6 @@ __global__ __launch_bounds__(512, 1) void linear_ring_kernel(const Params p) {
         }
       }
     }
-#endif
 
 #pragma unroll
     for (int a = 0; a < 4; ++a)

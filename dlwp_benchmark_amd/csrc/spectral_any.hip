@@ -2,7 +2,7 @@
 // multiple of 4, any kept rows / columns; and the FNO2d step built on it at any hidden / lifting / projection width.
 // fno2d.hip routes a plan here when its shape is outside the domain of the 32-channel kernels.
 //
-// One spectral convolution is three launches (pruned DFT, the factorisation of fno2d.hip without its fixed widths):
+// One spectral convolution is three launches (pruned DFT, the factorisation of fno_unfused.hpp without its fixed widths):
 //   fwd_kernel  one workgroup per (sample, in-channel) plane:
 //               W-direction  X1[h][k'] = sum_w x[h][w] tf[w][k']   [H x W] x [W x 2 n_cols] on v_mfma_f32_16x16x4_f32,
 //                            x read once as 16-byte vectors, X1 kept in LDS

@@ -1,5 +1,5 @@
 // Width-generic spectral path (spectral_any.hip): the SpectralConv2d and FNO2d plans for every shape the 32-channel
-// kernels of fno2d.hip do not take.  fno2d.hip keeps the C ABI and routes a plan here when its shape is outside the
+// kernels of fno_unfused.hpp / fno_trunk.hpp do not take.  fno2d.hip keeps the C ABI and routes a plan here when its shape is outside the
 // specialised domain; nothing here is reached by a plan the specialised kernels accept.
 #pragma once
 

@@ -51,7 +51,7 @@ int32_t dlwp_device_count(void);
 typedef struct dlwp_fno2d_plan dlwp_fno2d_plan;
 
 /* Two kernel sets behind one plan type, chosen at creation from the shape alone:
- *   specialised (csrc/fno2d.hip): hidden == 32, lifting and projection multiples of 16, in_channels <= 32,
+ *   specialised (csrc/fno_kernels.hip): hidden == 32, lifting and projection multiples of 16, in_channels <= 32,
  *     out_channels <= 16, n_cols <= 16 -- fused persistent kernels, the execution-form fields below apply;
  *   width-generic (csrc/spectral_any.hip): every other shape with every channel count in [1, 512] -- one fp32
  *     arithmetic (MFMA / FMA chains) and a fixed launch sequence per step (lifting 1x1 GELU 1x1, per layer the spectral
@@ -188,7 +188,7 @@ int32_t dlwp_fno2d_rollout_profiled_f32(const dlwp_fno2d_plan* plan, const float
  * un-normalised rfft2, rows [:m1] with weights1 and rows [-m1:] with weights2, cols [:m2],
  * irfft2).  x_dev [B, Ci, H, W] -> y_dev [B, Co, H, W], contiguous fp32.
  * Ci == Co == 32 on a width that is a multiple of 64 with at most 16 kept columns runs the specialised kernels
- * (csrc/fno2d.hip); every other shape with Ci, Co in [1, 512], any H, a width that is a multiple of 4 and
+ * (csrc/fno_unfused.hpp); every other shape with Ci, Co in [1, 512], any H, a width that is a multiple of 4 and
  * H x 2 n_cols within the transform kernels' LDS image (128 KB) runs the width-generic ones (csrc/spectral_any.hip,
  * fp32 throughout).  Shapes outside both return DLWP_ERR_UNSUPPORTED naming the limit.
  * ------------------------------------------------------------------------------------------ */

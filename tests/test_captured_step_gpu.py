@@ -25,7 +25,7 @@ def test_headline_rollout_replays_bit_identically():
     """BASELINE configs[1] at its full size (32 samples = 256 resident workgroups, 20 steps) through a recorded graph: six replays,
     each equal to the eager rollout to the last bit.  (Round 3: with the exchange buffers armed by hipMemsetD32Async the RECORDED
     rollout was 3.5 % off from step 1 on -- the fill of 12 MB did not do inside a graph what it does on a stream; the arming is a
-    kernel of the library now, csrc/fno2d.hip trunk_arm_kernel.)"""
+    kernel of the library now, csrc/fno_trunk.hpp trunk_arm_kernel.)"""
     from dlwp_benchmark_amd.sharding import CapturedStep, ShardedRollout
     from dlwp_benchmark_amd.synthetic import navier_stokes
 

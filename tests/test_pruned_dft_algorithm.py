@@ -1,7 +1,7 @@
 """CPU check of the ALGORITHM the HIP spectral kernels implement (pruned DFT factored as
 W-direction real matmul -> per-(sample, ky) H-direction/mixing -> W-direction back), against the
 oracle's FFT formulation.  Mirrors SpectralCore::build / fno_modes_kernel / fno_layer_kernel in
-dlwp_benchmark_amd/csrc/fno2d.hip with numpy float64, so a mismatch here is a maths error, not a
+dlwp_benchmark_amd/csrc/fno_unfused.hpp with numpy float64, so a mismatch here is a maths error, not a
 kernel bug."""
 import numpy as np
 import pytest

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of FNO step-kernel builds on the GPU box: bash tools/ab_fno.sh <outdir-under-gpurun_out> <tag>...   (tag "base" = the shipped library;
-# other tags = dlwp_benchmark_amd/ab/lib_<tag>.so from tools/ab_build2.sh).  Prints kernel ms per rollout and the parity figure per tag.
+# other tags = dlwp_benchmark_amd/ab/lib_<tag>.so from tools/ab_build.sh).  Prints kernel ms per rollout and the parity figure per tag.
 out=gpurun_out/$1; shift
 mkdir -p $out
 for tag in "$@"; do

@@ -1,6 +1,6 @@
 """Times SpectralConv2d and FNO2DModule rollouts across channel widths (B = 32, 64 x 64 grid).
 
-Width 32 runs the specialised 32-channel kernels (csrc/fno2d.hip), every other width the width-generic path
+Width 32 runs the specialised 32-channel kernels (csrc/fno_kernels.hip), every other width the width-generic path
 (csrc/spectral_any.hip).  For each row: ms per call / per rollout step, and the fraction of the HBM bound -- the bytes
 the row must move, from the shapes alone, at the measured copy rate of 6.29 TB/s:
 

@@ -5,7 +5,7 @@ The first four stamps of a step depend on the seam the kernel ran (DESIGN.md sec
 workgroup votes: "step top" = previous projection done -> this step's top, "lift vote" = input row, domain test, flag,
 "seam barrier" = wait for the workgroup's slowest wave (plus, after a vote for it, staging the exact MLP's weights and the
 barrier behind that), "lift" = gather from the table or the exact MLP (and then the barrier that frees its weights).  --staged-seam names them for the seam that always stages the exact path's weights
-(no live table: DLWP_FNO_LIFT_TABLE=0, more input channels, a rejected table; or a -DDLWP_LIFT_STAGE_ALWAYS build):
+(no live table: DLWP_FNO_LIFT_TABLE=0, more input channels, a rejected table):
 "step top" = end-of-step barrier + LDS write, "lift staged" = barrier, "lift seg" = gather or MLP, "lift all waves" = barrier."""
 import os
 import sys

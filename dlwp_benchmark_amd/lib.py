@@ -270,6 +270,13 @@ SIGNATURES = {
                                     c_void_p]),
     "dlwp_mt_ema_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_float, c_float,
                                   c_void_p]),
+    "dlwp_refiner_grid_span": (ctypes.c_int64, []),
+    "dlwp_philox_normal_f32": (c_int32, [c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_void_p]),
+    "dlwp_ddpm_step_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, POINTER(ctypes.c_double),
+                                     ctypes.c_int64, ctypes.c_int64, c_void_p]),
+    "dlwp_refiner_pair_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_float, c_float, ctypes.c_int64,
+                                        ctypes.c_int64, c_void_p]),
 }
 
 _lib = None

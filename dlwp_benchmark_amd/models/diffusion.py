@@ -12,7 +12,9 @@ dlwp_conv2d_f32 / dlwp_conv_transpose2d_f32.  What stays in torch: the sinusoida
 ([B, 64] operands), the AdaGN affine `h * (1 + scale) + shift` (one elementwise pass) and the noise scheduler itself, which the
 caller supplies (the reference scripts pass diffusers' DDPMScheduler, scripts/evaluate.py:186-202; any object with `.timesteps`
 and `.step(pred, k, sample).prev_sample` works).  The reference draws the start noise with `th.randn(shape)` on the host and
-moves it to the device (:186); so does this mirror, so a seeded run sees the same noise.
+moves it to the device (:186); so does this mirror, so a seeded run sees the same noise.  A scheduler that offers
+`randn(shape, device)` -- schedulers.RefinerScheduler, whose step and noise run on csrc/refiner.hip -- supplies the start noise
+itself; every other scheduler object takes the host line.
 
 `attention=True` (modern_unet.py:54, the PDE-Refiner paper's attention experiment; both reference configs run without it) adds
 an `AttentionBlock` after the residual block of every ENCODER level: global multi-head self-attention over the whole feature map
@@ -336,7 +338,11 @@ class DiffModernUNet(HipBackbone):
         if len(target_shape) == 6:
             b, t, c, f, h, w = target_shape
             target_shape = (b * f, t, c, h, w)
-        y_noised = torch.randn(target_shape).to(device=prognostic.device)      # host RNG, as the reference (:186)
+        device_randn = getattr(noise_scheduler, "randn", None)      # schedulers.RefinerScheduler: the start noise is its draw
+        if device_randn is not None:
+            y_noised = device_randn(tuple(target_shape), prognostic.device)
+        else:
+            y_noised = torch.randn(target_shape).to(device=prognostic.device)      # host RNG, as the reference (:186)
         for k in noise_scheduler.timesteps:
             k_tensor = torch.full((prognostic.shape[0],), int(k), dtype=torch.long, device=prognostic.device)
             pred = self.single_forward(constants, prescribed, prognostic, y_noised, time=k_tensor).unsqueeze(1)

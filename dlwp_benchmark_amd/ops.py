@@ -1937,3 +1937,122 @@ def mse_loss(x: torch.Tensor, target: torch.Tensor, weight: Optional[torch.Tenso
     training._MseLossFn (HIP forward that writes the gradient in the same pass)."""
     from . import training as _T
     return _T.mse_loss(x, target, weight)
+
+
+# ---- the PDE-Refiner noise scheduler on the device (csrc/refiner.hip; schedulers.RefinerScheduler drives these) ----------------
+def _i64(v: int) -> int:
+    """the low 64 bits of an integer as the signed value the C ABI carries"""
+    v = int(v) & 0xFFFFFFFFFFFFFFFF
+    return v - (1 << 64) if v >> 63 else v
+
+
+def _noise_offset(offset) -> int:
+    offset = int(offset)
+    if offset < 0 or offset % 4 or offset >= 1 << 62:
+        raise _lib.DlwpError(f"the noise offset must be a non-negative multiple of 4 below 2^62 (got {offset})")
+    return offset
+
+
+def refiner_grid_span() -> int:
+    """elements one sweep of the capped grid covers: above it the kernels' strided loop runs"""
+    return int(_lib.load().dlwp_refiner_grid_span())
+
+
+def philox_normal(shape_or_out, seed: int, offset: int = 0, device=None) -> torch.Tensor:
+    """Standard normals from the device stream (dlwp_philox_normal_f32; the reference: torch.randn(target_shape),
+    modern_unet.py:184): element e of the result is normal(seed, offset + e), a pure function of its arguments -- 10 000
+    normals in one call are bitwise the 4096 at offset 0 followed by the rest at offset 4096.  `shape_or_out`: a shape (the
+    result is allocated on `device`) or a contiguous float32 device tensor that is filled in place (an unaligned view is
+    fine).  A draw of n elements uses up the indices [offset, offset + ceil(n / 4) * 4)."""
+    if isinstance(shape_or_out, torch.Tensor):
+        out = shape_or_out
+        _lib.require_cuda_tensor(out, "out")
+        if not out.is_contiguous():
+            raise _lib.DlwpError("philox_normal: the output must be contiguous")
+    else:
+        dev = torch.device(device) if device is not None else None
+        if dev is None or dev.type != "cuda":
+            raise _lib.DlwpError(f"philox_normal: a device of the HIP path is needed (got {device}); the HIP path has no CPU "
+                                 "fallback")
+        out = torch.empty(tuple(int(s) for s in shape_or_out), dtype=torch.float32, device=dev)
+    if out.numel():
+        _lib.launch("dlwp_philox_normal_f32", out.device, out, out.numel(), _i64(seed), _noise_offset(offset))
+    return out
+
+
+def ddpm_step(sample: torch.Tensor, model_output: torch.Tensor, coefficients, noise: Optional[torch.Tensor] = None,
+              seed: int = 0, offset: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The DDPM ancestral step in one pass (dlwp_ddpm_step_f32; the reference: noise_scheduler.step, modern_unet.py:201):
+      prev = c0 (sa sample - sb model_output) + c1 sample + sigma z
+    `coefficients` = (sa, sb, c0, c1, sigma) as Python floats (RefinerScheduler.coefficients).  z is `noise` when given, else
+    philox_normal(seed, offset) evaluated inside the kernel (bitwise the same values); with sigma == 0 no noise is drawn or
+    read.  `out` may be `sample` (in place)."""
+    _lib.require_cuda_tensor(sample, "sample")
+    _lib.require_cuda_tensor(model_output, "model_output")
+    _lib.require_cuda_tensor(noise, "noise")
+    _lib.require_cuda_tensor(out, "out")
+    n = sample.numel()
+    others = [("model_output", model_output)] + ([("noise", noise)] if noise is not None else []) + \
+        ([("out", out)] if out is not None else [])
+    for name, t in others:
+        if t.numel() != n or t.device != sample.device:
+            raise _lib.DlwpError(f"ddpm_step: {name} {tuple(t.shape)} must have the sample's {n} elements on its device")
+    if n == 0:
+        raise _lib.DlwpError("ddpm_step: empty sample")
+    if out is not None and not out.is_contiguous():
+        raise _lib.DlwpError("ddpm_step: the output must be contiguous")
+    sa, sb, c0, c1, sigma = (float(c) for c in coefficients)
+    if not all(math.isfinite(c) for c in (sa, sb, c0, c1, sigma)) or sigma < 0:
+        raise _lib.DlwpError(f"ddpm_step: coefficients {(sa, sb, c0, c1, sigma)} must be finite with sigma >= 0")
+    same = out is sample
+    sample, model_output = sample.contiguous(), model_output.contiguous()
+    if out is None:
+        out = torch.empty_like(sample)
+    elif same:
+        out = sample
+    coef = (ctypes.c_double * 4)(c0 * sa, c0 * sb, c1, sigma)
+    _lib.launch("dlwp_ddpm_step_f32", sample.device, sample, model_output, noise.contiguous() if noise is not None else None, out,
+                n, coef, _i64(seed), _noise_offset(offset))
+    return out
+
+
+def refiner_pair(prognostic: torch.Tensor, target: torch.Tensor, context_size: int, sqrt_abar: float, sqrt_1m_abar: float,
+                 noise: Optional[torch.Tensor] = None, seed: int = 0, offset: int = 0):
+    """The training pair of PDE-Refiner in one pass (dlwp_refiner_pair_f32; the reference: scripts/train.py:228-255):
+      res = target - prognostic[:, context_size - 1 : context_size]
+      y_noised = sqrt_abar res + sqrt_1m_abar eps,   v_target = sqrt_abar eps - sqrt_1m_abar res
+    prognostic [B, T, C, H, W] with target [B, 1, C, H, W], or the HEALPix [B, T, C, 12, h, w] with [B, 1, C, 12, h, w]; the
+    outputs are [B, 1, C, H, W] resp. [(B 12), 1, C, h, w] (train.py:232-233).  The frame of `prognostic` is read in place
+    through its batch stride.  eps is `noise` (the outputs' shape) when given, else philox_normal(seed, offset) of the
+    outputs' shape evaluated inside the kernel.  Returns (y_noised, v_target)."""
+    _lib.require_cuda_tensor(prognostic, "prognostic")
+    _lib.require_cuda_tensor(target, "target")
+    _lib.require_cuda_tensor(noise, "noise")
+    if prognostic.dim() not in (5, 6) or target.dim() != prognostic.dim() or target.shape[1] != 1 \
+            or target.shape[0] != prognostic.shape[0] or target.shape[2:] != prognostic.shape[2:] or target.numel() == 0:
+        raise _lib.DlwpError(f"refiner_pair: prognostic {tuple(prognostic.shape)} and target {tuple(target.shape)} must be "
+                             "[B, T, C, (F,) H, W] and [B, 1, C, (F,) H, W]")
+    if not 1 <= int(context_size) <= prognostic.shape[1]:
+        raise _lib.DlwpError(f"refiner_pair: context_size {context_size} outside the {prognostic.shape[1]} frames")
+    if target.device != prognostic.device:
+        raise _lib.DlwpError("refiner_pair: prognostic and target are on different devices")
+    frame = prognostic[:, int(context_size) - 1]
+    if not frame[0].is_contiguous():                 # the batch stride is free, the frame itself is not
+        frame = frame.contiguous()
+    if not target[0].is_contiguous():
+        target = target.contiguous()
+    b, c = int(target.shape[0]), int(target.shape[2])
+    faces = int(target.shape[3]) if target.dim() == 6 else 1
+    plane = int(target.shape[-2]) * int(target.shape[-1])
+    t_bs = int(target.stride(0)) if b > 1 else c * faces * plane
+    p_bs = int(frame.stride(0)) if b > 1 else c * faces * plane
+    out_shape = (b * faces, 1, c) + tuple(target.shape[-2:])
+    if noise is not None:
+        if tuple(noise.shape) != out_shape or noise.device != target.device:
+            raise _lib.DlwpError(f"refiner_pair: the noise must be {out_shape} on the inputs' device (got {tuple(noise.shape)})")
+        noise = noise.contiguous()
+    y_noised = torch.empty(out_shape, dtype=torch.float32, device=target.device)
+    v_target = torch.empty_like(y_noised)
+    _lib.launch("dlwp_refiner_pair_f32", target.device, target, frame, noise, y_noised, v_target, b, faces, c, plane, t_bs, p_bs,
+                float(sqrt_abar), float(sqrt_1m_abar), _i64(seed), _noise_offset(offset))
+    return y_noised, v_target

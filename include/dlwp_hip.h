@@ -1099,6 +1099,42 @@ int32_t dlwp_mt_ema_f32(const int64_t* p_ptrs_dev, const int64_t* numel_dev, con
                         const int32_t* chunk_tensor_dev, const int64_t* chunk_first_dev, int32_t n_chunks, float* shadow_dev,
                         float decay, float one_minus_decay, void* stream);
 
+/* The PDE-Refiner noise scheduler on the device (csrc/refiner.hip, csrc/philox_normal.hpp): the noise, the ancestral step and
+ * the training pair of the diffusion backbones, one elementwise pass each.  256 threads per workgroup, one thread per block of
+ * 4 consecutive elements, the grid capped at 1024 workgroups and strided above (dlwp_refiner_grid_span() = the elements one
+ * sweep of a full grid covers); 16-byte accesses where every pointer of the call is 16-byte aligned, 4-byte ones for an
+ * unaligned view and for the ragged tail.  One writer per element; no entry point allocates, synchronises or reads a device
+ * value on the host.
+ *
+ * The noise stream is a pure function of (seed, global element index g): Philox4x32-10 with key = (seed low word, seed high
+ * word) and counter = (q low word, q high word, 0, 0) for q = g / 4; word pair (x0, x1) gives lanes 0 / 1 and (x2, x3) lanes
+ * 2 / 3 of the block by Box-Muller, u = float(x) 2^-32 + 2^-33, r = sqrt(-2 ln u_a), theta = 6.2831855f u_b, r cos theta /
+ * r sin theta.  `offset` is the global index of element 0 of a call: a non-negative multiple of 4.  `seed` carries 64 bits
+ * (an unsigned value reinterpreted). */
+int64_t dlwp_refiner_grid_span(void);
+/* y_noised = torch.randn(target_shape) of modern_unet.py:184 (and the variance noise inside noise_scheduler.step, :201),
+ * drawn on the device: out_dev[e] = normal(seed, offset + e) for e < n. */
+int32_t dlwp_philox_normal_f32(float* out_dev, int64_t n, int64_t seed, int64_t offset, void* stream);
+/* noise_scheduler.step(pred, k, y_noised).prev_sample of modern_unet.py:201 (DDPM ancestral step, v-prediction, variance
+ * "fixed_small") in one pass:
+ *   prev = c0 (sa sample - sb model_output) + c1 sample + sigma z
+ * coef (HOST doubles, read at the call) = { c0 sa, c0 sb, c1, sigma }; the launch folds them to A = c0 sa + c1 and B = -c0 sb in
+ * double and rounds once to fp32.  z is read from noise_or_null_dev when given, else drawn at the element's own index exactly
+ * as dlwp_philox_normal_f32 would draw it; with sigma == 0 (t = 0) no noise is drawn or read.  out_dev may be sample_dev. */
+int32_t dlwp_ddpm_step_f32(const float* sample_dev, const float* model_output_dev, const float* noise_or_null_dev,
+                           float* out_dev, int64_t n, const double coef[4], int64_t seed, int64_t offset, void* stream);
+/* The training pair of train.py:228-255 in one pass:
+ *   res = target - prog_last;  y_noised = sqrt_abar res + sqrt_1m_abar eps;  v_target = sqrt_abar eps - sqrt_1m_abar res
+ * target_dev is [batch, 1, channels, faces, plane] (plane = h w), prog_last_dev the frame prognostic[:, context_size - 1] read
+ * in place: [channels, faces, plane] contiguous per batch entry, the entries target_batch_stride / prog_batch_stride elements
+ * apart.  The outputs are [(batch faces), 1, channels, plane] contiguous: faces > 1 is the einops.rearrange
+ * "b t c f h w -> (b f) t c h w" of train.py:232-233 by index arithmetic, faces = 1 the lat-lon case.  eps is indexed by the
+ * OUTPUT's linear index: read from noise_or_null_dev when given, else drawn as dlwp_philox_normal_f32 would draw it. */
+int32_t dlwp_refiner_pair_f32(const float* target_dev, const float* prog_last_dev, const float* noise_or_null_dev,
+                              float* y_noised_dev, float* v_target_dev, int32_t batch, int32_t faces, int32_t channels,
+                              int64_t plane, int64_t target_batch_stride, int64_t prog_batch_stride, float sqrt_abar,
+                              float sqrt_1m_abar, int64_t seed, int64_t offset, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

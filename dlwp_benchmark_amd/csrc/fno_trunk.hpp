@@ -198,35 +198,41 @@ __device__ __forceinline__ void st_xchg(float* p, float v, bool fast) {
 __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
+// s_waitcnt immediate of gfx9 / CDNA: vmcnt = bits [3:0] and [15:14], expcnt = [6:4], lgkmcnt = [11:8].  vmcnt(0) alone: the other
+// two counters at their maxima (no wait).  Given as a builtin, not inline asm: hipcc's wait-count model reads it.  Where the step
+// loop uses it the wait only chooses WHERE the compiler waits (inside a rare branch, not where branches meet): correctness never
+// depends on it and no measured gain rests on it (DESIGN.md section 4.6 "Step I/O": 1.0838 ms per launch with and without).
+constexpr int kWaitVm0 = 0x0F70;
 __device__ __forceinline__ f32x4 shfl_xor4(f32x4 v, int m) {
   return f32x4{__shfl_xor(v[0], m), __shfl_xor(v[1], m), __shfl_xor(v[2], m), __shfl_xor(v[3], m)};
 }
 
 // ROWS = grid rows (= waves) per workgroup, G = workgroups per sample = H / ROWS (see trunk_rows() for the choice).
-// Input table / output slot / residual of rollout step t, exactly as fno_rollout_impl builds them on the host
-// (fno.py:49-62, :79-103): window of constants, prescribed[t-ctx:t], prognostic frames still taken from the input,
-// then frames already produced.
-__device__ __forceinline__ void rollout_step_io(const TrunkParams& p, int t, long long HW, ChanTable& in, float*& out,
-                                                long long& out_bs, const float*& resid, long long& resid_bs) {
-  const int T = p.r_T, ctx = p.r_ctx, To = T - ctx;
-  const long long prog_bs = (long long)T * p.r_nprog * HW;
-  out_bs = (long long)To * p.r_nprog * HW;
-  int k = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) in.seg[i] = ChanSeg{nullptr, 0, 0, 0};
-  if (p.r_nconst) in.seg[k++] = ChanSeg{p.r_const, (long long)p.r_nconst * HW, p.r_nconst, 0};
-  if (p.r_npresc)
-    in.seg[k++] = ChanSeg{p.r_presc + (long long)(t - ctx) * p.r_npresc * HW, (long long)T * p.r_npresc * HW, p.r_npresc * ctx, 0};
+// Output slot / input table / residual of rollout step t, exactly as fno_rollout_impl builds them on the host
+// (fno.py:49-62, :79-103).  Three functions, each called only where its result is read: a step whose input and residual are
+// still in registers (feed_regs) needs the output slot alone -- scalar multiplies in front of its one store.
+__device__ __forceinline__ void rollout_step_out(const TrunkParams& p, int t, long long HW, float*& out, long long& out_bs) {
+  out_bs = (long long)(p.r_T - p.r_ctx) * p.r_nprog * HW;
+  out = p.r_out + (long long)(t - p.r_ctx) * p.r_nprog * HW;
+}
+// The window in FIXED slots: constants, prescribed[t-ctx:t], prognostic frames still taken from the input, frames already
+// produced.  A part the step does not have is a slot of zero channels (chan_ptr skips it wherever it sits; its pointer is
+// never formed into an address), so no slot is chosen by a run-time index and the table needs no private memory.
+__device__ __forceinline__ void rollout_step_table(const TrunkParams& p, int t, long long HW, ChanTable& in) {
+  const int T = p.r_T, ctx = p.r_ctx;
   const int f0 = t - ctx;
   const int n_in = (f0 < ctx) ? (ctx - f0 < ctx ? ctx - f0 : ctx) : 0;
-  if (n_in > 0) in.seg[k++] = ChanSeg{p.r_prog + (long long)f0 * p.r_nprog * HW, prog_bs, p.r_nprog * n_in, 0};
-  if (ctx - n_in > 0) {
-    const int fo = f0 + n_in - ctx;
-    in.seg[k++] = ChanSeg{p.r_out + (long long)fo * p.r_nprog * HW, out_bs, p.r_nprog * (ctx - n_in), 0};
-  }
-  if (t - 1 < ctx) { resid = p.r_prog + (long long)(t - 1) * p.r_nprog * HW; resid_bs = prog_bs; }
-  else { resid = p.r_out + (long long)(t - 1 - ctx) * p.r_nprog * HW; resid_bs = out_bs; }
-  out = p.r_out + (long long)(t - ctx) * p.r_nprog * HW;
+  const int fo = f0 + n_in - ctx;   // first produced frame of the window; >= 0 always (0 while input frames remain, f0 - ctx after)
+  in.seg[0] = ChanSeg{p.r_const, (long long)p.r_nconst * HW, p.r_nconst, 0};
+  in.seg[1] = ChanSeg{p.r_presc + (long long)f0 * p.r_npresc * HW, (long long)T * p.r_npresc * HW, p.r_npresc * ctx, 0};
+  in.seg[2] = ChanSeg{p.r_prog + (long long)f0 * p.r_nprog * HW, (long long)T * p.r_nprog * HW, p.r_nprog * n_in, 0};
+  in.seg[3] = ChanSeg{p.r_out + (long long)fo * p.r_nprog * HW, (long long)(T - ctx) * p.r_nprog * HW, p.r_nprog * (ctx - n_in), 0};
+}
+// The residual: frame t - 1, from the input while t - 1 < ctx, from the frames already produced afterwards.
+__device__ __forceinline__ void rollout_step_resid(const TrunkParams& p, int t, long long HW, const float*& resid, long long& resid_bs) {
+  const int T = p.r_T, ctx = p.r_ctx;
+  if (t - 1 < ctx) { resid = p.r_prog + (long long)(t - 1) * p.r_nprog * HW; resid_bs = (long long)T * p.r_nprog * HW; }
+  else { resid = p.r_out + (long long)(t - 1 - ctx) * p.r_nprog * HW; resid_bs = (long long)(T - ctx) * p.r_nprog * HW; }
 }
 
 // STEP: the whole backbone step in this launch -- the lifting MLP produces the resident activation and its first Y row,
@@ -351,11 +357,8 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
   float* s_tr = smem + wave * (C * kTrStride);
   const int h = member * ROWS + wave;
   const long long pix = (long long)h * W + 4 * j;
-  ChanTable in = p.in;
-  float* out_p = p.out;
-  long long out_bs = p.out_bstride, resid_bs = p.resid_bstride;
-  const float* resid_p = p.resid;
-  if (STEP && p.n_steps > 1) rollout_step_io(p, p.r_t0 + st, HW, in, out_p, out_bs, resid_p, resid_bs);
+  // no step I/O here: the input table, the residual pointer and the output slot are formed where they are read (the lifting's
+  // loads, the projection's tail), so a step fed from registers builds no table and the top of the loop touches no memory
   // resident activation: vv[ot][r] = channel 16 ot + 4 g + r, pixels 4j..4j+3
   f32x4 vv[2][4];
   if constexpr (STEP) {
@@ -393,15 +396,28 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
 #pragma unroll
       for (int s = 1; s < 4; ++s) xs[s] = f32x4{0.f, 0.f, 0.f, 0.f};
     } else {
+      ChanTable in;
+      if (p.n_steps > 1) rollout_step_table(p, p.r_t0 + st, HW, in);
+      else in = p.in;
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
         const float* cp = s < p.lift_ns ? chan_ptr(in, 4 * s + g, gs, (int)HW) : nullptr;
         xs[s] = cp ? *reinterpret_cast<const f32x4*>(cp + pix) : f32x4{0.f, 0.f, 0.f, 0.f};
       }
+      // vmcnt(0), spelled out in THIS branch: otherwise hipcc waits for these loads where the branches meet, in front of the
+      // vote, and a fed step drains its previous output store there (one in-order counter for loads and stores).  Kept for the
+      // listing of the fed path (no full wait in front of the vote); not measurable on its own (kWaitVm0)
+      __builtin_amdgcn_s_waitcnt(kWaitVm0);
     }
-    f32x4 bias2[2];
-    bias2[0] = *reinterpret_cast<const f32x4*>(p.lift_b2 + 4 * g);
-    bias2[1] = *reinterpret_cast<const f32x4*>(p.lift_b2 + 16 + 4 * g);
+    // layer-2 bias of the exact MLP: requested here only when every step evaluates it; a voting step asks for it once it
+    // falls back, for the same reason -- no load may be in flight, behind the output store, when the vote reads the input
+    // (like the waits: for the fed path's listing, no measured gain)
+    f32x4 bias2[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+    auto lift_bias2 = [&]() {
+      bias2[0] = *reinterpret_cast<const f32x4*>(p.lift_b2 + 4 * g);
+      bias2[1] = *reinterpret_cast<const f32x4*>(p.lift_b2 + 16 + 4 * g);
+    };
+    if (!vote) lift_bias2();
     // One input channel and a table from the plan: the wave reads lift(x) from it when EVERY pixel of its row lies inside the
     // table's domain (one ballot; NaN and +-inf fail the test) and evaluates the MLP as before otherwise -- the decision
     // depends on the row's own data only, and no load address is formed from an unchecked x.
@@ -458,8 +474,12 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
     if (vote && weights_used) lift_stage_voted();
     if (weights_used) lds_barrier();
     DLWP_LIFT_STAMP();
-    if (!from_table) lift_exact();
-    else lift_gather();
+    if (!from_table) {
+      if (vote) lift_bias2();
+      lift_exact();
+    } else {
+      lift_gather();
+    }
     if (!vote) DLWP_LIFT_STAMP();
     if (weights_used) lds_barrier();   // every wave is done with the lifting weights: the region turns into transpose tiles
     DLWP_LIFT_STAMP();
@@ -981,10 +1001,19 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
     if (g < p.cout) {
       const float b2 = p.proj_b2[g];
       v += f32x4{b2, b2, b2, b2};
-      if (p.feed_regs && st > 0) v += vfeed;      // the residual is the previous output: still in this lane's registers
-      else if (resid_p) v += *reinterpret_cast<const f32x4*>(resid_p + (long long)gs * resid_bs + (long long)g * HW + pix);
+      if (p.feed_regs && st > 0) {
+        v += vfeed;      // the residual is the previous output: still in this lane's registers
+      } else {
+        const float* resid_p = p.resid;
+        long long resid_bs = p.resid_bstride;
+        if (p.n_steps > 1) rollout_step_resid(p, p.r_t0 + st, HW, resid_p, resid_bs);
+        if (resid_p) v += *reinterpret_cast<const f32x4*>(resid_p + (long long)gs * resid_bs + (long long)g * HW + pix);
+      }
       if (*s_fail) v = f32x4{__uint_as_float(0x7fc00000u), __uint_as_float(0x7fc00000u), __uint_as_float(0x7fc00000u),
                              __uint_as_float(0x7fc00000u)};
+      float* out_p = p.out;
+      long long out_bs = p.out_bstride;
+      if (p.n_steps > 1) rollout_step_out(p, p.r_t0 + st, HW, out_p, out_bs);
       *reinterpret_cast<f32x4*>(out_p + (long long)gs * out_bs + (long long)g * HW + pix) = v;
       if constexpr (F16) {
         // f16x3 range guard: an activation beyond the f16 range (|x| >= 65520) turns into inf and then NaN; a non-finite
@@ -1029,6 +1058,9 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
           if (i < n_w1) l_w1n[i] = pre_w1[k];
         }
         if (tid < p.lift_hid) l_b1n[tid] = pre_b1;
+        // vmcnt(0): a request whose lane stores nothing is still pending for the compiler; without this it drains at the top
+        // of the next step, on the path of the voting seam too (for the listing; not measurable on its own, kWaitVm0)
+        __builtin_amdgcn_s_waitcnt(kWaitVm0);
         staged = true;
       }
     }

@@ -225,6 +225,10 @@ SIGNATURES = {
                                             c_int32, c_void_p, c_size_t, c_void_p]),
     "dlwp_zonal_power_sums_acc_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                                 c_int32, c_void_p, c_size_t, c_void_p]),
+    "dlwp_climate_sums_acc_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                            c_int32, c_int32, c_void_p]),
+    "dlwp_insolation_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, ctypes.c_int64, ctypes.c_double, c_int32, c_int32,
+                                      c_float, c_float, c_void_p]),
     "dlwp_spectral_conv2d_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_size_t, c_void_p]),
     "dlwp_global_attn_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "dlwp_global_attn_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_size_t,

@@ -10,7 +10,11 @@ trajectories.
 `ZonalSpectrumMetrics` reduces the same tensors to zonal energy spectra and the mean energy log ratio (MELR) of
 reference scripts/losses.py:16-152, the spectral-blurring score scripts/train.py:434-445 takes of validation rollouts.
 
-Both classes also take HEALPix rollouts [B, K, C, 12, n, n] when they are given the longitudes of the lat-lon grid beside its
+`SoundnessMetrics` streams a rollout of any length chunk by chunk into the sums over lead time behind the physical-soundness
+scores of scripts/evaluate.py:832-872 (RMSE of the time-and-longitude mean per latitude band, RMSE of the mean field of lead days
+334-365); `soundness_scores` turns the sums into the scores in plain torch.
+
+All three classes also take HEALPix rollouts [B, K, C, 12, n, n] when they are given the longitudes of the lat-lon grid beside its
 latitudes: the reference remaps inits, outputs and targets to lat-lon before every metric (scripts/evaluate.py:298-303,
 scripts/train.py:430-441), on the host; here `ops.healpix_to_latlon` does it on the device, a chunk of samples at a time into one
 reused workspace, and the sums accumulate through the `*_acc` entry points.
@@ -33,7 +37,7 @@ DEFAULT_WORKSPACE_BYTES = 256 << 20
 
 
 class _HealpixInput:
-    """What the two metric classes share for HEALPix rollouts [B, K, C, 12, n, n]: the target grid and one workspace per device
+    """What the metric classes share for HEALPix rollouts [B, K, C, 12, n, n]: the target grid and one workspace per device
     that holds a chunk of samples of `out` and of `target` remapped to lat-lon, within `max_workspace_bytes`."""
 
     def _init_remap(self, lats_deg, lons_deg, max_workspace_bytes):
@@ -156,6 +160,217 @@ class RolloutMetrics(_HealpixInput):
         rmse = torch.sqrt(s[0] / count)
         acc = s[1] / torch.sqrt(s[2] * s[3]) if self.clim is not None else None
         return {"rmse": rmse, "acc": acc}
+
+
+DEFAULT_BANDS = {"global": None, "trade_winds": [(-20, -10), (10, 20)], "south_westerlies": [(-55, -45)]}   # evaluate.py:839-857
+_NS_PER_DAY = 86400 * 10 ** 9
+
+
+def window_steps(step_days: float, window_days=(334.0, 365.0)):
+    """The rollout steps [first, last + 1) whose lead time lies in the window: step k (0-based) has lead time (k + 1) step_days
+    (evaluate.py:346-347) and belongs when window_days[0] <= lead <= window_days[1], both ends included as in xarray's label
+    slice (evaluate.py:868-869).  Whole nanoseconds, as Timedelta labels compare; (0, 0) when no step belongs."""
+    sd, lo, hi = (int(round(float(v) * _NS_PER_DAY)) for v in (step_days, window_days[0], window_days[1]))
+    if sd <= 0:
+        raise _lib.DlwpError(f"step_days must be positive, got {step_days}")
+    first, end = max(-(-lo // sd) - 1, 0), hi // sd
+    return (first, end) if end > first else (0, 0)
+
+
+def band_rows(lats_deg: torch.Tensor, intervals) -> torch.Tensor:
+    """bool [H]: the latitude rows in any of the closed intervals [(lo, hi), ...] (`.sel(lat=slice(lo, hi))` and the merge of
+    evaluate.py:847-856); None = every row."""
+    lats = torch.as_tensor(lats_deg).detach().double().cpu().reshape(-1)
+    if intervals is None:
+        return torch.ones(lats.numel(), dtype=torch.bool)
+    rows = torch.zeros(lats.numel(), dtype=torch.bool)
+    for lo, hi in intervals:
+        rows |= (lats >= lo) & (lats <= hi)
+    return rows
+
+
+def soundness_scores(zonal: torch.Tensor, window: Optional[torch.Tensor], steps: int, n_window_steps: int, width: int, lats_deg,
+                     bands=None, std: Optional[torch.Tensor] = None, all_reduce=None):
+    """The physical-soundness scores of evaluate.py:832-872 from accumulated sums (dlwp_climate_sums_acc_f32), in plain torch
+    on whatever device the sums are on (CPU included).
+      zonal [2, B, C, H] double: sums over `steps` steps and `width` longitudes (0 = rollout, 1 = truth)
+      window [2, B, C, H, W] double or None: sums over the `n_window_steps` steps of the lead-time window
+    A = zonal / (steps width) is the mean over ("time", "lon") (:839-840), M = window / n_window_steps the window's mean over
+    "time" (:868-869).  rmse[band][c] = sqrt(mean over samples and the band's rows of (std_c (A_pred - A_true))^2) (:841-857),
+    rmse_window[c] = sqrt(mean over samples, rows and columns of (std_c (M_pred - M_true))^2) (:870); no latitude weights (the
+    reference applies none here).  A band without a row gives NaN, as an empty xarray mean does.  `all_reduce`: a callable
+    that sums a 1-D double tensor over the ranks of a sharded evaluation and returns it -- the squares and the sample count
+    go through it in ONE call."""
+    bands = DEFAULT_BANDS if bands is None else bands
+    dev = zonal.device
+    _, b, c, h = zonal.shape
+    scale = torch.ones(c, dtype=torch.float64, device=dev) if std is None else std.to(dev).double().reshape(c)
+    a = zonal / float(steps * width)
+    masks = {name: band_rows(lats_deg, iv) for name, iv in bands.items()}
+    for name, m in masks.items():
+        if m.numel() != h:
+            raise _lib.DlwpError(f"band {name!r}: {m.numel()} latitudes given, the sums have {h} rows")
+    d2 = ((a[0] - a[1]) * scale.view(1, c, 1)) ** 2                                   # [B, C, H]
+    squares = [(d2 * m.to(dev).view(1, 1, h)).sum(dim=(0, 2)) for m in masks.values()]  # [C] each
+    mean = None
+    if window is not None and n_window_steps > 0:
+        mean = window / float(n_window_steps)
+        squares.append((((mean[0] - mean[1]) * scale.view(1, c, 1, 1)) ** 2).sum(dim=(0, 2, 3)))
+    buf = torch.cat(squares + [torch.full((1,), float(b), dtype=torch.float64, device=dev)])
+    if all_reduce is not None:
+        buf = all_reduce(buf)
+    n = buf[-1]
+    rmse = {name: torch.sqrt(buf[i * c:(i + 1) * c] / (n * float(int(m.sum()))))     # 0 / 0 = NaN for an empty band
+            for i, (name, m) in enumerate(masks.items())}
+    rmse_window = torch.sqrt(buf[len(masks) * c:(len(masks) + 1) * c] / (n * float(h * width))) if mean is not None else None
+    return {"zonal_mean_pred": a[0], "zonal_mean_true": a[1],
+            "window_mean_pred": mean[0] if mean is not None else None, "window_mean_true": mean[1] if mean is not None else None,
+            "rmse": rmse, "rmse_window": rmse_window}
+
+
+class SoundnessMetrics(_HealpixInput):
+    """The physical-soundness evaluation of reference scripts/evaluate.py:832-872 for rollouts of any length, streamed: feed the
+    rollout and its truth chunk by chunk (`update`), in step order, and `finalize` gives the RMSE of the time-and-longitude mean
+    per latitude band (global, trade winds, south westerlies by default) and the RMSE of the field averaged over the lead-time
+    window (days 334-365, "months 11-12").  Only the running sums live on the device -- double [2, B, C, H] and, from the
+    first chunk that reaches the window, [2, B, C, H, W] -- and dlwp_climate_sums_acc_f32 adds a chunk to them in one launch that
+    reads it once, in an order that makes the sums bit-identical however the horizon is cut into chunks.  Nothing is copied to
+    the host per chunk.
+
+    `step_days`: the model's time step in days (rollout step k has lead time (k + 1) step_days, evaluate.py:346-347).  `std`:
+    the per-variable de-normalisation scale [C] of evaluate.py:281-296, as in RolloutMetrics (the means cancel).  `bands`:
+    {name: None or [(lat_lo, lat_hi), ...]}, closed intervals.  With `lons_deg` HEALPix chunks [B, K, C, 12, n, n] are taken too
+    and remapped to (lats_deg, lons_deg) on the device like in the other two classes; without it they are refused.  Samples are
+    sharded over ranks: `finalize(world_size)` moves the squares and the sample count in ONE all-reduce."""
+
+    def __init__(self, lats_deg, step_days: float, std: Optional[torch.Tensor] = None, bands=None, window_days=(334.0, 365.0),
+                 group=None, lons_deg=None, max_workspace_bytes: int = DEFAULT_WORKSPACE_BYTES):
+        self._init_remap(lats_deg, lons_deg, max_workspace_bytes)
+        self.height = len(self._lats)
+        self.step_days = float(step_days)
+        self.window_days = (float(window_days[0]), float(window_days[1]))
+        self.window = window_steps(self.step_days, self.window_days)      # rollout steps [first, last + 1)
+        self.bands = dict(DEFAULT_BANDS if bands is None else bands)
+        self.std = std.detach().double() if std is not None else None
+        self.group = group
+        self._scratch = {}
+        self.reset()
+
+    def reset(self):
+        self.steps = 0            # rollout steps seen so far
+        self.n_window_steps = 0   # of them, in the lead-time window
+        self._geom = None         # (B, C, H, W, device) of the first chunk
+        self._zonal = None
+        self._window = None
+        return self
+
+    def chunk_window(self, step_begin: int, steps: int):
+        """[win_begin, win_end) of a chunk of `steps` steps whose first is rollout step `step_begin`: its steps in the window"""
+        lo = min(max(self.window[0] - step_begin, 0), steps)
+        hi = min(max(self.window[1] - step_begin, 0), steps)
+        return (lo, hi) if hi > lo else (0, 0)
+
+    def state(self):
+        """The accumulators, to checkpoint a long evaluation: {"zonal", "window", "steps", "n_window_steps", "width"}"""
+        return {"zonal": self._zonal, "window": self._window, "steps": self.steps, "n_window_steps": self.n_window_steps,
+                "width": self._geom[3] if self._geom else None}
+
+    def load_state(self, state):
+        """Takes accumulators as `state()` gives them (tensors on any device: `finalize` is plain torch)."""
+        z, w = state["zonal"], state["window"]
+        if z.dim() != 4 or z.shape[0] != 2 or z.shape[3] != self.height or z.dtype != torch.float64:
+            raise _lib.DlwpError(f"zonal sums must be double [2, B, C, {self.height}], got {z.dtype} {tuple(z.shape)}")
+        width = int(state["width"])
+        if w is not None and (tuple(w.shape) != tuple(z.shape) + (width,) or w.dtype != torch.float64 or w.device != z.device):
+            raise _lib.DlwpError(f"window sums must be double {tuple(z.shape) + (width,)} on {z.device}")
+        self._zonal, self._window = z, w
+        self.steps, self.n_window_steps = int(state["steps"]), int(state["n_window_steps"])
+        self._geom = (z.shape[1], z.shape[2], z.shape[3], width, z.device)
+        return self
+
+    def update(self, out: torch.Tensor, target: torch.Tensor, step_begin: int):
+        """Adds a chunk [B, K, C, H, W] (or HEALPix [B, K, C, 12, n, n], see `lons_deg`) of K consecutive rollout steps, the first
+        of which is rollout step `step_begin`.  Chunks arrive in step order, each with the same B, C, H, W on one device."""
+        if not isinstance(out, torch.Tensor) or not isinstance(target, torch.Tensor):
+            raise _lib.DlwpError("out and target must be tensors")
+        if target.shape != out.shape:
+            raise _lib.DlwpError(f"target shape {tuple(target.shape)} != output shape {tuple(out.shape)}")
+        if int(step_begin) != self.steps:
+            raise _lib.DlwpError(f"chunks must arrive in order: this one starts at rollout step {step_begin}, "
+                                 f"{self.steps} steps have been seen")
+        hpx = out.dim() == 6
+        if hpx:
+            self._require_remap(out, target)
+            b, k, c = out.shape[:3]
+            h, w = self.height, len(self._lons)
+        elif out.dim() == 5:
+            b, k, c, h, w = out.shape
+        else:
+            raise _lib.DlwpError(f"expected a chunk [B, K, C, H, W], got {out.dim()}-D shape {tuple(out.shape)} (a HEALPix "
+                                 "chunk [B, K, C, 12, n, n] is remapped to lat-lon only when the metric is built with `lons_deg`)")
+        if h != self.height:
+            raise _lib.DlwpError(f"{h} latitudes in the chunk, {self.height} given to the metric")
+        if self.std is not None and self.std.numel() != c:
+            raise _lib.DlwpError(f"{c} variables in the chunk, {self.std.numel()} scales given to the metric")
+        if min(b, k, c, h, w) < 1:
+            raise _lib.DlwpError(f"empty chunk {tuple(out.shape)}")
+        if self._geom is not None and (b, c, h, w) != self._geom[:4]:
+            raise _lib.DlwpError(f"chunk with (B, C, H, W) = {(b, c, h, w)} after chunks with {self._geom[:4]}")
+        _lib.require_cuda_tensor(out, "out")
+        _lib.require_cuda_tensor(target, "target")
+        dev = out.device
+        if target.device != dev or (self._geom is not None and dev != self._geom[4]):
+            raise _lib.DlwpError(f"out is on {dev}, target on {target.device}"
+                                 + (f", the sums on {self._geom[4]}" if self._geom is not None else "") + ": one device is needed")
+        wb, we = self.chunk_window(self.steps, k)
+        if self._geom is None:
+            self._geom = (b, c, h, w, dev)
+            self._zonal = torch.zeros(2, b, c, h, dtype=torch.float64, device=dev)
+        if we > wb and self._window is None:                 # on first need: most chunks of a year never reach the window
+            self._window = torch.zeros(2, b, c, h, w, dtype=torch.float64, device=dev)
+        win = self._window if we > wb else None
+        if not hpx:
+            _lib.launch("dlwp_climate_sums_acc_f32", dev, out.contiguous(), target.contiguous(), self._zonal, win,
+                        b, k, c, h, w, wb, we)
+        else:
+            b0 = 0
+            for o, t in self._remapped_chunks(out, target):   # m samples at a time
+                m = o.shape[0]
+                if m == b:
+                    _lib.launch("dlwp_climate_sums_acc_f32", dev, o, t, self._zonal, win, b, k, c, h, w, wb, we)
+                else:   # the entry point's sums are [2, m, ...]: the samples' slices go through a contiguous copy, bit for bit
+                    z = self._zonal[:, b0:b0 + m].contiguous()
+                    ww = win[:, b0:b0 + m].contiguous() if win is not None else None
+                    _lib.launch("dlwp_climate_sums_acc_f32", dev, o, t, z, ww, m, k, c, h, w, wb, we)
+                    self._zonal[:, b0:b0 + m].copy_(z)
+                    if ww is not None:
+                        win[:, b0:b0 + m].copy_(ww)
+                b0 += m
+        self.steps += k
+        self.n_window_steps += we - wb
+        return self
+
+    def finalize(self, world_size: int = 1):
+        """{"zonal_mean_pred", "zonal_mean_true": [B, C, H], "window_mean_pred", "window_mean_true": [B, C, H, W] or None (this
+        rank's samples), "rmse": {band: [C]}, "rmse_window": [C] or None (ALL ranks' samples)}, float64 on the sums' device.  A
+        rollout that never reached the window gives None for the window's entries.  With world_size > 1 ONE all-reduce moves
+        [the sum of squares of every score, the sample count] (shards may differ in size): host tensors unless the group's
+        backend is nccl, as in RolloutMetrics.finalize."""
+        if self._zonal is None or self.steps == 0:
+            raise _lib.DlwpError("finalize() before any chunk: call update() first")
+        reduce = None
+        if world_size > 1:
+            import torch.distributed as dist
+
+            def reduce(buf):
+                host = dist.get_backend(self.group) != "nccl"
+                dev = buf.device
+                if host:
+                    buf = buf.cpu()
+                dist.all_reduce(buf, group=self.group)
+                return buf.to(dev)
+        return soundness_scores(self._zonal, self._window, self.steps, self.n_window_steps, self._geom[3], self._lats, self.bands,
+                                self.std, all_reduce=reduce)
 
 
 EARTH_RADIUS_M = 1000 * (6357 + 6378) / 2   # reference scripts/losses.py:13

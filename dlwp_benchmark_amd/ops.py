@@ -562,6 +562,128 @@ def healpix_to_latlon(x: torch.Tensor, lats_deg, lons_deg, out: Optional[torch.T
     return out
 
 
+# orbital constants of add_insolation.py:34-41 ("year 1995")
+_INSOL_EPS = 23.4441 * math.pi / 180.0      # obliquity
+_INSOL_ECC = 0.016715                       # eccentricity
+_INSOL_OM = 282.7 * math.pi / 180.0         # longitude of the perihelion
+
+
+def insolation_day_of_year(dates):
+    """float64 [T]: days since the start of each date's year (add_insolation.py:44-45).  `dates`: anything numpy.datetime64
+    takes (strings, datetime, datetime64 arrays)."""
+    import numpy as np
+
+    d = np.asarray(dates, dtype="datetime64[us]").reshape(-1)
+    return (d - d.astype("datetime64[Y]").astype("datetime64[us]")) / np.timedelta64(1, "D")
+
+
+def insolation_date_table(dates, daily: bool = False):
+    """float64 numpy [T, 5]: sin dec, cos dec, rho^-2, cos 2 pi frac(day), sin 2 pi frac(day) of every date
+    (add_insolation.py:55-64).  daily=True: the day is 0.5 + round(day) (:49-50)."""
+    import numpy as np
+
+    days = insolation_day_of_year(dates)
+    if daily:
+        days = 0.5 + np.round(days)
+    beta = math.sqrt(1.0 - _INSOL_ECC ** 2)
+    lambda_m = _INSOL_ECC * (1.0 + beta) * math.sin(_INSOL_OM) + 2.0 * np.pi * (days - 80.5) / 365.0
+    lambda_ = lambda_m + 2.0 * _INSOL_ECC * np.sin(lambda_m - _INSOL_OM)
+    sin_dec = math.sin(_INSOL_EPS) * np.sin(lambda_)
+    rho = (1.0 - _INSOL_ECC ** 2) / (1.0 + _INSOL_ECC * np.cos(lambda_ - _INSOL_OM))
+    day_angle = 2.0 * np.pi * (days - np.floor(days))
+    return np.ascontiguousarray(np.stack([sin_dec, np.cos(np.arcsin(sin_dec)), rho ** -2.0, np.cos(day_angle), np.sin(day_angle)],
+                                         axis=1))
+
+
+def _insolation_grid(lat_deg, lon_deg):
+    import numpy as np
+
+    def f64(a):
+        return np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+
+    lat, lon = f64(lat_deg), f64(lon_deg)
+    if lat.ndim != lon.ndim:
+        raise _lib.DlwpError("insolation: lat and lon must have the same number of dimensions")
+    if lat.ndim != 1 and lat.shape != lon.shape:
+        raise _lib.DlwpError(f"insolation: shape mismatch between lat {lat.shape} and lon {lon.shape}")
+    return lat, lon
+
+
+def insolation_point_table(lat_deg, lon_deg, daily: bool = False):
+    """(float64 numpy [N, 4], grid shape): sin lat, cos lat, cos 2 pi l, sin 2 pi l of every point with
+    l = float32(lon) / float32(360) -- the reference divides the longitude in float32 before it promotes
+    (add_insolation.py:54, :62), and so does this.  1-D `lat_deg` [H] and `lon_deg` [W] are a mesh (grid [H, W], :30-31);
+    otherwise they are equal-shape per-cell arrays.  daily=True: the longitude is 0 everywhere (:51-52)."""
+    import numpy as np
+
+    lat, lon = _insolation_grid(lat_deg, lon_deg)
+    if lat.ndim == 1:
+        lon, lat = np.meshgrid(lon, lat)
+    lon32 = np.zeros(lon.shape, dtype=np.float32) if daily else lon.astype(np.float32)
+    lat_r = (np.pi / 180.0 * lat).reshape(-1)
+    lon_angle = 2.0 * np.pi * (lon32 / np.float32(360.0)).astype(np.float64).reshape(-1)
+    table = np.stack([np.sin(lat_r), np.cos(lat_r), np.cos(lon_angle), np.sin(lon_angle)], axis=1)
+    return np.ascontiguousarray(table), tuple(lat.shape)
+
+
+def insolation_tables(dates, lat_deg, lon_deg, daily: bool = False):
+    """The host half of `insolation`, float64 numpy: (date table [T, 5], point table [N, 4], grid shape)."""
+    table, grid = insolation_point_table(lat_deg, lon_deg, daily)
+    return insolation_date_table(dates, daily), table, grid
+
+
+_INSOL_POINTS = {}        # (lat bytes, lon bytes, daily, device) -> (device point table, grid shape); the last few grids
+_INSOL_POINTS_KEPT = 8
+
+
+def _insolation_points_on(lat_deg, lon_deg, daily: bool, device):
+    """The point table on `device`, made and uploaded once per grid: a rollout asks for the same grid chunk after chunk"""
+    lat, lon = _insolation_grid(lat_deg, lon_deg)
+    key = (lat.shape, lat.tobytes(), lon.shape, lon.tobytes(), bool(daily), str(device))
+    hit = _INSOL_POINTS.pop(key, None)
+    if hit is None:
+        table, grid = insolation_point_table(lat, lon, daily)
+        hit = (torch.from_numpy(table).to(device), grid)
+        while len(_INSOL_POINTS) >= _INSOL_POINTS_KEPT:
+            _INSOL_POINTS.pop(next(iter(_INSOL_POINTS)))
+    _INSOL_POINTS[key] = hit                                   # most recently used last
+    return hit
+
+
+def insolation(dates, lat_deg, lon_deg, S: float = 1.0, daily: bool = False, clip_zero: bool = True, mean: Optional[float] = None,
+               std: Optional[float] = None, out: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
+    """Top-of-atmosphere insolation for `dates` on a grid, float32 [T, *grid] on the device (dlwp_insolation_f32; reference
+    data/datasets/add_insolation.py:9-73, the generator of the prescribed variable `tisr`).  1-D `lat_deg` / `lon_deg` are a mesh
+    ([T, H, W]); equal-shape arrays are per-cell coordinates (`healpix.cell_centres(n)` gives [T, 12, n, n]).  The host
+    tabulates the per-date and per-point factors in float64 (`insolation_tables`; the point table is uploaded once per grid
+    and kept, the date table -- 40 bytes a date -- goes up per call), the kernel forms the separable product in fp64 and rounds
+    once.  `mean` / `std`: the dataset's normalisation (x - mean) / std
+    (datasets.py:371) applied in the same pass.  `out`: a contiguous float32 [T, *grid] device tensor to write into (it is
+    returned); otherwise the result is allocated on `device` (default: the current device)."""
+    if out is not None:
+        _lib.require_cuda_tensor(out, "out")
+    dev = out.device if out is not None else (torch.device("cuda", torch.cuda.current_device()) if device is None
+                                              else torch.device(device))
+    date_tab = insolation_date_table(dates, daily)
+    pt, grid = _insolation_points_on(lat_deg, lon_deg, daily, dev)
+    t, n = date_tab.shape[0], int(pt.shape[0])
+    shape = (t,) + grid
+    if (mean is None) != (std is None):
+        raise _lib.DlwpError("insolation: give both mean and std, or neither")
+    if std is not None and float(std) == 0.0:
+        raise _lib.DlwpError("insolation: std must be non-zero")
+    if out is None:
+        out = torch.empty(shape, device=dev, dtype=torch.float32)
+    elif tuple(out.shape) != shape or not out.is_contiguous():
+        raise _lib.DlwpError(f"out must be a contiguous float32 {shape} tensor")
+    if t == 0 or n == 0:
+        return out
+    dt = torch.from_numpy(date_tab).to(dev, non_blocking=True)
+    _lib.launch("dlwp_insolation_f32", out.device, dt, pt, out, t, n, float(S), int(bool(clip_zero)), int(std is not None),
+                float(mean) if mean is not None else 0.0, float(std) if std is not None else 1.0)
+    return out
+
+
 def conv3x3_hpx_backward_data(dy: torch.Tensor, weight: torch.Tensor, cin: int) -> torch.Tensor:
     """Gradient of HEALPixPadding(1) + Conv2d(3x3, padding 0) with respect to its (activated, concatenated) input:
     dy [(B*12), Cout, H, W], weight [Cout, cin, 3, 3] in the forward layout -> [(B*12), cin, H, W]

@@ -50,6 +50,138 @@ def rollout_into(one_step: Callable[[torch.Tensor], torch.Tensor], context_size:
     return out
 
 
+def rollout_chunks(model, constants: Optional[torch.Tensor], prescribed, prognostic: torch.Tensor, n_steps: int,
+                   chunk_steps: int):
+    """A rollout of any length in fixed device memory: a generator of (step_begin, out_chunk), out_chunk [B, k, Cg, ...] holding
+    rollout steps [step_begin, step_begin + k), k = chunk_steps (less in the last chunk).  `out_chunk` is a view of a reused
+    buffer: valid until the next iteration.
+
+    `prognostic` holds only the context_size initial frames [B, ctx, Cg, ...].  `prescribed` is None, a device tensor
+    [B, ctx + n_steps, Cp, ...] or a callable (frame_begin, frame_end) -> device tensor [B, frame_end - frame_begin, Cp, ...]
+    (`insolation_forcing` builds one): frame f is what the one-shot forward would find at prescribed[:, f].
+
+    Every chunk is the model's own `rollout_into` (lat-lon tensors) or `forward` (HEALPix tensors, which the model folds
+    itself) over a window whose ctx leading frames are the last ctx frames produced so far -- so the FNO persistent kernel, step
+    graphs and precision forms run exactly as in a one-shot forward.  That is sound because every backbone that runs the
+    shared loop above reads prognostic[:, :ctx] and the LENGTH of the window only (rollout_into: frame f < ctx comes from the
+    input, every later one from `out`; the FNO kernels: csrc/fno2d.hip, fno_rollout_once, the same rule).  The driver holds
+    three buffers of ctx + chunk_steps frames at most, whatever n_steps is, and does not synchronise with the host.
+
+    ConvLSTM / ConvLSTMHPX carry a recurrent state that starts at frame 0 and cannot be resumed from frames; the diffusion
+    backbones' forward needs a noise scheduler.  Both are refused."""
+    from . import lib as _lib
+    from .models.diffusion import DiffModernUNet
+    from .models.unet import ConvLSTM
+
+    if isinstance(model, ConvLSTM):
+        raise _lib.DlwpError(f"rollout_chunks: {type(model).__name__} carries a recurrent (h, c) state that starts at frame 0 of a "
+                             "forward and cannot be resumed from the last frames of a chunk")
+    if isinstance(model, DiffModernUNet):
+        raise _lib.DlwpError(f"rollout_chunks: {type(model).__name__}.forward needs a noise scheduler, which this driver does not "
+                             "pass on")
+    ctx = int(model.context_size)
+    n_steps, chunk_steps = int(n_steps), int(chunk_steps)
+    if n_steps < 1 or chunk_steps < 1:
+        raise _lib.DlwpError(f"rollout_chunks: n_steps = {n_steps} and chunk_steps = {chunk_steps} must be positive")
+    _lib.require_cuda_tensor(prognostic, "prognostic")
+    _lib.require_cuda_tensor(constants, "constants")
+    if prognostic is None or prognostic.dim() < 5 or prognostic.shape[1] != ctx:
+        raise _lib.DlwpError(f"rollout_chunks: prognostic must hold the {ctx} initial frames [B, {ctx}, C, ...], got "
+                             f"{None if prognostic is None else tuple(prognostic.shape)}")
+    fixed = isinstance(prescribed, torch.Tensor)
+    if fixed:
+        _lib.require_cuda_tensor(prescribed, "prescribed")
+        if prescribed.shape[0] != prognostic.shape[0] or prescribed.shape[1] < ctx + n_steps:
+            raise _lib.DlwpError(f"rollout_chunks: prescribed {tuple(prescribed.shape)} must hold {ctx + n_steps} frames of "
+                                 f"{prognostic.shape[0]} samples")
+    elif prescribed is not None and not callable(prescribed):
+        raise _lib.DlwpError("rollout_chunks: prescribed must be None, a tensor or a callable (frame_begin, frame_end) -> tensor")
+    b, frame = prognostic.shape[0], tuple(prognostic.shape[2:])
+    fsz = 1
+    for d in frame:
+        fsz *= d
+    kmax = min(chunk_steps, n_steps)
+    dev = prognostic.device
+    into = prognostic.dim() == 5 and hasattr(model, "rollout_into")
+    constants = constants.contiguous() if constants is not None else None
+    context = prognostic.contiguous().clone()                                  # the last ctx frames produced so far
+    win_buf = torch.zeros(b * (ctx + kmax) * fsz, device=dev, dtype=torch.float32)   # frames past ctx are never read
+    out_buf = torch.empty(b * kmax * fsz, device=dev, dtype=torch.float32) if into else None
+    presc_buf = None
+
+    def chunks():
+        nonlocal presc_buf
+        for s0 in range(0, n_steps, kmax):
+            k = min(kmax, n_steps - s0)
+            win = win_buf[:b * (ctx + k) * fsz].view(b, ctx + k, *frame)
+            win[:, :ctx].copy_(context)
+            if prescribed is None:
+                presc = None
+            elif fixed:
+                presc = prescribed[:, s0:s0 + ctx + k]
+                if not presc.is_contiguous():
+                    if presc_buf is None:
+                        presc_buf = torch.empty(b * (ctx + kmax) * (prescribed[0, 0].numel()), device=dev, dtype=torch.float32)
+                    view = presc_buf[:presc.numel()].view(presc.shape)
+                    view.copy_(presc)
+                    presc = view
+            else:
+                presc = prescribed(s0, s0 + ctx + k)
+                _lib.require_cuda_tensor(presc, "prescribed(frame_begin, frame_end)")
+                if presc is None or presc.shape[0] != b or presc.shape[1] != ctx + k:
+                    raise _lib.DlwpError(f"rollout_chunks: prescribed({s0}, {s0 + ctx + k}) must give [{b}, {ctx + k}, Cp, ...], got "
+                                         f"{None if presc is None else tuple(presc.shape)}")
+                presc = presc.contiguous()
+            with torch.no_grad():           # not held across the yield: the consumer keeps its own grad mode
+                if into:
+                    out = out_buf[:b * k * fsz].view(b, k, *frame)
+                    model.rollout_into(out, constants, presc, win)
+                else:
+                    out = model(constants=constants, prescribed=presc, prognostic=win)
+                if k >= ctx:
+                    context.copy_(out[:, k - ctx:])
+                else:
+                    context[:, :ctx - k].copy_(context[:, k:].clone())
+                    context[:, ctx - k:].copy_(out)
+            yield s0, out
+
+    return chunks()
+
+
+def insolation_forcing(dates, lat_deg, lon_deg, batch: int, mean: Optional[float] = None, std: Optional[float] = None,
+                       S: float = 1.0, device=None):
+    """The callable form of `prescribed` for rollout_chunks when the prescribed variable is TOA insolation (the only one of the
+    reference configs): (frame_begin, frame_end) -> [batch, frame_end - frame_begin, 1, *grid], generated on the device by
+    ops.insolation for dates[frame_begin:frame_end] (one date per frame, ctx + n_steps in all) with the dataset's
+    normalisation folded in, and repeated over the batch.  A few KB of tables go to the device per call, no field does.  The
+    tensor is a reused buffer: valid until the next call."""
+    import numpy as np
+
+    from . import ops
+
+    dates = np.asarray(dates, dtype="datetime64[us]").reshape(-1)
+    bufs = {}
+
+    def forcing(frame_begin: int, frame_end: int) -> torch.Tensor:
+        n = frame_end - frame_begin
+        if n < 1 or frame_begin < 0 or frame_end > len(dates):
+            from . import lib as _lib
+
+            raise _lib.DlwpError(f"insolation_forcing: frames [{frame_begin}, {frame_end}) outside the {len(dates)} dates given")
+        buf = bufs.get(n)
+        if buf is None:
+            first = ops.insolation(dates[frame_begin:frame_end], lat_deg, lon_deg, S=S, mean=mean, std=std, device=device)
+            buf = bufs[n] = torch.empty((batch, n, 1) + tuple(first.shape[1:]), device=first.device, dtype=torch.float32)
+            buf[0, :, 0].copy_(first)
+        else:
+            ops.insolation(dates[frame_begin:frame_end], lat_deg, lon_deg, S=S, mean=mean, std=std, out=buf[0, :, 0])
+        if batch > 1:
+            buf[1:].copy_(buf[:1].expand_as(buf[1:]))
+        return buf
+
+    return forcing
+
+
 def rollout_train(one_step: Callable[[torch.Tensor], torch.Tensor], context_size: int, constants: Optional[torch.Tensor],
                   prescribed: Optional[torch.Tensor], prognostic: torch.Tensor) -> torch.Tensor:
     """The same loop with autograd alive (reference scripts/train.py:263-271 trains through it): nothing in place, the

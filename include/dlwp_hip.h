@@ -826,6 +826,30 @@ int32_t dlwp_zonal_power_sums_acc_f32(const float* out_dev, const float* target_
                                       double* sums_dev, int32_t batch, int32_t steps, int32_t channels, int32_t height,
                                       int32_t width, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Climate sums of a rollout chunk (csrc/climate_sums.hip): the reductions over lead time of the reference's physical-soundness
+ * scores (scripts/evaluate.py:832-872).  out_dev, target_dev [B, K, C, H, W] fp32, contiguous: K consecutive rollout steps.
+ *   zonal_dev  double [2, B, C, H]:    += sum over the chunk's steps and the W longitudes   (0 = out, 1 = target; :839-840)
+ *   window_dev double [2, B, C, H, W]: += sum over steps [win_begin, win_end) of THIS chunk (:868-869); may be null
+ * Both are RUNNING sums the caller zeroes once and divides at the end.  0 <= win_begin <= win_end <= K (an empty window leaves
+ * window_dev untouched), every dimension >= 1, else DLWP_ERR_INVALID_ARGUMENT; no limit on B C H, any W (16-byte loads where
+ * W % 4 == 0 and out / target are 16-byte aligned, 4-byte loads of the same elements otherwise).  Every add is fp64 from the
+ * first one; one lane group owns a row (b, c, h) for the whole call and adds in an order fixed by W alone, no atomics: the sums
+ * of a horizon are bit-identical however it is cut into chunks.  out and target are read once.  One launch on `stream`. */
+int32_t dlwp_climate_sums_acc_f32(const float* out_dev, const float* target_dev, double* zonal_dev, double* window_dev,
+                                  int32_t batch, int32_t steps, int32_t channels, int32_t height, int32_t width,
+                                  int32_t win_begin, int32_t win_end, void* stream);
+
+/* Top-of-atmosphere insolation on the device (csrc/insolation.hip; reference data/datasets/add_insolation.py:9-73):
+ *   out[t, p] = fp32(S (sin lat_p sin dec_t - cos lat_p cos dec_t cos h) rho_t^-2),  cos h = cd_t cl_p - sd_t sl_p
+ * date_table_dev double [dates, 5] = { sin dec, cos dec, rho^-2, cd = cos 2 pi frac(day), sd = sin 2 pi frac(day) },
+ * point_table_dev double [points, 4] = { sin lat, cos lat, cl = cos 2 pi lon/360, sl = sin 2 pi lon/360 } (lon / 360 taken in
+ * fp32 as the reference takes it, :54,:62), out_dev fp32 [dates, points].  fp64 FMAs, one rounding; clip_zero != 0 clips
+ * negative values (:70-71); normalise != 0 then applies (x - mean) / scale in fp32 (data/datasets/datasets.py:371), scale
+ * non-zero.  No device transcendental.  One writer per element. */
+int32_t dlwp_insolation_f32(const double* date_table_dev, const double* point_table_dev, float* out_dev, int32_t dates,
+                            int64_t points, double solar_constant, int32_t clip_zero, int32_t normalise, float mean, float scale,
+                            void* stream);
+
 /* Global multi-head self-attention of the diffusion U-Net's AttentionBlock (reference
  * models/diffusion_models/modern_unet/modern_unet.py:565-571: einsum -> softmax(dim=1) -> einsum, between the `projection`
  * and `output` Linears), fp32-accurate (v_mfma_f32_16x16x4_f32), with no N x N tensor anywhere.

@@ -21,6 +21,15 @@
 namespace dlwp {
 namespace afno {
 
+// kept_modes = int(total_modes * hard_thresholding_fraction) as fourcastnet.py:94 evaluates it: in DOUBLES.  The fraction crosses
+// the C ABI as a double for this product alone: float(0.7) and float(0.9) lie below 0.7 and 0.9, so wherever total * fraction is
+// an integer (H = 18: 10 * 0.7) the float product truncates to one mode fewer than the reference keeps.
+static inline int kept_modes(int total, double fraction) {
+  const double v = (double)total * fraction;
+  if (!(v >= 1.0)) return 0;                 // also NaN
+  return v >= 1073741824.0 ? 1073741824 : (int)v;
+}
+
 struct Params {
   const float2* x;   // [B][C][H][Wf]
   float2* y;         // [B][C][H][Wf]
@@ -359,7 +368,7 @@ __global__ __launch_bounds__(256) void afno_mix_bwd_kernel(const BwdParams p) {
 extern "C" int32_t dlwp_afno2d_mix_bwd_f32(const float* xf, const float* gf, float* gxf, float* xin, float* o1, float* d1, float* d2,
                                            const float* w1, const float* b1, const float* w2, const float* b2, int32_t batch,
                                            int32_t H, int32_t Wf, int32_t C, int32_t num_blocks, int32_t width,
-                                           float sparsity_threshold, float hard_thresholding_fraction, float in_scale,
+                                           float sparsity_threshold, double hard_thresholding_fraction, float in_scale,
                                            float out_scale, void* stream) {
   DLWP_REQUIRE(xf && gf && gxf && xin && o1 && d1 && d2 && w1 && b1 && w2 && b2, DLWP_ERR_INVALID_ARGUMENT, "null argument");
   DLWP_REQUIRE(batch > 0 && H > 0 && Wf > 0 && C > 0 && num_blocks > 0 && C % num_blocks == 0 && width > 0, DLWP_ERR_INVALID_ARGUMENT,
@@ -372,7 +381,7 @@ extern "C" int32_t dlwp_afno2d_mix_bwd_f32(const float* xf, const float* gf, flo
   p.B = batch; p.H = H; p.Wf = Wf; p.C = C; p.nb = num_blocks;
   const int bs = C / num_blocks;
   const int total = H / 2 + 1;
-  const int kept = (int)((double)total * (double)hard_thresholding_fraction);
+  const int kept = afno::kept_modes(total, hard_thresholding_fraction);
   DLWP_REQUIRE(kept >= 1, DLWP_ERR_INVALID_ARGUMENT, "hard_thresholding_fraction keeps no mode");
   p.row_lo = total - kept < 0 ? 0 : total - kept;
   p.row_hi = total + kept > H ? H : total + kept;
@@ -396,7 +405,7 @@ extern "C" int32_t dlwp_afno2d_mix_bwd_f32(const float* xf, const float* gf, flo
 extern "C" int32_t dlwp_afno2d_mix_scaled_f32(const float* xf, float* yf, const float* w1, const float* b1,
                                               const float* w2, const float* b2, int32_t batch, int32_t H, int32_t Wf,
                                               int32_t C, int32_t num_blocks, float sparsity_threshold,
-                                              float hard_thresholding_fraction, float in_scale, float out_scale,
+                                              double hard_thresholding_fraction, float in_scale, float out_scale,
                                               void* stream) {
   DLWP_REQUIRE(xf && yf && w1 && b1 && w2 && b2, DLWP_ERR_INVALID_ARGUMENT, "null argument");
   DLWP_REQUIRE(batch > 0 && H > 0 && Wf > 0 && C > 0 && num_blocks > 0 && C % num_blocks == 0, DLWP_ERR_INVALID_ARGUMENT,
@@ -408,7 +417,7 @@ extern "C" int32_t dlwp_afno2d_mix_scaled_f32(const float* xf, float* yf, const 
   p.B = batch; p.H = H; p.Wf = Wf; p.C = C; p.nb = num_blocks;
   const int bs = C / num_blocks;
   const int total = H / 2 + 1;
-  const int kept = (int)((double)total * (double)hard_thresholding_fraction);
+  const int kept = afno::kept_modes(total, hard_thresholding_fraction);
   DLWP_REQUIRE(kept >= 1, DLWP_ERR_INVALID_ARGUMENT, "hard_thresholding_fraction keeps no mode");
   p.row_lo = total - kept < 0 ? 0 : total - kept;
   p.row_hi = total + kept > H ? H : total + kept;
@@ -440,7 +449,7 @@ extern "C" int32_t dlwp_afno2d_mix_scaled_f32(const float* xf, float* yf, const 
 
 extern "C" int32_t dlwp_afno2d_mix_f32(const float* xf, float* yf, const float* w1, const float* b1, const float* w2,
                                        const float* b2, int32_t batch, int32_t H, int32_t Wf, int32_t C,
-                                       int32_t num_blocks, float sparsity_threshold, float hard_thresholding_fraction,
+                                       int32_t num_blocks, float sparsity_threshold, double hard_thresholding_fraction,
                                        void* stream) {
   return dlwp_afno2d_mix_scaled_f32(xf, yf, w1, b1, w2, b2, batch, H, Wf, C, num_blocks, sparsity_threshold,
                                     hard_thresholding_fraction, 1.0f, 1.0f, stream);

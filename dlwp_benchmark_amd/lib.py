@@ -109,12 +109,13 @@ SIGNATURES = {
     "dlwp_window_attn_bwd_workspace_bytes": (c_size_t, [POINTER(WAttnDesc), c_int32]),
     "dlwp_window_attn_bwd_f32": (c_int32, [POINTER(WAttnDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_int32, c_void_p, c_size_t, c_void_p]),
+    # hard_thresholding_fraction is a DOUBLE in the three mixing entry points: int(total * fraction) must be the reference's
     "dlwp_afno2d_mix_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
-                                      c_int32, c_int32, c_int32, c_float, c_float, c_void_p]),
+                                      c_int32, c_int32, c_int32, c_float, ctypes.c_double, c_void_p]),
     "dlwp_afno2d_mix_scaled_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
-                                             c_int32, c_int32, c_int32, c_float, c_float, c_float, c_float, c_void_p]),
-    "dlwp_afno2d_mix_bwd_f32": (c_int32, [c_void_p] * 11 + [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_float,
-                                          c_float, c_float, c_void_p]),
+                                             c_int32, c_int32, c_int32, c_float, ctypes.c_double, c_float, c_float, c_void_p]),
+    "dlwp_afno2d_mix_bwd_f32": (c_int32, [c_void_p] * 11 + [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float,
+                                          ctypes.c_double, c_float, c_float, c_void_p]),
     "dlwp_fft2_plan_create": (c_int32, [ctypes.POINTER(c_void_p), c_int32, c_int32, c_int32]),
     "dlwp_fft2_plan_destroy": (c_int32, [c_void_p]),
     "dlwp_rfft2_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -331,11 +331,13 @@ int32_t dlwp_window_attn_bwd_f32(const dlwp_wattn_desc* desc, const float* qkv_d
  * layout torch.fft.rfft2(x_nhwc, dim=(1,2)) produces and irfft2 consumes without a copy; weights in the
  * reference layouts w1,w2 [2, nb, bs, bs], b1,b2 [2, nb, bs] (device pointers), bs in {4,8,16,32}.
  * yf is fully written (zeros outside the kept modes).
+ * hard_thresholding_fraction is a DOUBLE in the three entry points below: kept = int((H/2+1) * fraction) must be the product of
+ * doubles the reference forms (:93-94); as a float, 0.7 and 0.9 keep one mode fewer wherever that product is an integer (H = 18).
  * ------------------------------------------------------------------------------------------ */
 int32_t dlwp_afno2d_mix_f32(const float* xf_dev, float* yf_dev, const float* w1_dev, const float* b1_dev,
                             const float* w2_dev, const float* b2_dev, int32_t batch, int32_t height,
                             int32_t wf, int32_t channels, int32_t num_blocks, float sparsity_threshold,
-                            float hard_thresholding_fraction, void* stream);
+                            double hard_thresholding_fraction, void* stream);
 /* Backward of the mixing between UNNORMALISED transforms (training; fourcastnet.py:96-121 under loss.backward()):
  * xf = R2C(x), gf = R2C(grad_y), both [B, C, H, Wf, 2] as above (Wf = the columns the transforms carry; `width` = W of the
  * real field, for the Hermitian weight of the Nyquist column).  Writes gxf (its C2R is grad_x) and the per-point factors of the
@@ -344,7 +346,7 @@ int32_t dlwp_afno2d_mix_f32(const float* xf_dev, float* yf_dev, const float* w1_
 int32_t dlwp_afno2d_mix_bwd_f32(const float* xf_dev, const float* gf_dev, float* gxf_dev, float* xin_dev, float* o1_dev,
                                 float* d1_dev, float* d2_dev, const float* w1_dev, const float* b1_dev, const float* w2_dev,
                                 const float* b2_dev, int32_t batch, int32_t height, int32_t wf, int32_t channels,
-                                int32_t num_blocks, int32_t width, float sparsity_threshold, float hard_thresholding_fraction,
+                                int32_t num_blocks, int32_t width, float sparsity_threshold, double hard_thresholding_fraction,
                                 float in_scale, float out_scale, void* stream);
 /* Same with yf = out_scale * mix(in_scale * xf): lets the caller use UNNORMALISED transforms (below) and still get
  * the reference's norm="ortho" arithmetic (:87, :122; in_scale = out_scale = 1/sqrt(H*W)) without two elementwise
@@ -353,7 +355,7 @@ int32_t dlwp_afno2d_mix_bwd_f32(const float* xf_dev, const float* gf_dev, float*
 int32_t dlwp_afno2d_mix_scaled_f32(const float* xf_dev, float* yf_dev, const float* w1_dev, const float* b1_dev,
                                    const float* w2_dev, const float* b2_dev, int32_t batch, int32_t height,
                                    int32_t wf, int32_t channels, int32_t num_blocks, float sparsity_threshold,
-                                   float hard_thresholding_fraction, float in_scale, float out_scale, void* stream);
+                                   double hard_thresholding_fraction, float in_scale, float out_scale, void* stream);
 
 /* Batched unnormalised 2-D real FFTs of `batch` contiguous [H, W] planes (reference fourcastnet.py:87
  * `torch.fft.rfft2(x, dim=(1, 2))` and :122-123 `irfft2`, applied channels-first so that batch = B * C) through

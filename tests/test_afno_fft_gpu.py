@@ -1,11 +1,13 @@
 """GPU parity of the hipFFT-backed AFNO filter (dlwp_rfft2_f32 -> dlwp_afno2d_mix_scaled_f32 in place ->
 dlwp_irfft2_f32) with the same filter through torch.fft and the unscaled mixing kernel, i.e. the arithmetic of
 reference fourcastnet.py:87-123 (`rfft2(norm="ortho")`, block MLP, softshrink, `irfft2(norm="ortho")`).
-The mixing kernel itself is pinned against the real reference class by the model fixtures (test_backbones_gpu.py,
-test_fullsize_gpu.py), which run through this path.  Tolerance: 2e-6 relative L2 (two fp32 FFT libraries' rounding)."""
+The mixing kernel itself is pinned by test_afno_mix_fp64_gpu.py (float64 reference, every variant) and, at two settings,
+against the real reference class by the model fixtures (test_backbones_gpu.py, test_fullsize_gpu.py); the filter here is
+compared with the float64 reference (tests/afno_ref.py) as well, at the same bound.  Tolerance: 2e-6 relative L2 (two fp32 FFT libraries' rounding)."""
 import pytest
 import torch
 
+import afno_ref
 from helpers import rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -31,6 +33,10 @@ def test_filter_matches_torch_fft_path(shape, nb, frac):
     want = torch.fft.irfft2(ops.afno2d_mix(xf, w1, b1, w2, b2, nb, lam, frac), s=(h, w), norm="ortho")
     assert got.shape == want.shape
     assert rel_l2(got, want) < 2e-6
+    # `want` runs the mixing kernel too, so an error in it cancels: the same filter from the float64 reference, which does not
+    y64, _ = afno_ref.mix(torch.fft.rfft2(x.cpu().double(), norm="ortho"), *(t.cpu() for t in (w1, b1, w2, b2)), nb, lam, frac)
+    want64 = torch.fft.irfft2(y64, s=(h, w), norm="ortho")
+    assert want64.dtype == torch.float64 and rel_l2(got, want64) < 2e-6, rel_l2(got, want64)
     # the input must survive (only the internal spectrum buffer is scratch for the C2R transform)
     again = ops.afno2d_filter_cf(x, w1, b1, w2, b2, nb, lam, frac)
     assert torch.equal(got, again)

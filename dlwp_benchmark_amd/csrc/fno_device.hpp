@@ -311,87 +311,83 @@ __device__ __forceinline__ void proj_segment(const u32x4 (&bx)[4][3], const u32x
                                              const float* s_w2, int ntile, int lane, float (&po)[CO][4], float f16_down = 1.f) {
   // F16: s_b1 holds b1 * 2^(11+s) and layer 1 comes out at that scale (common.hpp): one multiply per element in front of the GELU
   const int g = lane >> 4;
+  // Every loop-carried value lives in ONE register set (a back-edge without copies, DESIGN.md section 4.6 "projection loop"):
+  //   a[q]      layer-1 accumulators.  A half first forms x = a (x f16_down) of its two pixel chains, which leaves a dead, and the
+  //             matrix instructions of the NEXT tile then write a in place, under the GELU of x
+  //   ga, gb    GELU outputs of pixels 0-1 / 2-3.  ga is consumed by the layer-2 FMAs of half 1 of the same trip, gb by half 0 of
+  //             the next trip, before half 1 rewrites it
+  //   wa, bb    layer-1 operands, fetched from LDS right behind the last matrix instruction that reads them (they travel under
+  //             the second GELU and the loop tail); w2v likewise behind the FMAs of half 0 (tile t - 1 -> t)
+  u32x4 wa[3];
+  f32x4 bb, w2v[CO];
+  auto load_l1 = [&](int t) {
+#pragma unroll
+    for (int pp = 0; pp < 3; ++pp) wa[pp] = s_w1[(t * 3 + pp) * 64 + lane];
+    bb = *reinterpret_cast<const f32x4*>(s_b1 + 16 * t + 4 * g);
+  };
+  auto load_l2 = [&](int t) {
+#pragma unroll
+    for (int co = 0; co < CO; ++co) w2v[co] = *reinterpret_cast<const f32x4*>(s_w2 + (t * CO + co) * 16 + 4 * g);
+  };
+  auto down = [&](const f32x4& a) -> f32x4 { return F16 ? a * f16_down : a; };
 #pragma unroll
   for (int co = 0; co < CO; ++co)
 #pragma unroll
     for (int q = 0; q < 4; ++q) po[co][q] = 0.f;
-  auto fc1 = [&](int t, f32x4(&a1)[4]) {
-    const f32x4 bb = *reinterpret_cast<const f32x4*>(s_b1 + 16 * t + 4 * g);
-    u32x4 wa[3];
+  // layer 2 of pixels q0, q0 + 1: the 16 hidden units of the tile w2v holds, on PLAIN v_fma_f32.  These FMAs sit between the
+  // matrix instructions of the half, where a packed one costs far more than the two plain ones it replaces (MI355X: +22 cycles
+  // beside an MFMA); hipcc SLP-packs the two pixels' chains whenever it can see both, so each chain runs between two empty asm
+  // statements that make its accumulator opaque (no instruction, no constraint on order: the asm is not volatile)
+  auto fma2 = [&](int q0, const f32x4(&gg)[2]) {
 #pragma unroll
-    for (int pp = 0; pp < 3; ++pp) wa[pp] = s_w1[(t * 3 + pp) * 64 + lane];
+    for (int co = 0; co < CO; ++co)
 #pragma unroll
-    for (int q = 0; q < 4; ++q) a1[q] = mfma_x<F16>(wa, bx[q], bb);
+      for (int qq = 0; qq < 2; ++qq) {
+        float acc = po[co][q0 + qq];
+        asm("" : "+v"(acc));
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc = fmaf(w2v[co][r], gg[qq][r], acc);
+        asm("" : "+v"(acc));
+        po[co][q0 + qq] = acc;
+      }
   };
-  f32x4 a_cur[4], a_nxt[4], g_prev[4], g_new[4];
-  fc1(0, a_cur);
-  fc1(ntile > 1 ? 1 : 0, a_nxt);
+  f32x4 a[4], ga[2], gb[2];
+  // prologue: layer 1 of tiles 0 and 1, GELU of tile 0, layer 2 of its pixels 0-1
+  load_l1(0);
 #pragma unroll
-  for (int q = 0; q < 4; ++q) g_prev[q] = F16 ? a_cur[q] * f16_down : a_cur[q];
-  gelu_erf8(g_prev[0], g_prev[1]);
-  gelu_erf8(g_prev[2], g_prev[3]);
+  for (int q = 0; q < 4; ++q) a[q] = mfma_x<F16>(wa, bx[q], bb);
+  load_l1(ntile > 1 ? 1 : 0);
+  load_l2(0);
+  ga[0] = down(a[0]); ga[1] = down(a[1]);
+  gb[0] = down(a[2]); gb[1] = down(a[3]);
 #pragma unroll
-  for (int q = 0; q < 4; ++q) a_cur[q] = a_nxt[q];
-  // LDS operands are fetched ONE TILE AHEAD of the MFMAs / FMAs that consume them (the matrix instructions at the top
-  // of an iteration would otherwise wait out the LDS latency every tile)
-  u32x4 wa[3], wa_n[3];
-  f32x4 w2v[CO], w2v_n[CO], bb, bb_n;
-  {
-    const int tn = ntile > 2 ? 2 : ntile - 1;
-#pragma unroll
-    for (int pp = 0; pp < 3; ++pp) wa[pp] = s_w1[(tn * 3 + pp) * 64 + lane];
-#pragma unroll
-    for (int co = 0; co < CO; ++co) w2v[co] = *reinterpret_cast<const f32x4*>(s_w2 + co * 16 + 4 * g);
-    bb = *reinterpret_cast<const f32x4*>(s_b1 + 16 * tn + 4 * g);
-  }
+  for (int q = 0; q < 4; ++q) a[q] = mfma_x<F16>(wa, bx[q], bb);
+  load_l1(ntile > 2 ? 2 : ntile - 1);
+  gelu_erf8(ga[0], ga[1]);
+  gelu_erf8(gb[0], gb[1]);
+  fma2(0, ga);
+  // trip t: matrix pipe = layer 1 of tile min(t + 1, ntile - 1); fp32 lanes = GELU of tile t, layer 2 of pixels 2-3 of tile t - 1
+  // (half 0) and of pixels 0-1 of tile t (half 1).  sched_barrier keeps hipcc from moving a matrix instruction in front of the
+  // multiply that frees its destination
   for (int t = 1; t < ntile; ++t) {
-    {   // operands of iteration t + 1: tile min(t + 2, ntile - 1) for layer 1, tile t for layer 2
-      const int tn2 = (t + 2 < ntile) ? t + 2 : ntile - 1;
-#pragma unroll
-      for (int pp = 0; pp < 3; ++pp) wa_n[pp] = s_w1[(tn2 * 3 + pp) * 64 + lane];
-#pragma unroll
-      for (int co = 0; co < CO; ++co) w2v_n[co] = *reinterpret_cast<const f32x4*>(s_w2 + (t * CO + co) * 16 + 4 * g);
-      bb_n = *reinterpret_cast<const f32x4*>(s_b1 + 16 * tn2 + 4 * g);
-    }
-    // two slots: the bf16 MFMAs of tile tn for two pixel chains (matrix pipe), then GELU of two
-    // accumulator fragments of tile t and the layer-2 FMAs of tile t-1 (fp32 lanes)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      a_nxt[2 * i] = mfma_x<F16>(wa, bx[2 * i], bb);
-      a_nxt[2 * i + 1] = mfma_x<F16>(wa, bx[2 * i + 1], bb);
-      g_new[2 * i] = F16 ? a_cur[2 * i] * f16_down : a_cur[2 * i];
-      g_new[2 * i + 1] = F16 ? a_cur[2 * i + 1] * f16_down : a_cur[2 * i + 1];
-      gelu_erf8(g_new[2 * i], g_new[2 * i + 1]);
-#pragma unroll
-      for (int co = 0; co < CO; ++co)
-#pragma unroll
-        for (int qq = 2 * i; qq < 2 * i + 2; ++qq)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) po[co][qq] = fmaf(w2v[co][r], g_prev[qq][r], po[co][qq]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      g_prev[q] = g_new[q];
-      a_cur[q] = a_nxt[q];
-    }
-#pragma unroll
-    for (int pp = 0; pp < 3; ++pp) wa[pp] = wa_n[pp];
-#pragma unroll
-    for (int co = 0; co < CO; ++co) w2v[co] = w2v_n[co];
-    bb = bb_n;
+    ga[0] = down(a[0]); ga[1] = down(a[1]);
+    __builtin_amdgcn_sched_barrier(0);
+    a[0] = mfma_x<F16>(wa, bx[0], bb);
+    a[1] = mfma_x<F16>(wa, bx[1], bb);
+    gelu_erf8(ga[0], ga[1]);
+    fma2(2, gb);
+    load_l2(t);
+    __builtin_amdgcn_sched_barrier(0);
+    gb[0] = down(a[2]); gb[1] = down(a[3]);
+    __builtin_amdgcn_sched_barrier(0);
+    a[2] = mfma_x<F16>(wa, bx[2], bb);
+    a[3] = mfma_x<F16>(wa, bx[3], bb);
+    load_l1(t + 2 < ntile ? t + 2 : ntile - 1);
+    gelu_erf8(gb[0], gb[1]);
+    fma2(0, ga);
+    __builtin_amdgcn_sched_barrier(0);
   }
-  {
-    const int t = ntile - 1;
-#pragma unroll
-    for (int co = 0; co < CO; ++co) {
-      const f32x4 w2 = *reinterpret_cast<const f32x4*>(s_w2 + (t * CO + co) * 16 + 4 * g);
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) po[co][q] = fmaf(w2[r], g_prev[q][r], po[co][q]);
-    }
-  }
+  fma2(2, gb);   // pixels 2-3 of the last tile: w2v still holds it
 }
 
 // argument of fno_layer_kernel (fno_unfused.hpp); filled by the FNO step and by SpectralConv2d

@@ -376,16 +376,21 @@ __device__ __forceinline__ void split3_pair(float x0, float x1, unsigned& h, uns
   l = cvt_pk_bf16(s0, s1);
 }
 
-// D += A*B with A = (ah, am, al), B = (bh, bm, bl), smallest terms first
+// the six products of bf16x6, smallest first: (A part, B part) = (l,h) (h,l) (m,m) (m,h) (h,m) (h,h), parts indexed h, m, l = 0, 1, 2
+__device__ constexpr int kX6A[6] = {2, 0, 1, 1, 0, 0};
+__device__ constexpr int kX6B[6] = {0, 2, 1, 0, 1, 0};
+
+// D += A*B with A = (ah, am, al), B = (bh, bm, bl)
 __device__ __forceinline__ f32x4 mfma_bf16x6(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x4 c) {
-  c = mfma16x16x32_bf16(a[2], b[0], c);
-  c = mfma16x16x32_bf16(a[0], b[2], c);
-  c = mfma16x16x32_bf16(a[1], b[1], c);
-  c = mfma16x16x32_bf16(a[1], b[0], c);
-  c = mfma16x16x32_bf16(a[0], b[1], c);
-  c = mfma16x16x32_bf16(a[0], b[0], c);
+#pragma unroll
+  for (int term = 0; term < 6; ++term) c = mfma16x16x32_bf16(a[kX6A[term]], b[kX6B[term]], c);
   return c;
 }
+
+__device__ __forceinline__ unsigned short bf16_bits(float x) { return (unsigned short)(cvt_pk_bf16(x, 0.f) & 0xFFFFu); }
+__device__ __forceinline__ float bf16_to_f32(unsigned short b) { return __uint_as_float((unsigned)b << 16); }
+typedef short s16x4 __attribute__((ext_vector_type(4)));   // what ds_read_b64_tr_b16 returns (__builtin_amdgcn_ds_read_tr16_b64_v4i16)
+constexpr float kLog2e = 1.4426950408889634f;   // scores live in the log2 domain: softmax exponentials are bare v_exp_f32
 
 // ---------------------------------------------------------------------------------------------
 // fp32 GEMM on the f16 matrix instructions ("f16x3", round 2; residual scaling completed in round 3): half the matrix

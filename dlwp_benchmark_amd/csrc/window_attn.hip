@@ -42,8 +42,26 @@ namespace wattn {
 //       (rows 4g..4g+3 of the accumulator) are consecutive along longitude: ONE bias index per 4 scores.
 // All score arithmetic is in the log2 domain (q scale, bias table and mask are pre-multiplied by
 // log2 e) so the softmax exponentials are bare v_exp_f32.
-__device__ constexpr int kPA[6] = {2, 0, 1, 1, 0, 0};   // bf16x6 terms, smallest first: (A part, B part) =
-__device__ constexpr int kPB[6] = {0, 2, 1, 0, 1, 0};   // (l,h) (h,l) (m,m) (m,h) (h,m) (h,h)
+// LDS layout, read by the kernel and by its launcher: [bias column][two K / V tile buffers, overlaid by the epilogue's O tile]
+// [window token map: source offsets, packed coordinates].
+template <int DT, int DB, int SUB, int PREC>
+struct Layout {
+  static constexpr bool BF16 = PREC != 0;
+  static constexpr int NP = PREC == 2 ? 3 : 1;        // bf16 parts per operand
+  static constexpr int KT = 32;                       // keys per tile
+  static constexpr int LDK = 4 * DT + 2, LDV = 16 * DB + 4;   // fp32 K / V tile row strides (floats)
+  static constexpr int DK = (4 * DT + 31) / 32;       // bf16: k-steps of 32 over head_dim
+  static constexpr int LDKB = 32 * DK + 8, LDVB = KT + 8;     // bf16 K / V^T tile row strides (bf16 elements), 16-byte aligned rows
+  static constexpr int LDO = 16 * DB + 1;             // epilogue O tile row stride
+  static constexpr int KV_FLOATS = BF16 ? (NP * (KT * LDKB + 16 * DB * LDVB) + 1) / 2 : KT * (LDK + LDV);
+  static constexpr int INFO_OFF = (KV_FLOATS + 3) & ~3;          // [KT] packed key coords behind a tile's K / V
+  static constexpr int TILE_FLOATS = INFO_OFF + KT, EPI_FLOATS = 64 * SUB * LDO;
+  static constexpr int KV_AREA = ((2 * TILE_FLOATS > EPI_FLOATS ? 2 * TILE_FLOATS : EPI_FLOATS) + 3) & ~3;
+  __host__ __device__ static constexpr int tab_floats(int table_rows) { return (table_rows + 3) & ~3; }
+  __host__ __device__ static constexpr int map_floats(int N) { return (N + 3) & ~3; }   // one of the two token-map arrays
+  // the whole allocation: the three areas the kernel steps through by the same three terms
+  __host__ __device__ static constexpr int lds_floats(int table_rows, int N) { return tab_floats(table_rows) + KV_AREA + 2 * map_floats(N); }
+};
 
 template <int DT, int DB, int SUB, int PREC, bool LON4, bool MASK>
 __global__ __launch_bounds__(256) void window_attn_kernel(const Desc D, const float* __restrict__ qkv,
@@ -51,15 +69,10 @@ __global__ __launch_bounds__(256) void window_attn_kernel(const Desc D, const fl
                                                           const float* __restrict__ table,
                                                           float* __restrict__ out, long long L) {
   extern __shared__ __align__(16) float smem[];
-  constexpr bool BF16 = PREC != 0;
-  constexpr int NP = PREC == 2 ? 3 : 1;        // bf16 parts per operand
-  constexpr int KT = 32;                       // keys per tile
-  constexpr int LDK = 4 * DT + 2;              // fp32 K tile row stride (floats)
-  constexpr int LDV = 16 * DB + 4;             // fp32 V tile row stride
-  constexpr int DK = (4 * DT + 31) / 32;       // bf16: k-steps of 32 over head_dim
-  constexpr int LDKB = 32 * DK + 8;            // bf16 K tile row stride (bf16 elements), 16-byte aligned rows
-  constexpr int LDVB = KT + 8;                 // bf16 V^T tile row stride (bf16 elements)
-  constexpr float LOG2E = 1.4426950408889634f;
+  using LY = Layout<DT, DB, SUB, PREC>;
+  constexpr bool BF16 = LY::BF16;
+  constexpr int NP = LY::NP, KT = LY::KT, LDK = LY::LDK, LDV = LY::LDV, DK = LY::DK, LDKB = LY::LDKB, LDVB = LY::LDVB, LDO = LY::LDO;
+  constexpr int TILE_FLOATS = LY::TILE_FLOATS;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 15, g = lane >> 4;
   const int head = blockIdx.y;
@@ -73,34 +86,31 @@ __global__ __launch_bounds__(256) void window_attn_kernel(const Desc D, const fl
   const int d = D.d, C = D.C, N = D.N;
 
   float* s_tab = smem;                                   // [table_rows] bias column * log2 e
-  float* s_kv = s_tab + ((D.table_rows + 3) & ~3);       // TWO K / V tile buffers (layout depends on BF16)
+  float* s_kv = s_tab + LY::tab_floats(D.table_rows);    // TWO K / V tile buffers (layout depends on BF16)
   float* s_k;                                            // fp32: [KT][LDK]
   float* s_v;                                            // fp32: [KT][LDV]
   unsigned short* s_kb;                                  // bf16: [NP][KT][LDKB]
   unsigned short* s_vb;                                  // bf16: [NP][16*DB][LDVB]  (V transposed)
   int* s_info;                                           // [KT] packed key coords, -1 beyond N
-  constexpr int KV_FLOATS = BF16 ? (NP * (KT * LDKB + 16 * DB * LDVB) + 1) / 2 : KT * (LDK + LDV);
-  constexpr int EPI_FLOATS = 64 * SUB * (16 * DB + 1);
-  constexpr int TILE_FLOATS = ((KV_FLOATS + 3) & ~3) + KT;
   auto set_buf = [&](int bsel) {   // point the tile views at buffer bsel
     float* base = s_kv + bsel * TILE_FLOATS;
     s_k = base;
     s_v = s_k + KT * LDK;
     s_kb = reinterpret_cast<unsigned short*>(base);
     s_vb = s_kb + NP * KT * LDKB;
-    s_info = reinterpret_cast<int*>(base + ((KV_FLOATS + 3) & ~3));
+    s_info = reinterpret_cast<int*>(base + LY::INFO_OFF);
   };
   set_buf(0);
   // window token map, computed once per workgroup: source token (or -1 = zero-padded) and packed
   // coordinates / region of every in-window position (token_coord is ~10 integer divisions)
-  int* s_msrc = reinterpret_cast<int*>(s_kv + (((2 * TILE_FLOATS > EPI_FLOATS ? 2 * TILE_FLOATS : EPI_FLOATS) + 3) & ~3));  // [N]
-  int* s_minfo = s_msrc + ((N + 3) & ~3);                                                                        // [N]
+  int* s_msrc = reinterpret_cast<int*>(s_kv + LY::KV_AREA);   // [N]
+  int* s_minfo = s_msrc + LY::map_floats(N);                  // [N]
 
   {
     const int type = ipl * D.nlat + ilat;
     const long long stride = D.bias_mode ? (long long)D.types * D.heads : D.heads;
     const float* col = table + (D.bias_mode ? (long long)type * D.heads : 0) + head;
-    for (int i = tid; i < D.table_rows; i += 256) s_tab[i] = col[i * stride] * LOG2E;
+    for (int i = tid; i < D.table_rows; i += 256) s_tab[i] = col[i * stride] * kLog2e;
   }
 
   for (int n = tid; n < N; n += 256) {
@@ -112,7 +122,7 @@ __global__ __launch_bounds__(256) void window_attn_kernel(const Desc D, const fl
 
   const float* qkv_b = qkv + (long long)b * L * 3 * C;
   const int q_base = blockIdx.x * (64 * SUB) + wave * (16 * SUB);
-  const float qscale = D.scale * LOG2E;
+  const float qscale = D.scale * kLog2e;
   float qreg[BF16 ? 1 : SUB][BF16 ? 1 : DT];      // fp32 path: B[k = g][col j] per k-step
   u32x4 qb[BF16 ? SUB : 1][BF16 ? DK : 1][NP];     // bf16 paths: 8 consecutive head dims per k-step (x parts)
   int qinfo[SUB];
@@ -156,7 +166,7 @@ __global__ __launch_bounds__(256) void window_attn_kernel(const Desc D, const fl
 #pragma unroll
     for (int db = 0; db < DB; ++db) oacc[sub][db] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
-  const float mask_val = -100.0f * LOG2E;
+  const float mask_val = -100.0f * kLog2e;
 
   const int ntile = (N + KT - 1) / KT;
   // ---- K/V staging split in two (global -> registers early, registers -> LDS late) so the global
@@ -283,7 +293,7 @@ __global__ __launch_bounds__(256) void window_attn_kernel(const Desc D, const fl
             for (int term = 0; term < 6; ++term)
 #pragma unroll
               for (int kb = 0; kb < 2; ++kb)
-                sc[kb] = mfma16x16x32_bf16(ka[kb][kPA[term]], qb[sub][ks][kPB[term]], sc[kb]);
+                sc[kb] = mfma16x16x32_bf16(ka[kb][kX6A[term]], qb[sub][ks][kX6B[term]], sc[kb]);
           } else {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) sc[kb] = mfma16x16x32_bf16(ka[kb][0], qb[sub][ks][0], sc[kb]);
@@ -391,7 +401,7 @@ __global__ __launch_bounds__(256) void window_attn_kernel(const Desc D, const fl
           for (int term = 0; term < 6; ++term)
 #pragma unroll
             for (int db = 0; db < DB; ++db)
-              oacc[sub][db] = mfma16x16x32_bf16(va[db][kPA[term]], pb[kPB[term]], oacc[sub][db]);
+              oacc[sub][db] = mfma16x16x32_bf16(va[db][kX6A[term]], pb[kX6B[term]], oacc[sub][db]);
         } else {
 #pragma unroll
           for (int db = 0; db < DB; ++db) oacc[sub][db] = mfma16x16x32_bf16(va[db][0], pb[0], oacc[sub][db]);
@@ -407,8 +417,7 @@ __global__ __launch_bounds__(256) void window_attn_kernel(const Desc D, const fl
   }
 
   // ---- epilogue: normalise, transpose through LDS (reusing the K/V tile area), store whole rows
-  float* s_o = s_kv;  // [64*SUB queries][16*DB + 1]
-  constexpr int LDO = 16 * DB + 1;
+  float* s_o = s_kv;  // [64*SUB queries][LDO]
 #pragma unroll
   for (int sub = 0; sub < SUB; ++sub) {
     float l = l_run[sub];
@@ -436,17 +445,6 @@ __global__ __launch_bounds__(256) void window_attn_kernel(const Desc D, const fl
 }  // namespace wattn
 }  // namespace dlwp
 
-namespace dlwp {   // window_attn2.hip: the 2-D (Swin) fast path
-size_t wattn2_workspace_bytes(const dlwp_wattn_desc* u, int batch, int np);
-int32_t wattn2_run(const dlwp_wattn_desc* u, const float* qkv, const float* table, float* out, int batch, void* workspace,
-                   size_t workspace_bytes, hipStream_t s, int np);
-const int* wattn2_fallback_counter(const dlwp_wattn_desc* u, int batch, int np, const void* workspace);
-// window_attn3.hip: the small 3-D windows of Pangu's earth-specific attention (bias_mode 1, head_dim 32)
-size_t wattn3_workspace_bytes(const dlwp_wattn_desc* u, int batch, int np);
-int32_t wattn3_run(const dlwp_wattn_desc* u, const float* qkv, const float* qkv_bias, const float* table, float* out, int batch,
-                   void* workspace, size_t workspace_bytes, hipStream_t s, int np);
-}
-
 using namespace dlwp;
 using namespace dlwp::wattn;
 
@@ -454,12 +452,7 @@ template <int DT, int DB, int SUB, int PREC, bool LON4>
 static int32_t launch_wattn_k(const Desc& D, const float* qkv, const float* qkv_bias, const float* table, float* out,
                               int batch, long long L, hipStream_t s) {
   const int nwin = D.npl * D.nlat * D.nlon;
-  constexpr int KT = 32, LDK = 4 * DT + 2, LDV = 16 * DB + 4, DK = (4 * DT + 31) / 32, LDKB = 32 * DK + 8, LDVB = KT + 8;
-  constexpr int NP = PREC == 2 ? 3 : 1;
-  constexpr int KV_FLOATS = PREC ? (NP * (KT * LDKB + 16 * DB * LDVB) + 1) / 2 : KT * (LDK + LDV);
-  const size_t tab = (size_t)((D.table_rows + 3) & ~3);
-  const size_t tile_f = 2 * ((size_t)((KV_FLOATS + 3) & ~3) + KT), epi_f = (size_t)64 * SUB * (16 * DB + 1);
-  const size_t lds = (tab + (((tile_f > epi_f ? tile_f : epi_f) + 3) & ~(size_t)3) + 2 * (size_t)((D.N + 3) & ~3)) * 4;
+  const size_t lds = (size_t)Layout<DT, DB, SUB, PREC>::lds_floats(D.table_rows, D.N) * 4;
   DLWP_REQUIRE(lds <= 160 * 1024, DLWP_ERR_UNSUPPORTED, "window attention needs %zu bytes of LDS (bias table too large)", lds);
   const dim3 grid((D.N + 64 * SUB - 1) / (64 * SUB), D.heads, batch * nwin);
   auto kern = D.use_mask ? window_attn_kernel<DT, DB, SUB, PREC, LON4, true> : window_attn_kernel<DT, DB, SUB, PREC, LON4, false>;
@@ -476,9 +469,7 @@ static int32_t launch_wattn(const Desc& D, const float* qkv, const float* qkv_bi
   // queries per workgroup = 64 * SUB.  Large windows: 128; small windows: the whole window in one
   // workgroup when it fits 256 queries, so the bias column / token map staging is paid once per
   // (window, head) instead of once per 64 queries (Pangu: N = 144 -> SUB = 3)
-  int sub = D.N >= 512 ? 2 : (D.N <= 64 ? 1 : (D.N <= 128 ? 2 : (D.N <= 192 ? 3 : 4)));
-  static const char* sub_env = getenv("DLWP_WATTN_SUB");   // A/B: 16-query sub-tiles per wave for large windows
-  if (sub_env && D.N >= 512 && atoi(sub_env) >= 1 && atoi(sub_env) <= 4) sub = atoi(sub_env);
+  const int sub = D.N >= 512 ? 2 : (D.N <= 64 ? 1 : (D.N <= 128 ? 2 : (D.N <= 192 ? 3 : 4)));
   const bool lon4 = (D.wlon % 4) == 0;
 #define DLWP_WA2(SUB_, BF_) \
   do { if (lon4) return launch_wattn_k<DT, DB, SUB_, BF_, true>(D, qkv, qkv_bias, table, out, batch, L, s); \
@@ -494,16 +485,10 @@ static int32_t launch_wattn(const Desc& D, const float* qkv, const float* qkv_bi
 #undef DLWP_WA2
 }
 
-static int32_t window_attn_impl(const dlwp_wattn_desc* u, const float* qkv, const float* qkv_bias, const float* table,
-                                float* out, int32_t batch, void* stream, int prec) {
-  DLWP_REQUIRE(u && qkv && table && out, DLWP_ERR_INVALID_ARGUMENT, "null argument");
-  DLWP_REQUIRE(batch > 0, DLWP_ERR_INVALID_ARGUMENT, "batch must be positive");
-  Desc D;
-  {
-    const int32_t rc = make_desc(u, qkv_bias, D);
-    if (rc != DLWP_OK) return rc;
-  }
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+// the generic kernel, PREC = prec, on a normalised descriptor: the descriptor's argument checks are made here
+static int32_t run_generic(const Desc& D, const float* qkv, const float* qkv_bias, const float* table, float* out, int32_t batch,
+                           hipStream_t s, int prec) {
+  if (const int32_t rc = check_desc(D, qkv_bias); rc != DLWP_OK) return rc;
   const long long L = (long long)D.pl * D.lat * D.lon;
   DLWP_REQUIRE(L * 3 * D.C < (1ll << 31), DLWP_ERR_UNSUPPORTED, "window attention: %lld tokens x 3 x %d channels overflow the 31-bit token offsets", L, D.C);
   const float* qb = qkv_bias ? qkv_bias : qkv;  // never dereferenced when nothing is padded
@@ -517,19 +502,65 @@ static int32_t window_attn_impl(const dlwp_wattn_desc* u, const float* qkv, cons
   return fail(DLWP_ERR_UNSUPPORTED, "head_dim %d not supported", D.d);
 }
 
+// ---- dispatch: which kernel takes a descriptor.  Every entry point below asks select_path, nothing else orders the paths:
+// Fast2D (window_attn2.hip: 2-D windows, every Swin block), Earth (window_attn3.hip: small 3-D windows with the earth-specific bias,
+// every Pangu block), Generic (window_attn_kernel above: any descriptor that passes check_desc, no workspace)
+enum class Path { Generic, Fast2D, Earth };
+
+struct Route {
+  Path path = Path::Generic;
+  size_t workspace = 0;   // bytes the path needs
+  bool usable = false;    // normalise_desc filled D: all extents positive (false also for a null descriptor)
+  Desc D = {};
+};
+
+static Route select_path(const dlwp_wattn_desc* u, int batch, Form form) {
+  Route r;
+  if (!u || !(r.usable = normalise_desc(u, r.D)) || batch <= 0) return r;
+  if (form == Form::X6 && u->form == 0) return r;     // the fp32-MFMA form is the generic kernel
+  if ((r.workspace = wattn2::workspace_bytes(r.D, batch, form)) != 0) r.path = Path::Fast2D;
+  else if ((r.workspace = wattn3::workspace_bytes(r.D)) != 0) r.path = Path::Earth;
+  return r;
+}
+
+// The three run entry points.  A fast path that answers kNotCovered (workspace missing or too small, pointer alignment, a grid
+// beyond the launch limits) has launched nothing: the generic kernel takes the call, or reports what is wrong with it.
+static int32_t window_attn(const dlwp_wattn_desc* u, const void* qkv, const void* qkv_bias, const float* table, void* out,
+                           int32_t batch, void* workspace, size_t workspace_bytes, void* stream, Form form) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const Route r = select_path(u, batch, form);
+  if (qkv && table && out) {
+    int32_t rc = kNotCovered;
+    if (r.path == Path::Fast2D) rc = wattn2::run(r.D, qkv, table, out, batch, workspace, workspace_bytes, s, form);
+    else if (r.path == Path::Earth) rc = wattn3::run(r.D, qkv, qkv_bias, table, out, batch, workspace, workspace_bytes, s, form);
+    if (rc != kNotCovered) return rc;
+  }
+  DLWP_REQUIRE(u && qkv && table && out, DLWP_ERR_INVALID_ARGUMENT, "null argument");
+  DLWP_REQUIRE(batch > 0, DLWP_ERR_INVALID_ARGUMENT, "batch must be positive");
+  if (form == Form::Bf16Io) {   // only the two fast kernels read bfloat16 tensors
+    if (!r.usable) return check_desc(r.D, static_cast<const float*>(qkv_bias));
+    return fail(DLWP_ERR_UNSUPPORTED, "window attention with bfloat16 tensors: descriptor not covered by the fast kernels");
+  }
+  // fp32-accurate: desc->form picks the form of the two contractions: 0 fp32 MFMA, 1 bf16x6 (each is the other's cross-check), -1 by
+  // window size as measured (whole-map windows, >= 512 tokens: fp32 MFMA; small windows: bf16x6)
+  const int prec = form == Form::Bf16 ? 1 : ((u->form > 0 || (u->form < 0 && r.D.N < 512)) ? 2 : 0);
+  return run_generic(r.D, static_cast<const float*>(qkv), static_cast<const float*>(qkv_bias), table, static_cast<float*>(out),
+                     batch, s, prec);
+}
+
 extern "C" size_t dlwp_window_attn_workspace_bytes(const dlwp_wattn_desc* u, int32_t batch, int32_t bf16) {
-  if (!u || batch <= 0) return 0;
-  if (!bf16 && u->form == 0) return 0;     // the fp32-MFMA form is the generic kernel
-  const size_t w2 = wattn2_workspace_bytes(u, batch, bf16 ? 1 : 3);
-  return w2 ? w2 : wattn3_workspace_bytes(u, batch, bf16 ? 1 : 3);
+  return select_path(u, batch, bf16 ? Form::Bf16 : Form::X6).workspace;
 }
 
 extern "C" int32_t dlwp_window_attn_fallbacks(const dlwp_wattn_desc* u, int32_t batch, int32_t bf16, const void* workspace,
                                               void* stream, int32_t* count) {
   DLWP_REQUIRE(u && count, DLWP_ERR_INVALID_ARGUMENT, "null argument");
   *count = 0;
-  const int* dev = wattn2_fallback_counter(u, batch, bf16 ? 1 : 3, workspace);
-  if (!dev) return DLWP_OK;   // generic kernel: exact running maximum, no fallback exists
+  const Form form = bf16 ? Form::Bf16 : Form::X6;
+  const Route r = select_path(u, batch, form);
+  // generic and earth-window kernels: exact row maximum, no fallback exists
+  if (r.path != Path::Fast2D || !workspace) return DLWP_OK;
+  const int* dev = wattn2::fallback_counter(r.D, batch, form, workspace);
   DLWP_HIP_CHECK(hipMemcpyAsync(count, dev, sizeof(int32_t), hipMemcpyDeviceToHost, reinterpret_cast<hipStream_t>(stream)));
   DLWP_HIP_CHECK(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
   return DLWP_OK;
@@ -538,34 +569,15 @@ extern "C" int32_t dlwp_window_attn_fallbacks(const dlwp_wattn_desc* u, int32_t 
 extern "C" int32_t dlwp_window_attn_f32(const dlwp_wattn_desc* u, const float* qkv, const float* qkv_bias,
                                         const float* table, float* out, int32_t batch, void* workspace,
                                         size_t workspace_bytes, void* stream) {
-  // fp32-accurate either way; desc->form picks the form of the two contractions: 0 fp32 MFMA, 1 bf16x6, -1 by window
-  // size as measured (whole-map windows, >= 512 tokens: fp32 MFMA; small windows: bf16x6).  Each is the other's cross-check.
   DLWP_REQUIRE(u, DLWP_ERR_INVALID_ARGUMENT, "null descriptor");
   DLWP_REQUIRE(u->form >= -1 && u->form <= 1, DLWP_ERR_INVALID_ARGUMENT, "form %d not in {-1, 0, 1}", u->form);
-  const int n_win = u->window[0] * u->window[1] * u->window[2];
-  const bool x6 = u->form > 0 || (u->form < 0 && n_win < 512);
-  if (u->form != 0 && qkv && table && out && batch > 0) {
-    // 2-D windows (every Swin block): the second-generation kernel (bf16x6 operands, bias through the accumulator,
-    // masked tiles skipped); returns 1 when the descriptor or the workspace does not fit -> generic kernel below
-    int32_t rc = wattn2_run(u, qkv, table, out, batch, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), 3);
-    if (rc != 1) return rc;
-    // small 3-D windows with the earth-specific bias (every Pangu block): the third kernel, same convention
-    rc = wattn3_run(u, qkv, qkv_bias, table, out, batch, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), 3);
-    if (rc != 1) return rc;
-  }
-  return window_attn_impl(u, qkv, qkv_bias, table, out, batch, stream, x6 ? 2 : 0);
+  return window_attn(u, qkv, qkv_bias, table, out, batch, workspace, workspace_bytes, stream, Form::X6);
 }
 
 extern "C" int32_t dlwp_window_attn_bf16(const dlwp_wattn_desc* u, const float* qkv, const float* qkv_bias,
                                          const float* table, float* out, int32_t batch, void* workspace,
                                          size_t workspace_bytes, void* stream) {
-  if (u && qkv && table && out && batch > 0) {
-    int32_t rc = wattn2_run(u, qkv, table, out, batch, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), 1);
-    if (rc != 1) return rc;
-    rc = wattn3_run(u, qkv, qkv_bias, table, out, batch, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), 1);
-    if (rc != 1) return rc;
-  }
-  return window_attn_impl(u, qkv, qkv_bias, table, out, batch, stream, 1);
+  return window_attn(u, qkv, qkv_bias, table, out, batch, workspace, workspace_bytes, stream, Form::Bf16);
 }
 
 // bf16 form with bfloat16 TENSORS: qkv [B, L, 3 C], the qkv bias [3 C] (read for zero-padded tokens) and the output [B, L, C] are
@@ -574,13 +586,6 @@ extern "C" int32_t dlwp_window_attn_bf16(const dlwp_wattn_desc* u, const float* 
 extern "C" int32_t dlwp_window_attn_bf16_io(const dlwp_wattn_desc* u, const void* qkv_bf16, const void* qkv_bias_bf16,
                                             const float* table, void* out_bf16, int32_t batch, void* workspace,
                                             size_t workspace_bytes, void* stream) {
-  DLWP_REQUIRE(u && qkv_bf16 && table && out_bf16, DLWP_ERR_INVALID_ARGUMENT, "null argument");
-  DLWP_REQUIRE(batch > 0, DLWP_ERR_INVALID_ARGUMENT, "batch must be positive");
-  int32_t rc = wattn2_run(u, reinterpret_cast<const float*>(qkv_bf16), table, reinterpret_cast<float*>(out_bf16), batch, workspace,
-                          workspace_bytes, reinterpret_cast<hipStream_t>(stream), 16);
-  if (rc != 1) return rc;
-  rc = wattn3_run(u, reinterpret_cast<const float*>(qkv_bf16), reinterpret_cast<const float*>(qkv_bias_bf16), table,
-                  reinterpret_cast<float*>(out_bf16), batch, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), 16);
-  if (rc != 1) return rc;
-  return fail(DLWP_ERR_UNSUPPORTED, "window attention with bfloat16 tensors: descriptor not covered by the fast kernels");
+  return window_attn(u, qkv_bf16, qkv_bias_bf16, table, out_bf16, batch, workspace, workspace_bytes, stream, Form::Bf16Io);
 }
+

@@ -28,11 +28,13 @@
 // Precision forms: NP = 1 bf16 operands (dlwp_window_attn_bf16), NP = 3 exact three-way bf16 splits of Q, K, V, P with
 // six cross products per contraction = fp32-GEMM accuracy (dlwp_window_attn_f32, form 1 / default).
 #include "common.hpp"
+#include "window_attn_desc.hpp"
 
 namespace dlwp {
 namespace wattn2 {
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
+using wattn::Desc;
+using wattn::Form;
 
 struct Geo {
   int lat, lon;            // token grid = padded grid (no zero padding on this path)
@@ -59,9 +61,6 @@ struct Images {           // device pointers into the caller's workspace
   const unsigned short* qkv16;   // DIRECT: the bfloat16 qkv tensor [B][L][3 C] itself -- no operand images, no prep kernel
   const float* table;            // DIRECT: the relative-position bias table [TR][heads] as the caller holds it
 };
-
-__device__ __forceinline__ unsigned short bf16_bits(float x) { return (unsigned short)(cvt_pk_bf16(x, 0.f) & 0xFFFFu); }
-__device__ __forceinline__ float bf16_to_f32(unsigned short b) { return __uint_as_float((unsigned)b << 16); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // prep: window token order, bf16 operand images, reversed bias table, destination map
@@ -103,17 +102,8 @@ __global__ __launch_bounds__(256) void wattn2_prep_kernel(const Geo G, const flo
 #pragma unroll
     for (int i = 0; i < 8; ++i) x[i] = 0.f;
     if (e0 < G.d) {   // d is a multiple of 8: a chunk is entirely inside or outside the head dimension
-      if (G.io16) {
-        const u32x4 raw = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(qkv) + eoff + e0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          x[2 * i] = __uint_as_float(raw[i] << 16);
-          x[2 * i + 1] = __uint_as_float(raw[i] & 0xFFFF0000u);
-        }
-      } else {
-        const float4 lo = *reinterpret_cast<const float4*>(src + e0), hi = *reinterpret_cast<const float4*>(src + e0 + 4);
-        x[0] = lo.x; x[1] = lo.y; x[2] = lo.z; x[3] = lo.w; x[4] = hi.x; x[5] = hi.y; x[6] = hi.z; x[7] = hi.w;
-      }
+      const float4 lo = *reinterpret_cast<const float4*>(src + e0), hi = *reinterpret_cast<const float4*>(src + e0 + 4);
+      x[0] = lo.x; x[1] = lo.y; x[2] = lo.z; x[3] = lo.w; x[4] = hi.x; x[5] = hi.y; x[6] = hi.z; x[7] = hi.w;
       if (which == 0) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) x[i] *= G.qscale;
@@ -156,11 +146,10 @@ __global__ __launch_bounds__(256) void wattn2_prep_kernel(const Geo G, const flo
     }
   }
   // reversed, log2e-scaled bias columns and the destination map (small; the first blocks do them)
-  const float LOG2E = 1.4426950408889634f;
   if (blockIdx.x == 0 && threadIdx.x == 0) *I.fallbacks = 0;
   for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < (long long)G.heads * TRP; t += (long long)gridDim.x * 256) {
     const int head = (int)(t / TRP), x = (int)(t % TRP);
-    I.rev[t] = x < G.TR ? table[(long long)(G.TR - 1 - x) * G.heads + head] * LOG2E : 0.f;
+    I.rev[t] = x < G.TR ? table[(long long)(G.TR - 1 - x) * G.heads + head] * kLog2e : 0.f;
   }
   for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < (long long)G.nwin * G.N; t += (long long)gridDim.x * 256) {
     const int win = (int)(t / G.N), n = (int)(t % G.N);
@@ -215,8 +204,31 @@ __global__ __launch_bounds__(256) void wattn2_kmax_kernel(const Geo G, Images I)
 //   SUB 16-query sub-tiles per wave; a workgroup = 4 waves = 64 SUB consecutive window positions
 //   NP  bf16 parts per operand (1: bf16 form, 3: bf16x6 = fp32-accurate)
 // ---------------------------------------------------------------------------------------------------------------
-__device__ constexpr int kTA[6] = {2, 0, 1, 1, 0, 0};   // bf16x6 terms, smallest first: (A part, B part)
-__device__ constexpr int kTB[6] = {0, 2, 1, 0, 1, 0};
+// LDS layout, read by the kernel and by launch(): [slice of the reversed bias column][two K + V tile buffers][flags][tile table]
+// [tile list][DIRECT: token map], all of it overlaid by the epilogue's O tile, then (DIRECT) the queries' output tokens
+template <int D8, int SUB, int NP, bool DIRECT>
+struct Layout {
+  static constexpr int KT = 32;                                     // keys per tile
+  static constexpr int d = 8 * D8;                                  // head dimension (compile time)
+  static constexpr int DK = d / 32 + 1, DB = (d + 15) / 16, DKP = 32 * DK, DVP = 16 * DB;
+  // LDS row strides (bf16 elements), chosen bank-conflict free for the two operand reads: K rows are read with
+  // ds_read_b128 by lanes (row j, 16-byte slot g) -> stride/8 dwords-of-4 must map the 16 lanes of each b128 lane group
+  // to distinct slots: DKP + 16 (48, 80) does; V rows are read with ds_read_b64_tr_b16 by (row 4g + q, 8-byte slot p)
+  // -> stride/2 dwords = 8 mod 16 puts the 8 rows of a 32-lane half on disjoint 8-dword ranges: 16, 48, 48, 80
+  static constexpr int LDK = DKP + 16, LDV = DVP == 16 ? 16 : (DVP <= 48 ? 48 : 80);
+  static constexpr int TILE_U16 = NP * KT * (LDK + LDV);            // one K + V tile (all parts)
+  static constexpr int TILE_F = (((TILE_U16 + 1) / 2) + 3) & ~3;
+  static constexpr int LDO = DVP + 1, EPI_F = 64 * SUB * LDO;       // epilogue O tile: row stride, size
+  // slice of the reversed bias column a workgroup keeps in LDS: (wlat + rows of its query block - 1) table rows (+ alignment)
+  __host__ __device__ static constexpr int nq_rows(int wlon) { return (64 * SUB + wlon - 1) / wlon; }
+  static int rev_floats(int wlat, int wlon, int W2) { return (((wlat + nq_rows(wlon) - 1) * W2 + 3 + 3) & ~3) + 4; }
+  // dwords in front of s_dst: the tile loop's arrays (N keys, N / KT tiles) or the O tile, whichever is larger
+  __host__ __device__ static constexpr int dst_offset(int rev_floats, int N) {
+    const int ntile = N / KT, loop_f = rev_floats + 2 * TILE_F + 4 + 4 * ntile + ntile + (DIRECT ? N : 0);
+    return loop_f > EPI_F ? loop_f : EPI_F;
+  }
+  __host__ __device__ static constexpr int lds_bytes(int rev_floats, int N) { return (dst_offset(rev_floats, N) + (DIRECT ? 64 * SUB : 0)) * 4; }
+};
 
 //   DIRECT (NP = 1 with bfloat16 tensors, round 3): Q, K and V are gathered from the qkv tensor the block's qkv Linear wrote --
 //   the window order (roll included) through an LDS token map, the spare-slot constants formed in registers, the bias slice
@@ -226,18 +238,9 @@ __global__ __launch_bounds__(256, NP == 3 ? 2 : 4) void wattn2_kernel(const Geo 
                                                                        int groups, int nqb, int rev_floats) {
   static_assert(!DIRECT || NP == 1, "the direct form reads bf16 tensors: one part per operand");
   extern __shared__ __align__(16) float smem[];
-  constexpr int KT = 32;
-  constexpr int d = 8 * D8;                                         // head dimension (compile time)
-  constexpr int DK = d / 32 + 1, DB = (d + 15) / 16;
-  constexpr int DKP = 32 * DK, DVP = 16 * DB;
-  // LDS row strides (bf16 elements), chosen bank-conflict free for the two operand reads: K rows are read with
-  // ds_read_b128 by lanes (row j, 16-byte slot g) -> stride/8 dwords-of-4 must map the 16 lanes of each b128 lane group
-  // to distinct slots: DKP + 16 (48, 80) does; V rows are read with ds_read_b64_tr_b16 by (row 4g + q, 8-byte slot p)
-  // -> stride/2 dwords = 8 mod 16 puts the 8 rows of a 32-lane half on disjoint 8-dword ranges: 16, 48, 48, 80
-  constexpr int LDK = DKP + 16, LDV = DVP == 16 ? 16 : (DVP <= 48 ? 48 : 80);
-  constexpr int TILE_U16 = NP * KT * (LDK + LDV);                   // one K + V tile (all parts)
-  constexpr int TILE_F = (((TILE_U16 + 1) / 2) + 3) & ~3;
-  constexpr int LDO = DVP + 1;
+  using LY = Layout<D8, SUB, NP, DIRECT>;
+  constexpr int KT = LY::KT, d = LY::d, DK = LY::DK, DB = LY::DB, DKP = LY::DKP, DVP = LY::DVP, LDK = LY::LDK, LDV = LY::LDV;
+  constexpr int TILE_F = LY::TILE_F, LDO = LY::LDO;
   constexpr unsigned ALLSUB = (1u << SUB) - 1u;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 15, g = lane >> 4;
@@ -259,7 +262,7 @@ __global__ __launch_bounds__(256, NP == 3 ? 2 : 4) void wattn2_kernel(const Geo 
   // row is wlat - 1 .. 0 rows away -> (wlat + nq_rows - 1) table rows, contiguous in the reversed column
   const int TRP = (G.TR + 3) & ~3;
   const int qrow0 = (qblk * (64 * SUB)) / G.wlon;
-  const int nq_rows = (64 * SUB + G.wlon - 1) / G.wlon;
+  const int nq_rows = LY::nq_rows(G.wlon);
   const int rev_lo = (G.TR - (qrow0 + G.wlat + nq_rows - 1) * G.W2) & ~3;   // 16-byte aligned start (>= 0)
   float* s_rev = smem;                                               // [rev_floats] slice of the reversed bias column * log2 e
   float* s_tiles = s_rev + rev_floats;                               // 2 tile buffers
@@ -267,14 +270,9 @@ __global__ __launch_bounds__(256, NP == 3 ? 2 : 4) void wattn2_kernel(const Geo 
   int4* s_tinfo = reinterpret_cast<int4*>(s_flag + 4);               // [ntile] {bias term block 0, block 1, regions, tile}
   int* s_list = reinterpret_cast<int*>(s_tinfo + ntile);             // [ntile] needed tiles of this workgroup, in order
   int* s_src = s_list + ntile;                                       // DIRECT: [N] qkv row offset of window position n (forward roll applied)
-  // DIRECT: [64 SUB] output token of the workgroup's queries, behind everything the epilogue's O tile overlays (launch(): lds)
-  int* s_dst;
-  {
-    const int loop_f = rev_floats + 2 * TILE_F + 4 + 4 * ntile + ntile + N, epi_f = 64 * SUB * (16 * ((8 * D8 + 15) / 16) + 1);
-    s_dst = reinterpret_cast<int*>(smem) + (loop_f > epi_f ? loop_f : epi_f);
-  }
+  // DIRECT: [64 SUB] output token of the workgroup's queries, behind everything the epilogue's O tile overlays
+  int* s_dst = reinterpret_cast<int*>(smem) + LY::dst_offset(rev_floats, N);
   if constexpr (DIRECT) {
-    const float LOG2E = 1.4426950408889634f;
     // eight loads in flight per thread (a load-then-store loop would pay one L2 round trip per element: ~17 in a row at Swin stage 0)
     for (int i0 = tid; i0 < rev_floats; i0 += 256 * 8) {
       float v[8];
@@ -285,7 +283,7 @@ __global__ __launch_bounds__(256, NP == 3 ? 2 : 4) void wattn2_kernel(const Geo 
       }
 #pragma unroll
       for (int u = 0; u < 8; ++u)
-        if (i0 + 256 * u < rev_floats) s_rev[i0 + 256 * u] = v[u] * LOG2E;
+        if (i0 + 256 * u < rev_floats) s_rev[i0 + 256 * u] = v[u] * kLog2e;
     }
     // token (times the row length 3 C of the qkv tensor) of window position n, forward roll applied; one division per thread,
     // then n += 256 as (zlat, zlon) += (256 / wlon, 256 % wlon) with a carry
@@ -499,7 +497,7 @@ __global__ __launch_bounds__(256, NP == 3 ? 2 : 4) void wattn2_kernel(const Geo 
   auto qk = [&](const u32x4 (&ka)[NP], int sub, int ks, f32x4 c) {
     if constexpr (NP == 3) {
 #pragma unroll
-      for (int term = 0; term < 6; ++term) c = mfma16x16x32_bf16(ka[kTA[term]], qb[sub][ks][kTB[term]], c);
+      for (int term = 0; term < 6; ++term) c = mfma16x16x32_bf16(ka[kX6A[term]], qb[sub][ks][kX6B[term]], c);
     } else {
       c = mfma16x16x32_bf16(ka[0], qb[sub][ks][0], c);
     }
@@ -522,7 +520,7 @@ __global__ __launch_bounds__(256, NP == 3 ? 2 : 4) void wattn2_kernel(const Geo 
   auto pv = [&](const u32x4 (&va)[NP], const u32x4 (&pb)[NP], f32x4 c) {
     if constexpr (NP == 3) {
 #pragma unroll
-      for (int term = 0; term < 6; ++term) c = mfma16x16x32_bf16(va[kTA[term]], pb[kTB[term]], c);
+      for (int term = 0; term < 6; ++term) c = mfma16x16x32_bf16(va[kX6A[term]], pb[kX6B[term]], c);
     } else {
       c = mfma16x16x32_bf16(va[0], pb[0], c);
     }
@@ -592,7 +590,7 @@ __global__ __launch_bounds__(256, NP == 3 ? 2 : 4) void wattn2_kernel(const Geo 
         sc[kb] = f32x4{br[0], br[1], br[2], br[3]};
         if (MASK && (((kb == 0 ? msk0 : msk1) >> sub) & 1u)) {
           // exact mode: a masked block is INCLUDED with the reference's additive -100 (swin_transformer.py:396-401)
-          const float mv = -100.0f * 1.4426950408889634f;
+          const float mv = -100.0f * kLog2e;
           sc[kb] += f32x4{mv, mv, mv, mv};
         }
 #pragma unroll
@@ -805,48 +803,48 @@ __global__ __launch_bounds__(256, NP == 3 ? 2 : 4) void wattn2_kernel(const Geo 
 struct Plan {
   bool ok = false;
   Geo G;
-  int DK, DB, DKP, DVP, TRP, NP, SUB;
+  int DKP, DVP, TRP, SUB;
   size_t bytes = 0;
   size_t off_q[3], off_k[3], off_v[3], off_rev, off_dest, off_fb, off_kmax;
   int groups = 0;
 };
 
-static Plan make_plan(const dlwp_wattn_desc* u, int batch, int np) {
+// D: the normalised descriptor (normalise_desc said usable).  ok = this path covers it; then G is the kernels' geometry and
+// the off_* place the call's images in the workspace.
+static Plan make_plan(const Desc& D, int batch, Form form) {
   Plan P;
-  if (!u || batch <= 0) return P;
-  if (u->bias_mode != 0 || u->grid[0] != 1 || u->window[0] != 1 || u->padded[0] != 1) return P;
-  for (int i = 0; i < 3; ++i)
-    if (u->padded[i] != u->grid[i] || u->pad_lead[i] != 0) return P;
-  const int lat = u->grid[1], lon = u->grid[2], wlat = u->window[1], wlon = u->window[2];
+  if (batch <= 0) return P;
+  if (D.bias_mode != 0 || D.pl != 1 || D.wpl != 1 || D.ppl != 1) return P;
+  if (D.ppl != D.pl || D.plat != D.lat || D.plon != D.lon || D.pad_f != 0 || D.pad_t != 0 || D.pad_l != 0) return P;
+  const int lat = D.lat, lon = D.lon, wlat = D.wlat, wlon = D.wlon;
   if (wlat <= 0 || wlon <= 0 || lat % wlat || lon % wlon || wlon % 16) return P;
-  const int N = wlat * wlon, d = u->head_dim;
+  const int N = wlat * wlon, d = D.d;
   if (N % 64 || N > 16384) return P;       // whole 64-query workgroup blocks; tile table + list fit LDS
   if (d != 8 && d != 16 && d != 24 && d != 48) return P;      // instantiated head dims (each leaves a spare k-slot)
-  if (u->use_mask) {
+  if (D.use_mask) {
     // a 16-key block lies in one latitude row, so latitude boundaries are free; longitude boundaries must not cut it
-    for (int b : {u->mask_b1[2], u->mask_b2[2]})
+    for (int b : {D.b1[2], D.b2[2]})
       if (b < lon && b % 16) return P;
   }
   Geo& G = P.G;
-  G.lat = lat; G.lon = lon; G.wlat = wlat; G.wlon = wlon; G.nlat = lat / wlat; G.nlon = lon / wlon;
-  G.sf[0] = ((u->shift_fwd[1] % lat) + lat) % lat; G.sf[1] = ((u->shift_fwd[2] % lon) + lon) % lon;
-  G.sb[0] = ((u->shift_back[1] % lat) + lat) % lat; G.sb[1] = ((u->shift_back[2] % lon) + lon) % lon;
-  G.use_mask = u->use_mask;
-  G.b1[0] = u->mask_b1[1]; G.b1[1] = u->mask_b1[2]; G.b2[0] = u->mask_b2[1]; G.b2[1] = u->mask_b2[2];
-  G.heads = u->heads; G.d = d; G.C = u->heads * d; G.N = N; G.nwin = G.nlat * G.nlon;
-  G.W2 = 2 * wlon - 1; G.TR = (2 * wlat - 1) * G.W2;
-  G.qscale = u->scale * 1.4426950408889634f;
-  G.io16 = 0;
-  P.DK = d / 32 + 1; P.DKP = 32 * P.DK;
-  P.DB = (d + 15) / 16; P.DVP = 16 * P.DB;
+  G.lat = lat; G.lon = lon; G.wlat = wlat; G.wlon = wlon; G.nlat = D.nlat; G.nlon = D.nlon;
+  G.sf[0] = D.sf[1]; G.sf[1] = D.sf[2];     // (padded grid = grid on this path)
+  G.sb[0] = D.sb[1]; G.sb[1] = D.sb[2];
+  G.use_mask = D.use_mask;
+  G.b1[0] = D.b1[1]; G.b1[1] = D.b1[2]; G.b2[0] = D.b2[1]; G.b2[1] = D.b2[2];
+  G.heads = D.heads; G.d = d; G.C = D.C; G.N = N; G.nwin = G.nlat * G.nlon;
+  G.W2 = 2 * wlon - 1; G.TR = D.table_rows;
+  G.qscale = D.scale * kLog2e;
+  G.io16 = form == Form::Bf16Io;
+  P.DKP = 32 * (d / 32 + 1);
+  P.DVP = 16 * ((d + 15) / 16);
   P.TRP = (G.TR + 3) & ~3;
-  P.NP = np;
   P.SUB = (N >= 2048 && N % 256 == 0) ? 4 : ((N >= 256 && N % 128 == 0) ? 2 : 1);   // N % (64 SUB) == 0
   if (d == 48 && P.SUB == 4) P.SUB = 2;     // 64 queries per wave at head_dim 48 do not fit the register file
   const size_t rows = (size_t)batch * G.heads * G.nwin * N;
   size_t off = 0;
   auto take = [&](size_t n) { const size_t o = off; off += align_up(n, 256); return o; };
-  for (int p = 0; p < np; ++p) { P.off_q[p] = take(rows * P.DKP * 2); P.off_k[p] = take(rows * P.DKP * 2); P.off_v[p] = take(rows * P.DVP * 2); }
+  for (int p = 0; p < parts(form); ++p) { P.off_q[p] = take(rows * P.DKP * 2); P.off_k[p] = take(rows * P.DKP * 2); P.off_v[p] = take(rows * P.DVP * 2); }
   P.off_rev = take((size_t)G.heads * P.TRP * 4);
   P.off_dest = take((size_t)G.nwin * N * 4);
   P.off_fb = take(256);
@@ -857,85 +855,28 @@ static Plan make_plan(const dlwp_wattn_desc* u, int batch, int np) {
   return P;
 }
 
-template <int D8, int SUB, int NP, bool DIRECT = false>
-static int32_t launch(const Plan& P, const Images& I, float* out, int batch, hipStream_t s) {
-  constexpr int KT = 32, DK = (8 * D8) / 32 + 1, DB = (8 * D8 + 15) / 16, DKP = 32 * DK, DVP = 16 * DB, LDK = DKP + 16,
-                LDV = DVP == 16 ? 16 : (DVP <= 48 ? 48 : 80);
-  constexpr int TILE_F = (((NP * KT * (LDK + LDV) + 1) / 2) + 3) & ~3;
-  const size_t ntile = (size_t)P.G.N / KT;
-  // slice of the reversed bias column a workgroup keeps in LDS: (wlat + rows of its query block - 1) table rows (+ alignment)
-  const int nq_rows = (64 * SUB + P.G.wlon - 1) / P.G.wlon;
-  const int rev_floats = (((P.G.wlat + nq_rows - 1) * P.G.W2 + 3 + 3) & ~3) + 4;
-  const size_t loop_f = (size_t)rev_floats + 2 * TILE_F + 4 + 4 * ntile + ntile + (DIRECT ? (size_t)P.G.N : 0);
-  const size_t epi_f = (size_t)64 * SUB * (DVP + 1);
-  const size_t lds = (loop_f > epi_f ? loop_f : epi_f) * 4 + (DIRECT ? 64 * SUB * 4 : 0);
+template <int D8, int SUB, int NP, bool DIRECT>
+static int32_t launch(const Plan& P, const Images& I, void* out, hipStream_t s) {
+  using LY = Layout<D8, SUB, NP, DIRECT>;
+  const int rev_floats = LY::rev_floats(P.G.wlat, P.G.wlon, P.G.W2);
+  const size_t lds = (size_t)LY::lds_bytes(rev_floats, P.G.N);
   DLWP_REQUIRE(lds <= 160 * 1024, DLWP_ERR_UNSUPPORTED, "window attention needs %zu bytes of LDS (bias table too large)", lds);
-  const int groups = batch * P.G.heads * P.G.nwin;
   const int nqb = P.G.N / (64 * SUB);
-  const int grid = ((groups + 7) / 8) * 8 * nqb;
+  const int grid = ((P.groups + 7) / 8) * 8 * nqb;
   auto kern = P.G.use_mask ? wattn2_kernel<D8, SUB, NP, true, DIRECT> : wattn2_kernel<D8, SUB, NP, false, DIRECT>;
   if (lds > 48 * 1024)
     DLWP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, P.G, I, out, groups, nqb, rev_floats);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, P.G, I, static_cast<float*>(out), P.groups, nqb, rev_floats);
   DLWP_HIP_CHECK(hipGetLastError());
   return DLWP_OK;
 }
 
-template <int NP>
-static int32_t run_np(const Plan& P_in, const float* qkv, const float* table, float* out, int batch, void* workspace,
-                      hipStream_t s, int io16 = 0) {
-  Plan P = P_in;
-  P.G.io16 = io16;
-  Images I = {};
-  char* w = reinterpret_cast<char*>(workspace);
-  for (int p = 0; p < NP; ++p) {
-    I.q[p] = reinterpret_cast<unsigned short*>(w + P.off_q[p]);
-    I.k[p] = reinterpret_cast<unsigned short*>(w + P.off_k[p]);
-    I.v[p] = reinterpret_cast<unsigned short*>(w + P.off_v[p]);
-  }
-  I.rev = reinterpret_cast<float*>(w + P.off_rev);
-  I.dest = reinterpret_cast<int*>(w + P.off_dest);
-  I.fallbacks = reinterpret_cast<int*>(w + P.off_fb);
-  I.kmax2 = reinterpret_cast<float*>(w + P.off_kmax);
-  if constexpr (NP == 1) {
-    // bfloat16 tensors: the attention kernel gathers its operands itself (DLWP_WATTN2_DIRECT=0, read once: the prep kernel + images, A/B)
-    static const bool direct = !(getenv("DLWP_WATTN2_DIRECT") && atoi(getenv("DLWP_WATTN2_DIRECT")) == 0);
-    if (io16 && direct) {
-      I.qkv16 = reinterpret_cast<const unsigned short*>(qkv);
-      I.table = table;
-      const int groups = batch * P.G.heads * P.G.nwin;
-      // shifted blocks: the key-norm pass (it also resets the fallback counter).  Plain blocks launch nothing in front of the attention
-      // kernel: their counter is NOT maintained (dlwp_window_attn_fallbacks describes the fp32-tensor entry points; include/dlwp_hip.h)
-      if (P.G.use_mask) {
-        hipLaunchKernelGGL(wattn2_kmax_kernel, dim3((unsigned)groups, (unsigned)((P.G.N + 255) / 256)), dim3(256), 0, s, P.G, I);
-        DLWP_HIP_CHECK(hipGetLastError());
-      }
-#define DLWP_W2D(D8_)                                                         \
-  do {                                                                        \
-    if (P.SUB == 4) return launch<D8_, 4, 1, true>(P, I, out, batch, s);      \
-    if (P.SUB == 2) return launch<D8_, 2, 1, true>(P, I, out, batch, s);      \
-    return launch<D8_, 1, 1, true>(P, I, out, batch, s);                      \
-  } while (0)
-      if (P.G.d == 8) DLWP_W2D(1);
-      if (P.G.d == 16) DLWP_W2D(2);
-      if (P.G.d == 24) DLWP_W2D(3);
-      if (P.G.d == 48) DLWP_W2D(6);
-#undef DLWP_W2D
-      return fail(DLWP_ERR_UNSUPPORTED, "window attention fast path: head_dim %d not instantiated", P.G.d);
-    }
-  }
-  const long long chunks = (long long)batch * P.G.heads * P.G.nwin * P.G.N * (2 * P.DKP / 8 + P.DVP / 8);
-  long long blocks = (chunks + 255) / 256;
-  if (blocks > 256 * 32) blocks = 256 * 32;
-  hipLaunchKernelGGL(wattn2_prep_kernel<NP>, dim3((unsigned)blocks), dim3(256), 0, s, P.G, qkv, table, I, batch, P.DKP,
-                     P.DVP, P.TRP);
-  DLWP_HIP_CHECK(hipGetLastError());
-#define DLWP_W2(D8_)                                                    \
-  do {                                                                   \
-    if (P.SUB == 4) return launch<D8_, 4, NP>(P, I, out, batch, s);      \
-    if (P.SUB == 2) return launch<D8_, 2, NP>(P, I, out, batch, s);      \
-    return launch<D8_, 1, NP>(P, I, out, batch, s);                      \
-  } while (0)
+// the attention kernel of the plan's head_dim and SUB
+template <int NP, bool DIRECT>
+static int32_t launch_attention(const Plan& P, const Images& I, void* out, hipStream_t s) {
+#define DLWP_W2(D8_) \
+  return P.SUB == 4 ? launch<D8_, 4, NP, DIRECT>(P, I, out, s) \
+                    : (P.SUB == 2 ? launch<D8_, 2, NP, DIRECT>(P, I, out, s) : launch<D8_, 1, NP, DIRECT>(P, I, out, s))
   if (P.G.d == 8) DLWP_W2(1);
   if (P.G.d == 16) DLWP_W2(2);
   if (P.G.d == 24) DLWP_W2(3);
@@ -944,32 +885,61 @@ static int32_t run_np(const Plan& P_in, const float* qkv, const float* table, fl
   return fail(DLWP_ERR_UNSUPPORTED, "window attention fast path: head_dim %d not instantiated", P.G.d);
 }
 
-}  // namespace wattn2
-}  // namespace dlwp
+// fp32 tensors: the prep kernel writes the operand images (NP parts each), the attention kernel reads them
+template <int NP>
+static int32_t run_images(const Plan& P, Images& I, const void* qkv, const float* table, void* out, int batch, hipStream_t s) {
+  const long long chunks = (long long)batch * P.G.heads * P.G.nwin * P.G.N * (2 * P.DKP / 8 + P.DVP / 8);
+  long long blocks = (chunks + 255) / 256;
+  if (blocks > 256 * 32) blocks = 256 * 32;
+  hipLaunchKernelGGL(wattn2_prep_kernel<NP>, dim3((unsigned)blocks), dim3(256), 0, s, P.G, static_cast<const float*>(qkv), table, I,
+                     batch, P.DKP, P.DVP, P.TRP);
+  DLWP_HIP_CHECK(hipGetLastError());
+  return launch_attention<NP, false>(P, I, out, s);
+}
 
-// Entry points used by window_attn.hip's dispatcher
-namespace dlwp {
-size_t wattn2_workspace_bytes(const dlwp_wattn_desc* u, int batch, int np) {
-  const wattn2::Plan P = wattn2::make_plan(u, batch, np);
+// bfloat16 tensors: the attention kernel gathers its operands from the qkv tensor itself
+static int32_t run_direct(const Plan& P, Images& I, const void* qkv, const float* table, void* out, hipStream_t s) {
+  I.qkv16 = static_cast<const unsigned short*>(qkv);
+  I.table = table;
+  // shifted blocks: the key-norm pass (it also resets the fallback counter).  Plain blocks launch nothing in front of the attention
+  // kernel: their counter is NOT maintained (dlwp_window_attn_fallbacks describes the fp32-tensor entry points; include/dlwp_hip.h)
+  if (P.G.use_mask) {
+    hipLaunchKernelGGL(wattn2_kmax_kernel, dim3((unsigned)P.groups, (unsigned)((P.G.N + 255) / 256)), dim3(256), 0, s, P.G, I);
+    DLWP_HIP_CHECK(hipGetLastError());
+  }
+  return launch_attention<1, true>(P, I, out, s);
+}
+
+// ---- the path's interface (window_attn_desc.hpp), used by window_attn.hip's dispatcher
+size_t workspace_bytes(const Desc& D, int batch, Form form) {
+  const Plan P = make_plan(D, batch, form);
   return P.ok ? P.bytes : 0;
 }
-// device address of the call's fallback counter inside the workspace (nullptr: descriptor not covered)
-const int* wattn2_fallback_counter(const dlwp_wattn_desc* u, int batch, int np, const void* workspace) {
-  const wattn2::Plan P = wattn2::make_plan(u, batch, np);
-  if (!P.ok || !workspace) return nullptr;
-  return reinterpret_cast<const int*>(reinterpret_cast<const char*>(workspace) + P.off_fb);
+
+const int* fallback_counter(const Desc& D, int batch, Form form, const void* workspace) {
+  return reinterpret_cast<const int*>(reinterpret_cast<const char*>(workspace) + make_plan(D, batch, form).off_fb);
 }
-// returns DLWP_OK, an error, or 1 when this descriptor is not covered (the caller takes the generic kernel)
-int32_t wattn2_run(const dlwp_wattn_desc* u, const float* qkv, const float* table, float* out, int batch, void* workspace,
-                   size_t workspace_bytes, hipStream_t s, int np) {
-  const int io16 = np == 16 ? 1 : 0;        // bf16 form with bfloat16 qkv / output tensors
-  if (io16) np = 1;
-  const wattn2::Plan P = wattn2::make_plan(u, batch, np);
-  if (!P.ok || !workspace || workspace_bytes < P.bytes) return 1;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255) || (reinterpret_cast<uintptr_t>(qkv) & 15) ||
-      (reinterpret_cast<uintptr_t>(out) & 15))
-    return 1;
-  return np == 3 ? wattn2::run_np<3>(P, qkv, table, out, batch, workspace, s)
-                 : wattn2::run_np<1>(P, qkv, table, out, batch, workspace, s, io16);
+
+int32_t run(const Desc& D, const void* qkv, const float* table, void* out, int batch, void* workspace, size_t workspace_bytes,
+            hipStream_t s, Form form) {
+  const Plan P = make_plan(D, batch, form);
+  if (!P.ok || !workspace || workspace_bytes < P.bytes) return wattn::kNotCovered;
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255) || ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(out)) & 15))
+    return wattn::kNotCovered;
+  Images I = {};
+  char* w = reinterpret_cast<char*>(workspace);
+  for (int p = 0; p < parts(form); ++p) {
+    I.q[p] = reinterpret_cast<unsigned short*>(w + P.off_q[p]);
+    I.k[p] = reinterpret_cast<unsigned short*>(w + P.off_k[p]);
+    I.v[p] = reinterpret_cast<unsigned short*>(w + P.off_v[p]);
+  }
+  I.rev = reinterpret_cast<float*>(w + P.off_rev); I.dest = reinterpret_cast<int*>(w + P.off_dest);
+  I.fallbacks = reinterpret_cast<int*>(w + P.off_fb); I.kmax2 = reinterpret_cast<float*>(w + P.off_kmax);
+  switch (form) {
+    case Form::X6: return run_images<3>(P, I, qkv, table, out, batch, s);
+    case Form::Bf16: return run_images<1>(P, I, qkv, table, out, batch, s);
+    default: return run_direct(P, I, qkv, table, out, s);
+  }
 }
+}  // namespace wattn2
 }  // namespace dlwp

@@ -23,11 +23,13 @@
 // NP = 1: bf16 operands (dlwp_window_attn_bf16); NP = 3: exact three-way bf16 splits of Q, K, V, P with six cross products
 // per contraction = fp32-GEMM accuracy (dlwp_window_attn_f32).
 #include "common.hpp"
+#include "window_attn_desc.hpp"
 
 namespace dlwp {
 namespace wattn3 {
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
+using wattn::Desc;
+using wattn::Form;
 
 struct Geo {
   int pl, lat, lon;           // un-padded token grid
@@ -48,15 +50,24 @@ struct Geo {
 constexpr int D = 32;          // head dim
 constexpr int LDK = 48;        // bf16 elements per K row in LDS (96 bytes: conflict free for the b128 operand reads)
 constexpr int LDV = 48;        // V row: 32 dims + the ones column + 15 zeros (three 16-dim output blocks)
-__device__ constexpr int kTA[6] = {2, 0, 1, 1, 0, 0};   // bf16x6 terms, smallest first: (A part, B part)
-__device__ constexpr int kTB[6] = {0, 2, 1, 0, 1, 0};
+
+// LDS layout, read by wattn3_kernel<RP, PP, PB, NP, ...> and by its launcher: [bias column TRP floats][K: NP parts of KR rows]
+// [V: NP parts of VR rows][key part of the bias index, NS slots][shift-mask region, NS slots]
+template <int RP, int PP, int PB, int NP>
+struct Layout {
+  static constexpr int KB = (RP + PP) * PB;               // 16-key blocks
+  static constexpr int NS = 16 * KB;                      // logical key slots (plane-major, each plane padded to 16 PB)
+  static constexpr int KR = RP * 16 * PB + PP * 16;       // K rows in LDS
+  static constexpr int VR = RP * 16 * PB + PP * 32;       // V rows in LDS
+  __host__ __device__ static constexpr int lds_bytes(int TRP) { return TRP * 4 + NP * (KR * LDK + VR * LDV) * 2 + 2 * NS * 4; }
+};
 
 // transposed + scaled bias table: [types][heads][TRP] = table[row][type][head] * log2 e
 __global__ __launch_bounds__(256) void wattn3_table_kernel(const float* __restrict__ table, float* __restrict__ tabT, int rows,
                                                            int rows_p, int types, int heads) {
   const int th = blockIdx.x;                      // type * heads + head
   for (int i = threadIdx.x; i < rows_p; i += 256)
-    tabT[(long long)th * rows_p + i] = i < rows ? table[(long long)i * types * heads + th] * 1.4426950408889634f : 0.f;
+    tabT[(long long)th * rows_p + i] = i < rows ? table[(long long)i * types * heads + th] * kLog2e : 0.f;
 }
 
 // RP real planes (staged per window) + PP (0 / 1) plane that is zero padding as a whole: its tokens all carry the qkv
@@ -82,20 +93,17 @@ __global__ __launch_bounds__(64 * PB) __attribute__((amdgpu_waves_per_eu(PP == 1
   const unsigned short* bias16 = reinterpret_cast<const unsigned short*>(qkv_bias);
   constexpr bool MASK = true;
   constexpr int WPL = RP + PP;
-  constexpr int KB = WPL * PB;                    // 16-key blocks
-  constexpr int NS = 16 * KB;                     // logical key slots (plane-major, each plane padded to 16 PB)
-  constexpr int KR = RP * 16 * PB + PP * 16;      // K rows in LDS
-  constexpr int VR = RP * 16 * PB + PP * 32;      // V rows in LDS
+  using LY = Layout<RP, PP, PB, NP>;
+  constexpr int KB = LY::KB, NS = LY::NS, KR = LY::KR, VR = LY::VR;
   constexpr int NT = 64 * PB;                     // threads
   constexpr int CPT = 2 * RP;                     // 16-byte fp32 chunks of K (and of V) a thread stages per window
   constexpr int KS2 = (KB + 1) / 2;               // 32-key k-steps of the PV product
-  constexpr float LOG2E = 1.4426950408889634f;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   float* s_tab = reinterpret_cast<float*>(smem_raw);                                   // [TRP]
   unsigned short* s_k = reinterpret_cast<unsigned short*>(s_tab + G.TRP);              // [NP][KR][LDK]
   unsigned short* s_v = s_k + NP * KR * LDK;                                           // [NP][VR][LDV]
   int* s_bkey = reinterpret_cast<int*>(s_v + NP * VR * LDV);                           // [NS] key part of the bias index
-  int* s_rkey = s_bkey + NS;                                                           // [NS] shift-mask region of the slot
+  int* s_rkey = reinterpret_cast<int*>(smem_raw + LY::lds_bytes(G.TRP)) - NS;          // [NS] shift-mask region of the slot
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // query block of the plane
@@ -252,7 +260,7 @@ __global__ __launch_bounds__(64 * PB) __attribute__((amdgpu_waves_per_eu(PP == 1
   for (int i = 0; i < WPL; ++i) {
     const int pk = ipl * WPL + zplane[i], pq = ipl * WPL + zq;
     const bool differ = ((pk >= G.b1[0]) + (pk >= G.b2[0])) != ((pq >= G.b1[0]) + (pq >= G.b2[0]));
-    plane_mask[i] = (MASK && differ) ? -100.0f * LOG2E : 0.f;
+    plane_mask[i] = (MASK && differ) ? -100.0f * kLog2e : 0.f;
   }
 
   const float* qkv_b = qkv + (long long)b * L * 3 * C;
@@ -388,7 +396,7 @@ __global__ __launch_bounds__(64 * PB) __attribute__((amdgpu_waves_per_eu(PP == 1
       asm volatile("" ::: "memory");                   // keep the halves apart
     }
     if constexpr (MODE == 2) {
-      const float mv = -100.0f * LOG2E;
+      const float mv = -100.0f * kLog2e;
 #pragma unroll
       for (int kb = 0; kb < KB; ++kb) {
         const int4 rk = *reinterpret_cast<const int4*>(s_rkey + 16 * kb + 4 * g);
@@ -411,7 +419,7 @@ __global__ __launch_bounds__(64 * PB) __attribute__((amdgpu_waves_per_eu(PP == 1
       for (int p = 0; p < NP; ++p) ka[p] = *reinterpret_cast<const u32x4*>(s_k + (p * KR + krow(kb) + j) * LDK + 8 * g);
       if constexpr (NP == 3) {
 #pragma unroll
-        for (int term = 0; term < 6; ++term) sc[kb] = mfma16x16x32_bf16(ka[kTA[term]], qb[kTB[term]], sc[kb]);
+        for (int term = 0; term < 6; ++term) sc[kb] = mfma16x16x32_bf16(ka[kX6A[term]], qb[kX6B[term]], sc[kb]);
       } else {
         sc[kb] = mfma16x16x32_bf16(ka[0], qb[0], sc[kb]);
       }
@@ -483,7 +491,7 @@ __global__ __launch_bounds__(64 * PB) __attribute__((amdgpu_waves_per_eu(PP == 1
             oacc[db] = mfma16x16x32_bf16(va[0], pb[0], oacc[db]);
           } else {
 #pragma unroll
-            for (int term = 0; term < 6; ++term) oacc[db] = mfma16x16x32_bf16(va[kTA[term]], pb[kTB[term]], oacc[db]);
+            for (int term = 0; term < 6; ++term) oacc[db] = mfma16x16x32_bf16(va[kX6A[term]], pb[kX6B[term]], oacc[db]);
           }
         } else {
           oacc[db] = mfma16x16x32_bf16(va[0], pb[0], oacc[db]);
@@ -511,44 +519,37 @@ __global__ __launch_bounds__(64 * PB) __attribute__((amdgpu_waves_per_eu(PP == 1
   }
 }
 
-}  // namespace wattn3
-
-using namespace wattn3;
-
+// ---- host
 struct Plan3 {
   Geo G;
-  int rp, pp, pb;
-  bool ok;
+  int rp, pp, pb;      // real planes, padded planes, 16-key blocks per plane
+  bool ok = false;
 };
 
-static Plan3 make_plan3(const dlwp_wattn_desc* u) {
+// desc: the normalised descriptor (normalise_desc said usable).  ok = this kernel covers it; then G is its geometry.
+static Plan3 make_plan3(const Desc& desc) {
   Plan3 P;
-  P.ok = false;
-  if (!u || u->bias_mode != 1 || u->head_dim != 32 || u->heads <= 0) return P;
-  const int wpl = u->window[0], wlat = u->window[1], wlon = u->window[2];
+  if (desc.bias_mode != 1 || desc.d != 32 || desc.heads <= 0) return P;
+  const int wpl = desc.wpl, wlat = desc.wlat, wlon = desc.wlon;
   if (wpl < 1 || wpl > 2 || wlat < 1 || wlon < 1 || wlat * wlon > 80) return P;
-  for (int i = 0; i < 3; ++i)
-    if (u->grid[i] <= 0 || u->padded[i] <= 0 || u->padded[i] % u->window[i] || u->padded[i] < u->grid[i] + u->pad_lead[i] ||
-        u->pad_lead[i] < 0)
-      return P;
   Geo& G = P.G;
-  G.pl = u->grid[0]; G.lat = u->grid[1]; G.lon = u->grid[2];
-  G.ppl = u->padded[0]; G.plat = u->padded[1]; G.plon = u->padded[2];
-  G.pad_f = u->pad_lead[0]; G.pad_t = u->pad_lead[1]; G.pad_l = u->pad_lead[2];
+  G.pl = desc.pl; G.lat = desc.lat; G.lon = desc.lon;
+  G.ppl = desc.ppl; G.plat = desc.plat; G.plon = desc.plon;
+  G.pad_f = desc.pad_f; G.pad_t = desc.pad_t; G.pad_l = desc.pad_l;
   G.wpl = wpl; G.wlat = wlat; G.wlon = wlon;
-  G.npl = G.ppl / wpl; G.nlat = G.plat / wlat; G.nlon = G.plon / wlon;
+  const int grid[3] = {G.pl, G.lat, G.lon}, padded[3] = {G.ppl, G.plat, G.plon}, window[3] = {wpl, wlat, wlon}, lead[3] = {G.pad_f, G.pad_t, G.pad_l};
+  for (int i = 0; i < 3; ++i)
+    if (grid[i] <= 0 || padded[i] <= 0 || padded[i] % window[i] || padded[i] < grid[i] + lead[i] || lead[i] < 0) return P;
+  G.npl = desc.npl; G.nlat = desc.nlat; G.nlon = desc.nlon;
   for (int i = 0; i < 3; ++i) {
-    const int dim = u->padded[i];
-    G.sf[i] = ((u->shift_fwd[i] % dim) + dim) % dim;
-    G.sb[i] = ((u->shift_back[i] % dim) + dim) % dim;
-    G.b1[i] = u->use_mask ? u->mask_b1[i] : (1 << 30);
-    G.b2[i] = u->use_mask ? u->mask_b2[i] : (1 << 30);
+    G.sf[i] = desc.sf[i];
+    G.sb[i] = desc.sb[i];
+    G.b1[i] = desc.use_mask ? desc.b1[i] : (1 << 30);
+    G.b2[i] = desc.use_mask ? desc.b2[i] : (1 << 30);
   }
-  G.heads = u->heads; G.C = u->heads * 32;
-  G.W2 = 2 * wlon - 1;
-  G.TR = wpl * wpl * wlat * wlat * G.W2;
-  G.TRP = (G.TR + 3) & ~3;
-  G.qscale = u->scale * 1.4426950408889634f;
+  G.heads = desc.heads; G.C = desc.C;
+  G.W2 = 2 * wlon - 1; G.TR = desc.table_rows; G.TRP = (G.TR + 3) & ~3;
+  G.qscale = desc.scale * kLog2e;
   // planes: every plane of every window real (no level padding), or ONE window level of two planes of which one is real
   int real_min = wpl, real_max = 0;
   for (int ipl = 0; ipl < G.npl; ++ipl) {
@@ -568,7 +569,7 @@ static Plan3 make_plan3(const dlwp_wattn_desc* u) {
   // cut windows (shifted blocks): rows / columns with a region boundary strictly inside
   G.ncr = G.ncc = G.ncut = 0;
   G.cr[0] = G.cr[1] = G.cc[0] = G.cc[1] = 0;
-  if (u->use_mask) {
+  if (desc.use_mask) {
     auto inside = [](int bb, int lo, int n) { return bb > lo && bb < lo + n; };
     for (int r = 0; r < G.nlat; ++r)
       if (inside(G.b1[1], r * wlat, wlat) || inside(G.b2[1], r * wlat, wlat)) {
@@ -590,77 +591,69 @@ static Plan3 make_plan3(const dlwp_wattn_desc* u) {
   return P;
 }
 
-template <int RP, int PP, int PB, int NP>
-static size_t lds_bytes(const Geo& G) {
-  constexpr int KB = (RP + PP) * PB, NS = 16 * KB, KR = RP * 16 * PB + PP * 16, VR = RP * 16 * PB + PP * 32;
-  return (size_t)G.TRP * 4 + (size_t)NP * KR * LDK * 2 + (size_t)NP * VR * LDV * 2 + (size_t)2 * NS * 4;
-}
+static size_t table_bytes(const Geo& G) { return (size_t)G.npl * G.nlat * G.heads * G.TRP * sizeof(float); }
 
-template <int RP, int PP, int PB, int NP, bool IO16 = false>
-static int32_t launch3(const Geo& G, bool mask, const float* qkv, const float* qkv_bias, const float* tabT, float* out, int batch,
+// the tensors are fp32, or bfloat16 when IO16: the kernel reinterprets its pointers
+template <int RP, int PP, int PB, int NP, bool IO16>
+static int32_t launch3(const Geo& G, bool mask, const void* qkv, const void* qkv_bias, const float* tabT, void* out, int batch,
                        long long L, hipStream_t s) {
-  const size_t lds = lds_bytes<RP, PP, PB, NP>(G);
-  if (lds > 160 * 1024) return 1;
+  const size_t lds = (size_t)Layout<RP, PP, PB, NP>::lds_bytes(G.TRP);
+  if (lds > 160 * 1024) return wattn::kNotCovered;
   const long long gy = (long long)batch * G.npl * G.nlat * (RP + PP) * G.nch;
   const long long gy2 = (long long)batch * G.npl * (RP + PP) * G.ncut;
-  if (gy >= 65536 || gy2 >= 65536) return 1;      // beyond the grid's y extent: the generic kernel takes the call
+  if (gy >= 65536 || gy2 >= 65536) return wattn::kNotCovered;      // beyond the grid's y extent: the generic kernel takes the call
   const dim3 grid((unsigned)G.heads, (unsigned)gy), block(64 * PB);
   auto go = [&](auto kern, dim3 gr) -> int32_t {
     if (lds > 48 * 1024)
       DLWP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, gr, block, lds, s, G, qkv, qkv_bias, tabT, out, L);
+    hipLaunchKernelGGL(kern, gr, block, lds, s, G, static_cast<const float*>(qkv), static_cast<const float*>(qkv_bias), tabT,
+                       static_cast<float*>(out), L);
     return DLWP_OK;
   };
   // (unshifted blocks run the same kernel: boundaries at 2^30, nothing cut, plane constants 0.  A mask-free instantiation
   // was no faster at NP = 1 and needed 9 spilled registers at NP = 3.)
-  int32_t rc = go(wattn3_kernel<RP, PP, PB, NP, 1, IO16>, grid);
-  if (rc != DLWP_OK) return rc;
-  if (mask && G.ncut > 0) {
-    rc = go(wattn3_kernel<RP, PP, PB, NP, 2, IO16>, dim3((unsigned)G.heads, (unsigned)gy2));
-    if (rc != DLWP_OK) return rc;
-  }
+  if (const int32_t rc = go(wattn3_kernel<RP, PP, PB, NP, 1, IO16>, grid); rc != DLWP_OK) return rc;
+  if (mask && G.ncut > 0)
+    if (const int32_t rc = go(wattn3_kernel<RP, PP, PB, NP, 2, IO16>, dim3((unsigned)G.heads, (unsigned)gy2)); rc != DLWP_OK) return rc;
   DLWP_HIP_CHECK(hipGetLastError());
   return DLWP_OK;
 }
 
-size_t wattn3_workspace_bytes(const dlwp_wattn_desc* u, int /*batch*/, int /*np*/) {
-  const Plan3 P = make_plan3(u);
-  if (!P.ok) return 0;
-  return (size_t)P.G.npl * P.G.nlat * P.G.heads * P.G.TRP * sizeof(float);
+// The path's interface (window_attn_desc.hpp), used by window_attn.hip's dispatcher
+size_t workspace_bytes(const Desc& desc) {
+  const Plan3 P = make_plan3(desc);
+  return P.ok ? table_bytes(P.G) : 0;
 }
 
-// 0 = done, 1 = not covered by this kernel (the caller falls through to the generic one), < 0 = error
-// np: 3 bf16x6 (fp32-accurate), 1 bf16, 16 bf16 with bfloat16 qkv / qkv bias / output tensors (the pointers are reinterpreted)
-int32_t wattn3_run(const dlwp_wattn_desc* u, const float* qkv, const float* qkv_bias, const float* table, float* out, int batch,
-                   void* workspace, size_t workspace_bytes, hipStream_t s, int np) {
-  const Plan3 P = make_plan3(u);
-  if (!P.ok) return 1;
+int32_t run(const Desc& desc, const void* qkv, const void* qkv_bias, const float* table, void* out, int batch, void* workspace,
+            size_t workspace_bytes, hipStream_t s, Form form) {
+  const Plan3 P = make_plan3(desc);
+  if (!P.ok) return wattn::kNotCovered;
   const Geo& G = P.G;
-  const size_t need = wattn3_workspace_bytes(u, batch, np);
-  if (!workspace || workspace_bytes < need) return 1;
   const bool padded = G.ppl != G.pl || G.plat != G.lat || G.plon != G.lon;
-  if (padded && !qkv_bias) return 1;
   const long long L = (long long)G.pl * G.lat * G.lon;
-  if (L * 3 * G.C >= (1ll << 31)) return 1;
-  if ((reinterpret_cast<uintptr_t>(qkv) & 15) || (reinterpret_cast<uintptr_t>(out) & 15) ||
-      (reinterpret_cast<uintptr_t>(qkv_bias) & 15) || (reinterpret_cast<uintptr_t>(workspace) & 15))
-    return 1;
+  const uintptr_t ptrs = reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(qkv_bias) |
+                         reinterpret_cast<uintptr_t>(workspace);
+  if (!workspace || workspace_bytes < table_bytes(G) || (padded && !qkv_bias) || L * 3 * G.C >= (1ll << 31) || (ptrs & 15))
+    return wattn::kNotCovered;
   float* tabT = reinterpret_cast<float*>(workspace);
   const int types = G.npl * G.nlat;
   hipLaunchKernelGGL(wattn3_table_kernel, dim3((unsigned)(types * G.heads)), dim3(256), 0, s, table, tabT, G.TR, G.TRP, types,
                      G.heads);
   DLWP_HIP_CHECK(hipGetLastError());
-  const float* qb = qkv_bias ? qkv_bias : qkv;      // never dereferenced when nothing is padded
-  const bool mask = u->use_mask != 0;
-#define DLWP_W3(RP_, PP_, PB_)                                                                                  \
-  if (P.rp == RP_ && P.pp == PP_ && P.pb == PB_)                                                                \
-    return np == 3 ? launch3<RP_, PP_, PB_, 3>(G, mask, qkv, qb, tabT, out, batch, L, s)                        \
-                   : (np == 16 ? launch3<RP_, PP_, PB_, 1, true>(G, mask, qkv, qb, tabT, out, batch, L, s)      \
-                               : launch3<RP_, PP_, PB_, 1>(G, mask, qkv, qb, tabT, out, batch, L, s));
+  const void* qb = qkv_bias ? qkv_bias : qkv;      // never dereferenced when nothing is padded
+  const bool mask = desc.use_mask != 0;
+#define DLWP_W3(RP_, PP_, PB_)                                                                                            \
+  if (P.rp == RP_ && P.pp == PP_ && P.pb == PB_)                                                                          \
+    return form == Form::X6 ? launch3<RP_, PP_, PB_, 3, false>(G, mask, qkv, qb, tabT, out, batch, L, s)                  \
+                            : (form == Form::Bf16Io ? launch3<RP_, PP_, PB_, 1, true>(G, mask, qkv, qb, tabT, out, batch, L, s)   \
+                                                    : launch3<RP_, PP_, PB_, 1, false>(G, mask, qkv, qb, tabT, out, batch, L, s));
   DLWP_W3(1, 1, 5) DLWP_W3(1, 1, 3) DLWP_W3(1, 1, 2) DLWP_W3(2, 0, 5) DLWP_W3(2, 0, 3) DLWP_W3(2, 0, 2) DLWP_W3(1, 0, 5)
   DLWP_W3(1, 0, 3) DLWP_W3(1, 0, 2)
 #undef DLWP_W3
-  return 1;
+  return wattn::kNotCovered;
 }
 
+}  // namespace wattn3
 }  // namespace dlwp
+

@@ -24,7 +24,6 @@ namespace dlwp {
 namespace wattn {
 
 constexpr int BT = 32;               // tile edge: 32 queries x 32 keys
-constexpr float kLog2e = 1.4426950408889634f;
 
 // per-row statistics: [(b * nwin + win) * heads + head][N][3] = {m (log2 domain), l, delta}
 struct BwdArgs {
@@ -353,10 +352,8 @@ extern "C" int32_t dlwp_window_attn_bwd_f32(const dlwp_wattn_desc* u, const floa
   DLWP_REQUIRE(u && qkv && table && grad_out && grad_qkv && grad_table && workspace, DLWP_ERR_INVALID_ARGUMENT, "null argument");
   DLWP_REQUIRE(batch > 0, DLWP_ERR_INVALID_ARGUMENT, "batch must be positive");
   Desc D;
-  {
-    const int32_t rc = make_desc(u, qkv_bias, D);
-    if (rc != DLWP_OK) return rc;
-  }
+  normalise_desc(u, D);
+  if (const int32_t rc = check_desc(D, qkv_bias); rc != DLWP_OK) return rc;
   const bool padded = (D.ppl != D.pl) || (D.plat != D.lat) || (D.plon != D.lon);
   DLWP_REQUIRE(!padded || grad_qkv_bias, DLWP_ERR_INVALID_ARGUMENT,
                "padded windows: zero-padded tokens carry the qkv bias, its gradient buffer is needed");

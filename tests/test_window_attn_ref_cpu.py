@@ -3,8 +3,10 @@
 * training.window_attention_torch -- the differentiable restatement the backward tests differentiate -- equals the
   independent float64 reference (tests/window_attn_ref.py) at every geometry of the tables, in float64;
 * the tables reach the kernels they claim.  plan2 / plan3 / generic_variant restate the host rules (wattn2::make_plan in
-  csrc/window_attn2.hip, make_plan3 in csrc/window_attn3.hip, launch_wattn in csrc/window_attn.hip); the GPU tests assert
-  the same coverage again with dlwp_window_attn_workspace_bytes, so a stale restatement cannot hide a miss.
+  csrc/window_attn2.hip, wattn3::make_plan3 in csrc/window_attn3.hip, launch_wattn in csrc/window_attn.hip; the first two on
+  the Desc that normalise_desc of csrc/window_attn_desc.hpp fills, ordered by select_path of csrc/window_attn.hip); the GPU
+  tests and tests/test_window_attn_host_cpu.py assert the same coverage again with dlwp_window_attn_workspace_bytes, so a
+  stale restatement cannot hide a miss.
 """
 import dataclasses
 import functools
@@ -180,7 +182,7 @@ def plan2(spec):
 
 
 def plan3(spec):
-    """make_plan3 (csrc/window_attn3.hip): None when the earth-window kernel declines the descriptor, else (RP, PP, PB):
+    """wattn3::make_plan3 (csrc/window_attn3.hip): None when the earth-window kernel declines the descriptor, else (RP, PP, PB):
     real planes and padded planes per window, 16-key blocks per plane."""
     if spec.bias_mode != 1 or spec.head_dim != 32 or spec.heads <= 0:
         return None

@@ -9,7 +9,7 @@
 // tile of a chunk of input channels is staged in LDS with the cylinder rule applied at load time
 // (longitude wraps, latitude pads with zeros), every thread owns one pixel and accumulates a chunk of
 // output channels with weights broadcast from LDS; bias + activation fused in the epilogue.  The per-element load of the
-// halo tile is conv3x3_load.hpp's, which the weight gradient (conv3x3_wgrad.hip) shares.
+// halo tile is conv3x3_load.hpp's, which the weight gradient (conv_wgrad.hip) shares.
 #include "act_common.hpp"
 #include "conv3x3_load.hpp"
 

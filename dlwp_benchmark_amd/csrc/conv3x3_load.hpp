@@ -1,6 +1,6 @@
 // The padded, pre-activated, two-segment input load of the 3x3 convolution family: one element of
 // P(act_pre(cat([x0, x1], 1))) at (sample b, channel c, row ih, column iw), ih in [-1, H], iw in [-1, W].  Shared by the direct
-// forward (conv.hip: conv3x3_cyl_kernel) and the weight gradient (conv3x3_wgrad.hip), so both read the same padded tensor.
+// forward (conv.hip: conv3x3_cyl_kernel) and the weight gradient (conv_wgrad.hip: PaddedLoad), so both read the same padded tensor.
 //   P = CylinderPad(1) when p.hpx is null: longitude wraps, latitude pads zeros (utils/utils.py:11-26);
 //   P = HEALPixPadding(1) through the ring table otherwise (utils/healpix.py:316-368).
 // `Src` is any parameter block with the fields x0, c0, x1, c1, H, W, pre_act, hpx of conv::Params.

@@ -1,14 +1,12 @@
-// The second launch of the convolution weight gradients (conv3x3_wgrad.hip, conv2_wgrad.hip): the K-slices' partial dW / db,
-// which the first launch left in the workspace, summed in slice order.  One writer per element and a fixed order: with a slice
-// count that depends on the shape alone the result is bit-identical from run to run.
+// The second launch of the convolution weight gradients (conv_wgrad.hip): the K-slices' partial dW / db, which the first launch
+// left in the workspace, summed in slice order (layernorm_bwd.hip and bias_act.hip sum their partials with it too).  One writer
+// per element and a fixed order: with a slice count that depends on the shape alone the result is bit-identical from run to run.
 #pragma once
 
 #include "common.hpp"
 
 namespace dlwp {
 namespace wgrad {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // dw[i] = sum over the slices, in index order, of part_w[s][i]; db likewise behind it (n_b = 0: no bias gradient)
 static __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ part_w,

@@ -4,7 +4,7 @@ references, the exchange of roles that lets one kernel serve Conv2d and ConvTran
 C ABI table.
 
 CASES: tag -> (B, cin, cout, H, W of the layer's input, k, stride, padding, pre_act, transposed, offset).  The kernel
-(csrc/conv2_wgrad.hip) works on 64 x 64 channel blocks as 2 x 2 waves of 32 x 32, on tiles of the smaller map of 8 x 8 pixels
+(csrc/conv_wgrad.hip) works on 64 x 64 channel blocks as 2 x 2 waves of 32 x 32, on tiles of the smaller map of 8 x 8 pixels
 (stride 1) or 4 x 8 (stride 2) consumed two pixels per matrix instruction, one instantiation per (k, stride), the taps of k = 4
 in two groups of two kernel rows, K-slices of at least 256 pixels (4 / 8 tiles).  Each case is the smallest at which a part of
 it can go wrong:
@@ -206,6 +206,39 @@ def test_envelope_needs_no_gpu():
     assert not ops.conv2d_weight_grad_supported(1, 1, 1, 4, 4, 3, 1, 3)
     assert not ops.conv2d_weight_grad_supported(1, 1, 1, 2, 2, 3, 1, 0)          # the kernel does not fit the map
     assert not ops.conv2d_weight_grad_supported(1, 1, 1, 1, 1, 2, 2, 1, True)    # ConvTranspose2d with an empty output
+
+
+def test_padded_3x3_layer_is_planned_as_k3_s1_p1():
+    """one planner: the 3x3 entry points' slice count and workspace are those of the k x k ones at k 3, stride 1, padding 1,
+    shape for shape (the reruns of both are bit-identical by the one slice rule); channels past the envelope give 0 on both"""
+    l = lib.load()
+    for b in (1, 4, 5, 8, 9):
+        for h, w in ((1, 1), (3, 32), (3, 33), (8, 8)):
+            for cin, cout in ((1, 1), (2, 3), (65, 64), (1024, 1024), (1025, 1)):
+                slices = int(l.dlwp_conv3x3_wgrad_slices(b, h, w, cin, cout))
+                nbytes = int(l.dlwp_conv3x3_wgrad_workspace_bytes(b, h, w, cin, cout))
+                assert slices == int(l.dlwp_conv2d_wgrad_slices(b, cin, h, w, cout, 3, 1, 1, 0)), (b, h, w, cin, cout)
+                assert nbytes == int(l.dlwp_conv2d_wgrad_workspace_bytes(b, cin, h, w, cout, 3, 1, 1, 0)), (b, h, w, cin, cout)
+                assert (slices > 0) == (nbytes > 0) == (cin <= 1024)
+
+
+@pytest.mark.parametrize("tag", ["multi_slice", "tiles"])
+def test_cylinder_and_zero_padding_share_the_centre_column(tag):
+    """which taps tell CylinderPad(1) from zero padding: the rules differ in the wrapped longitude columns -1 and W alone (the
+    latitude rows are zeros under both), and tap (ky, kx) reads column x + kx - 1, so only kx = 0 and kx = 2 reach them.
+    In fp64: dW[:, :, :, 1] and db agree, each of the other two columns differs.  What the GPU comparison of the two loaders
+    (test_conv2_wgrad_gpu.test_padded_3x3_layer_is_the_k3_s1_p1_instance) relies on."""
+    import test_conv3x3_wgrad_cpu as c3
+
+    x0, x1, dz = c3.inputs(tag)
+    assert x1 is None and not c3.CASES[tag][7]
+    cyl_w, cyl_b = c3.reference(tag, A["relu"])
+    zero_w, zero_b = reference_of(x0, dz, 3, 1, 1, A["relu"], False)
+    scale = float(cyl_w.abs().max())
+    assert float((cyl_w[:, :, :, 1] - zero_w[:, :, :, 1]).abs().max()) <= 1e-12 * scale and scale > 0
+    assert float((cyl_b - zero_b).abs().max()) <= 1e-12 * float(cyl_b.abs().max())
+    for kx in (0, 2):
+        assert float((cyl_w[:, :, :, kx] - zero_w[:, :, :, kx]).abs().max()) > 1e-3 * scale
 
 
 def test_c_abi_table_has_the_entries():

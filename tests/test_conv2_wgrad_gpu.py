@@ -1,4 +1,4 @@
-"""dlwp_conv2d_wgrad_f32 (csrc/conv2_wgrad.hip) on the GPU: the weight / bias gradient of the strided, 1x1 and transposed
+"""dlwp_conv2d_wgrad_f32 (csrc/conv_wgrad.hip) on the GPU: the weight / bias gradient of the strided, 1x1 and transposed
 convolutions of the U-Net family, and its wiring into training._Conv2dFn / _ConvTranspose2dFn under DLWP_CONV_WGRAD.
 
   * every case of test_conv2_wgrad_cpu.CASES against fp64 autograd of training.conv2d_torch / conv_transpose2d_torch: relative
@@ -121,6 +121,27 @@ def test_need_flags(tag):
     assert none is None and torch.equal(dw, dw2)
     none, db2 = _run(tag, need_weight=False)
     assert none is None and torch.equal(db, db2)
+
+
+@pytest.mark.parametrize("tag", ["multi_slice", "tiles"])
+def test_padded_3x3_layer_is_the_k3_s1_p1_instance(tag):
+    """one kernel, two loaders: on a cylinder the padded 3x3 layer and the zero-padded k3 s1 p1 layer differ only in the
+    wrapped longitude columns -1 and W, which the taps kx = 0 and kx = 2 alone reach (the latitude rows are zeros under both
+    rules, ReLU keeps them so: test_conv2_wgrad_cpu.test_cylinder_and_zero_padding_share_the_centre_column).  The taps
+    kx = 1 are fed the same values in the same tile, pixel-pair and slice order, each into its own accumulator, and db is the
+    same sum: bitwise equal.  3x3 cases: two slices with a short last one (multi_slice), partial channel quarters (tiles)."""
+    import test_conv3x3_wgrad_cpu as c3
+    from dlwp_benchmark_amd import ops
+
+    x0, x1, dz = c3.inputs(tag)
+    assert x1 is None and not c3.CASES[tag][7]
+    relu = ops.ACTS["relu"]
+    dw3, db3 = ops.conv3x3_weight_grad(x0.to(DEV), None, dz.to(DEV), pre_act=relu, hpx=False)
+    dw2, db2 = ops.conv2d_weight_grad(x0.to(DEV), dz.to(DEV), 3, 1, 1, pre_act=relu)
+    torch.cuda.synchronize()
+    assert float(dw3[:, :, :, 1].abs().max()) > 0 and not torch.equal(dw3, dw2)
+    assert torch.equal(db3, db2)
+    assert torch.equal(dw3[:, :, :, 1], dw2[:, :, :, 1])
 
 
 def test_bad_arguments():

@@ -1,4 +1,4 @@
-"""dlwp_conv3x3_wgrad_f32 (csrc/conv3x3_wgrad.hip) on the GPU: the weight / bias gradient of the 3x3 convolutions of the U-Net
+"""dlwp_conv3x3_wgrad_f32 (csrc/conv_wgrad.hip) on the GPU: the weight / bias gradient of the 3x3 convolutions of the U-Net
 and ConvLSTM families, and its wiring into training._Conv3x3Fn.backward under DLWP_CONV_WGRAD.
 
   * every case of test_conv3x3_wgrad_cpu.CASES against fp64 autograd of training.conv3x3_torch: relative L2 of dW and of db

@@ -1,6 +1,6 @@
 // The pointwise activations of the U-Net family (codes 0 identity, 1 exact-erf GELU, 2 tanh, 3 ReLU, 4 SiLU), their
-// derivatives, and the workgroup sum: shared by the convolutions (conv.hip, conv2.hip, and conv_mfma.hip / conv2_mfma.hip
-// through conv_mfma_common.hpp: staging and epilogues) and groupnorm_bwd.hip (GroupNorm forward and backward).
+// derivatives, and the workgroup sum: shared by the convolutions (conv.hip, conv2.hip, conv_mfma.hip: staging and
+// epilogues) and groupnorm_bwd.hip (GroupNorm forward and backward).
 #pragma once
 
 #include "common.hpp"

@@ -1,70 +1,114 @@
-// pad(1) + Conv2d(3x3) of the U-Net / ConvLSTM / diffusion backbones as an implicit GEMM on the bf16 matrix pipe (gfx950).
+// The U-Net / ConvLSTM / diffusion backbones' convolutions as implicit GEMMs on the bf16 matrix pipe (gfx950), one kernel for
+//   * pad(1) + Conv2d(3x3) on cat([x0, x1], 1) under CylinderPad or HEALPixPadding                (dlwp_conv3x3_mfma_f32),
+//   * the zero-padded k x k Conv2d, stride 1 or 2: 1x1 shortcuts and heads, the strided 3x3       (dlwp_conv2d_mfma_f32),
+//   * ConvTranspose2d 4x4 s2 p1 and 2x2 s2                                                        (dlwp_conv_transpose2d_mfma_f32).
 //
-// The opt-in forms "bf16x6" and "bf16" of ops.conv3x3*; the scalar-FMA direct kernel of conv.hip stays the default.  Same
-// semantics as conv3x3_cyl_kernel (reference utils/utils.py:11-26; models/unet/unet.py:456-470, :512-525, :553, :886, :901;
-// models/convlstm/convlstm.py:47-55, :94, :148-157; utils/healpix.py:316-368): two input segments (the folded torch.cat),
-// `pre_act` while staging, either padding rule, bias + resid + act in the epilogue.
+// The opt-in forms "bf16x6" and "bf16" of ops.conv3x3*, ops.conv2d and ops.conv_transpose2d; the kernels of conv.hip and
+// conv2.hip stay the default.  Same semantics as those (reference utils/utils.py:11-26; utils/healpix.py:316-368;
+// models/unet/unet.py:450-470, :512-533, :553, :583-584, :719, :879-886, :901; models/convlstm/convlstm.py:47-55, :94,
+// :148-157): `pre_act` while staging, the layer's padding rule, bias + resid + act in the epilogue.
 //
-// One workgroup (4 waves) = one tile of 128 output pixels (8 x 16, or 16 x 8 on maps that waste less that way) of one
-// sample and NF x 16 output channels.  GEMM per workgroup: D[cout][pixel] += W[cout][tap, cin] X[tap, cin][pixel], K walked
-// as slabs of 32 input channels x 9 taps:
-//   * per slab the (TH+2) x (TW+2) halo tile is staged ONCE into LDS, channel-innermost, already converted (bf16x6: the exact
-//     three-part split, one LDS image per part; bf16: the RNE value) -- the nine taps read shifted windows of that image as
-//     MFMA B operands (lane = pixel, 8 consecutive channels = one ds_read_b128);
-//   * the weights are packed once (dlwp_conv3x3_mfma_pack_f32) in A-operand order, [image][tap][slab][16-channel fragment]
-//     [lane][8 bf16], so a fragment is one coalesced 1 KiB global load; cin is zero-filled to the slab, cout to 16;
+// D[cout][pixel] += W[cout][tap, cin] X[tap, cin][pixel], K walked as slabs of 32 input channels x the taps.  One workgroup
+// (4 waves) = MFRAGS fragments of 16 GEMM pixels (a row of 16, or two rows of 8 on maps that waste less that way) of one sample
+// x NF x 16 output channels:
+//   * per slab the window of input cells the tile's taps reach is staged ONCE into LDS, channel-innermost, already converted
+//     (bf16x6: the exact three-part split, one LDS image per part; bf16: the RNE value); where each cell comes from is the same
+//     for every channel, so it is resolved once per workgroup into a source table.  The taps read shifted windows of the image
+//     as MFMA B operands (lane = pixel, 8 consecutive channels = one ds_read_b128);
+//   * the weights are packed once (dlwp_conv2d_mfma_pack_f32) in A-operand order, [image][tap][slab][16-channel fragment][lane]
+//     [8 bf16], so a fragment is one coalesced 1 KiB global load; cin is zero-filled to the slab, cout to 16;
 //   * A = weights, B = pixels: accumulator register r of lane l is channel 4 (l >> 4) + r of pixel l & 15, so a store
 //     instruction writes runs of 16 (or 8) consecutive pixels of the NCHW output.
 // No atomics, no split-K across workgroups: one writer per output, reruns are bit-identical.
-#include "conv_mfma_common.hpp"
+//
+// What the layers do not share is a geometry policy: where a staged cell comes from (locate, fetch), which window and pack
+// index a tap has (kt, tap), and the store.
+//   Padded3x3<TW>     compile-time tile (8 x 16 or 16 x 8 pixels) and 10 x 18 / 18 x 10 window, nine unrolled taps; a cell is the
+//                     circular longitude or the HEALPix ring table's one or two cells (a synthesised corner is their mean) of
+//                     either input segment.
+//   ZeroPadWindow<MFRAGS>  runtime k and stride s; GEMM pixel = output pixel.  The window, ((TH-1) s + k) x ((TW-1) s + k) cells, is
+//                     staged with its columns split by parity when s = 2 (row = [even columns | odd columns]): lane i's cell for tap
+//                     kw is then (kw % s) * plane + i + kw / s -- unit stride over the lanes, the conflict-free read of the 3x3 tile,
+//                     not the 4-way conflict of every second cell.  s = 1: MFRAGS = 8; s = 2: MFRAGS = 2 (2 x 16 outputs, a 5 x 33
+//                     window for k = 3: 170 cells) so that three images fit several times into a CU's 160 KiB.
+//   TransposedParity  stride 2 by output parity: output (2a + ph, 2b + pw) is a stride-1 convolution of the input around (a, b) with
+//                     the (k/2)^2 taps kh = (ph + pad) % 2 + 2 jh, ih = a + (ph + pad) / 2 - jh.  GEMM pixel = input pixel (a, b);
+//                     the tile with its +-1 halo (k = 4; none for k = 2) feeds BOTH column parities, whose accumulators a lane
+//                     combines into one 8-byte store: 16 lanes write 32 consecutive floats of an output row.  The row parity
+//                     rides on the grid (blockIdx.z), which keeps the accumulators at 2 per fragment.
+// The staging loop stands in the kernel body and indexes the LDS array itself (conv_wgrad.hip's note on staging functions).
+#include "act_common.hpp"
 
 namespace dlwp {
 namespace convm {
 
-constexpr int HALO = 180;    // (8 + 2) * (16 + 2) = (16 + 2) * (8 + 2) halo pixels; PS dwords each (conv_mfma_common.hpp)
+using actc::apply_act;
 
-struct Params {
-  const float* x0; int c0;   // first input segment [B][c0][H][W]
-  const float* x1; int c1;   // second segment or null
-  const u32x4* wp;           // packed weights, see dlwp_conv3x3_mfma_pack_f32
-  const float* bias;         // [Cout] or null
-  const float* resid;        // [B][Cout][H][W] or null: added after bias, before `act`
-  float* y;                  // [B][Cout][H][W]
-  int B, H, W, Cout, act, pre_act;
-  const int2* hpx;           // HEALPix ring table (null = cylinder), as conv::Params::hpx
-  int kslabs, nfrags;        // ceil(cin / 32), ceil(Cout / 16)
-};
+constexpr int KSLAB = 32;    // input channels per K-slab: one v_mfma_f32_16x16x32_bf16 per tap and slab
+// dwords per staged cell in LDS (16 hold the 32 channels).  24: the four 16-lane groups of a ds_read_b128 (lanes
+// {0-3, 12-15, 20-27}, ...) then start at bank (6 i + g) * 4 mod 64 for cell i, channel group g -- even for one g, odd for
+// the other, all distinct over a row of 16 cells: reads of 16 consecutive staged cells are conflict-free (16 would be 4-way,
+// 20 2-way).  Where a fragment is two rows of 8 pixels, lanes 0-3 and 12-15 of a group can meet 2-way.  The staging stores are
+// 16-byte stores of consecutive cells, the same address pattern as the reads.
+constexpr int PS = 24;
 
-// the padded, activated fp32 value of channel c at a halo pixel whose sources are e = (sample a, pixel a, sample b, pixel b)
-__device__ __forceinline__ float fetch(const Params& p, const int4 e, int c, int HW) {
-  if (c >= p.c0 + p.c1) return 0.f;
-  const bool seg0 = c < p.c0;
-  const float* base = seg0 ? p.x0 : p.x1;
-  const int cs = seg0 ? p.c0 : p.c1, cl = seg0 ? c : c - p.c0;
-  float v = apply_act(base[(long long)e.x * cs * HW + (cl * HW + e.y)], p.pre_act);
-  // a synthesised corner is the mean of two cells of the ACTIVATED tensor (the reference pads after the activation)
-  if (e.z >= 0) v = 0.5f * v + 0.5f * apply_act(base[(long long)e.z * cs * HW + (cl * HW + e.w)], p.pre_act);
-  return v;
+// eight consecutive channels of one staged cell -> one 16-byte B-operand group per image (NIMG 3: the exact three-part
+// split of form "bf16x6"; NIMG 1: the RNE value of form "bf16")
+template <int NIMG>
+__device__ __forceinline__ void convert_group(const float (&v)[8], u32x4 (&part)[3]) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    unsigned h, m, l;
+    if (NIMG == 3) split3_pair(v[2 * q], v[2 * q + 1], h, m, l);
+    else { h = cvt_pk_bf16(v[2 * q], v[2 * q + 1]); m = 0u; l = 0u; }
+    part[0][q] = h; part[1][q] = m; part[2][q] = l;
+  }
 }
 
-// TW: tile width (16 -> 8 x 16 pixels, 8 -> 16 x 8); NF: 16-channel output fragments per workgroup; NIMG: 3 bf16x6, 1 bf16.
-// Waves: WN along the output channels x WM along the pixels; each owns NFW x MF accumulator fragments.
-template <int TW, int NF, int NIMG>
-__global__ __launch_bounds__(256) void conv3x3_mfma_kernel(const Params p) {
-  constexpr int TH = 128 / TW, HWD = TW + 2;
-  constexpr int WN = NF >= 2 ? 2 : 1, WM = 4 / WN, MF = 8 / WM, NFW = NF / WN;
-  static_assert((TH + 2) * HWD == HALO, "halo size");
-  __shared__ __attribute__((aligned(16))) unsigned s_x[NIMG][HALO * PS];
-  __shared__ int4 s_src[HALO];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, li = lane & 15, g = lane >> 4;
-  const int wm = wv / WN, wn = wv % WN;
-  const int tiles_w = (p.W + TW - 1) / TW;
-  const int w0 = (blockIdx.x % tiles_w) * TW, h0 = (blockIdx.x / tiles_w) * TH;
-  const int b = blockIdx.y;
-  const int HW = p.H * p.W;
+struct Params {
+  const float* x0; int c0;   // first input segment [B][c0][H][W]: the whole input except under Padded3x3
+  const float* x1; int c1;   // Padded3x3: second segment or null
+  const u32x4* wp;           // packed weights, see dlwp_conv2d_mfma_pack_f32
+  const float* bias;         // [Cout] or null
+  const float* resid;        // [B][Cout][OH][OW] or null (not transposed): added after bias, before `act`
+  float* y;                  // [B][Cout][OH][OW]
+  int B, H, W, Cout, OH, OW, k, pad, act, pre_act;
+  const int2* hpx;           // Padded3x3: HEALPix ring table (null = cylinder), as conv::Params::hpx
+  int kslabs, nfrags;        // ceil(cin / 32), ceil(Cout / 16)
+  int GH, GW;                // the GEMM pixel grid: the output; transposed: the input
+  int tw8;                   // fragment = 0: a row of 16 GEMM pixels, 1: two rows of 8
+  int tiles_w;               // tiles across the GEMM pixel grid
+  int ws;                    // stride of the staged window (Conv2d: its stride; otherwise 1)
+  int wc, rowp, planew;      // window columns; cells per staged row (ws * planew); cells per column-parity plane
+  int npix;                  // staged cells: window rows * rowp
+  int wpad;                  // rows and columns the window begins before the tile's first input pixel (Conv2d: pad;
+                             // transposed: 1 for k = 4, 0 for k = 2)
+};
 
-  // sources of the halo pixels: the same for every channel, so resolved once (padding rules of conv3x3_cyl_kernel)
-  for (int i = tid; i < HALO; i += 256) {
+// One GEMM per workgroup and the plain NCHW store with the residual: everything but the transposed layer
+struct PlainStore {
+  static constexpr int NPW = 1;        // accumulators per fragment (output column parities)
+  static constexpr int ROWPAR = 1;     // output row parities on blockIdx.z
+  static __device__ __forceinline__ void store(const Params& p, float* yb, const float* rb, int co_off, int, int prow, int pcol,
+                                               const float (&a)[1], float bv) {
+    const int o = co_off + prow * p.OW + pcol;
+    float v = a[0] + bv;
+    if (rb) v += rb[o];
+    yb[o] = apply_act(v, p.act);
+  }
+};
+
+template <int TW_>
+struct Padded3x3 : PlainStore {
+  static constexpr int MFRAGS = 8, TW = TW_, TH = 128 / TW, HWD = TW + 2, NPIX = (TH + 2) * HWD;
+  static_assert(NPIX == 180, "(8 + 2) * (16 + 2) = (16 + 2) * (8 + 2) cells");
+  using Source = int4;                 // (sample a, pixel a, sample b, pixel b); sample < 0: none
+  static __device__ __forceinline__ int npix(const Params&) { return NPIX; }
+  static __device__ __forceinline__ bool tw8(const Params&) { return TW == 8; }
+  static __device__ __forceinline__ int row_step(const Params&) { return HWD; }   // staged cells from a GEMM row to the next
+  // the padding rules of conv3x3_cyl_kernel
+  static __device__ __forceinline__ Source locate(const Params& p, int b, int h0, int w0, int i) {
+    const int HW = p.H * p.W;
     const int r = i / HWD, cc = i % HWD;
     const int ih = h0 + r - 1;
     int iw = w0 + cc - 1;
@@ -88,63 +132,160 @@ __global__ __launch_bounds__(256) void conv3x3_mfma_kernel(const Params p) {
       iw = iw < 0 ? iw + p.W : (iw >= p.W ? iw - p.W : iw);      // circular longitude
       e.x = b; e.y = ih * p.W + iw;
     }
-    s_src[i] = e;
+    return e;
   }
+  // the padded, activated fp32 value of channel c; padding zeros stay zero (act(0) = 0)
+  static __device__ __forceinline__ float fetch(const Params& p, int, const int4 e, int c, int HW) {
+    if (e.x < 0 || c >= p.c0 + p.c1) return 0.f;
+    const bool seg0 = c < p.c0;
+    const float* base = seg0 ? p.x0 : p.x1;
+    const int cs = seg0 ? p.c0 : p.c1, cl = seg0 ? c : c - p.c0;
+    float v = apply_act(base[(long long)e.x * cs * HW + (cl * HW + e.y)], p.pre_act);
+    // a synthesised corner is the mean of two cells of the ACTIVATED tensor (the reference pads after the activation)
+    if (e.z >= 0) v = 0.5f * v + 0.5f * apply_act(base[(long long)e.z * cs * HW + (cl * HW + e.w)], p.pre_act);
+    return v;
+  }
+  // taps per axis of one GEMM, and tap (th, tw) of output parity (ph, pw): the staged-cell offset of its window and its index
+  // in the pack
+  static constexpr int KT = 3;         // compile-time: the kernel unrolls the taps
+  static __device__ __forceinline__ int kt(const Params&) { return KT; }
+  static __device__ __forceinline__ void tap(const Params&, int, int, int th, int tw, int& shift, int& tap) {
+    shift = th * HWD + tw; tap = th * 3 + tw;
+  }
+};
 
-  int hp0[MF];         // halo pixel of tap (0, 0) for this lane's pixel of every M fragment
-  bool live[MF];       // wave-uniform: the fragment has a row inside the map
+template <int MFRAGS_>
+struct ZeroPadWindow : PlainStore {
+  static constexpr int MFRAGS = MFRAGS_;
+  using Source = int;                  // pixel of this sample; -1 = zero (padding, or a cell no tap reads)
+  static __device__ __forceinline__ int npix(const Params& p) { return p.npix; }
+  static __device__ __forceinline__ bool tw8(const Params& p) { return p.tw8; }
+  static __device__ __forceinline__ int row_step(const Params& p) { return p.ws * p.rowp; }
+  static __device__ __forceinline__ Source locate(const Params& p, int, int h0, int w0, int i) {
+    const int r = i / p.rowp, rem = i - r * p.rowp;
+    const int plane = rem / p.planew, q = rem - plane * p.planew;
+    const int c = q * p.ws + plane;
+    const int ih = h0 * p.ws - p.wpad + r, iw = w0 * p.ws - p.wpad + c;
+    return (c < p.wc && ih >= 0 && ih < p.H && iw >= 0 && iw < p.W) ? ih * p.W + iw : -1;
+  }
+  // padding zeros stay zero (act(0) = 0), channels past the layer too
+  static __device__ __forceinline__ float fetch(const Params& p, int b, int src, int c, int HW) {
+    return (src >= 0 && c < p.c0) ? apply_act((p.x0 + (long long)b * p.c0 * HW)[c * HW + src], p.pre_act) : 0.f;
+  }
+  static constexpr int KT = 0;         // runtime: the taps stay loops
+  static __device__ __forceinline__ int kt(const Params& p) { return p.k; }
+  static __device__ __forceinline__ void tap(const Params& p, int, int, int th, int tw, int& shift, int& tap) {
+    shift = th * p.rowp + (tw % p.ws) * p.planew + tw / p.ws; tap = th * p.k + tw;
+  }
+};
+
+struct TransposedParity : ZeroPadWindow<8> {
+  static constexpr int NPW = 2, ROWPAR = 2;
+  static __device__ __forceinline__ int kt(const Params& p) { return p.k / 2; }
+  static __device__ __forceinline__ void tap(const Params& p, int ph, int pw, int th, int tw, int& shift, int& tap) {
+    const int kh0 = (ph + p.pad) & 1, kw0 = (pw + p.pad) & 1;
+    const int dh = (ph + p.pad - kh0) / 2 - th, dw = (pw + p.pad - kw0) / 2 - tw;
+    shift = (dh + p.wpad) * p.rowp + (dw + p.wpad);
+    tap = (kh0 + 2 * th) * p.k + (kw0 + 2 * tw);
+  }
+  // both column parities of input pixel (a, b): outputs (2a + ph, 2b) and (2a + ph, 2b + 1), one 8-byte store
+  static __device__ __forceinline__ void store(const Params& p, float* yb, const float*, int co_off, int ph, int prow, int pcol,
+                                               const float (&a)[2], float bv) {
+    const int o = co_off + (2 * prow + ph) * p.OW + 2 * pcol;
+    float2 v = {apply_act(a[0] + bv, p.act), apply_act(a[1] + bv, p.act)};
+    *reinterpret_cast<float2*>(yb + o) = v;
+  }
+};
+
+// G: the geometry policy; NF: 16-channel output fragments per workgroup; NIMG: 3 bf16x6, 1 bf16.
+// Waves: WN along the output channels x WM along the pixels; each owns NFW x MF accumulator fragments per column parity.
+template <class G, int NF, int NIMG>
+__global__ __launch_bounds__(256) void conv_mfma_kernel(const Params p) {
+  constexpr int MFRAGS = G::MFRAGS, NPW = G::NPW;
+  constexpr int WN = (NF >= 2 || MFRAGS == 2) ? 2 : 1, WM = 4 / WN, MF = MFRAGS / WM, NFW = NF / WN;
+  static_assert(MF >= 1 && NFW >= 1 && MF * WM == MFRAGS && NFW * WN == NF, "wave layout");
+  using Source = typename G::Source;
+  extern __shared__ __attribute__((aligned(16))) unsigned s_dyn[];     // [NIMG][npix * PS] images, then Source s_src[npix]
+  const int npix = G::npix(p);
+  Source* s_src = reinterpret_cast<Source*>(s_dyn + NIMG * npix * PS);
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, li = lane & 15, g = lane >> 4;
+  const int wm = wv / WN, wn = wv % WN;
+  const bool tw8 = G::tw8(p);
+  const int TWr = tw8 ? 8 : 16, THr = tw8 ? 2 * MFRAGS : MFRAGS;
+  const int w0 = (blockIdx.x % p.tiles_w) * TWr, h0 = (blockIdx.x / p.tiles_w) * THr;
+  const int b = blockIdx.y;
+  const int ph = (int)(blockIdx.z % G::ROWPAR), chunk = (int)(blockIdx.z / G::ROWPAR);
+  const int HW = p.H * p.W, OHW = p.OH * p.OW;
+
+  // sources of the staged cells: the same for every channel, so resolved once
+  for (int i = tid; i < npix; i += 256) s_src[i] = G::locate(p, b, h0, w0, i);
+
+  int hp0[MF];         // staged cell of tap (0, 0) for this lane's pixel of every M fragment
+  bool live[MF];       // wave-uniform: the fragment has a row inside the grid
 #pragma unroll
   for (int m = 0; m < MF; ++m) {
     const int f = wm * MF + m;
-    if (TW == 16) { hp0[m] = f * HWD + li; live[m] = h0 + f < p.H; }
-    else { hp0[m] = (2 * f + (li >> 3)) * HWD + (li & 7); live[m] = h0 + 2 * f < p.H; }
+    hp0[m] = (tw8 ? 2 * f + (li >> 3) : f) * G::row_step(p) + (tw8 ? (li & 7) : li);
+    live[m] = h0 + (tw8 ? 2 * f : f) < p.GH;
   }
-  const int nf0 = blockIdx.z * NF + wn * NFW;
-  f32x4 acc[NFW][MF];
+  const int nf0 = chunk * NF + wn * NFW;
+  f32x4 acc[NFW][MF][NPW];
 #pragma unroll
   for (int j = 0; j < NFW; ++j)
 #pragma unroll
-    for (int m = 0; m < MF; ++m) acc[j][m] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const size_t img_stride = (size_t)9 * p.kslabs * p.nfrags * 64;
+    for (int m = 0; m < MF; ++m)
+#pragma unroll
+      for (int w = 0; w < NPW; ++w) acc[j][m][w] = f32x4{0.f, 0.f, 0.f, 0.f};
+  constexpr int UNROLL = G::KT ? G::KT : 1;     // compile-time taps are unrolled, runtime taps stay loops
+  const int kt = G::kt(p);                      // taps per axis of one GEMM
+  const size_t img_stride = (size_t)p.k * p.k * p.kslabs * p.nfrags * 64;
 
   for (int ks = 0; ks < p.kslabs; ++ks) {
     __syncthreads();
-    // one K group (8 channels) of one halo pixel per item, pixels fastest: eight loads in flight per thread, each a coalesced
-    // row of an NCHW plane across the lanes; one 16-byte LDS store per image, in the pattern the taps read
-    for (int i = tid; i < 4 * HALO; i += 256) {
-      const int kg = i / HALO, pix = i - kg * HALO;
+    // one K group (8 channels) of one staged cell per item, cells fastest: eight loads in flight per thread, each a run of an
+    // NCHW plane across the lanes; one 16-byte LDS store per image, in the pattern the taps read
+    for (int i = tid; i < 4 * npix; i += 256) {
+      const int kg = i / npix, pix = i - kg * npix;
       const int c = ks * KSLAB + 8 * kg;
-      const int4 e = s_src[pix];
+      const Source e = s_src[pix];
       float v[8];
 #pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] = e.x >= 0 ? fetch(p, e, c + q, HW) : 0.f;   // padding zeros stay zero (act(0) = 0)
+      for (int q = 0; q < 8; ++q) v[q] = G::fetch(p, b, e, c + q, HW);
       u32x4 part[3];
       convert_group<NIMG>(v, part);
 #pragma unroll
-      for (int q = 0; q < NIMG; ++q) *reinterpret_cast<u32x4*>(&s_x[q][pix * PS + kg * 4]) = part[q];
+      for (int q = 0; q < NIMG; ++q) *reinterpret_cast<u32x4*>(&s_dyn[q * npix * PS + pix * PS + kg * 4]) = part[q];
     }
     __syncthreads();
 #pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      const int shift = (tap / 3) * HWD + (tap % 3);
-      u32x4 xf[MF][NIMG];
+    for (int w = 0; w < NPW; ++w) {
+#pragma unroll UNROLL
+      for (int th = 0; th < kt; ++th) {
+#pragma unroll UNROLL
+        for (int tw = 0; tw < kt; ++tw) {
+          int shift, tap;      // staged-cell offset of this tap's window, and its index in the pack
+          G::tap(p, ph, w, th, tw, shift, tap);
+          u32x4 xf[MF][NIMG];
 #pragma unroll
-      for (int m = 0; m < MF; ++m)
+          for (int m = 0; m < MF; ++m)
 #pragma unroll
-        for (int q = 0; q < NIMG; ++q) xf[m][q] = *reinterpret_cast<const u32x4*>(&s_x[q][(hp0[m] + shift) * PS + g * 4]);
+            for (int q = 0; q < NIMG; ++q)
+              xf[m][q] = *reinterpret_cast<const u32x4*>(&s_dyn[q * npix * PS + (hp0[m] + shift) * PS + g * 4]);
 #pragma unroll
-      for (int j = 0; j < NFW; ++j) {
-        const int nf = nf0 + j;
-        if (nf < p.nfrags) {
-          u32x4 wf[NIMG];
-          const size_t o = (((size_t)tap * p.kslabs + ks) * p.nfrags + nf) * 64 + lane;
+          for (int j = 0; j < NFW; ++j) {
+            const int nf = nf0 + j;
+            if (nf < p.nfrags) {
+              u32x4 wf[NIMG];
+              const size_t o = (((size_t)tap * p.kslabs + ks) * p.nfrags + nf) * 64 + lane;
 #pragma unroll
-          for (int q = 0; q < NIMG; ++q) wf[q] = p.wp[q * img_stride + o];
+              for (int q = 0; q < NIMG; ++q) wf[q] = p.wp[q * img_stride + o];
 #pragma unroll
-          for (int m = 0; m < MF; ++m) {
-            if (live[m]) {
-              if constexpr (NIMG == 3) acc[j][m] = mfma_bf16x6(wf, xf[m], acc[j][m]);
-              else acc[j][m] = mfma16x16x32_bf16(wf[0], xf[m][0], acc[j][m]);
+              for (int m = 0; m < MF; ++m) {
+                if (live[m]) {
+                  if constexpr (NIMG == 3) acc[j][m][w] = mfma_bf16x6(wf, xf[m], acc[j][m][w]);
+                  else acc[j][m][w] = mfma16x16x32_bf16(wf[0], xf[m][0], acc[j][m][w]);
+                }
+              }
             }
           }
         }
@@ -152,32 +293,35 @@ __global__ __launch_bounds__(256) void conv3x3_mfma_kernel(const Params p) {
     }
   }
 
+  float* yb = p.y + (long long)b * p.Cout * OHW;
+  const float* rb = p.resid ? p.resid + (long long)b * p.Cout * OHW : nullptr;
 #pragma unroll
   for (int m = 0; m < MF; ++m) {
     const int f = wm * MF + m;
-    const int oh = TW == 16 ? h0 + f : h0 + 2 * f + (li >> 3);
-    const int ow = TW == 16 ? w0 + li : w0 + (li & 7);
-    if (oh >= p.H || ow >= p.W) continue;
+    const int prow = h0 + (tw8 ? 2 * f + (li >> 3) : f), pcol = w0 + (tw8 ? (li & 7) : li);   // this lane's GEMM pixel
+    if (prow >= p.GH || pcol >= p.GW) continue;
 #pragma unroll
     for (int j = 0; j < NFW; ++j) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int co = (nf0 + j) * 16 + 4 * g + r;
         if (co < p.Cout) {
-          float v = acc[j][m][r] + (p.bias ? p.bias[co] : 0.f);
-          const long long o = (long long)b * p.Cout * HW + (co * HW + oh * p.W + ow);
-          if (p.resid) v += p.resid[o];
-          p.y[o] = apply_act(v, p.act);
+          float a[NPW];
+#pragma unroll
+          for (int w = 0; w < NPW; ++w) a[w] = acc[j][m][w][r];
+          G::store(p, yb, rb, co * OHW, ph, prow, pcol, a, p.bias ? p.bias[co] : 0.f);
         }
       }
     }
   }
 }
 
-// weight [cout][cin][3][3] -> three bf16 images [tap][slab][fragment][lane][8]: lane l of fragment nf holds output channel
-// 16 nf + (l & 15), input channels 32 slab + 8 (l >> 4) + 0..7 (element 0 in the low half of dword 0); zero outside
-__global__ __launch_bounds__(256) void conv3x3_mfma_pack_kernel(const float* __restrict__ w, unsigned short* __restrict__ out,
-                                                                int cout, int cin, int kslabs, int nfrags, long long total) {
+// weight [cout][cin][k][k] (transposed: [cin][cout][k][k]) -> three bf16 images [tap][slab][fragment][lane][8]: lane l of
+// fragment nf holds output channel 16 nf + (l & 15), input channels 32 slab + 8 (l >> 4) + 0..7 (element 0 in the low half of
+// dword 0); zero outside
+__global__ __launch_bounds__(256) void conv_mfma_pack_kernel(const float* __restrict__ w, unsigned short* __restrict__ out,
+                                                             int cout, int cin, int kk, int transposed, int kslabs, int nfrags,
+                                                             long long total) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int e = (int)(i & 7), lane = (int)((i >> 3) & 63);
     long long rest = i >> 9;
@@ -185,8 +329,13 @@ __global__ __launch_bounds__(256) void conv3x3_mfma_pack_kernel(const float* __r
     const int ks = (int)(rest % kslabs);
     const int tap = (int)(rest / kslabs);
     const int co = nf * 16 + (lane & 15), c = ks * KSLAB + 8 * (lane >> 4) + e;
-    const float v = (co < cout && c < cin) ? w[((long long)co * cin + c) * 9 + tap] : 0.f;
-    pack_store(v, out, i, total);
+    float v = 0.f;
+    if (co < cout && c < cin) v = transposed ? w[((long long)c * cout + co) * kk + tap] : w[((long long)co * cin + c) * kk + tap];
+    unsigned h, m, l;
+    split3_pair(v, 0.f, h, m, l);
+    out[i] = (unsigned short)(h & 0xffffu);
+    out[total + i] = (unsigned short)(m & 0xffffu);
+    out[2 * total + i] = (unsigned short)(l & 0xffffu);
   }
 }
 
@@ -195,66 +344,164 @@ __global__ __launch_bounds__(256) void conv3x3_mfma_pack_kernel(const float* __r
 
 using namespace dlwp;
 
-template <int TW, int NIMG>
-static void launch_nf(const convm::Params& p, int nf, int tiles, hipStream_t s) {
-  const dim3 grid(tiles, p.B, (p.nfrags + nf - 1) / nf);
-  if (nf == 4) hipLaunchKernelGGL((convm::conv3x3_mfma_kernel<TW, 4, NIMG>), grid, dim3(256), 0, s, p);
-  else if (nf == 2) hipLaunchKernelGGL((convm::conv3x3_mfma_kernel<TW, 2, NIMG>), grid, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((convm::conv3x3_mfma_kernel<TW, 1, NIMG>), grid, dim3(256), 0, s, p);
-}
+namespace {
 
-// the kernel instance of a shape: tile width (16 -> 8 x 16, 8 -> 16 x 8), output fragments per workgroup, tile count
-static void choose_variant(int B, int H, int W, int nfrags, int& tw, int& nf_out, int& tiles_out) {
-  const struct { int B, H, W, nfrags; } p{B, H, W, nfrags};
-  // tile: a 16-pixel MFMA fragment is one row of 16 (8 x 16 tile) or two rows of 8 (16 x 8 tile); fragments wholly below the
-  // map are skipped, so the cost of a shape is its count of live fragments -- take the smaller (8 x 8 maps: 4 against 8; 20 x 20:
-  // 30 against 40), on a tie the 8 x 16 tile (longer runs of consecutive pixels per load and store; every 16 | W map)
-  const long long frags16 = (long long)((p.W + 15) / 16) * p.H, frags8 = (long long)((p.W + 7) / 8) * ((p.H + 1) / 2);
+constexpr int kMaxLds = 64 * 1024;      // dynamic LDS a launch may ask for without a function attribute
+
+enum Layer { PADDED3X3, CONV2D, TRANSPOSED };
+
+// the kernel instance and the staged window of a shape.  GH x GW: the GEMM pixel grid (the output; transposed: the input);
+// ws: the window's stride (Conv2d: its stride; otherwise 1).  The padded 3x3 layer is (tr false, k 3, ws 1): a window of
+// (TH + 2) x (TW + 2) = 180 cells
+struct Variant {
+  int tw, mfrags, nf, tiles, tiles_w, wc, rowp, planew, npix;
+};
+
+Variant choose_variant(bool tr, int B, int GH, int GW, int nfrags, int k, int ws) {
+  Variant v;
+  // Conv2d s = 2 stages (TH - 1) 2 + k rows of 2 TW + k - 1 columns: a 128-pixel tile would need 17 x 33 cells, 3 x 54 KiB
+  v.mfrags = (!tr && ws == 2) ? 2 : 8;
+  // tile: a 16-pixel MFMA fragment is one row of 16 or two rows of 8; fragments wholly below the grid are skipped, so the
+  // cost of a shape is its count of live fragments -- take the smaller (8 x 8 maps: 4 against 8; 20 x 20: 30 against 40), on a
+  // tie the rows of 16 (longer runs of consecutive pixels per load and store; every 16 | W map)
+  const long long frags16 = (long long)((GW + 15) / 16) * GH, frags8 = (long long)((GW + 7) / 8) * ((GH + 1) / 2);
   const bool narrow = frags8 < frags16;
-  const int tiles = narrow ? ((p.W + 7) / 8) * ((p.H + 15) / 16) : ((p.W + 15) / 16) * ((p.H + 7) / 8);
-  // output fragments per workgroup: 4 (64 channels: every staged halo tile feeds the most MFMAs) while the layer still makes
-  // >= 512 workgroups (2 per CU); fewer channels per workgroup, i.e. more workgroups, on the small maps
+  v.tw = narrow ? 8 : 16;
+  const int th = narrow ? 2 * v.mfrags : v.mfrags;
+  v.tiles_w = (GW + v.tw - 1) / v.tw;
+  v.tiles = v.tiles_w * ((GH + th - 1) / th);
+  // output fragments per workgroup: 4 (64 channels: every staged window feeds the most MFMAs) while the layer still makes
+  // >= 512 workgroups, 2 per CU (the transposed kernel makes two per tile and channel chunk, one per row parity); the 32-pixel
+  // tile has two wave columns, so at least 2
+  const int nfmin = v.mfrags == 2 ? 2 : 1;
+  const long long wgs = (long long)v.tiles * B * (tr ? 2 : 1);      // per channel chunk
   int nf = 4;
-  while (nf > 1 && (nf / 2 >= p.nfrags || (long long)tiles * p.B * ((p.nfrags + nf - 1) / nf) < 512)) nf /= 2;
-  tw = narrow ? 8 : 16; nf_out = nf; tiles_out = tiles;
+  while (nf > nfmin && (nf / 2 >= nfrags || (wgs < 512 && wgs * ((nfrags + nf - 1) / nf) < 512))) nf /= 2;
+  v.nf = nf;
+  const int halo = tr ? (k == 4 ? 1 : 0) : 0;
+  const int wr = tr ? th + 2 * halo : (th - 1) * ws + k;
+  v.wc = tr ? v.tw + 2 * halo : (v.tw - 1) * ws + k;
+  v.planew = (v.wc + ws - 1) / ws;
+  v.rowp = ws * v.planew;
+  v.npix = wr * v.rowp;
+  return v;
 }
 
-static void launch_conv3x3_mfma(const convm::Params& p, int form, hipStream_t s) {
-  int tw, nf, tiles;
-  choose_variant(p.B, p.H, p.W, p.nfrags, tw, nf, tiles);
-  const bool narrow = tw == 8;
-  if (form == 0) narrow ? launch_nf<8, 3>(p, nf, tiles, s) : launch_nf<16, 3>(p, nf, tiles, s);
-  else narrow ? launch_nf<8, 1>(p, nf, tiles, s) : launch_nf<16, 1>(p, nf, tiles, s);
+size_t lds_bytes(const Variant& v, int nimg, Layer layer) {
+  return (size_t)v.npix * (nimg * convm::PS * 4 + (layer == PADDED3X3 ? sizeof(int4) : sizeof(int)));
 }
 
-extern "C" int32_t dlwp_conv3x3_mfma_variant(int32_t batch, int32_t H, int32_t W, int32_t cout) {
-  if (batch <= 0 || H <= 0 || W <= 0 || cout <= 0) return 0;
-  int tw, nf, tiles;
-  choose_variant(batch, H, W, (cout + 15) / 16, tw, nf, tiles);
-  return tw * 16 + nf;
+bool conv_geometry_ok(int k, int stride, int pad) { return k >= 1 && k <= 4 && (stride == 1 || stride == 2) && pad >= 0 && pad < k; }
+bool transposed_geometry_ok(int k, int stride, int pad) { return stride == 2 && ((k == 4 && pad == 1) || (k == 2 && pad == 0)); }
+
+template <class G, int NIMG>
+void launch_nf(const convm::Params& p, int nf, dim3 grid, size_t lds, hipStream_t s) {
+  if (nf == 4) hipLaunchKernelGGL((convm::conv_mfma_kernel<G, 4, NIMG>), grid, dim3(256), lds, s, p);
+  else if (nf == 2) hipLaunchKernelGGL((convm::conv_mfma_kernel<G, 2, NIMG>), grid, dim3(256), lds, s, p);
+  else if constexpr (G::MFRAGS != 2) hipLaunchKernelGGL((convm::conv_mfma_kernel<G, 1, NIMG>), grid, dim3(256), lds, s, p);
 }
 
-extern "C" size_t dlwp_conv3x3_mfma_packed_bytes(int32_t cout, int32_t cin) {
-  if (cout <= 0 || cin <= 0) return 0;
-  const long long kslabs = (cin + convm::KSLAB - 1) / convm::KSLAB, nfrags = (cout + 15) / 16;
-  const long long bytes = 3ll * 9 * kslabs * nfrags * 1024;
+template <class G>
+void launch_form(const convm::Params& p, int form, int nf, dim3 grid, size_t lds, hipStream_t s) {
+  form == 0 ? launch_nf<G, 3>(p, nf, grid, lds, s) : launch_nf<G, 1>(p, nf, grid, lds, s);
+}
+
+// What the three launch entries share.  `p` arrives with its tensors, H, W, OH, OW, k, pad and ws described; the checks of
+// form, activations, the grid's y and z, the kernel's 32-bit offsets (inside one sample: channel plane + pixel; the tile
+// count and the window sources too) and the pack's size, then the variant, the Params fields that follow from it, and the launch.
+int32_t check_and_launch(convm::Params& p, Layer layer, int form, const char* name, hipStream_t s) {
+  const bool tr = layer == TRANSPOSED;
+  DLWP_REQUIRE(p.act >= 0 && p.act <= 4 && p.pre_act >= 0 && p.pre_act <= 4, DLWP_ERR_INVALID_ARGUMENT, "%s: unknown activation",
+               name);
+  DLWP_REQUIRE(form == 0 || form == 1, DLWP_ERR_INVALID_ARGUMENT, "%s: unknown form %d (0 bf16x6, 1 bf16)", name, form);
+  DLWP_REQUIRE(p.B <= 65535, DLWP_ERR_UNSUPPORTED, "%s: batch %d exceeds the grid's y dimension", name, p.B);
+  const long long HW = (long long)p.H * p.W, OHW = (long long)p.OH * p.OW;
+  const long long cin = (long long)p.c0 + p.c1, cseg = p.c0 > p.c1 ? p.c0 : p.c1;
+  DLWP_REQUIRE(((long long)p.H + 40) * ((long long)p.W + 40) < (1ll << 31) && ((long long)p.OH + 40) * ((long long)p.OW + 40) < (1ll << 31),
+               DLWP_ERR_UNSUPPORTED, "%s: maps of %d x %d -> %d x %d exceed the kernel's 32-bit offsets", name, p.H, p.W, p.OH, p.OW);
+  DLWP_REQUIRE(cin < (1ll << 31) - 64 && (cseg + 32) * HW < (1ll << 31) && (long long)p.Cout * OHW < (1ll << 31),
+               DLWP_ERR_UNSUPPORTED, "%s: %lld -> %d channels of %d x %d -> %d x %d exceed the kernel's 32-bit offsets", name, cin,
+               p.Cout, p.H, p.W, p.OH, p.OW);
+  p.kslabs = (int)((cin + convm::KSLAB - 1) / convm::KSLAB); p.nfrags = (p.Cout + 15) / 16;
+  DLWP_REQUIRE(p.nfrags * 2 <= 65535, DLWP_ERR_UNSUPPORTED, "%s: %d output channels exceed the grid's z dimension", name, p.Cout);
+  DLWP_REQUIRE(dlwp_conv2d_mfma_packed_bytes(p.Cout, (int32_t)cin, p.k) > 0, DLWP_ERR_UNSUPPORTED,
+               "%s: unsupported shape cout=%d cin=%lld k=%d", name, p.Cout, cin, p.k);
+  p.GH = tr ? p.H : p.OH; p.GW = tr ? p.W : p.OW;
+  const Variant v = choose_variant(tr, p.B, p.GH, p.GW, p.nfrags, p.k, p.ws);
+  DLWP_REQUIRE(lds_bytes(v, 3, layer) <= (size_t)kMaxLds, DLWP_ERR_UNSUPPORTED, "%s: window of %d cells exceeds the LDS budget", name, v.npix);
+  p.tw8 = v.tw == 8; p.tiles_w = v.tiles_w; p.wc = v.wc; p.rowp = v.rowp; p.planew = v.planew; p.npix = v.npix;
+  p.wpad = tr ? (p.k == 4 ? 1 : 0) : p.pad;
+  const dim3 grid(v.tiles, p.B, (tr ? 2 : 1) * ((p.nfrags + v.nf - 1) / v.nf));    // transposed: z = channel chunk * 2 + output row parity
+  const size_t lds = lds_bytes(v, form == 0 ? 3 : 1, layer);
+  if (layer == PADDED3X3) {
+    if (v.tw == 8) launch_form<convm::Padded3x3<8>>(p, form, v.nf, grid, lds, s);
+    else launch_form<convm::Padded3x3<16>>(p, form, v.nf, grid, lds, s);
+  } else if (tr) {
+    launch_form<convm::TransposedParity>(p, form, v.nf, grid, lds, s);
+  } else if (v.mfrags == 8) {
+    launch_form<convm::ZeroPadWindow<8>>(p, form, v.nf, grid, lds, s);
+  } else {
+    launch_form<convm::ZeroPadWindow<2>>(p, form, v.nf, grid, lds, s);
+  }
+  DLWP_HIP_CHECK(hipGetLastError());
+  return DLWP_OK;
+}
+
+}  // namespace
+
+extern "C" size_t dlwp_conv2d_mfma_packed_bytes(int32_t cout, int32_t cin, int32_t k) {
+  if (cout <= 0 || cin <= 0 || k <= 0 || k > 4) return 0;
+  const long long kslabs = ((long long)cin + convm::KSLAB - 1) / convm::KSLAB, nfrags = ((long long)cout + 15) / 16;
+  if (kslabs * nfrags > (1ll << 21)) return 0;                         // 3 KiB per (slab, fragment) and tap: past 2 GiB already
+  const long long bytes = 3ll * k * k * kslabs * nfrags * 1024;
   return bytes < (1ll << 31) ? (size_t)bytes : 0;
 }
 
-extern "C" int32_t dlwp_conv3x3_mfma_pack_f32(const float* weight_dev, int32_t cout, int32_t cin, void* packed_dev,
-                                              void* stream) {
+extern "C" size_t dlwp_conv3x3_mfma_packed_bytes(int32_t cout, int32_t cin) { return dlwp_conv2d_mfma_packed_bytes(cout, cin, 3); }
+
+// 16 * fragment width (16: rows of 16 GEMM pixels, 8: two rows of 8) + output fragments per workgroup, the launchers' own rule
+extern "C" int32_t dlwp_conv2d_mfma_variant(int32_t transposed, int32_t batch, int32_t H, int32_t W, int32_t cout, int32_t k,
+                                            int32_t stride, int32_t pad) {
+  if (batch <= 0 || H <= 0 || W <= 0 || cout <= 0) return 0;
+  if (transposed ? !transposed_geometry_ok(k, stride, pad) : !conv_geometry_ok(k, stride, pad)) return 0;
+  long long GH = H, GW = W;
+  if (!transposed) {
+    if ((long long)H + 2 * pad < k || (long long)W + 2 * pad < k) return 0;
+    GH = ((long long)H + 2 * pad - k) / stride + 1; GW = ((long long)W + 2 * pad - k) / stride + 1;
+  }
+  if (GH <= 0 || GW <= 0 || (GH + 40) * (GW + 40) >= (1ll << 31)) return 0;
+  const Variant v = choose_variant(transposed != 0, batch, (int)GH, (int)GW, (int)(((long long)cout + 15) / 16), k, transposed ? 1 : stride);
+  return v.tw * 16 + v.nf;
+}
+
+extern "C" int32_t dlwp_conv3x3_mfma_variant(int32_t batch, int32_t H, int32_t W, int32_t cout) {
+  return dlwp_conv2d_mfma_variant(0, batch, H, W, cout, 3, 1, 1);
+}
+
+static int32_t pack(const char* name, const float* weight_dev, int32_t cout, int32_t cin, int32_t k, int32_t transposed,
+                    void* packed_dev, void* stream) {
   DLWP_REQUIRE(weight_dev && packed_dev, DLWP_ERR_INVALID_ARGUMENT, "null argument");
-  const size_t bytes = dlwp_conv3x3_mfma_packed_bytes(cout, cin);
-  DLWP_REQUIRE(bytes > 0, DLWP_ERR_UNSUPPORTED, "conv3x3_mfma: unsupported shape cout=%d cin=%d", cout, cin);
+  const size_t bytes = dlwp_conv2d_mfma_packed_bytes(cout, cin, k);
+  DLWP_REQUIRE(bytes > 0, DLWP_ERR_UNSUPPORTED, "%s: unsupported shape cout=%d cin=%d k=%d", name, cout, cin, k);
   const int kslabs = (cin + convm::KSLAB - 1) / convm::KSLAB, nfrags = (cout + 15) / 16;
   const long long total = (long long)(bytes / 6);               // bf16 elements per image
   long long blocks = (total + 255) / 256;
   if (blocks > 256 * 16) blocks = 256 * 16;
-  hipLaunchKernelGGL(convm::conv3x3_mfma_pack_kernel, dim3((unsigned)blocks), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), weight_dev, reinterpret_cast<unsigned short*>(packed_dev), cout,
-                     cin, kslabs, nfrags, total);
+  hipLaunchKernelGGL(convm::conv_mfma_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     weight_dev, reinterpret_cast<unsigned short*>(packed_dev), cout, cin, k * k, transposed != 0, kslabs, nfrags,
+                     total);
   DLWP_HIP_CHECK(hipGetLastError());
   return DLWP_OK;
+}
+
+extern "C" int32_t dlwp_conv2d_mfma_pack_f32(const float* weight_dev, int32_t cout, int32_t cin, int32_t k, int32_t transposed,
+                                             void* packed_dev, void* stream) {
+  return pack("conv2d_mfma", weight_dev, cout, cin, k, transposed, packed_dev, stream);
+}
+
+extern "C" int32_t dlwp_conv3x3_mfma_pack_f32(const float* weight_dev, int32_t cout, int32_t cin, void* packed_dev,
+                                              void* stream) {
+  return pack("conv3x3_mfma", weight_dev, cout, cin, 3, 0, packed_dev, stream);
 }
 
 extern "C" int32_t dlwp_conv3x3_mfma_f32(const float* x0, int32_t c0, const float* x1, int32_t c1, const void* packed,
@@ -264,29 +511,48 @@ extern "C" int32_t dlwp_conv3x3_mfma_f32(const float* x0, int32_t c0, const floa
   DLWP_REQUIRE(x0 && packed && y, DLWP_ERR_INVALID_ARGUMENT, "null argument");
   DLWP_REQUIRE(batch > 0 && H > 0 && W > 0 && c0 > 0 && cout > 0 && c1 >= 0, DLWP_ERR_INVALID_ARGUMENT, "bad shape");
   DLWP_REQUIRE(c1 == 0 || x1, DLWP_ERR_INVALID_ARGUMENT, "second segment pointer missing");
-  DLWP_REQUIRE(act >= 0 && act <= 4 && pre_act >= 0 && pre_act <= 4, DLWP_ERR_INVALID_ARGUMENT, "unknown activation");
-  DLWP_REQUIRE(form == 0 || form == 1, DLWP_ERR_INVALID_ARGUMENT, "unknown form %d (0 bf16x6, 1 bf16)", form);
-  DLWP_REQUIRE(batch <= 65535, DLWP_ERR_UNSUPPORTED, "batch %d exceeds the grid's y dimension", batch);
   if (ring_table) {
     DLWP_REQUIRE(batch % 12 == 0, DLWP_ERR_INVALID_ARGUMENT, "n_faces=%d is not a multiple of 12", batch);
     DLWP_REQUIRE((long long)12 * H * W < (1ll << 31), DLWP_ERR_INVALID_ARGUMENT, "face too large for the 32-bit table");
   } else {
     DLWP_REQUIRE(W > 1, DLWP_ERR_INVALID_ARGUMENT, "bad shape");
   }
-  // offsets inside one sample (channel plane + pixel) are 32-bit in the kernel; the halo table index and the tile count too
-  const long long HW = (long long)H * W;
-  const long long cmax = c0 > c1 ? (c0 > cout ? c0 : cout) : (c1 > cout ? c1 : cout);
-  DLWP_REQUIRE((long long)c0 + c1 < (1ll << 31) - 64, DLWP_ERR_UNSUPPORTED, "conv3x3_mfma: too many input channels");
-  DLWP_REQUIRE(cmax * HW < (1ll << 31) && ((long long)H + 17) * ((long long)W + 17) < (1ll << 31), DLWP_ERR_UNSUPPORTED,
-               "conv3x3_mfma: %lld channels of %d x %d exceed the kernel's 32-bit offsets", cmax, H, W);
-  DLWP_REQUIRE(dlwp_conv3x3_mfma_packed_bytes(cout, c0 + c1) > 0, DLWP_ERR_UNSUPPORTED,
-               "conv3x3_mfma: unsupported shape cout=%d cin=%d", cout, c0 + c1);
-  convm::Params p;
+  convm::Params p = {};
   p.x0 = x0; p.c0 = c0; p.x1 = x1; p.c1 = c1; p.wp = reinterpret_cast<const u32x4*>(packed); p.bias = bias; p.resid = resid;
-  p.y = y; p.B = batch; p.H = H; p.W = W; p.Cout = cout; p.act = act; p.pre_act = pre_act;
-  p.hpx = reinterpret_cast<const int2*>(ring_table);
-  p.kslabs = (c0 + c1 + convm::KSLAB - 1) / convm::KSLAB; p.nfrags = (cout + 15) / 16;
-  launch_conv3x3_mfma(p, form, reinterpret_cast<hipStream_t>(stream));
-  DLWP_HIP_CHECK(hipGetLastError());
-  return DLWP_OK;
+  p.y = y; p.B = batch; p.H = H; p.W = W; p.Cout = cout; p.OH = H; p.OW = W; p.k = 3; p.pad = 1; p.act = act; p.pre_act = pre_act;
+  p.hpx = reinterpret_cast<const int2*>(ring_table); p.ws = 1;
+  return check_and_launch(p, PADDED3X3, form, "conv3x3_mfma", reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t dlwp_conv2d_mfma_f32(const float* x, const void* packed, const float* bias, const float* resid, float* y,
+                                        int32_t batch, int32_t cin, int32_t H, int32_t W, int32_t cout, int32_t k, int32_t stride,
+                                        int32_t pad, int32_t pre_act, int32_t act, int32_t form, void* stream) {
+  DLWP_REQUIRE(x && packed && y, DLWP_ERR_INVALID_ARGUMENT, "null argument");
+  DLWP_REQUIRE(batch > 0 && cin > 0 && cout > 0 && H > 0 && W > 0 && k > 0 && stride > 0 && pad >= 0, DLWP_ERR_INVALID_ARGUMENT, "bad shape");
+  DLWP_REQUIRE(conv_geometry_ok(k, stride, pad), DLWP_ERR_UNSUPPORTED,
+               "conv2d_mfma: k=%d stride=%d pad=%d has no matrix-pipe kernel (k <= 4, stride 1 or 2, pad < k)", k, stride, pad);
+  const long long OH = ((long long)H + 2 * pad - k) / stride + 1, OW = ((long long)W + 2 * pad - k) / stride + 1;
+  DLWP_REQUIRE(OH > 0 && OW > 0 && (long long)H + 2 * pad >= k && (long long)W + 2 * pad >= k, DLWP_ERR_INVALID_ARGUMENT, "empty output");
+  DLWP_REQUIRE(OH < (1ll << 31) && OW < (1ll << 31), DLWP_ERR_UNSUPPORTED, "conv2d_mfma: output too large");
+  convm::Params p = {};
+  p.x0 = x; p.c0 = cin; p.wp = reinterpret_cast<const u32x4*>(packed); p.bias = bias; p.resid = resid; p.y = y;
+  p.B = batch; p.H = H; p.W = W; p.Cout = cout; p.OH = (int)OH; p.OW = (int)OW; p.k = k; p.pad = pad;
+  p.act = act; p.pre_act = pre_act; p.ws = stride;
+  return check_and_launch(p, CONV2D, form, "conv2d_mfma", reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t dlwp_conv_transpose2d_mfma_f32(const float* x, const void* packed, const float* bias, float* y, int32_t batch,
+                                                  int32_t cin, int32_t H, int32_t W, int32_t cout, int32_t k, int32_t stride,
+                                                  int32_t pad, int32_t act, int32_t form, void* stream) {
+  DLWP_REQUIRE(x && packed && y, DLWP_ERR_INVALID_ARGUMENT, "null argument");
+  DLWP_REQUIRE(batch > 0 && cin > 0 && cout > 0 && H > 0 && W > 0 && k > 0 && stride > 0 && pad >= 0, DLWP_ERR_INVALID_ARGUMENT, "bad shape");
+  DLWP_REQUIRE(transposed_geometry_ok(k, stride, pad), DLWP_ERR_UNSUPPORTED,
+               "conv_transpose2d_mfma: k=%d stride=%d pad=%d has no matrix-pipe kernel (4x4 s2 p1 and 2x2 s2 p0 have)", k, stride, pad);
+  DLWP_REQUIRE(H < (1 << 30) && W < (1 << 30), DLWP_ERR_UNSUPPORTED, "conv_transpose2d_mfma: output too large");
+  DLWP_REQUIRE((reinterpret_cast<uintptr_t>(y) & 7) == 0, DLWP_ERR_INVALID_ARGUMENT, "conv_transpose2d_mfma: y must be 8-byte aligned");
+  convm::Params p = {};
+  p.x0 = x; p.c0 = cin; p.wp = reinterpret_cast<const u32x4*>(packed); p.bias = bias; p.y = y;
+  p.B = batch; p.H = H; p.W = W; p.Cout = cout; p.OH = 2 * H; p.OW = 2 * W; p.k = k; p.pad = pad;   // both geometries double
+  p.act = act; p.ws = 1;
+  return check_and_launch(p, TRANSPOSED, form, "conv_transpose2d_mfma", reinterpret_cast<hipStream_t>(stream));
 }

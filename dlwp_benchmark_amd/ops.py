@@ -179,46 +179,22 @@ def act_code(activation) -> int:
     raise _lib.DlwpError(f"activation {activation!r} has no fused kernel (supported: GELU, Tanh, ReLU, SiLU)")
 
 
-# forms of pad(1) + Conv2d(3x3): "direct" (default) is the scalar-FMA kernel of csrc/conv.hip; "bf16x6" / "bf16" are the
-# implicit GEMM of csrc/conv_mfma.hip on the bf16 matrix instructions (fp32-grade three-part splits / RNE bf16 operands)
-# -- and of conv2d / conv_transpose2d / small_module, whose "direct" is csrc/conv2.hip and whose matrix forms are csrc/conv2_mfma.hip
+# forms of the convolutions: "direct" (default) is the scalar-FMA kernel of csrc/conv.hip (pad(1) + Conv2d(3x3)) or the
+# one-thread-per-output kernels of csrc/conv2.hip (conv2d / conv_transpose2d / small_module); "bf16x6" / "bf16" are the implicit
+# GEMM of csrc/conv_mfma.hip on the bf16 matrix instructions (fp32-grade three-part splits / RNE bf16 operands), one kernel for all
 CONV_FORMS = ("direct", "bf16x6", "bf16")
 
 
-class Conv3x3Weights:
-    """A 3x3 convolution weight [cout, cin, 3, 3] in the MFMA operand layout dlwp_conv3x3_mfma_f32 reads (three bf16 images;
-    form "bf16" reads the first), re-packed on the device whenever the parameter has been written to -- the derivation rule of
-    LinearWeights.  Packing is a launch of its own and allocates: it happens in the eager or warm-up pass; inside a graph
-    capture a stale or missing pack is an error."""
+class ConvWeights:
+    """A convolution weight ([cout, cin, k, k]; transposed: ConvTranspose2d's [cin, cout, k, k]) in the MFMA operand layout the
+    kernel of csrc/conv_mfma.hip reads (three bf16 images; form "bf16" reads the first), re-packed on the device whenever the
+    parameter has been written to -- the derivation rule of LinearWeights.  Packing is a launch of its own and allocates: it
+    happens in the eager or warm-up pass; inside a graph capture a stale or missing pack is an error.  `op` names the operation
+    in messages."""
 
-    def __init__(self):
-        self._derived = Derived(eager_only="conv3x3")
-
-    def get(self, weight: torch.Tensor) -> torch.Tensor:
-        def build():
-            cout, cin = weight.shape[:2]
-            lib = _lib.load()
-            nbytes = int(lib.dlwp_conv3x3_mfma_packed_bytes(cout, cin))
-            if nbytes == 0:
-                raise _lib.DlwpError(f"conv3x3: unsupported shape cout={cout} cin={cin} for the matrix-pipe forms")
-            buf = torch.empty(nbytes // 4, dtype=torch.int32, device=weight.device)
-            _lib.launch("dlwp_conv3x3_mfma_pack_f32", weight.device, weight.detach().contiguous(), cout, cin, buf)
-            return buf
-
-        return self._derived.get(source_key(weight), build)
-
-
-def conv3x3_weights(weight: torch.Tensor) -> Conv3x3Weights:
-    """The pack cache that belongs to `weight` (a Parameter, or any tensor the caller keeps alive)."""
-    return derived_for(weight, "conv3x3", Conv3x3Weights)
-
-
-class Conv2dWeights:
-    """A k x k convolution weight ([cout, cin, k, k]; transposed: ConvTranspose2d's [cin, cout, k, k]) in the MFMA operand
-    layout dlwp_conv2d_mfma_f32 / dlwp_conv_transpose2d_mfma_f32 read: Conv3x3Weights' rule for csrc/conv2_mfma.hip."""
-
-    def __init__(self, transposed: bool):
-        self._derived = Derived(eager_only="conv2d")
+    def __init__(self, op: str, transposed: bool = False):
+        self._derived = Derived(eager_only=op)
+        self._op = op
         self._transposed = bool(transposed)
 
     def get(self, weight: torch.Tensor) -> torch.Tensor:
@@ -228,7 +204,7 @@ class Conv2dWeights:
             lib = _lib.load()
             nbytes = int(lib.dlwp_conv2d_mfma_packed_bytes(cout, cin, k))
             if nbytes == 0:
-                raise _lib.DlwpError(f"conv2d: unsupported shape cout={cout} cin={cin} k={k} for the matrix-pipe forms")
+                raise _lib.DlwpError(f"{self._op}: unsupported shape cout={cout} cin={cin} k={k} for the matrix-pipe forms")
             buf = torch.empty(nbytes // 4, dtype=torch.int32, device=weight.device)
             _lib.launch("dlwp_conv2d_mfma_pack_f32", weight.device, weight.detach().contiguous(), cout, cin, k,
                         int(self._transposed), buf)
@@ -237,10 +213,15 @@ class Conv2dWeights:
         return self._derived.get(source_key(weight), build)
 
 
-def conv2d_weights(weight: torch.Tensor, transposed: bool = False) -> Conv2dWeights:
+def conv3x3_weights(weight: torch.Tensor) -> ConvWeights:
+    """The pack cache of ops.conv3x3* that belongs to `weight` (a Parameter, or any tensor the caller keeps alive)."""
+    return derived_for(weight, "conv3x3", lambda: ConvWeights("conv3x3"))
+
+
+def conv2d_weights(weight: torch.Tensor, transposed: bool = False) -> ConvWeights:
     """The pack cache of ops.conv2d (transposed: of ops.conv_transpose2d) that belongs to `weight`; the layout flag is part
     of the slot, so a ConvTranspose2d weight and a Conv2d weight of the same shape never share a pack."""
-    return derived_for(weight, ("conv2d", bool(transposed)), lambda: Conv2dWeights(transposed))
+    return derived_for(weight, ("conv2d", bool(transposed)), lambda: ConvWeights("conv2d", transposed))
 
 
 def _conv_form(form: str) -> str:

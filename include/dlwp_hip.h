@@ -412,7 +412,9 @@ int32_t dlwp_conv3x3_ex_f32(const float* x0_dev, int32_t c0, const float* x1_dev
  * argument and check as dlwp_conv3x3_ex_f32; shapes whose per-sample offsets leave 32 bits return DLWP_ERR_UNSUPPORTED.
  * One writer per output element: results are bit-identical from run to run.
  * dlwp_conv3x3_mfma_variant names the kernel instance the launcher takes for a shape: 16 * tile width (16: 8 x 16 pixels,
- * 8: 16 x 8) + output fragments per workgroup (4, 2 or 1); 0 for a non-positive size.  For tests and tools. */
+ * 8: 16 x 8) + output fragments per workgroup (4, 2 or 1); 0 for a non-positive size or a map past the 32-bit offsets: it is
+ * dlwp_conv2d_mfma_variant(0, batch, height, width, cout, 3, 1, 1), as dlwp_conv3x3_mfma_packed_bytes(cout, cin) is
+ * dlwp_conv2d_mfma_packed_bytes(cout, cin, 3).  For tests and tools. */
 size_t dlwp_conv3x3_mfma_packed_bytes(int32_t cout, int32_t cin);
 int32_t dlwp_conv3x3_mfma_variant(int32_t batch, int32_t height, int32_t width, int32_t cout);
 int32_t dlwp_conv3x3_mfma_pack_f32(const float* weight_dev, int32_t cout, int32_t cin, void* packed_dev, void* stream);
@@ -421,7 +423,8 @@ int32_t dlwp_conv3x3_mfma_f32(const float* x0_dev, int32_t c0, const float* x1_d
                               int32_t width, int32_t cout, int32_t pre_act, int32_t act, const int32_t* ring_table,
                               int32_t form, void* stream);
 
-/* dlwp_conv2d_f32 and dlwp_conv_transpose2d_f32 as implicit GEMMs on the bf16 matrix instructions (csrc/conv2_mfma.hip; the
+/* dlwp_conv2d_f32 and dlwp_conv_transpose2d_f32 as implicit GEMMs on the bf16 matrix instructions (csrc/conv_mfma.hip, the kernel of
+ * dlwp_conv3x3_mfma_f32 under another geometry policy; the
  * same reference lines: models/unet/unet.py:583 (3x3, stride 2, zero padding 1), :584 and :879-881 (1x1), :450 / :533 (1x1
  * head) for the convolution, :719 (4x4, stride 2, padding 1) and :523 (2x2, stride 2) for the transposed one).  The weight
  * ([cout, cin, k, k]; transposed != 0: [cin, cout, k, k]) is packed once into MFMA operand order, [image][tap][slab][16-channel
@@ -579,7 +582,7 @@ int32_t dlwp_conv3x3_hpx_bwd_data_f32(const float* dy_dev, const float* weight_d
 int32_t dlwp_healpix_to_latlon_f32(const float* x_dev, const int32_t* index_dev, const float* weight_dev, float* y_dev,
                                    int64_t planes, int32_t nside, int32_t cells, void* stream);
 
-/* Weight and bias gradient of pad(1) + Conv2d(3x3, padding 0) on cat([x0, x1], 1), either padding rule (csrc/conv3x3_wgrad.hip;
+/* Weight and bias gradient of pad(1) + Conv2d(3x3, padding 0) on cat([x0, x1], 1), either padding rule (csrc/conv_wgrad.hip;
  * the reference lines differentiated: scripts/train.py:271 through models/unet/unet.py:456-470, :512-525, :886,
  * models/convlstm/convlstm.py:94, :148-157, utils/healpix.py:69-114):
  *   dw[co][ci][ky][kx] = sum_{b,y,x} dz[b][co][y][x] * P(act_pre(xcat))[b][ci][y+ky][x+kx],   db[co] = sum_{b,y,x} dz[b][co][y][x]
@@ -603,7 +606,7 @@ int32_t dlwp_conv3x3_wgrad_f32(const float* x0_dev, int32_t c0, const float* x1_
                                void* stream);
 
 /* Weight and bias gradient of the zero-padded Conv2d (dlwp_conv2d_f32's layer) and of ConvTranspose2d (dlwp_conv_transpose2d_f32's,
- * output_padding 0) with a square k x k kernel (csrc/conv2_wgrad.hip; the reference lines differentiated: scripts/train.py:271
+ * output_padding 0) with a square k x k kernel (csrc/conv_wgrad.hip; the reference lines differentiated: scripts/train.py:271
  * through models/unet/unet.py:450, :583-584, :879 (Conv2d 1x1, 3x3 stride 2) and :523, :719 (ConvTranspose2d 2x2 s2, 4x4 s2 p1)):
  *   transposed == 0: dw[co][ci][ky][kx] = sum_{b,i,j} dz[b][co][i][j] * act_pre(x)[b][ci][i s - p + ky][j s - p + kx]
  *   transposed != 0: dw[ci][co][ky][kx] = sum_{b,i,j} x[b][ci][i][j] * dz[b][co][i s - p + ky][j s - p + kx]

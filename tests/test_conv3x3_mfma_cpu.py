@@ -114,6 +114,21 @@ def test_variant_query():
     assert v(8, 64, 64, 64) == 16 * 16 + 2 and v(24, 20, 20, 200) == 8 * 16 + 4
 
 
+def test_the_3x3_queries_are_the_kxk_queries_at_k3():
+    """the padded 3x3 layer is (k 3, stride 1, pad 1) of the k x k planner and pack: one tile rule, one pack size"""
+    lib = L.load()
+    sizes = (1, 2, 3, 7, 8, 9, 15, 16, 17, 20, 32, 33, 37, 64, 181)
+    for b in (1, 2, 8, 12, 24, 32, 384, 513):
+        for H in sizes:
+            for W in sizes:
+                for co in (1, 15, 16, 17, 33, 120, 136, 170, 272, 512):
+                    assert lib.dlwp_conv3x3_mfma_variant(b, H, W, co) == lib.dlwp_conv2d_mfma_variant(0, b, H, W, co, 3, 1, 1), (b, H, W, co)
+    for co, ci in ((1, 1), (16, 33), (170, 19), (272, 272), (65536, 65536), (1 << 20, 1 << 20)):
+        got = lib.dlwp_conv3x3_mfma_packed_bytes(co, ci)        # the last two: 0 or a size, no crash
+        assert got == lib.dlwp_conv2d_mfma_packed_bytes(co, ci, 3), (co, ci)
+    assert lib.dlwp_conv3x3_mfma_packed_bytes(272, 272) == 3 * 9 * 9 * 17 * 1024
+
+
 def test_c_abi_is_in_the_ctypes_table():
     for name in ("dlwp_conv3x3_mfma_f32", "dlwp_conv3x3_mfma_pack_f32", "dlwp_conv3x3_mfma_packed_bytes",
                  "dlwp_conv3x3_mfma_variant"):

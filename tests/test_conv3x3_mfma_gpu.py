@@ -1,11 +1,11 @@
-"""The matrix-pipe forms of pad(1) + Conv2d(3x3) (csrc/conv_mfma.hip: conv3x3_mfma_kernel<TW, NF, NIMG>, forms "bf16x6" and
+"""The matrix-pipe forms of pad(1) + Conv2d(3x3) (csrc/conv_mfma.hip: conv_mfma_kernel<Padded3x3<TW>, NF, NIMG>, forms "bf16x6" and
 "bf16" of ops.conv3x3*) against float64, through the networks against the committed real-class goldens, and under graph replay.
 
 Bounds: form "bf16x6" is held to the direct kernel's bounds of tests/test_conv3x3_variants_gpu.py (rel-L2 1e-6 cylinder / 2e-6
 HEALPix, max-abs 1e-5 max(1, |want|)); form "bf16" to the project's bf16 bound 5e-3, and -- without an input activation -- to
 2e-6 against the float64 convolution of the RNE-bf16-rounded operands: its only error is the operand rounding.
 
-launch_conv3x3_mfma picks the tile (8 x 16, or 16 x 8 where that leaves fewer live 16-pixel fragments) and NF = 4 / 2 / 1
+The launcher picks the tile (8 x 16, or 16 x 8 where that leaves fewer live 16-pixel fragments) and NF = 4 / 2 / 1
 16-channel fragments per workgroup (the largest that still makes 512 workgroups); mfma_variant() asks the library which instance
 it launches for a shape (dlwp_conv3x3_mfma_variant: the launcher's own rule, not a copy) and a CPU test asserts that the cases
 reach both tiles and every NF."""
@@ -25,7 +25,7 @@ TOL_BF16 = 5e-3
 
 
 def mfma_variant(n, H, W, cout):
-    """(tile width, NF) launch_conv3x3_mfma (csrc/conv_mfma.hip) takes for n images of H x W and cout output channels"""
+    """(tile width, NF) the launcher of csrc/conv_mfma.hip takes for n images of H x W and cout output channels"""
     from dlwp_benchmark_amd import lib as L
 
     v = int(L.load().dlwp_conv3x3_mfma_variant(n, H, W, cout))
@@ -288,6 +288,44 @@ def test_graph_replay_and_form_change():
     assert torch.equal(run(model), eager)          # replay of the cached graph
     model.set_conv_form("direct")                  # drops the capture: the next call runs (and captures) the direct kernel
     assert torch.equal(run(model), default)
+
+
+@pytest.mark.gpu
+def test_the_3x3_pack_is_the_kxk_pack_at_k3():
+    """[17, 33, 3, 3] (a partial fragment and a partial slab): dlwp_conv3x3_mfma_pack_f32 and dlwp_conv2d_mfma_pack_f32(k 3, not
+    transposed) write the same bytes"""
+    from dlwp_benchmark_amd import lib as L
+
+    lib = L.load()
+    w = _rand(17, 33, 3, 3, g=torch.Generator(device=DEV).manual_seed(3))
+    nbytes = int(lib.dlwp_conv3x3_mfma_packed_bytes(17, 33))
+    assert nbytes == int(lib.dlwp_conv2d_mfma_packed_bytes(17, 33, 3)) == 3 * 9 * 2 * 2 * 1024
+    a = torch.full((nbytes // 4,), -1, dtype=torch.int32, device=DEV)
+    b = torch.full((nbytes // 4,), -2, dtype=torch.int32, device=DEV)
+    L.launch("dlwp_conv3x3_mfma_pack_f32", w.device, w, 17, 33, a)
+    L.launch("dlwp_conv2d_mfma_pack_f32", w.device, w, 17, 33, 3, 0, b)
+    assert torch.equal(a, b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("H,W,variant", [(9, 10, (16, 1)), (20, 20, (8, 1))])
+@pytest.mark.parametrize("form", ["bf16x6", "bf16"])
+def test_cylinder_and_zero_padding_agree_bitwise_inside(H, W, variant, form):
+    """One kernel body, two loaders: on output columns 1 .. W-2 the circular and the zero padding read the same cells, and the
+    tile, the window and the tap order are the same (one planner), so pad(1) + 3x3 on the cylinder and Conv2d(3, 1, 1) agree
+    bit for bit there.  9 x 10: fragment rows of 16; 20 x 20: two rows of 8."""
+    from dlwp_benchmark_amd import ops
+    from test_conv_aux_mfma_gpu import aux_variant
+
+    assert mfma_variant(1, H, W, 17) == variant and aux_variant(False, 1, H, W, 17, 3, 1, 1) == variant
+    g = torch.Generator(device=DEV).manual_seed(H * 100 + W)
+    x, w, b = _rand(1, 33, H, W, g=g, scale=1.5), _rand(17, 33, 3, 3, g=g, scale=1.0 / (3.0 * 33 ** 0.5)), _rand(17, g=g)
+    with torch.no_grad():
+        cyl = ops.conv3x3_cyl(x, w, b, ACT["gelu"], form=form)
+        zero = ops.conv2d(x, w, b, 1, 1, act=ACT["gelu"], form=form)
+    assert cyl.shape == zero.shape == (1, 17, H, W)
+    assert torch.equal(cyl[..., 1:W - 1], zero[..., 1:W - 1])
+    assert not torch.equal(cyl[..., 0], zero[..., 0])        # the paddings themselves differ
 
 
 @pytest.mark.gpu

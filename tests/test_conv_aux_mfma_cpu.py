@@ -1,7 +1,7 @@
 """Host side of the matrix-pipe forms of the U-Net family's non-3x3 convolutions: every module whose forward calls ops.conv2d,
 ops.conv_transpose2d or ops.small_module carries `aux_conv_form`, set_aux_conv_form and the constructor key reach it and
 nothing else (`conv_form`, compute_precision and models without such modules stay as they were), and the C ABI of
-csrc/conv2_mfma.hip is in the ctypes table."""
+csrc/conv_mfma.hip is in the ctypes table."""
 import pytest
 import torch
 

@@ -1,5 +1,5 @@
-"""The matrix-pipe forms of the U-Net family's non-3x3 convolutions (csrc/conv2_mfma.hip: conv2_mfma_kernel<TR, MFRAGS, NF, NIMG>,
-forms "bf16x6" and "bf16" of ops.conv2d / ops.conv_transpose2d / ops.small_module) against float64, through the networks
+"""The matrix-pipe forms of the U-Net family's non-3x3 convolutions (csrc/conv_mfma.hip: conv_mfma_kernel<G, NF, NIMG> under the
+policies ZeroPadWindow<MFRAGS> and TransposedParity, forms "bf16x6" and "bf16" of ops.conv2d / ops.conv_transpose2d / ops.small_module) against float64, through the networks
 against the committed real-class goldens, and under graph replay.
 
 Bounds: form "bf16x6" is held to the direct kernels' bounds of tests/test_unet_ops_gpu.py (rel-L2 1e-6; max-abs 1e-5 max(1,
@@ -26,7 +26,7 @@ TOL_BF16 = 5e-3
 
 
 def aux_variant(tr, n, H, W, cout, k, s, p):
-    """(fragment width, NF) the launcher of csrc/conv2_mfma.hip takes"""
+    """(fragment width, NF) the launcher of csrc/conv_mfma.hip takes"""
     from dlwp_benchmark_amd import lib as L
 
     v = int(L.load().dlwp_conv2d_mfma_variant(int(tr), n, H, W, cout, k, s, p))

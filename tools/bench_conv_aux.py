@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-layer and whole-step timing of the forms of the U-Net family's non-3x3 convolutions: "direct" (csrc/conv2.hip), "bf16x6"
-and "bf16" (csrc/conv2_mfma.hip), and torch's F.conv2d / F.conv_transpose2d (MIOpen), in one process.
+and "bf16" (csrc/conv_mfma.hip), and torch's F.conv2d / F.conv_transpose2d (MIOpen), in one process.
 
 Layers: every distinct ops.conv2d / ops.conv_transpose2d call of C1's UNet at the benchmark's batch (bench.config_table) and of
 the yaml-width UNetHPX / MUNetHPX [136, 68, 34] at nside 32, batch 32 (384 faces), as the networks call them (pre_act, act,

@@ -1,22 +1,29 @@
-// Host-side check of the argument checks of csrc/conv2_mfma.hip: a stand-alone program that calls the packed-size and variant
+// Host-side check of the argument checks of csrc/conv_mfma.hip: a stand-alone program that calls the packed-size and variant
 // entries and the three launch entries with bad and oversized shapes.  Every such call returns before any launch, so the
 // program needs no GPU; build it with the host sanitizers and run it directly:
 //
 //   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-//         -I include tools/check_conv2_mfma_args.cpp dlwp_benchmark_amd/csrc/conv2_mfma.hip dlwp_benchmark_amd/csrc/core.hip \
-//         -o check_conv2_mfma_args && ./check_conv2_mfma_args
+//         -I include tools/check_conv_mfma_args.cpp dlwp_benchmark_amd/csrc/conv_mfma.hip dlwp_benchmark_amd/csrc/core.hip \
+//         -o check_conv_mfma_args && ./check_conv_mfma_args
 //
-// Exit status 0 and "ok" on success; a sanitizer report or a failed expectation otherwise.
+// Exit status 0 and "ok" on success; a sanitizer report or a failed expectation otherwise.  With -DPRINT_STATUS every call's
+// result is printed too, one per line: the list two builds of the library are compared by.
 #include <cstdint>
 #include <cstdio>
 
 #include "dlwp_hip.h"
 
 static int failures = 0;
+#ifdef PRINT_STATUS
+static const bool print_status = true;
+#else
+static const bool print_status = false;
+#endif
 
 #define EXPECT(expr, want)                                                                       \
   do {                                                                                           \
     const long long got_ = (long long)(expr);                                                    \
+    if (print_status) std::printf("%d %lld\n", __LINE__, got_);                                   \
     if (got_ != (long long)(want)) {                                                             \
       std::printf("%s:%d: %s = %lld, expected %lld\n", __FILE__, __LINE__, #expr, got_, (long long)(want)); \
       ++failures;                                                                                \
@@ -91,6 +98,58 @@ int main() {
   EXPECT(tconv(1, 1 << 20, 4, 4, 1 << 20, 2, 2, 0, 0), DLWP_ERR_UNSUPPORTED);
   EXPECT(tconv(big, big, big, big, big, 2, 2, 0, 1), DLWP_ERR_UNSUPPORTED);
   EXPECT(dlwp_conv_transpose2d_mfma_f32(x, pk, nullptr, x + 1, 1, 4, 8, 8, 4, 2, 2, 0, 0, 0, nullptr), DLWP_ERR_INVALID_ARGUMENT);  // y 4-byte aligned
+
+  // the padded 3x3 layer: the k x k queries at k = 3, and its own launch entry
+  EXPECT(dlwp_conv3x3_mfma_packed_bytes(170, 19), 3ll * 9 * 1 * 11 * 1024);
+  EXPECT(dlwp_conv3x3_mfma_packed_bytes(272, 272), dlwp_conv2d_mfma_packed_bytes(272, 272, 3));
+  EXPECT(dlwp_conv3x3_mfma_packed_bytes(0, 8), 0);
+  EXPECT(dlwp_conv3x3_mfma_packed_bytes(8, -1), 0);
+  EXPECT(dlwp_conv3x3_mfma_packed_bytes(1 << 20, 1 << 20), 0);
+  EXPECT(dlwp_conv3x3_mfma_packed_bytes(big, 8), 0);
+  EXPECT(dlwp_conv3x3_mfma_packed_bytes(8, big), 0);                               // cin + 31 in int: overflowed before
+  EXPECT(dlwp_conv3x3_mfma_packed_bytes(big, big), 0);                             // 27 KiB * slabs * fragments: past long long before
+
+  EXPECT(dlwp_conv3x3_mfma_variant(12, 8, 8, 6), 8 * 16 + 1);
+  EXPECT(dlwp_conv3x3_mfma_variant(384, 32, 32, 136), dlwp_conv2d_mfma_variant(0, 384, 32, 32, 136, 3, 1, 1));
+  EXPECT(dlwp_conv3x3_mfma_variant(0, 8, 8, 8), 0);
+  EXPECT(dlwp_conv3x3_mfma_variant(1, -8, 8, 8), 0);
+  EXPECT(dlwp_conv3x3_mfma_variant(1, 8, 8, 0), 0);
+  EXPECT(dlwp_conv3x3_mfma_variant(big, 20, 20, big) > 0, 1);
+
+  EXPECT(dlwp_conv3x3_mfma_pack_f32(nullptr, 8, 8, pk, nullptr), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(dlwp_conv3x3_mfma_pack_f32(x, 0, 8, pk, nullptr), DLWP_ERR_UNSUPPORTED);
+  EXPECT(dlwp_conv3x3_mfma_pack_f32(x, 1 << 20, 1 << 20, pk, nullptr), DLWP_ERR_UNSUPPORTED);
+  EXPECT(dlwp_conv3x3_mfma_pack_f32(x, big, big, pk, nullptr), DLWP_ERR_UNSUPPORTED);
+
+  static int32_t ring[16];
+  auto c3 = [&](int32_t batch, int32_t c0, int32_t c1, int32_t H, int32_t W, int32_t cout, int32_t form, const int32_t* table) {
+    return dlwp_conv3x3_mfma_f32(x, c0, c1 ? x : nullptr, c1, pk, nullptr, nullptr, x, batch, H, W, cout, 0, 0, table, form, nullptr);
+  };
+  EXPECT(dlwp_conv3x3_mfma_f32(nullptr, 4, nullptr, 0, pk, nullptr, nullptr, x, 1, 8, 8, 4, 0, 0, nullptr, 0, nullptr), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(dlwp_conv3x3_mfma_f32(x, 4, nullptr, 2, pk, nullptr, nullptr, x, 1, 8, 8, 4, 0, 0, nullptr, 0, nullptr), DLWP_ERR_INVALID_ARGUMENT);  // c1 > 0, x1 null
+  EXPECT(dlwp_conv3x3_mfma_f32(x, 4, nullptr, 0, pk, nullptr, nullptr, x, 1, 8, 8, 4, 5, 0, nullptr, 0, nullptr), DLWP_ERR_INVALID_ARGUMENT);  // unknown pre_act
+  EXPECT(dlwp_conv3x3_mfma_f32(x, 4, nullptr, 0, pk, nullptr, nullptr, x, 1, 8, 8, 4, 0, -1, nullptr, 0, nullptr), DLWP_ERR_INVALID_ARGUMENT); // unknown act
+  EXPECT(c3(0, 4, 0, 8, 8, 4, 0, nullptr), DLWP_ERR_INVALID_ARGUMENT);            // zero and negative extents
+  EXPECT(c3(1, 0, 0, 8, 8, 4, 0, nullptr), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(c3(1, 4, -1, 8, 8, 4, 0, nullptr), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(c3(1, 4, 0, -8, 8, 4, 0, nullptr), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(c3(1, 4, 0, 8, 0, 4, 0, nullptr), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(c3(1, 4, 0, 8, 8, -4, 0, nullptr), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(c3(1, 4, 0, 8, 1, 4, 0, nullptr), DLWP_ERR_INVALID_ARGUMENT);            // a cylinder of one column
+  EXPECT(c3(1, 4, 0, 8, 8, 4, 2, nullptr), DLWP_ERR_INVALID_ARGUMENT);            // unknown form
+  EXPECT(c3(13, 4, 0, 8, 8, 4, 0, ring), DLWP_ERR_INVALID_ARGUMENT);              // faces not a multiple of 12
+  EXPECT(c3(12, 4, 0, 16384, 16384, 4, 0, ring), DLWP_ERR_INVALID_ARGUMENT);      // face too large for the ring table
+  EXPECT(c3(65536, 4, 0, 8, 8, 4, 0, nullptr), DLWP_ERR_UNSUPPORTED);             // batch over the grid
+  EXPECT(c3(big, 4, 0, 8, 8, 4, 0, nullptr), DLWP_ERR_UNSUPPORTED);
+  EXPECT(c3(1, 4, 0, 32768, 32768, 4, 0, nullptr), DLWP_ERR_UNSUPPORTED);         // 32-bit offsets inside a sample
+  EXPECT(c3(1, 4, 0, big, 8, 4, 0, nullptr), DLWP_ERR_UNSUPPORTED);
+  EXPECT(c3(1, 4, 0, 8, big, 4, 0, nullptr), DLWP_ERR_UNSUPPORTED);
+  EXPECT(c3(1, 4, 0, big, big, 4, 0, nullptr), DLWP_ERR_UNSUPPORTED);
+  EXPECT(c3(1, big, 0, 1, 2, 4, 0, nullptr), DLWP_ERR_UNSUPPORTED);               // input channels
+  EXPECT(c3(1, big, big, 1, 2, 4, 0, nullptr), DLWP_ERR_UNSUPPORTED);             // c0 + c1 past int
+  EXPECT(c3(1, 4, 0, 1, 2, big, 0, nullptr), DLWP_ERR_UNSUPPORTED);               // output channels
+  EXPECT(c3(1, 1 << 20, 0, 4, 4, 1 << 20, 0, nullptr), DLWP_ERR_UNSUPPORTED);     // pack of 2 GiB and more
+  EXPECT(c3(big, big, big, big, big, big, 1, nullptr), DLWP_ERR_UNSUPPORTED);
 
   if (failures == 0) std::printf("ok\n");
   return failures ? 1 : 0;

@@ -7,9 +7,20 @@
   the Desc that normalise_desc of csrc/window_attn_desc.hpp fills, ordered by select_path of csrc/window_attn.hip); the GPU
   tests and tests/test_window_attn_host_cpu.py assert the same coverage again with dlwp_window_attn_workspace_bytes, so a
   stale restatement cannot hide a miss.
+
+And the case tables of the fp64 backward tests (tests/test_window_attn_bwd_fp64_gpu.py), BWD_SWIN / BWD_PANGU and the three
+large-logit inputs, chosen by what csrc/window_attn_bwd.hip branches on (the six DH instances, the bias mode, ragged or whole
+32-row tiles, npl / nlat / nlon, padding per axis, mask, heads, batch):
+* the tables reach what they claim (asserted from the descriptors);
+* autograd through the float64 reference equals autograd through the restatement in float64, at every backward case and every
+  row of the forward tables;
+* the reference gradient is a gradient (central finite differences), and the figures the GPU file asserts see a wrong
+  descriptor.
 """
+import collections
 import dataclasses
 import functools
+import zlib
 
 import pytest
 import torch
@@ -330,3 +341,347 @@ def test_bf16_operand_model_costs_what_bf16_costs():
     qkv, _, table = swin_inputs(case)
     e = rel_l2(swin_reference(case, True, qkv, table, operands="bf16"), swin_reference(case, True, qkv, table))
     assert 2.0 ** -11 < e < 2.0 ** -6, e
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the backward tables (tests/test_window_attn_bwd_fp64_gpu.py).  The forward's k2 / k3 / gen paths do not matter to
+# csrc/window_attn_bwd.hip; what it branches on does.  Each row runs unshifted and shifted wherever a shift exists.
+# ---------------------------------------------------------------------------------------------------------------------
+# (h, w, wh, ww, heads, d, batch)
+BWD_SWIN = [
+    (8, 8, 4, 4, 1, 8, 1),              # N = 16: one partial tile, 4 windows
+    (12, 20, 6, 10, 2, 32, 3),          # N = 60, ragged
+    (14, 24, 7, 12, 3, 64, 2),          # N = 84, three heads, d 64
+    (15, 34, 15, 17, 2, 16, 2),         # N = 255
+    (16, 36, 16, 36, 1, 24, 2),         # N = 576: 18 tiles, 2201 table rows
+    (12, 64, 6, 32, 2, 48, 1),          # N = 192: whole tiles, d 48
+]
+# (grid, window, heads, d, batch)
+BWD_PANGU = [
+    ((1, 16, 32), (2, 6, 12), 2, 32, 2),    # the geometry of tests/test_window_attn_bwd_gpu.py
+    ((3, 7, 13), (2, 6, 12), 2, 24, 3),     # two level windows, one half padded; padded on every axis
+    ((4, 8, 16), (2, 4, 8), 3, 8, 1),       # npl = nlat = nlon = 2: four types, N = 64
+    ((2, 11, 13), (2, 5, 7), 2, 48, 2),     # N = 70, padded in lat and lon
+    ((2, 12, 24), (1, 6, 12), 2, 64, 2),    # wpl 1, two level windows; no roll exists
+    ((1, 9, 30), (2, 3, 10), 1, 16, 2),     # rolled: the padded level is masked off, the reference dbias is ~1e-16 of dqkv
+]
+BWD_SWIN_PARAMS = [(c, s) for c in BWD_SWIN for s in (False, True)]
+BWD_PANGU_PARAMS = [(c, s) for c in BWD_PANGU for s in ((False, True) if pangu_rolls(c[1]) else (False,))]
+LARGE_LOGIT_NAMES = ("slack", "slack-shifted", "earth-large-logits")
+
+# one backward case: CPU fp32 inputs, the descriptor, and ref(qkv, bias, table) -> the float64 reference output
+BwdCase = collections.namedtuple("BwdCase", "name spec qkv bias table gout ref")
+
+
+def _seed(tag, case):
+    return zlib.crc32(repr((tag, case)).encode())
+
+
+def _swin_ref(h, w, wh, ww, heads, d, shifted):
+    shift = (wh // 2, ww // 2) if shifted else (0, 0)
+    return lambda qkv, bias, table: R.ref_swin(qkv, table, h, w, (wh, ww), shift, heads, d)
+
+
+def _pangu_ref(grid, window, heads, d, shifted):
+    shift = tuple(w // 2 for w in window) if shifted else (0, 0, 0)
+    return lambda qkv, bias, table: R.ref_pangu(qkv, bias, table, grid, window, shift, heads, d)
+
+
+@functools.lru_cache(maxsize=None)
+def bwd_swin_case(case, shifted):
+    from test_window_attn_gpu import _sub_window_spec
+
+    h, w, wh, ww, heads, d, batch = case
+    spec, rows = _sub_window_spec(h, w, wh, ww, heads, d, shifted)
+    g = torch.Generator().manual_seed(_seed("bwd_swin", case))
+    qkv = torch.randn(batch, h * w, 3, heads, d, generator=g)
+    qkv[:, :, :2] *= 2.0
+    bias = torch.randn(3 * heads * d, generator=g) * 0.1
+    table = torch.randn(rows, heads, generator=g) * 0.5
+    gout = torch.randn(batch, h * w, heads * d, generator=g)
+    return BwdCase(case_id((case, shifted)), spec, qkv.reshape(batch, h * w, 3 * heads * d), bias, table, gout,
+                   _swin_ref(h, w, wh, ww, heads, d, shifted))
+
+
+@functools.lru_cache(maxsize=None)
+def bwd_pangu_case(case, shifted):
+    from test_window_attn_gpu import _earth_spec
+
+    grid, window, heads, d, batch = case
+    spec, rows, types = _earth_spec(grid, window, heads, shifted)
+    spec = dataclasses.replace(spec, head_dim=d, scale=d ** -0.5)
+    ltok = grid[0] * grid[1] * grid[2]
+    g = torch.Generator().manual_seed(_seed("bwd_pangu", case))
+    qkv = torch.randn(batch, ltok, 3, heads, d, generator=g)
+    qkv[:, :, :2] *= 1.5
+    bias = torch.randn(3 * heads * d, generator=g) * 0.3
+    table = torch.randn(rows, types, heads, generator=g) * 0.5
+    gout = torch.randn(batch, ltok, heads * d, generator=g)
+    return BwdCase(case_id((case, shifted)), spec, qkv.reshape(batch, ltok, 3 * heads * d), bias, table, gout,
+                   _pangu_ref(grid, window, heads, d, shifted and pangu_rolls(window)))
+
+
+@functools.lru_cache(maxsize=None)
+def bwd_large_logit_case(name):
+    """slack_case(False), slack_case(True), earth_large_logits_case() with a seeded grad_out"""
+    if name == "earth-large-logits":
+        spec, qkv, bias, table, _ = earth_large_logits_case()
+        ref = _pangu_ref((1, 16, 32), (2, 6, 12), 2, 32, True)
+    else:
+        shifted = name == "slack-shifted"
+        spec, qkv, bias, table, _ = slack_case(shifted)
+        ref = _swin_ref(16, 32, 16, 32, 2, 24, shifted)
+    g = torch.Generator().manual_seed(_seed("bwd_large", name))
+    gout = torch.randn(qkv.shape[0], qkv.shape[1], spec.heads * spec.head_dim, generator=g)
+    return BwdCase(name, spec, qkv, bias, table, gout, ref)
+
+
+@functools.lru_cache(maxsize=None)
+def fwd_row_as_bwd_case(kind, p):
+    """a row of SWIN_PARAMS / PANGU_PARAMS with a seeded grad_out"""
+    case, shifted = p
+    if kind == "swin":
+        qkv, bias, table = swin_inputs(case)
+        spec, ref = swin_spec(case, shifted), _swin_ref(*case, shifted)
+    else:
+        qkv, bias, table = pangu_inputs(case)
+        spec, ref = pangu_spec(case, shifted)[0], _pangu_ref(case[0], case[1], PANGU_HEADS, case[2], shifted)
+    g = torch.Generator().manual_seed(_seed("fwd_row", p))
+    gout = torch.randn(qkv.shape[0], qkv.shape[1], spec.heads * spec.head_dim, generator=g)
+    return BwdCase("fwd-" + case_id(p), spec, qkv, bias, table, gout, ref)
+
+
+def all_bwd_cases():
+    """(id, thunk) of every backward case: the two tables and the three large-logit inputs"""
+    out = [(case_id(p), functools.partial(bwd_swin_case, *p)) for p in BWD_SWIN_PARAMS]
+    out += [(case_id(p), functools.partial(bwd_pangu_case, *p)) for p in BWD_PANGU_PARAMS]
+    out += [(n, functools.partial(bwd_large_logit_case, n)) for n in LARGE_LOGIT_NAMES]
+    return out
+
+
+def _grads(fn, case, dtype, gout):
+    leaves = [t.detach().to(dtype).clone().requires_grad_(True) for t in (case.qkv, case.bias, case.table)]
+    out = fn(*leaves)
+    assert out.dtype == dtype and not out.is_cuda
+    gout = case.gout if gout is None else gout
+    return tuple(torch.autograd.grad(out, leaves, gout.to(dtype), allow_unused=True))
+
+
+def reference_grads(case, gout=None):
+    """the float64 reference gradients (dqkv, dbias, dtable) of a case: torch.autograd.grad through R.ref_swin / R.ref_pangu on
+    leaf copies.  dbias is None where the reference never reads the bias (Swin); a Pangu case that pads nothing gives zeros."""
+    return _grads(case.ref, case, torch.float64, gout)
+
+
+def restatement_grads(case, dtype, spec=None, gout=None):
+    """the same three gradients from training.window_attention_torch on the CPU, under `spec` (default: the case's own)"""
+    from dlwp_benchmark_amd import training
+
+    spec = case.spec if spec is None else spec
+    return _grads(lambda q, b, t: training.window_attention_torch(q, b, t, spec), case, dtype, gout)
+
+
+def floor_grads(case, gout=None):
+    """the fp32 floor: what fp32 arithmetic costs at these inputs -- the restatement's gradients in float32 on the CPU"""
+    return restatement_grads(case, torch.float32, gout=gout)
+
+
+# every case's reference gradients and floor, computed once and shared (nothing may write into them)
+@functools.lru_cache(maxsize=None)
+def cached_reference_grads(name):
+    return reference_grads(bwd_case(name))
+
+
+@functools.lru_cache(maxsize=None)
+def cached_floor_grads(name):
+    return floor_grads(bwd_case(name))
+
+
+_CASES = dict(all_bwd_cases())
+BWD_IDS = list(_CASES)
+
+
+def bwd_case(name):
+    return _CASES[name]()
+
+
+# ---- the figures of the backward comparison (got: anything; want: the float64 reference) --------------------------------------
+def _f64(t):
+    return t.detach().double().cpu()
+
+
+def per_token_rms(got, want):
+    """max over (batch, token) of |got_t - want_t|_2 over the RMS over tokens of |want_t|_2.  NOT over the token's own norm:
+    rolled and padded cases have tokens whose reference gradient is 1e-45 of the RMS, where fp32 itself is off by order 1."""
+    got, want = _f64(got), _f64(want)
+    return float((got - want).norm(dim=-1).max() / want.norm(dim=-1).square().mean().sqrt())
+
+
+def per_entry(got, want):
+    """max |got - want| / max |want|"""
+    got, want = _f64(got), _f64(want)
+    return float((got - want).abs().max() / want.abs().max())
+
+
+def is_padded(spec):
+    return tuple(spec.padded) != tuple(spec.grid)
+
+
+def dbias_on_its_own_scale(want):
+    """the qkv-bias gradient is judged on its own norm wherever the reference's is at least 1e-3 of |dqkv|; below that (the
+    rolled (1, 9, 30) case, whose padded level is masked off) on the scale of dqkv"""
+    return float(_f64(want[1]).norm()) >= 1e-3 * float(_f64(want[0]).norm())
+
+
+def grad_figures(spec, got, want, outputs=("dqkv", "dbias", "dtable")):
+    """{figure name: value} of gradients `got` = (dqkv, dbias, dtable) against the float64 reference `want`, for the named
+    outputs (the others of `got` are not looked at)"""
+    f = {}
+    if "dqkv" in outputs:
+        f.update({"dqkv rel-L2": rel_l2(got[0], want[0]), "dqkv per token": per_token_rms(got[0], want[0])})
+    if "dtable" in outputs:
+        f.update({"dtable rel-L2": rel_l2(got[2], want[2]), "dtable per entry": per_entry(got[2], want[2])})
+    if "dbias" in outputs and is_padded(spec):
+        err = float((_f64(got[1]) - _f64(want[1])).norm())
+        if dbias_on_its_own_scale(want):
+            f["dbias own scale"] = err / float(_f64(want[1]).norm())
+        else:
+            f["dbias on dqkv scale"] = err / float(_f64(want[0]).norm())
+    return f
+
+
+def exact_zero_entries(want_dtable):
+    """where the reference table gradient is exactly 0.0: never indexed, or indexed only by cropped queries"""
+    return _f64(want_dtable) == 0.0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# backward tests
+# ---------------------------------------------------------------------------------------------------------------------
+def test_backward_tables_reach_what_they_claim():
+    specs = [bwd_swin_case(*p).spec for p in BWD_SWIN_PARAMS] + [bwd_pangu_case(*p).spec for p in BWD_PANGU_PARAMS]
+    batches = {c[-1] for c in BWD_SWIN} | {c[-1] for c in BWD_PANGU}
+    n_of = lambda s: s.window[0] * s.window[1] * s.window[2]
+    all_d = {8, 16, 24, 32, 48, 64}
+    assert {s.head_dim for s in specs if s.bias_mode == 1} == all_d        # the six DH instances under the earth bias ...
+    assert {s.head_dim for s in specs if s.bias_mode == 0} == all_d        # ... and under the Swin bias
+    assert any(n_of(s) < 32 for s in specs)                                # a window below one 32-row tile
+    assert any(n_of(s) > 32 and n_of(s) % 32 for s in specs)               # ragged last tile after whole ones
+    assert any(n_of(s) % 32 == 0 for s in specs)
+    assert any(s.padded[0] // s.window[0] > 1 and s.padded[0] > s.grid[0] for s in specs)   # npl > 1 beside a padded level
+    assert any(s.window[0] == 1 and s.bias_mode == 1 and s.padded[0] // s.window[0] > 1 for s in specs)   # wpl 1, npl 2
+    assert {s.heads for s in specs} == {1, 2, 3} and batches == {1, 2, 3}
+    assert any(is_padded(s) and s.use_mask and any(s.shift_fwd) for s in specs)             # padded and rolled
+    # all three window counts above one at once, and a padded level next to real ones in the same window
+    assert any(all(p // w > 1 for p, w in zip(s.padded, s.window)) and s.bias_mode == 1 for s in specs)
+    spec = bwd_pangu_case(((3, 7, 13), (2, 6, 12), 2, 24, 3), True).spec
+    assert all(p > g for p, g in zip(spec.padded, spec.grid)) and spec.padded[0] // spec.window[0] == 2
+    # the shifted rows are really shifted and masked, the wpl 1 row has no roll
+    assert all(bwd_swin_case(c, True).spec.use_mask for c in BWD_SWIN)
+    assert [c for c in BWD_PANGU if not pangu_rolls(c[1])] == [((2, 12, 24), (1, 6, 12), 2, 64, 2)]
+    # the large-logit inputs are what tests/test_window_attn_fp64_gpu.py runs forward
+    for name in LARGE_LOGIT_NAMES:
+        c = bwd_large_logit_case(name)
+        assert c.gout.shape == (c.qkv.shape[0], c.qkv.shape[1], c.spec.heads * c.spec.head_dim)
+
+
+def _assert_restatement_equals_reference(case, want):
+    got = restatement_grads(case, torch.float64)
+    eq, et = rel_l2(got[0], want[0]), rel_l2(got[2], want[2])
+    print(case.name, "gradient of the restatement vs of the reference, fp64: dqkv %.2e dtable %.2e" % (eq, et))
+    assert eq <= 1e-12 and et <= 1e-12
+    if got[1] is None or want[1] is None:
+        # the Swin reference takes no bias; the restatement reads it only where the descriptor pads
+        assert not is_padded(case.spec)
+        assert all(g is None or float(g.abs().max()) == 0.0 for g in (got[1], want[1]))
+    else:
+        err = float((got[1] - want[1]).norm())
+        print(case.name, "dbias %.2e of max(|dbias|, |dqkv|)" % (err / max(float(want[1].norm()), float(want[0].norm()))))
+        assert err <= 1e-12 * max(float(want[1].norm()), float(want[0].norm()))
+
+
+@pytest.mark.parametrize("name", BWD_IDS)
+def test_backward_case_restatement_gradient_equals_the_reference_gradient(name):
+    _assert_restatement_equals_reference(bwd_case(name), cached_reference_grads(name))
+
+
+def test_backward_tables_dbias_scale_and_exact_zero_conditions():
+    """Two conditions the GPU file relies on, from the reference alone: the qkv-bias gradient has a scale of its own at every
+    padded case but the rolled (1, 9, 30) one, and every Pangu case with a padded level leaves at least a quarter of the
+    table gradient exactly zero (so the exact-zero check is not vacuous)."""
+    for p in BWD_PANGU_PARAMS:
+        name = case_id(p)
+        spec, want = bwd_case(name).spec, cached_reference_grads(name)
+        if is_padded(spec):
+            own = dbias_on_its_own_scale(want)
+            ratio = float(want[1].norm() / want[0].norm())
+            print(name, "|dbias| / |dqkv| = %.2e" % ratio)
+            assert own == (p != (((1, 9, 30), (2, 3, 10), 1, 16, 2), True)), (name, ratio)
+        else:
+            assert float(want[1].abs().max()) == 0.0
+        if spec.padded[0] > spec.grid[0]:
+            frac = float(exact_zero_entries(want[2]).double().mean())
+            print(name, "exactly-zero table gradient entries: %.2f" % frac)
+            assert frac >= 0.25, (name, frac)
+    for p in BWD_SWIN_PARAMS:
+        assert cached_reference_grads(case_id(p))[1] is None
+    want = cached_reference_grads("earth-large-logits")
+    assert dbias_on_its_own_scale(want)
+
+
+@pytest.mark.parametrize("p", SWIN_PARAMS, ids=case_id)
+def test_swin_restatement_gradient_equals_the_reference_gradient(p):
+    case = fwd_row_as_bwd_case("swin", p)
+    _assert_restatement_equals_reference(case, reference_grads(case))
+
+
+@pytest.mark.parametrize("p", PANGU_PARAMS, ids=case_id)
+def test_pangu_restatement_gradient_equals_the_reference_gradient(p):
+    case = fwd_row_as_bwd_case("pangu", p)
+    _assert_restatement_equals_reference(case, reference_grads(case))
+
+
+@pytest.mark.parametrize("name", [case_id((((3, 7, 13), (2, 6, 12), 2, 24, 3), True)), case_id(((8, 8, 4, 4, 1, 8, 1), True))])
+def test_reference_gradient_is_a_gradient(name):
+    """One central finite difference of sum(ref(x) * grad_out) along a seeded random direction in each input, float64, h = 1e-6:
+    truncation ~h^2 and rounding ~2^-53 |f| / h are both far below 1e-6 of the directional derivative."""
+    case, want = bwd_case(name), cached_reference_grads(name)
+    x0 = [t.double() for t in (case.qkv, case.bias, case.table)]
+    gout = case.gout.double()
+    g = torch.Generator().manual_seed(_seed("fd", name))
+    h = 1e-6
+    for i, what in enumerate(("qkv", "bias", "table")):
+        if want[i] is None:
+            assert what == "bias" and case.spec.bias_mode == 0       # ref_swin takes no bias
+            continue
+        u = torch.randn(x0[i].shape, generator=g, dtype=torch.float64)
+        f = []
+        for sign in (1.0, -1.0):
+            x = list(x0)
+            x[i] = x0[i] + sign * h * u
+            f.append(float((case.ref(*x) * gout).sum()))
+        fd, ip = (f[0] - f[1]) / (2 * h), float((want[i] * u).sum())
+        print(name, what, "finite difference %.9e  <gradient, direction> %.9e" % (fd, ip))
+        assert abs(ip) > 1e-3 * float(want[i].norm())               # the direction is not orthogonal to the gradient by accident
+        assert abs(fd - ip) <= 1e-6 * abs(ip), (what, fd, ip)
+
+
+def test_reference_gradient_sees_a_wrong_descriptor():
+    """The figures of tests/test_window_attn_bwd_fp64_gpu.py are not blind: the three corruptions of
+    test_reference_sees_a_wrong_descriptor, differentiated through the restatement in float64, all move dqkv's per-token figure
+    by more than 1e-2 (a bound of 1e-4 is asserted there), and at least one moves the table gradient's per-entry figure so."""
+    name = case_id((BWD_PANGU[0], True))
+    case, want = bwd_case(name), cached_reference_grads(name)
+    spec = case.spec
+    b1, lead = tuple(spec.mask_b1), tuple(spec.pad_lead)
+    moved_table = 0
+    for wrong in (dataclasses.replace(spec, shift_fwd=tuple(spec.shift_back)),
+                  dataclasses.replace(spec, mask_b1=(b1[0], b1[1], b1[2] + 1)),
+                  dataclasses.replace(spec, pad_lead=(lead[0], lead[1] - 1, lead[2]))):
+        f = grad_figures(spec, restatement_grads(case, torch.float64, spec=wrong), want)
+        print(", ".join("%s %.2e" % kv for kv in f.items()))
+        assert f["dqkv per token"] > 1e-2
+        moved_table += f["dtable per entry"] > 1e-2
+    assert moved_table >= 1
+    right = grad_figures(spec, restatement_grads(case, torch.float64), want)
+    assert max(right.values()) <= 1e-12

@@ -4,7 +4,11 @@
 //
 //   generator   Philox4x32-10 (Salmon et al., SC 2011; Random123): multipliers 0xD2511F53 / 0xCD9E8D57, the key bumped by
 //               the Weyl constants 0x9E3779B9 / 0xBB67AE85 between rounds; key = (seed low word, seed high word),
-//               counter = (q low word, q high word, 0, 0)
+//               counter = (q low word, q high word, member, 0)
+//   members     `member` (a uint32) selects one of 2^32 independent streams of a seed: the draws of ensemble member m of a
+//               forecast.  Member 0 is the stream of every call that names no member.  Element (m, e) of a member-major
+//               draw [members][n_per_member] with base `offset` is normal(seed, first_member + m, offset + e): a member's
+//               values depend on neither how many members are drawn beside it nor where it sits in the call
 //   indexing    element e of a draw with base `offset` (a multiple of 4) has the global index g = offset + e and is lane
 //               g % 4 of block q = g / 4
 //   uniforms    u = float(x) * 2^-32 + 2^-33 in fp32 (the product is exact, the sum is rounded once): never 0
@@ -49,9 +53,9 @@ __device__ __forceinline__ void box_muller(uint32_t xa, uint32_t xb, float& n0, 
   n1 = r * s;
 }
 
-// the four normals of block q
-__device__ __forceinline__ f32x4 normal4(uint64_t seed, uint64_t q) {
-  const u32x4s x = philox4x32_10((uint32_t)q, (uint32_t)(q >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+// the four normals of block q of stream `member`
+__device__ __forceinline__ f32x4 normal4(uint64_t seed, uint32_t member, uint64_t q) {
+  const u32x4s x = philox4x32_10((uint32_t)q, (uint32_t)(q >> 32), member, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
   f32x4 z;
   float a, b;
   box_muller(x.x, x.y, a, b);
@@ -61,6 +65,38 @@ __device__ __forceinline__ f32x4 normal4(uint64_t seed, uint64_t q) {
   z[2] = a;
   z[3] = b;
   return z;
+}
+
+// the four normals of block q (member 0)
+__device__ __forceinline__ f32x4 normal4(uint64_t seed, uint64_t q) { return normal4(seed, 0u, q); }
+
+// A member-major draw [members][npm] (npm = n_per_member, any positive value): the normals of the flat elements i .. i + 3.
+// Flat element t is element e = t % npm of member t / npm and has the stream index 4 q0 + e.  With npm a multiple of 4 the
+// four are one Philox block; otherwise they may straddle blocks and members, and a block is evaluated whenever (member,
+// block) changes along the four -- at most four times (npm = 1).  Elements at and past `live` are left 0.
+__device__ __forceinline__ f32x4 member_normal4(uint64_t seed, uint32_t first_member, long long npm, uint64_t q0, long long i,
+                                                int live) {
+  long long m = i / npm, e = i - m * npm;
+  if ((npm & 3) == 0) return normal4(seed, first_member + (uint32_t)m, q0 + (uint64_t)(e >> 2));
+  f32x4 r = {0.f, 0.f, 0.f, 0.f}, z = r;
+  long long have_m = -1, have_b = -1;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (k < live) {
+      if (m != have_m || (e >> 2) != have_b) {
+        z = normal4(seed, first_member + (uint32_t)m, q0 + (uint64_t)(e >> 2));
+        have_m = m;
+        have_b = e >> 2;
+      }
+      const int lane = (int)(e & 3);
+      r[k] = lane == 0 ? z[0] : lane == 1 ? z[1] : lane == 2 ? z[2] : z[3];
+      if (++e == npm) {
+        e = 0;
+        ++m;
+      }
+    }
+  }
+  return r;
 }
 
 }  // namespace philox

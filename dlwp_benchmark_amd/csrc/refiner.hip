@@ -76,6 +76,36 @@ __global__ __launch_bounds__(THREADS) void ddpm_step_kernel(const float* sample,
   }
 }
 
+// ---- (a', b') the member-major forms: [members][npm] flat, n = members * npm ------------------------------------------------
+// Element (m, e) takes normal(seed, first_member + m, offset + e) (philox_normal.hpp).  The threads still own blocks of 4
+// consecutive FLAT elements, so the accesses are the ones of (a) and (b); only the noise knows about members.  The step with
+// sigma = 0 or with explicit noise has nothing to know: the launch function sends it to ddpm_step_kernel<0 / 1> over n.
+__global__ __launch_bounds__(THREADS) void philox_normal_members_kernel(float* __restrict__ out, long long n, long long npm,
+                                                                        uint32_t first_member, uint64_t seed, uint64_t q0) {
+  const bool vec = aligned16(out);
+  const long long nblk = (n + 3) >> 2;
+  for (long long b = (long long)blockIdx.x * THREADS + threadIdx.x; b < nblk; b += (long long)gridDim.x * THREADS) {
+    const long long i = 4 * b;
+    const int live = n - i < 4 ? (int)(n - i) : 4;
+    store4(out, i, live, vec, philox::member_normal4(seed, first_member, npm, q0, i, live));
+  }
+}
+
+__global__ __launch_bounds__(THREADS) void ddpm_step_members_kernel(const float* sample, const float* __restrict__ model_output,
+                                                                    float* out, long long n, long long npm,
+                                                                    uint32_t first_member, float A, float B, float sigma,
+                                                                    uint64_t seed, uint64_t q0) {
+  const bool vec = aligned16(sample) && aligned16(model_output) && aligned16(out);
+  const long long nblk = (n + 3) >> 2;
+  for (long long b = (long long)blockIdx.x * THREADS + threadIdx.x; b < nblk; b += (long long)gridDim.x * THREADS) {
+    const long long i = 4 * b;
+    const int live = n - i < 4 ? (int)(n - i) : 4;
+    const f32x4 s = load4(sample, i, live, vec), v = load4(model_output, i, live, vec);
+    const f32x4 r = A * s + B * v + sigma * philox::member_normal4(seed, first_member, npm, q0, i, live);
+    store4(out, i, live, vec, r);
+  }
+}
+
 // ---- (c) the training pair (train.py:228-255) -------------------------------------------------------------------------
 //   res = target - prog_last;  y_noised = sa res + sb eps;  v_target = sa eps - sb res
 // Outputs are [(batch faces), 1, channels, plane] contiguous; output element o = ((b faces + f) channels + c) plane + p reads
@@ -164,6 +194,52 @@ extern "C" int32_t dlwp_ddpm_step_f32(const float* sample, const float* model_ou
   else
     hipLaunchKernelGGL(refiner::ddpm_step_kernel<2>, grid, block, 0, s, sample, model_output, noise_or_null, out, (long long)n, A, B,
                        sigma, (uint64_t)seed, q0);
+  DLWP_HIP_CHECK(hipGetLastError());
+  return DLWP_OK;
+}
+
+// what the two member-major entry points share: the shape and the member range (a member is a uint32 counter word; the C ABI
+// carries first_member and the count as int32, so the last member is 2^31 - 1)
+static int32_t check_members(int64_t n_per_member, int32_t members, int32_t first_member, int64_t offset) {
+  DLWP_REQUIRE(n_per_member > 0 && members > 0, DLWP_ERR_INVALID_ARGUMENT, "bad size");
+  DLWP_REQUIRE(first_member >= 0 && (int64_t)first_member + members <= (int64_t)1 << 31, DLWP_ERR_INVALID_ARGUMENT,
+               "members [%d, %lld) outside [0, 2^31)", first_member, (long long)first_member + members);
+  DLWP_REQUIRE(n_per_member <= INT64_MAX / 2 / members, DLWP_ERR_INVALID_ARGUMENT, "bad size");
+  DLWP_REQUIRE(offset >= 0 && (offset & 3) == 0, DLWP_ERR_INVALID_ARGUMENT, "the offset must be a non-negative multiple of 4");
+  return DLWP_OK;
+}
+
+extern "C" int32_t dlwp_philox_normal_members_f32(float* out, int64_t n_per_member, int32_t members, int32_t first_member,
+                                                  int64_t seed, int64_t offset, void* stream) {
+  DLWP_REQUIRE(out, DLWP_ERR_INVALID_ARGUMENT, "null argument");
+  if (const int32_t rc = check_members(n_per_member, members, first_member, offset)) return rc;
+  const long long n = (long long)n_per_member * members;
+  hipLaunchKernelGGL(refiner::philox_normal_members_kernel, dim3(refiner::grid_for(n)), dim3(refiner::THREADS), 0,
+                     reinterpret_cast<hipStream_t>(stream), out, n, (long long)n_per_member, (uint32_t)first_member, (uint64_t)seed,
+                     (uint64_t)offset >> 2);
+  DLWP_HIP_CHECK(hipGetLastError());
+  return DLWP_OK;
+}
+
+extern "C" int32_t dlwp_ddpm_step_members_f32(const float* sample, const float* model_output, const float* noise_or_null,
+                                              float* out, int64_t n_per_member, int32_t members, int32_t first_member,
+                                              const double coef[4], int64_t seed, int64_t offset, void* stream) {
+  DLWP_REQUIRE(sample && model_output && out && coef, DLWP_ERR_INVALID_ARGUMENT, "null argument");
+  if (const int32_t rc = check_members(n_per_member, members, first_member, offset)) return rc;
+  const long long n = (long long)n_per_member * members;
+  const float A = (float)(coef[0] + coef[2]), B = (float)(-coef[1]), sigma = (float)coef[3];      // as dlwp_ddpm_step_f32
+  const dim3 grid(refiner::grid_for(n)), block(refiner::THREADS);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const uint64_t q0 = (uint64_t)offset >> 2;
+  if (coef[3] == 0.0)
+    hipLaunchKernelGGL(refiner::ddpm_step_kernel<0>, grid, block, 0, s, sample, model_output, noise_or_null, out, n, A, B, sigma,
+                       (uint64_t)seed, q0);
+  else if (noise_or_null)
+    hipLaunchKernelGGL(refiner::ddpm_step_kernel<1>, grid, block, 0, s, sample, model_output, noise_or_null, out, n, A, B, sigma,
+                       (uint64_t)seed, q0);
+  else
+    hipLaunchKernelGGL(refiner::ddpm_step_members_kernel, grid, block, 0, s, sample, model_output, out, n, (long long)n_per_member,
+                       (uint32_t)first_member, A, B, sigma, (uint64_t)seed, q0);
   DLWP_HIP_CHECK(hipGetLastError());
   return DLWP_OK;
 }

@@ -228,6 +228,10 @@ SIGNATURES = {
                                                 c_int32, c_void_p, c_size_t, c_void_p]),
     "dlwp_climate_sums_acc_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                             c_int32, c_int32, c_void_p]),
+    "dlwp_ensemble_sums_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "dlwp_ensemble_sums_acc_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, ctypes.c_int64,
+                                             c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_size_t,
+                                             c_void_p]),
     "dlwp_insolation_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, ctypes.c_int64, ctypes.c_double, c_int32, c_int32,
                                       c_float, c_float, c_void_p]),
     "dlwp_spectral_conv2d_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_size_t, c_void_p]),
@@ -282,6 +286,10 @@ SIGNATURES = {
     "dlwp_refiner_pair_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                         ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_float, c_float, ctypes.c_int64,
                                         ctypes.c_int64, c_void_p]),
+    "dlwp_philox_normal_members_f32": (c_int32, [c_void_p, ctypes.c_int64, c_int32, c_int32, ctypes.c_int64, ctypes.c_int64,
+                                                 c_void_p]),
+    "dlwp_ddpm_step_members_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int32, c_int32,
+                                             POINTER(ctypes.c_double), ctypes.c_int64, ctypes.c_int64, c_void_p]),
 }
 
 _lib = None

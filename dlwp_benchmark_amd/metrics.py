@@ -14,7 +14,12 @@ reference scripts/losses.py:16-152, the spectral-blurring score scripts/train.py
 scores of scripts/evaluate.py:832-872 (RMSE of the time-and-longitude mean per latitude band, RMSE of the mean field of lead days
 334-365); `soundness_scores` turns the sums into the scores in plain torch.
 
-All three classes also take HEALPix rollouts [B, K, C, 12, n, n] when they are given the longitudes of the lat-lon grid beside its
+`EnsembleMetrics` scores ensemble forecasts of the diffusion backbones [M, B, K, C, H, W] (rollout.ensemble_chunks /
+ensemble_forecast): RMSE of the ensemble mean, spread, spread / skill, CRPS and the rank histogram, streamed chunk by chunk
+through dlwp_ensemble_sums_acc_f32 (csrc/ensemble_scores.hip).  The reference has only a commented sketch of it
+(scripts/train.py:352-371): PARITY UNPINNED.
+
+All four classes also take HEALPix rollouts [B, K, C, 12, n, n] when they are given the longitudes of the lat-lon grid beside its
 latitudes: the reference remaps inits, outputs and targets to lat-lon before every metric (scripts/evaluate.py:298-303,
 scripts/train.py:430-441), on the host; here `ops.healpix_to_latlon` does it on the device, a chunk of samples at a time into one
 reused workspace, and the sums accumulate through the `*_acc` entry points.
@@ -484,3 +489,196 @@ class ZonalSpectrumMetrics(_HealpixInput):
         energy = s / (n_samples * self.height)
         log_ratio = torch.log((energy[0] + MELR_EPS) / (energy[1] + MELR_EPS))
         return {"energy_pred": energy[0], "energy_true": energy[1], "log_ratio": log_ratio, "melr": log_ratio.mean(dim=-1)}
+
+
+def ensemble_scores(sums: torch.Tensor, ranks: torch.Tensor, count: torch.Tensor, members: int, cells: int):
+    """The ensemble scores from accumulated sums (dlwp_ensemble_sums_acc_f32), in plain torch on whatever device they are on:
+    sums double [4, K, C], ranks int64 [K, C, M + 1], count double [K] (the samples that went into each step), cells = H W.
+    With N = count cells:
+      rmse_mean = sqrt(s0 / N)                         RMSE of the ensemble mean
+      spread = sqrt(s1 / N)                            root of the mean ensemble variance (1 / (M - 1) form)
+      spread_skill = sqrt((M + 1) / M) spread / rmse_mean      1 for a statistically consistent ensemble (Fortin et al. 2014)
+      crps = (s2 - s3 / (M (M - 1))) / N               the fair CRPS (Ferro et al. 2008)
+      crps_ens = (s2 - s3 / M^2) / N                   the CRPS of the ensemble's own empirical distribution
+    all [K, C] double, and rank_histogram = ranks.  A step no sample reached gives NaN."""
+    m = int(members)
+    n = (count.double() * float(cells)).view(-1, 1)
+    rmse_mean = torch.sqrt(sums[0] / n)
+    spread = torch.sqrt(sums[1] / n)
+    return {"rmse_mean": rmse_mean, "spread": spread, "spread_skill": math.sqrt((m + 1) / m) * spread / rmse_mean,
+            "crps": (sums[2] - sums[3] / float(m * (m - 1))) / n, "crps_ens": (sums[2] - sums[3] / float(m * m)) / n,
+            "rank_histogram": ranks}
+
+
+class EnsembleMetrics(_HealpixInput):
+    """Scores of an ensemble forecast [M, B, k, C, H, W] against its truth [B, k, C, H, W], streamed: feed chunks of lead steps
+    and / or of samples (`update`), `finalize` gives the latitude-weighted RMSE of the ensemble mean, the spread, their
+    ratio, the CRPS (fair and plain) and the rank histogram per lead step and variable.  Only the running sums -- double
+    [4, steps, C], int64 [steps, C, M + 1] and the per-step sample count -- live on the device; dlwp_ensemble_sums_acc_f32 adds a
+    chunk to them in one call that reads every member value once, sorts the members of a grid point in registers and writes
+    nothing of the ensemble's size.  Sums are fp64 in a fixed order: two evaluations give the same bits.  NaNs are not treated.
+
+    PARITY UNPINNED: the reference holds only a commented sketch of an ensemble evaluation (scripts/train.py:352-371: the
+    ensemble mean and a standard deviation); the scores here are the usual ensemble-verification forms (see `ensemble_scores`)
+    and are pinned by the float64 restatement in the tests, not by the reference.
+
+    `members`: M, 2 to 64.  `steps`, `channels`: the lead steps and variables of the whole evaluation.  `std`: the per-variable
+    de-normalisation scale [C] as in RolloutMetrics.  With `lons_deg` HEALPix ensembles [M, B, k, C, 12, n, n] are taken too and
+    remapped to (lats_deg, lons_deg) on the device, a chunk of samples -- all members of each -- at a time within
+    `max_workspace_bytes`.  Samples are sharded over ranks: `finalize(world_size)` moves sums, ranks and counts in ONE
+    all-reduce."""
+
+    def __init__(self, lats_deg, members: int, steps: int, channels: int, std: Optional[torch.Tensor] = None, group=None,
+                 lons_deg=None, max_workspace_bytes: int = DEFAULT_WORKSPACE_BYTES):
+        self._init_remap(lats_deg, lons_deg, max_workspace_bytes)
+        self.members, self.steps, self.channels = int(members), int(steps), int(channels)
+        if not 2 <= self.members <= 64:
+            raise _lib.DlwpError(f"EnsembleMetrics: {self.members} members (2 to 64 are supported)", status=_lib.ERR_UNSUPPORTED)
+        if self.steps < 1 or self.channels < 1:
+            raise _lib.DlwpError(f"EnsembleMetrics: steps = {self.steps} and channels = {self.channels} must be positive")
+        self.latw = latitude_weights(torch.as_tensor(lats_deg).reshape(-1))
+        self.height = int(self.latw.numel())
+        self.std = std.detach().float().reshape(-1) if std is not None else None
+        if self.std is not None and self.std.numel() != self.channels:
+            raise _lib.DlwpError(f"EnsembleMetrics: {self.std.numel()} scales given for {self.channels} variables")
+        self.group = group
+        self._dev = {}   # device -> (latw, std) copies made once
+        self._ws = {}    # device -> partials workspace, grown when a chunk needs more
+        self.reset()
+
+    def reset(self):
+        self._sums = self._ranks = self._count = None
+        self._width = len(self._lons) if self._lons is not None else None
+        return self
+
+    def state(self):
+        """The accumulators, to checkpoint a long evaluation: {"sums", "ranks", "count", "width"}"""
+        return {"sums": self._sums, "ranks": self._ranks, "count": self._count, "width": self._width}
+
+    def _check_state(self, s, r, n):
+        k, c, m = self.steps, self.channels, self.members
+        if not isinstance(s, torch.Tensor) or s.dtype != torch.float64 or tuple(s.shape) != (4, k, c):
+            raise _lib.DlwpError(f"sums must be a double [4, {k}, {c}] tensor, got "
+                                 f"{getattr(s, 'dtype', type(s))} {tuple(getattr(s, 'shape', ()))}")
+        if not isinstance(r, torch.Tensor) or r.dtype != torch.int64 or tuple(r.shape) != (k, c, m + 1) or r.device != s.device:
+            raise _lib.DlwpError(f"ranks must be an int64 [{k}, {c}, {m + 1}] tensor on {s.device}")
+        if not isinstance(n, torch.Tensor) or n.dtype != torch.float64 or tuple(n.shape) != (k,) or n.device != s.device:
+            raise _lib.DlwpError(f"count must be a double [{k}] tensor on {s.device}")
+
+    def load_state(self, state):
+        """Takes accumulators as `state()` gives them (tensors on any device: `finalize` is plain torch)."""
+        self._check_state(state["sums"], state["ranks"], state["count"])
+        width = int(state["width"])
+        if width < 1 or (self._lons is not None and width != len(self._lons)):
+            raise _lib.DlwpError(f"width {width} does not fit the metric's grid")
+        self._sums, self._ranks, self._count, self._width = state["sums"], state["ranks"], state["count"], width
+        return self
+
+    def _on(self, dev):
+        key = str(dev)
+        if key not in self._dev:
+            self._dev[key] = (self.latw.to(dev).contiguous(), self.std.to(dev).contiguous() if self.std is not None else None)
+        return self._dev[key]
+
+    def _workspace(self, dev, shape):
+        n = max(int(_lib.load().dlwp_ensemble_sums_workspace_bytes(*shape)), 8)
+        buf = self._ws.get(str(dev))
+        if buf is None or buf.numel() < n:
+            buf = self._ws[str(dev)] = torch.empty(n, dtype=torch.uint8, device=dev)
+        return buf
+
+    def _launch(self, ens, member_stride, target, b, k, h, w, step_begin):
+        dev = target.device
+        latw, std = self._on(dev)
+        ws = self._workspace(dev, (b, k, self.channels, h, w))
+        _lib.launch("dlwp_ensemble_sums_acc_f32", dev, ens, target, latw, std, self._sums, self._ranks, self.members, member_stride,
+                    b, k, self.channels, h, w, self.steps, step_begin, ws, ws.numel())
+
+    def update(self, ens: torch.Tensor, target: torch.Tensor, step_begin: int = 0):
+        """Adds a chunk: ens [M, B, k, C, H, W] (each member contiguous; the members may be any stride apart, e.g. a group view
+        of a wider buffer) or HEALPix [M, B, k, C, 12, n, n] (see `lons_deg`) with target [B, k, C, ...], the k consecutive lead
+        steps from `step_begin`.  Chunks may arrive in any order; every one counts B samples for its steps."""
+        if not isinstance(ens, torch.Tensor) or not isinstance(target, torch.Tensor):
+            raise _lib.DlwpError("ens and target must be tensors")
+        _lib.require_cuda_tensor(ens, "ens")
+        _lib.require_cuda_tensor(target, "target")
+        if ens.dim() not in (6, 7) or ens.shape[0] != self.members:
+            raise _lib.DlwpError(f"expected an ensemble [{self.members}, B, k, C, H, W], got shape {tuple(ens.shape)}")
+        if tuple(target.shape) != tuple(ens.shape[1:]):
+            raise _lib.DlwpError(f"target shape {tuple(target.shape)} != the members' shape {tuple(ens.shape[1:])}")
+        if target.device != ens.device:
+            raise _lib.DlwpError(f"target is on {target.device}, the ensemble on {ens.device}: both must be on one device")
+        hpx = ens.dim() == 7
+        if hpx and self._lons is None:
+            raise _lib.DlwpError(f"got a 7-D ensemble {tuple(ens.shape)}: a HEALPix ensemble [M, B, k, C, 12, n, n] is remapped to "
+                                 "lat-lon only when the metric is built with `lons_deg` (the longitudes of the lat-lon grid)")
+        m, b, k, c = (int(v) for v in ens.shape[:4])
+        h, w = (self.height, len(self._lons)) if hpx else (int(ens.shape[4]), int(ens.shape[5]))
+        step_begin = int(step_begin)
+        if h != self.height:
+            raise _lib.DlwpError(f"{h} latitudes in the chunk, {self.height} given to the metric")
+        if c != self.channels:
+            raise _lib.DlwpError(f"{c} variables in the chunk, {self.channels} given to the metric")
+        if min(b, k, w) < 1:
+            raise _lib.DlwpError(f"empty chunk {tuple(ens.shape)}")
+        if step_begin < 0 or step_begin + k > self.steps:
+            raise _lib.DlwpError(f"steps [{step_begin}, {step_begin + k}) outside the {self.steps} steps of the metric")
+        if self._width is not None and w != self._width:
+            raise _lib.DlwpError(f"{w} longitudes in the chunk after chunks with {self._width}")
+        dev = ens.device
+        if self._sums is None:
+            self._sums = torch.zeros(4, self.steps, c, dtype=torch.float64, device=dev)
+            self._ranks = torch.zeros(self.steps, c, m + 1, dtype=torch.int64, device=dev)
+            self._count = torch.zeros(self.steps, dtype=torch.float64, device=dev)
+        elif self._sums.device != dev:
+            raise _lib.DlwpError(f"the chunk is on {dev}, the sums on {self._sums.device}: one device is needed")
+        self._width = w
+        if not hpx:
+            if not ens[0].is_contiguous() or (m > 1 and ens.stride(0) < ens[0].numel()):
+                ens = ens.contiguous()
+            self._launch(ens, int(ens.stride(0)), target.contiguous(), b, k, h, w, step_begin)
+        else:
+            per = k * c * h * w                                    # floats of one sample of one member on the grid
+            chunk = min(b, self.max_workspace_bytes // (4 * (m + 1) * per))
+            if chunk < 1:
+                raise _lib.DlwpError(f"max_workspace_bytes = {self.max_workspace_bytes} does not hold one sample of the {m} members "
+                                     f"and of the target on the {h}x{w} grid ({4 * (m + 1) * per} bytes)")
+            from . import ops as _ops
+
+            buf = self._remap_ws.get(str(dev))
+            if buf is None or buf.numel() < (m + 1) * chunk * per:
+                buf = self._remap_ws[str(dev)] = torch.empty((m + 1) * chunk * per, dtype=torch.float32, device=dev)
+            for b0 in range(0, b, chunk):                          # all members of a sample in one chunk, a chunk in one call
+                n = min(chunk, b - b0)
+                e = buf[:m * n * per].view(m, n, k, c, h, w)
+                t = buf[m * chunk * per:m * chunk * per + n * per].view(n, k, c, h, w)
+                for j in range(m):
+                    _ops.healpix_to_latlon(ens[j, b0:b0 + n], self._lats, self._lons, out=e[j])
+                _ops.healpix_to_latlon(target[b0:b0 + n], self._lats, self._lons, out=t)
+                self._launch(e, n * per, t, n, k, h, w, step_begin)
+        self._count[step_begin:step_begin + k] += float(b)
+        return self
+
+    def finalize(self, world_size: int = 1):
+        """{"rmse_mean", "spread", "spread_skill", "crps", "crps_ens": [steps, C] double, "rank_histogram": [steps, C, M + 1]
+        int64} over ALL ranks' samples (see `ensemble_scores`), on the sums' device.  With world_size > 1 ONE all-reduce moves
+        sums, ranks and counts (the rank counts travel as doubles: exact below 2^53); host tensors unless the group's backend is
+        nccl, as in RolloutMetrics.finalize."""
+        if self._sums is None:
+            raise _lib.DlwpError("finalize() before any chunk: call update() or load_state() first")
+        self._check_state(self._sums, self._ranks, self._count)
+        s, r, n = self._sums, self._ranks, self._count
+        if world_size > 1:
+            import torch.distributed as dist
+
+            host = dist.get_backend(self.group) != "nccl"
+            dev = s.device
+            buf = torch.cat([s.flatten(), r.flatten().double(), n])
+            if host:
+                buf = buf.cpu()
+            dist.all_reduce(buf, group=self.group)
+            buf = buf.to(dev)
+            s = buf[:s.numel()].view_as(s)
+            r = buf[s.numel():s.numel() + r.numel()].round().long().view_as(r)
+            n = buf[s.numel() + r.numel():]
+        return ensemble_scores(s, r, n, self.members, self.height * self._width)

@@ -2083,13 +2083,54 @@ def philox_normal(shape_or_out, seed: int, offset: int = 0, device=None) -> torc
     return out
 
 
+def _member_range(members, first_member, what: str):
+    members, first_member = int(members), int(first_member)
+    if members < 1 or first_member < 0 or first_member + members > 1 << 31:
+        raise _lib.DlwpError(f"{what}: members = {members}, first_member = {first_member} must name members within [0, 2^31)")
+    return members, first_member
+
+
+def philox_normal_members(shape_or_out, seed: int, members: int, first_member: int = 0, offset: int = 0,
+                          device=None) -> torch.Tensor:
+    """philox_normal for ensembles (dlwp_philox_normal_members_f32): the result is member-major along dim 0, which `members`
+    must divide, and element e of member m is normal(seed, first_member + m, offset + e) -- the stream of philox_normal with the
+    member in the counter, member 0 being that stream itself.  A member's values depend on (seed, member, offset, its own
+    element count) only: members 0..5 of one call are bitwise the members of (first 0, 2 members) and (first 2, 4 members).
+    Every member uses up the indices [offset, offset + ceil(n_per_member / 4) * 4)."""
+    members, first_member = _member_range(members, first_member, "philox_normal_members")
+    if isinstance(shape_or_out, torch.Tensor):
+        out = shape_or_out
+        _lib.require_cuda_tensor(out, "out")
+        if not out.is_contiguous():
+            raise _lib.DlwpError("philox_normal_members: the output must be contiguous")
+    else:
+        dev = torch.device(device) if device is not None else None
+        if dev is None or dev.type != "cuda":
+            raise _lib.DlwpError(f"philox_normal_members: a device of the HIP path is needed (got {device}); the HIP path has no "
+                                 "CPU fallback")
+        out = torch.empty(tuple(int(s) for s in shape_or_out), dtype=torch.float32, device=dev)
+    if out.dim() < 1 or out.shape[0] % members:
+        raise _lib.DlwpError(f"philox_normal_members: dim 0 of {tuple(out.shape)} is not divisible by the {members} members")
+    if out.numel():
+        _lib.launch("dlwp_philox_normal_members_f32", out.device, out, out.numel() // members, members, first_member, _i64(seed),
+                    _noise_offset(offset))
+    return out
+
+
 def ddpm_step(sample: torch.Tensor, model_output: torch.Tensor, coefficients, noise: Optional[torch.Tensor] = None,
-              seed: int = 0, offset: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+              seed: int = 0, offset: int = 0, out: Optional[torch.Tensor] = None, members: int = 1,
+              first_member: int = 0) -> torch.Tensor:
     """The DDPM ancestral step in one pass (dlwp_ddpm_step_f32; the reference: noise_scheduler.step, modern_unet.py:201):
       prev = c0 (sa sample - sb model_output) + c1 sample + sigma z
     `coefficients` = (sa, sb, c0, c1, sigma) as Python floats (RefinerScheduler.coefficients).  z is `noise` when given, else
     philox_normal(seed, offset) evaluated inside the kernel (bitwise the same values); with sigma == 0 no noise is drawn or
-    read.  `out` may be `sample` (in place)."""
+    read.  `out` may be `sample` (in place).  With `members` > 1 or `first_member` > 0 the tensors are member-major along dim 0
+    (which `members` must divide) and z is philox_normal_members(seed, members, first_member, offset) instead
+    (dlwp_ddpm_step_members_f32)."""
+    members, first_member = _member_range(members, first_member, "ddpm_step")
+    by_member = members > 1 or first_member > 0
+    if by_member and (sample.dim() < 1 or sample.shape[0] % members):
+        raise _lib.DlwpError(f"ddpm_step: dim 0 of the sample {tuple(sample.shape)} is not divisible by the {members} members")
     _lib.require_cuda_tensor(sample, "sample")
     _lib.require_cuda_tensor(model_output, "model_output")
     _lib.require_cuda_tensor(noise, "noise")
@@ -2114,8 +2155,13 @@ def ddpm_step(sample: torch.Tensor, model_output: torch.Tensor, coefficients, no
     elif same:
         out = sample
     coef = (ctypes.c_double * 4)(c0 * sa, c0 * sb, c1, sigma)
-    _lib.launch("dlwp_ddpm_step_f32", sample.device, sample, model_output, noise.contiguous() if noise is not None else None, out,
-                n, coef, _i64(seed), _noise_offset(offset))
+    noise = noise.contiguous() if noise is not None else None
+    if by_member:
+        _lib.launch("dlwp_ddpm_step_members_f32", sample.device, sample, model_output, noise, out, n // members, members,
+                    first_member, coef, _i64(seed), _noise_offset(offset))
+    else:
+        _lib.launch("dlwp_ddpm_step_f32", sample.device, sample, model_output, noise, out, n, coef, _i64(seed),
+                    _noise_offset(offset))
     return out
 
 

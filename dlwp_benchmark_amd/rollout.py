@@ -51,7 +51,7 @@ def rollout_into(one_step: Callable[[torch.Tensor], torch.Tensor], context_size:
 
 
 def rollout_chunks(model, constants: Optional[torch.Tensor], prescribed, prognostic: torch.Tensor, n_steps: int,
-                   chunk_steps: int):
+                   chunk_steps: int, noise_scheduler=None):
     """A rollout of any length in fixed device memory: a generator of (step_begin, out_chunk), out_chunk [B, k, Cg, ...] holding
     rollout steps [step_begin, step_begin + k), k = chunk_steps (less in the last chunk).  `out_chunk` is a view of a reused
     buffer: valid until the next iteration.
@@ -67,8 +67,10 @@ def rollout_chunks(model, constants: Optional[torch.Tensor], prescribed, prognos
     input, every later one from `out`; the FNO kernels: csrc/fno2d.hip, fno_rollout_once, the same rule).  The driver holds
     three buffers of ctx + chunk_steps frames at most, whatever n_steps is, and does not synchronise with the host.
 
-    ConvLSTM / ConvLSTMHPX carry a recurrent state that starts at frame 0 and cannot be resumed from frames; the diffusion
-    backbones' forward needs a noise scheduler.  Both are refused."""
+    ConvLSTM / ConvLSTMHPX carry a recurrent state that starts at frame 0 and cannot be resumed from frames: they are refused.
+    The diffusion backbones (DiffModernUNet, DiffMUNetHPX) need `noise_scheduler` and are refused without it; with it every
+    chunk is their own forward(..., noise_scheduler=...), which draws per rollout step on per-step shapes, so a chunked run is
+    bitwise the one-shot forward with a scheduler in the same state.  Other models take no scheduler."""
     from . import lib as _lib
     from .models.diffusion import DiffModernUNet
     from .models.unet import ConvLSTM
@@ -76,9 +78,11 @@ def rollout_chunks(model, constants: Optional[torch.Tensor], prescribed, prognos
     if isinstance(model, ConvLSTM):
         raise _lib.DlwpError(f"rollout_chunks: {type(model).__name__} carries a recurrent (h, c) state that starts at frame 0 of a "
                              "forward and cannot be resumed from the last frames of a chunk")
-    if isinstance(model, DiffModernUNet):
-        raise _lib.DlwpError(f"rollout_chunks: {type(model).__name__}.forward needs a noise scheduler, which this driver does not "
-                             "pass on")
+    diffusion = isinstance(model, DiffModernUNet)
+    if diffusion and noise_scheduler is None:
+        raise _lib.DlwpError(f"rollout_chunks: {type(model).__name__}.forward needs a noise scheduler: pass noise_scheduler=...")
+    if not diffusion and noise_scheduler is not None:
+        raise _lib.DlwpError(f"rollout_chunks: {type(model).__name__} is no diffusion backbone and takes no noise scheduler")
     ctx = int(model.context_size)
     n_steps, chunk_steps = int(n_steps), int(chunk_steps)
     if n_steps < 1 or chunk_steps < 1:
@@ -102,7 +106,7 @@ def rollout_chunks(model, constants: Optional[torch.Tensor], prescribed, prognos
         fsz *= d
     kmax = min(chunk_steps, n_steps)
     dev = prognostic.device
-    into = prognostic.dim() == 5 and hasattr(model, "rollout_into")
+    into = prognostic.dim() == 5 and hasattr(model, "rollout_into")      # the diffusion backbones have none
     constants = constants.contiguous() if constants is not None else None
     context = prognostic.contiguous().clone()                                  # the last ctx frames produced so far
     win_buf = torch.zeros(b * (ctx + kmax) * fsz, device=dev, dtype=torch.float32)   # frames past ctx are never read
@@ -136,6 +140,8 @@ def rollout_chunks(model, constants: Optional[torch.Tensor], prescribed, prognos
                 if into:
                     out = out_buf[:b * k * fsz].view(b, k, *frame)
                     model.rollout_into(out, constants, presc, win)
+                elif diffusion:
+                    out = model(constants=constants, prescribed=presc, prognostic=win, noise_scheduler=noise_scheduler)
                 else:
                     out = model(constants=constants, prescribed=presc, prognostic=win)
                 if k >= ctx:
@@ -146,6 +152,85 @@ def rollout_chunks(model, constants: Optional[torch.Tensor], prescribed, prognos
             yield s0, out
 
     return chunks()
+
+
+def _require_ensemble(model, noise_scheduler, members, first_member, what: str):
+    from . import lib as _lib
+    from .models.diffusion import DiffModernUNet
+
+    if not isinstance(model, DiffModernUNet):
+        raise _lib.DlwpError(f"{what}: {type(model).__name__} is no diffusion backbone (DiffModernUNet, DiffMUNetHPX): a "
+                             "deterministic model has one forecast per initial condition")
+    if not callable(getattr(noise_scheduler, "set_members", None)):
+        raise _lib.DlwpError(f"{what}: the noise scheduler ({type(noise_scheduler).__name__}) has no set_members: member streams "
+                             "need schedulers.RefinerScheduler")
+    members, first_member = int(members), int(first_member)
+    if members < 1 or first_member < 0:
+        raise _lib.DlwpError(f"{what}: members = {members} must be at least 1 and first_member = {first_member} non-negative")
+    return members, first_member
+
+
+def _repeat_members(t: Optional[torch.Tensor], members: int) -> Optional[torch.Tensor]:
+    """[B, ...] -> member-major [members * B, ...] (member m holds rows m B .. (m + 1) B - 1)"""
+    if t is None or members == 1:
+        return t
+    return t.unsqueeze(0).expand(members, *t.shape).reshape(members * t.shape[0], *t.shape[1:])
+
+
+def ensemble_chunks(model, noise_scheduler, constants: Optional[torch.Tensor], prescribed, prognostic: torch.Tensor, n_steps: int,
+                    chunk_steps: int, members: int, first_member: int = 0):
+    """An ensemble forecast of a diffusion backbone in fixed device memory: a generator of (step_begin, ens_chunk), ens_chunk
+    [members, B, k, C, ...] holding rollout steps [step_begin, step_begin + k) of members first_member .. first_member +
+    members - 1 -- a view of a reused buffer, valid until the next iteration.  The inputs (as rollout_chunks takes them;
+    a callable `prescribed` is wrapped) are repeated member-major on the batch axis, the scheduler is put in member mode
+    (schedulers.RefinerScheduler.set_members) for the run and restored afterwards, also on an exception, and everything else is
+    rollout_chunks.  Member m's noise does not depend on the members beside it: an ensemble too large for the device runs in
+    groups (first_member = 0, g, 2 g, ...), each after noise_scheduler.reseed(), and stays one ensemble."""
+    from . import lib as _lib
+
+    members, first_member = _require_ensemble(model, noise_scheduler, members, first_member, "ensemble_chunks")
+    _lib.require_cuda_tensor(prognostic, "prognostic")
+    if prognostic is None or prognostic.dim() < 5:
+        raise _lib.DlwpError("ensemble_chunks: prognostic must hold the initial frames [B, ctx, C, ...]")
+    b = prognostic.shape[0]
+    if callable(prescribed) and not isinstance(prescribed, torch.Tensor):
+        forcing = prescribed
+
+        def prescribed(frame_begin, frame_end):
+            return _repeat_members(forcing(frame_begin, frame_end), members)
+    else:
+        prescribed = _repeat_members(prescribed, members)
+
+    def chunks():
+        before = (noise_scheduler.members, noise_scheduler.first_member)
+        noise_scheduler.set_members(members, first_member)
+        try:
+            for s0, out in rollout_chunks(model, _repeat_members(constants, members), prescribed,
+                                          _repeat_members(prognostic, members), n_steps, chunk_steps,
+                                          noise_scheduler=noise_scheduler):
+                yield s0, out.view(members, b, *out.shape[1:])
+        finally:
+            noise_scheduler.set_members(*before)
+
+    return chunks()
+
+
+def ensemble_forecast(model, noise_scheduler, constants: Optional[torch.Tensor], prescribed: Optional[torch.Tensor],
+                      prognostic: torch.Tensor, members: int, first_member: int = 0) -> torch.Tensor:
+    """The one-shot form: [members, B, K, C, ...] from `prognostic` with all ctx + K frames, as the model's forward takes it (only
+    the first ctx are read).  One forward over the member-major batch with the scheduler in member mode, restored afterwards."""
+    from . import lib as _lib
+
+    members, first_member = _require_ensemble(model, noise_scheduler, members, first_member, "ensemble_forecast")
+    _lib.require_cuda_tensor(prognostic, "prognostic")
+    before = (noise_scheduler.members, noise_scheduler.first_member)
+    noise_scheduler.set_members(members, first_member)
+    try:
+        out = model(constants=_repeat_members(constants, members), prescribed=_repeat_members(prescribed, members),
+                    prognostic=_repeat_members(prognostic, members), noise_scheduler=noise_scheduler)
+    finally:
+        noise_scheduler.set_members(*before)
+    return out.view(members, prognostic.shape[0], *out.shape[1:])
 
 
 def insolation_forcing(dates, lat_deg, lon_deg, batch: int, mean: Optional[float] = None, std: Optional[float] = None,

@@ -33,7 +33,8 @@ class RefinerScheduler:
     Interface as diffusers': betas, alphas, alphas_cumprod (float32 CPU tensors), num_train_timesteps, num_inference_steps,
     timesteps, set_timesteps(n), step(model_output, timestep, sample, generator=None, noise=None).prev_sample,
     add_noise(original, noise, timesteps).  Beyond it: coefficients(t), randn(shape, device), training_pair(...), seed,
-    offset, reseed(seed=None).
+    offset, reseed(seed=None), and for ensembles set_members(count, first=0), members, first_member (rollout.ensemble_chunks
+    and rollout.ensemble_forecast drive them).
 
     Noise.  noise="device" (the default): every draw is a range of ONE counter-based stream (ops.philox_normal: Philox4x32-10
     and Box-Muller, a pure function of (seed, element index)).  The scheduler keeps `offset`, the index of the next unused
@@ -70,6 +71,7 @@ class RefinerScheduler:
         self.init_noise_sigma = 1.0
         self.seed = 0
         self.offset = 0
+        self._members, self._first_member = 1, 0
         self.reseed(seed)
 
     @classmethod
@@ -95,11 +97,44 @@ class RefinerScheduler:
         self.offset = at + _ceil4(n)
         return at
 
+    # ---- ensemble members ----------------------------------------------------------------------------------------------
+    @property
+    def members(self) -> int:
+        return self._members
+
+    @property
+    def first_member(self) -> int:
+        return self._first_member
+
+    def set_members(self, count: int, first: int = 0):
+        """Member mode, for ensembles of one initial condition: with count > 1 or first > 0, randn() and step() treat dim 0 of
+        their tensors as member-major [count * B, ...] and member m of them draws from the stream normal(seed, first + m, .)
+        (ops.philox_normal_members); the offset advances by ONE member's element count rounded up to 4, which is what a
+        single-member run of the per-member shape uses.  So member m's noise is a function of (seed, first + m, the per-member
+        shape, the call order) only: a large ensemble run in groups is bitwise the same ensemble.  (1, 0), the default, is the
+        scheduler without members, call for call.  training_pair is not concerned."""
+        count, first = int(count), int(first)
+        if count < 1 or first < 0 or first + count > 1 << 31:
+            raise _lib.DlwpError(f"set_members: count = {count}, first = {first} must name members within [0, 2^31)")
+        if self.noise == "host" and (count, first) != (1, 0):
+            raise _lib.DlwpError("set_members: noise='host' draws from torch's generators, which have no member streams")
+        self._members, self._first_member = count, first
+        return self
+
+    def _per_member(self, shape, what: str) -> int:
+        """elements of one member of a member-major tensor of `shape`"""
+        if len(shape) < 1 or shape[0] % self._members:
+            raise _lib.DlwpError(f"{what}: dim 0 of {tuple(shape)} is not divisible by the {self._members} members")
+        return math.prod(shape) // self._members
+
     def randn(self, shape, device):
         """the start noise of a forecast step (modern_unet.py:184)"""
         shape = tuple(int(s) for s in shape)
         if self.noise == "host":
             return torch.randn(shape).to(device=device)
+        if (self._members, self._first_member) != (1, 0):
+            at = self._take(self._per_member(shape, "randn"))
+            return _ops.philox_normal_members(shape, self.seed, self._members, self._first_member, at, device=device)
         return _ops.philox_normal(shape, self.seed, self._take(math.prod(shape)), device=device)
 
     # ---- sampling -----------------------------------------------------------------------------------------------------
@@ -143,16 +178,23 @@ class RefinerScheduler:
         t = int(timestep)
         coef = self.coefficients(t)
         offset = 0
+        by_member = (self._members, self._first_member) != (1, 0)
         if t > 0 and noise is None:
             if generator is not None:
                 noise = torch.randn(model_output.shape, generator=generator, device=generator.device).to(model_output.device)
             elif self.noise == "host":
                 noise = torch.randn(model_output.shape, generator=self._gen).to(model_output.device)
+            elif by_member:
+                offset = self._take(self._per_member(tuple(model_output.shape), "step"))
             else:
                 offset = self._take(model_output.numel())
         if t == 0:
             noise = None
-        prev = _ops.ddpm_step(sample, model_output, coef, noise=noise, seed=self.seed, offset=offset)
+        if by_member:
+            prev = _ops.ddpm_step(sample, model_output, coef, noise=noise, seed=self.seed, offset=offset, members=self._members,
+                                  first_member=self._first_member)
+        else:
+            prev = _ops.ddpm_step(sample, model_output, coef, noise=noise, seed=self.seed, offset=offset)
         return SimpleNamespace(prev_sample=prev.view(sample.shape))
 
     # ---- training -----------------------------------------------------------------------------------------------------

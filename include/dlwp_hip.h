@@ -844,6 +844,28 @@ int32_t dlwp_climate_sums_acc_f32(const float* out_dev, const float* target_dev,
                                   int32_t batch, int32_t steps, int32_t channels, int32_t height, int32_t width,
                                   int32_t win_begin, int32_t win_end, void* stream);
 
+/* Ensemble scores of a forecast chunk (csrc/ensemble_scores.hip; the reference: only the commented sketch of
+ * scripts/train.py:352-371 -- the definitions are the usual ensemble-verification forms).  ens_dev is
+ * `members` planes [B, K, C, H, W] fp32, member_stride elements apart (at least one plane: a group view of a wider buffer
+ * works); target_dev [B, K, C, H, W]; lat_weights_dev [H]; scale_or_null_dev [C].  With x_(0) <= ... <= x_(M-1) the members at
+ * a grid point, y the target, w the row's weight and s the variable's scale (1 when null) the call ADDS, for the steps
+ * k' = step_begin + k of sums_dev double [4][steps_total][C] and ranks_dev int64 [steps_total][C][M + 1]:
+ *   sums[0] += sum w (s (mean_m x_m - y))^2               sums[1] += sum w s^2 1/(M-1) sum_m (x_m - mean)^2   (two-pass)
+ *   sums[2] += sum w s 1/M sum_m |x_m - y|                sums[3] += sum w s sum_{i<j} |x_i - x_j|            (unnormalised)
+ *   ranks[..][r] += 1 with r = #{m : x_m < y}             (strict, unweighted)
+ * Per-point arithmetic is fp32, every accumulation across points fp64 in a fixed order (per-workgroup partials in
+ * workspace_dev, then one ordered sum per (k, c)): no floating-point atomics, two runs give the same bits; the rank counts are
+ * integer atomics.  NaNs are not treated.  2 <= members <= 64 (any value, chosen at run time), else DLWP_ERR_UNSUPPORTED;
+ * steps * channels and batch at most 65535.  Every member value is read once; nothing but the partials is written.
+ * dlwp_ensemble_sums_workspace_bytes: the size of the partials (0 for a bad shape); a smaller workspace is DLWP_ERR_WORKSPACE.
+ * No allocation, no synchronisation. */
+size_t dlwp_ensemble_sums_workspace_bytes(int32_t batch, int32_t steps, int32_t channels, int32_t height, int32_t width);
+int32_t dlwp_ensemble_sums_acc_f32(const float* ens_dev, const float* target_dev, const float* lat_weights_dev,
+                                   const float* scale_or_null_dev, double* sums_dev, int64_t* ranks_dev, int32_t members,
+                                   int64_t member_stride, int32_t batch, int32_t steps, int32_t channels, int32_t height,
+                                   int32_t width, int32_t steps_total, int32_t step_begin, void* workspace_dev,
+                                   size_t workspace_bytes, void* stream);
+
 /* Top-of-atmosphere insolation on the device (csrc/insolation.hip; reference data/datasets/add_insolation.py:9-73):
  *   out[t, p] = fp32(S (sin lat_p sin dec_t - cos lat_p cos dec_t cos h) rho_t^-2),  cos h = cd_t cl_p - sd_t sl_p
  * date_table_dev double [dates, 5] = { sin dec, cos dec, rho^-2, cd = cos 2 pi frac(day), sd = sin 2 pi frac(day) },
@@ -1163,6 +1185,19 @@ int32_t dlwp_refiner_pair_f32(const float* target_dev, const float* prog_last_de
                               float* y_noised_dev, float* v_target_dev, int32_t batch, int32_t faces, int32_t channels,
                               int64_t plane, int64_t target_batch_stride, int64_t prog_batch_stride, float sqrt_abar,
                               float sqrt_1m_abar, int64_t seed, int64_t offset, void* stream);
+/* Member streams, for ensembles of one initial condition: normal(seed, member, g) is the stream above with counter word 2 =
+ * member (a uint32; word 3 stays 0), so member 0 is the stream of the entry points above bit for bit.  The two entry points
+ * below are dlwp_philox_normal_f32 and dlwp_ddpm_step_f32 on member-major tensors [members][n_per_member]: element (m, e) uses
+ * normal(seed, first_member + m, offset + e), with 0 <= first_member and first_member + members <= 2^31.  The definition is
+ * per element: n_per_member need not be a multiple of 4 (a thread's block of four may then straddle a member boundary), and
+ * members first_member .. first_member + members - 1 drawn in one call are bitwise the members of any split of that range into
+ * several calls.  Launch rules as above; with sigma == 0 nothing is drawn or read, with noise_or_null_dev given it is read
+ * ([members][n_per_member], like the sample) and nothing is drawn. */
+int32_t dlwp_philox_normal_members_f32(float* out_dev, int64_t n_per_member, int32_t members, int32_t first_member,
+                                       int64_t seed, int64_t offset, void* stream);
+int32_t dlwp_ddpm_step_members_f32(const float* sample_dev, const float* model_output_dev, const float* noise_or_null_dev,
+                                   float* out_dev, int64_t n_per_member, int32_t members, int32_t first_member,
+                                   const double coef[4], int64_t seed, int64_t offset, void* stream);
 
 #ifdef __cplusplus
 }

@@ -102,6 +102,24 @@ __global__ __launch_bounds__(256) void avgpool2x2_kernel(const float* __restrict
   }
 }
 
+// the adjoint: dx[2i + u][2j + v] = 0.25 gy[i][j]; a trailing odd row or column, which no window covers, is 0.  One dx
+// element per item, so every element is written and a store instruction writes a run of a dx row.  I: the type the element
+// index is decomposed in -- unsigned 32-bit wherever planes * H * W allows it (two 32-bit divisions per element, not two
+// 64-bit ones, in a kernel that otherwise only moves bytes), 64-bit beyond
+template <typename I>
+__global__ __launch_bounds__(256) void avgpool2x2_bwd_kernel(const float* __restrict__ gy, float* __restrict__ dx, long long planes,
+                                                             int H, int W) {
+  const I OH = H / 2, OW = W / 2, h = H, w = W;
+  const I total = (I)planes * h * w, step = (I)gridDim.x * 256;
+  // (i + step may not wrap: the launcher gives the 32-bit form totals below 2^31, and step <= 2^20)
+  for (I i = (I)blockIdx.x * 256 + threadIdx.x; i < total; i += step) {
+    const I r = i / w, iw = i - r * w;
+    const I pl = r / h, ih = r - pl * h;
+    const I oh = ih >> 1, ow = iw >> 1;
+    dx[i] = (oh < OH && ow < OW) ? 0.25f * gy[(pl * OH + oh) * OW + ow] : 0.f;
+  }
+}
+
 }  // namespace conv2
 }  // namespace dlwp
 
@@ -152,6 +170,21 @@ extern "C" int32_t dlwp_avgpool2x2_f32(const float* x, float* y, int64_t planes,
   DLWP_REQUIRE(planes > 0 && H >= 2 && W >= 2, DLWP_ERR_INVALID_ARGUMENT, "bad shape");
   hipLaunchKernelGGL(conv2::avgpool2x2_kernel, dim3(grid_for(planes * (H / 2) * (W / 2))), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), x, y, (long long)planes, H, W);
+  DLWP_HIP_CHECK(hipGetLastError());
+  return DLWP_OK;
+}
+
+extern "C" int32_t dlwp_avgpool2x2_bwd_f32(const float* gy, float* dx, int64_t planes, int32_t H, int32_t W, void* stream) {
+  DLWP_REQUIRE(gy && dx, DLWP_ERR_INVALID_ARGUMENT, "null argument");
+  DLWP_REQUIRE(planes > 0 && H >= 2 && W >= 2, DLWP_ERR_INVALID_ARGUMENT, "bad shape");
+  DLWP_REQUIRE(planes <= (1ll << 62) / ((long long)H * W), DLWP_ERR_UNSUPPORTED, "avgpool2x2_bwd: element count overflows");
+  const long long total = (long long)planes * H * W;
+  if (total < (1ll << 31))
+    hipLaunchKernelGGL(conv2::avgpool2x2_bwd_kernel<unsigned>, dim3(grid_for(total)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), gy, dx, (long long)planes, H, W);
+  else
+    hipLaunchKernelGGL(conv2::avgpool2x2_bwd_kernel<long long>, dim3(grid_for(total)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), gy, dx, (long long)planes, H, W);
   DLWP_HIP_CHECK(hipGetLastError());
   return DLWP_OK;
 }

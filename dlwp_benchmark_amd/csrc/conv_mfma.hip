@@ -36,6 +36,9 @@
 //                     the tile with its +-1 halo (k = 4; none for k = 2) feeds BOTH column parities, whose accumulators a lane
 //                     combines into one 8-byte store: 16 lanes write 32 consecutive floats of an output row.  The row parity
 //                     rides on the grid (blockIdx.z), which keeps the accumulators at 2 per fragment.
+//   DgradParity       the input gradient of the stride-2 Conv2d (dlwp_conv2d_dgrad_mfma_f32): TransposedParity's staging and taps
+//                     on a GEMM pixel grid that comes from the map it writes, and a cropping store.  The stride-1 input gradient
+//                     is ZeroPadWindow<8> itself on a pack with the channels exchanged and the taps reversed.
 // The staging loop stands in the kernel body and indexes the LDS array itself (conv_wgrad.hip's note on staging functions).
 #include "act_common.hpp"
 
@@ -197,6 +200,23 @@ struct TransposedParity : ZeroPadWindow<8> {
   }
 };
 
+// The input gradient of Conv2d(k, stride 2, pad): the parity form again, driven by the map it WRITES.  dx (OH x OW here) row
+// 2a + ph collects gz (H x W here) rows a + (ph + pad - kh0) / 2 - jh through taps kh = kh0 + 2 jh -- TransposedParity's
+// arithmetic with the Conv2d weight [cout][cin][k][k] read as the ConvTranspose2d weight it is.  An odd k arrives zero-extended
+// to k + 1 at the high tap index (the pack's k_packed), so p.k is even.  GEMM pixel (a, b), a < ceil(OH / 2), b < ceil(OW / 2):
+// gz cells outside its map stage as zeros (ZeroPadWindow::locate), so rows and columns of dx that no output read come out as
+// computed zeros; the store crops to OH x OW.  OW may be odd and dx may lie at any 4-byte offset: two scalar stores.
+struct DgradParity : TransposedParity {
+  static __device__ __forceinline__ void store(const Params& p, float* yb, const float*, int co_off, int ph, int prow, int pcol,
+                                               const float (&a)[2], float) {
+    const int row = 2 * prow + ph, col = 2 * pcol;
+    if (row >= p.OH) return;
+    float* d = yb + (co_off + row * p.OW + col);
+    if (col < p.OW) d[0] = a[0];
+    if (col + 1 < p.OW) d[1] = a[1];
+  }
+};
+
 // G: the geometry policy; NF: 16-channel output fragments per workgroup; NIMG: 3 bf16x6, 1 bf16.
 // Waves: WN along the output channels x WM along the pixels; each owns NFW x MF accumulator fragments per column parity.
 template <class G, int NF, int NIMG>
@@ -318,19 +338,23 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const Params p) {
 
 // weight [cout][cin][k][k] (transposed: [cin][cout][k][k]) -> three bf16 images [tap][slab][fragment][lane][8]: lane l of
 // fragment nf holds output channel 16 nf + (l & 15), input channels 32 slab + 8 (l >> 4) + 0..7 (element 0 in the low half of
-// dword 0); zero outside
+// dword 0); zero outside.  The pack has kp x kp taps, kp >= k: taps at index k and above are zero (the even window of
+// DgradParity); flip: pack tap (th, tw) holds weight tap (k - 1 - th, k - 1 - tw) (the stride-1 adjoint)
 __global__ __launch_bounds__(256) void conv_mfma_pack_kernel(const float* __restrict__ w, unsigned short* __restrict__ out,
-                                                             int cout, int cin, int kk, int transposed, int kslabs, int nfrags,
-                                                             long long total) {
+                                                             int cout, int cin, int k, int kp, int transposed, int flip, int kslabs,
+                                                             int nfrags, long long total) {
+  const int kk = k * k;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int e = (int)(i & 7), lane = (int)((i >> 3) & 63);
     long long rest = i >> 9;
     const int nf = (int)(rest % nfrags); rest /= nfrags;
     const int ks = (int)(rest % kslabs);
-    const int tap = (int)(rest / kslabs);
+    const int ptap = (int)(rest / kslabs);
+    const int th = ptap / kp, tw = ptap - th * kp;
+    const int tap = flip ? (k - 1 - th) * k + (k - 1 - tw) : th * k + tw;
     const int co = nf * 16 + (lane & 15), c = ks * KSLAB + 8 * (lane >> 4) + e;
     float v = 0.f;
-    if (co < cout && c < cin) v = transposed ? w[((long long)c * cout + co) * kk + tap] : w[((long long)co * cin + c) * kk + tap];
+    if (co < cout && c < cin && th < k && tw < k) v = transposed ? w[((long long)c * cout + co) * kk + tap] : w[((long long)co * cin + c) * kk + tap];
     unsigned h, m, l;
     split3_pair(v, 0.f, h, m, l);
     out[i] = (unsigned short)(h & 0xffffu);
@@ -348,7 +372,7 @@ namespace {
 
 constexpr int kMaxLds = 64 * 1024;      // dynamic LDS a launch may ask for without a function attribute
 
-enum Layer { PADDED3X3, CONV2D, TRANSPOSED };
+enum Layer { PADDED3X3, CONV2D, TRANSPOSED, DGRAD_PARITY };
 
 // the kernel instance and the staged window of a shape.  GH x GW: the GEMM pixel grid (the output; transposed: the input);
 // ws: the window's stride (Conv2d: its stride; otherwise 1).  The padded 3x3 layer is (tr false, k 3, ws 1): a window of
@@ -406,11 +430,14 @@ void launch_form(const convm::Params& p, int form, int nf, dim3 grid, size_t lds
   form == 0 ? launch_nf<G, 3>(p, nf, grid, lds, s) : launch_nf<G, 1>(p, nf, grid, lds, s);
 }
 
-// What the three launch entries share.  `p` arrives with its tensors, H, W, OH, OW, k, pad and ws described; the checks of
+// What the launch entries share.  `p` arrives with its tensors, H, W, OH, OW, k, pad and ws described; the checks of
 // form, activations, the grid's y and z, the kernel's 32-bit offsets (inside one sample: channel plane + pixel; the tile
 // count and the window sources too) and the pack's size, then the variant, the Params fields that follow from it, and the launch.
-int32_t check_and_launch(convm::Params& p, Layer layer, int form, const char* name, hipStream_t s) {
-  const bool tr = layer == TRANSPOSED;
+// `check` stops before the launch and leaves the variant in `v`: what the entries and the dgrad query both run.
+// DGRAD_PARITY: p.H x p.W is the map read (gz), p.OH x p.OW the map written (dx), and the GEMM pixel grid is one pixel per 2 x 2
+// block of the map written, ceil(OH / 2) x ceil(OW / 2).
+int32_t check(convm::Params& p, Layer layer, int form, const char* name, Variant& v) {
+  const bool tr = layer == TRANSPOSED || layer == DGRAD_PARITY;
   DLWP_REQUIRE(p.act >= 0 && p.act <= 4 && p.pre_act >= 0 && p.pre_act <= 4, DLWP_ERR_INVALID_ARGUMENT, "%s: unknown activation",
                name);
   DLWP_REQUIRE(form == 0 || form == 1, DLWP_ERR_INVALID_ARGUMENT, "%s: unknown form %d (0 bf16x6, 1 bf16)", name, form);
@@ -422,20 +449,28 @@ int32_t check_and_launch(convm::Params& p, Layer layer, int form, const char* na
   DLWP_REQUIRE(cin < (1ll << 31) - 64 && (cseg + 32) * HW < (1ll << 31) && (long long)p.Cout * OHW < (1ll << 31),
                DLWP_ERR_UNSUPPORTED, "%s: %lld -> %d channels of %d x %d -> %d x %d exceed the kernel's 32-bit offsets", name, cin,
                p.Cout, p.H, p.W, p.OH, p.OW);
-  p.kslabs = (int)((cin + convm::KSLAB - 1) / convm::KSLAB); p.nfrags = (p.Cout + 15) / 16;
+  p.kslabs = (int)((cin + convm::KSLAB - 1) / convm::KSLAB); p.nfrags = (int)(((long long)p.Cout + 15) / 16);
   DLWP_REQUIRE(p.nfrags * 2 <= 65535, DLWP_ERR_UNSUPPORTED, "%s: %d output channels exceed the grid's z dimension", name, p.Cout);
   DLWP_REQUIRE(dlwp_conv2d_mfma_packed_bytes(p.Cout, (int32_t)cin, p.k) > 0, DLWP_ERR_UNSUPPORTED,
                "%s: unsupported shape cout=%d cin=%lld k=%d", name, p.Cout, cin, p.k);
-  p.GH = tr ? p.H : p.OH; p.GW = tr ? p.W : p.OW;
-  const Variant v = choose_variant(tr, p.B, p.GH, p.GW, p.nfrags, p.k, p.ws);
+  if (layer == DGRAD_PARITY) { p.GH = p.OH / 2 + (p.OH & 1); p.GW = p.OW / 2 + (p.OW & 1); }    // no OH + 1: OH may be INT_MAX
+  else { p.GH = tr ? p.H : p.OH; p.GW = tr ? p.W : p.OW; }
+  v = choose_variant(tr, p.B, p.GH, p.GW, p.nfrags, p.k, p.ws);
   DLWP_REQUIRE(lds_bytes(v, 3, layer) <= (size_t)kMaxLds, DLWP_ERR_UNSUPPORTED, "%s: window of %d cells exceeds the LDS budget", name, v.npix);
   p.tw8 = v.tw == 8; p.tiles_w = v.tiles_w; p.wc = v.wc; p.rowp = v.rowp; p.planew = v.planew; p.npix = v.npix;
   p.wpad = tr ? (p.k == 4 ? 1 : 0) : p.pad;
+  return DLWP_OK;
+}
+
+int32_t launch_checked(const convm::Params& p, Layer layer, int form, const Variant& v, hipStream_t s) {
+  const bool tr = layer == TRANSPOSED || layer == DGRAD_PARITY;
   const dim3 grid(v.tiles, p.B, (tr ? 2 : 1) * ((p.nfrags + v.nf - 1) / v.nf));    // transposed: z = channel chunk * 2 + output row parity
   const size_t lds = lds_bytes(v, form == 0 ? 3 : 1, layer);
   if (layer == PADDED3X3) {
     if (v.tw == 8) launch_form<convm::Padded3x3<8>>(p, form, v.nf, grid, lds, s);
     else launch_form<convm::Padded3x3<16>>(p, form, v.nf, grid, lds, s);
+  } else if (layer == DGRAD_PARITY) {
+    launch_nf<convm::DgradParity, 3>(p, v.nf, grid, lds, s);        // the gradient has the one fp32-grade form
   } else if (tr) {
     launch_form<convm::TransposedParity>(p, form, v.nf, grid, lds, s);
   } else if (v.mfrags == 8) {
@@ -445,6 +480,12 @@ int32_t check_and_launch(convm::Params& p, Layer layer, int form, const char* na
   }
   DLWP_HIP_CHECK(hipGetLastError());
   return DLWP_OK;
+}
+
+int32_t check_and_launch(convm::Params& p, Layer layer, int form, const char* name, hipStream_t s) {
+  Variant v;
+  const int32_t status = check(p, layer, form, name, v);
+  return status != DLWP_OK ? status : launch_checked(p, layer, form, v, s);
 }
 
 }  // namespace
@@ -478,30 +519,31 @@ extern "C" int32_t dlwp_conv3x3_mfma_variant(int32_t batch, int32_t H, int32_t W
   return dlwp_conv2d_mfma_variant(0, batch, H, W, cout, 3, 1, 1);
 }
 
-static int32_t pack(const char* name, const float* weight_dev, int32_t cout, int32_t cin, int32_t k, int32_t transposed,
-                    void* packed_dev, void* stream) {
+static int32_t pack(const char* name, const float* weight_dev, int32_t cout, int32_t cin, int32_t k, int32_t k_packed,
+                    int32_t transposed, int32_t flip, void* packed_dev, void* stream) {
   DLWP_REQUIRE(weight_dev && packed_dev, DLWP_ERR_INVALID_ARGUMENT, "null argument");
-  const size_t bytes = dlwp_conv2d_mfma_packed_bytes(cout, cin, k);
-  DLWP_REQUIRE(bytes > 0, DLWP_ERR_UNSUPPORTED, "%s: unsupported shape cout=%d cin=%d k=%d", name, cout, cin, k);
+  DLWP_REQUIRE(k >= 1 && k_packed >= k, DLWP_ERR_INVALID_ARGUMENT, "%s: k=%d does not fit a pack of %d x %d taps", name, k, k_packed, k_packed);
+  const size_t bytes = dlwp_conv2d_mfma_packed_bytes(cout, cin, k_packed);
+  DLWP_REQUIRE(bytes > 0, DLWP_ERR_UNSUPPORTED, "%s: unsupported shape cout=%d cin=%d k=%d", name, cout, cin, k_packed);
   const int kslabs = (cin + convm::KSLAB - 1) / convm::KSLAB, nfrags = (cout + 15) / 16;
   const long long total = (long long)(bytes / 6);               // bf16 elements per image
   long long blocks = (total + 255) / 256;
   if (blocks > 256 * 16) blocks = 256 * 16;
   hipLaunchKernelGGL(convm::conv_mfma_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     weight_dev, reinterpret_cast<unsigned short*>(packed_dev), cout, cin, k * k, transposed != 0, kslabs, nfrags,
-                     total);
+                     weight_dev, reinterpret_cast<unsigned short*>(packed_dev), cout, cin, k, k_packed, transposed != 0, flip != 0,
+                     kslabs, nfrags, total);
   DLWP_HIP_CHECK(hipGetLastError());
   return DLWP_OK;
 }
 
 extern "C" int32_t dlwp_conv2d_mfma_pack_f32(const float* weight_dev, int32_t cout, int32_t cin, int32_t k, int32_t transposed,
                                              void* packed_dev, void* stream) {
-  return pack("conv2d_mfma", weight_dev, cout, cin, k, transposed, packed_dev, stream);
+  return pack("conv2d_mfma", weight_dev, cout, cin, k, k, transposed, 0, packed_dev, stream);
 }
 
 extern "C" int32_t dlwp_conv3x3_mfma_pack_f32(const float* weight_dev, int32_t cout, int32_t cin, void* packed_dev,
                                               void* stream) {
-  return pack("conv3x3_mfma", weight_dev, cout, cin, 3, 0, packed_dev, stream);
+  return pack("conv3x3_mfma", weight_dev, cout, cin, 3, 3, 0, 0, packed_dev, stream);
 }
 
 extern "C" int32_t dlwp_conv3x3_mfma_f32(const float* x0, int32_t c0, const float* x1, int32_t c1, const void* packed,
@@ -555,4 +597,71 @@ extern "C" int32_t dlwp_conv_transpose2d_mfma_f32(const float* x, const void* pa
   p.B = batch; p.H = H; p.W = W; p.Cout = cout; p.OH = 2 * H; p.OW = 2 * W; p.k = k; p.pad = pad;   // both geometries double
   p.act = act; p.ws = 1;
   return check_and_launch(p, TRANSPOSED, form, "conv_transpose2d_mfma", reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t dlwp_conv2d_mfma_pack_ex_f32(const float* weight_dev, int32_t cout, int32_t cin, int32_t k, int32_t k_packed,
+                                                int32_t exchange, int32_t flip, void* packed_dev, void* stream) {
+  return pack("conv2d_mfma_pack_ex", weight_dev, cout, cin, k, k_packed, exchange, flip, packed_dev, stream);
+}
+
+namespace {
+
+// The input gradient of Conv2d(cin -> cout, k, stride, pad) on an H x W map, as the launcher runs it.  Stride 1: the Conv2d
+// forward of gz with padding k - 1 - pad (pack: channels exchanged, taps reversed, k_packed = k).  Stride 2: DgradParity on
+// the even window k_packed = k + k % 2 (pack: channels exchanged, taps as they lie, zero-extended); a 2 x 2 window has no halo,
+// so it takes pad 0 alone, a 4 x 4 window reaches one cell either way, which covers pad 0, 1 and 2.
+struct DgradPlan {
+  Layer layer;
+  int k_packed, flip;
+  long long SH, SW;          // gz's map
+};
+
+bool dgrad_plan(int32_t H, int32_t W, int32_t k, int32_t stride, int32_t pad, DgradPlan& d) {
+  if (!conv_geometry_ok(k, stride, pad)) return false;
+  if ((long long)H + 2 * pad < k || (long long)W + 2 * pad < k) return false;
+  d.SH = ((long long)H + 2 * pad - k) / stride + 1; d.SW = ((long long)W + 2 * pad - k) / stride + 1;
+  if (stride == 1) { d.layer = CONV2D; d.k_packed = k; d.flip = 1; return true; }
+  d.layer = DGRAD_PARITY; d.k_packed = k + (k & 1); d.flip = 0;
+  return d.k_packed == 2 ? pad == 0 : pad <= 2;
+}
+
+// the Params of the launch (tensors aside) and every check of it short of the launch
+int32_t dgrad_check(convm::Params& p, const DgradPlan& d, int32_t batch, int32_t cin, int32_t cout, int32_t H, int32_t W, int32_t k,
+                    int32_t pad, Variant& v) {
+  p.c0 = cout; p.B = batch; p.H = (int)d.SH; p.W = (int)d.SW; p.Cout = cin; p.OH = H; p.OW = W; p.k = d.k_packed;
+  p.pad = d.layer == CONV2D ? k - 1 - pad : pad; p.ws = 1;
+  return check(p, d.layer, 0, "conv2d_dgrad_mfma", v);
+}
+
+}  // namespace
+
+// 4096 * k_packed + 1024 * policy (0: ZeroPadWindow<8> on the reversed pack, stride 1; 1: DgradParity, stride 2) + 16 * fragment
+// width + output fragments per workgroup; 0 for what dlwp_conv2d_dgrad_mfma_f32 refuses
+extern "C" int32_t dlwp_conv2d_dgrad_mfma_variant(int32_t batch, int32_t cin, int32_t cout, int32_t H, int32_t W, int32_t k,
+                                                  int32_t stride, int32_t pad) {
+  if (batch <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0 || k <= 0 || stride <= 0 || pad < 0) return 0;
+  DgradPlan d;
+  if (!dgrad_plan(H, W, k, stride, pad, d) || d.SH <= 0 || d.SW <= 0 || d.SH >= (1ll << 31) || d.SW >= (1ll << 31)) return 0;
+  convm::Params p = {};
+  Variant v;
+  if (dgrad_check(p, d, batch, cin, cout, H, W, k, pad, v) != DLWP_OK) return 0;
+  return 4096 * d.k_packed + 1024 * (d.layer == DGRAD_PARITY) + 16 * v.tw + v.nf;
+}
+
+extern "C" int32_t dlwp_conv2d_dgrad_mfma_f32(const float* gz, const void* packed, float* dx, int32_t batch, int32_t cin, int32_t H,
+                                              int32_t W, int32_t cout, int32_t k, int32_t stride, int32_t pad, void* stream) {
+  DLWP_REQUIRE(gz && packed && dx, DLWP_ERR_INVALID_ARGUMENT, "null argument");
+  DLWP_REQUIRE(batch > 0 && cin > 0 && cout > 0 && H > 0 && W > 0 && k > 0 && stride > 0 && pad >= 0, DLWP_ERR_INVALID_ARGUMENT, "bad shape");
+  DgradPlan d;
+  DLWP_REQUIRE(dgrad_plan(H, W, k, stride, pad, d), DLWP_ERR_UNSUPPORTED,
+               "conv2d_dgrad_mfma: k=%d stride=%d pad=%d on %d x %d has no matrix-pipe kernel (stride 1: k <= 4, pad < k; stride 2: "
+               "k 1 or 2 with pad 0, k 3 or 4 with pad <= 2; an output map of at least one pixel)", k, stride, pad, H, W);
+  DLWP_REQUIRE(d.SH > 0 && d.SW > 0, DLWP_ERR_INVALID_ARGUMENT, "empty output");
+  DLWP_REQUIRE(d.SH < (1ll << 31) && d.SW < (1ll << 31), DLWP_ERR_UNSUPPORTED, "conv2d_dgrad_mfma: output too large");
+  convm::Params p = {};
+  p.x0 = gz; p.wp = reinterpret_cast<const u32x4*>(packed); p.y = dx;
+  Variant v;
+  const int32_t status = dgrad_check(p, d, batch, cin, cout, H, W, k, pad, v);
+  if (status != DLWP_OK) return status;
+  return launch_checked(p, d.layer, 0, v, reinterpret_cast<hipStream_t>(stream));
 }

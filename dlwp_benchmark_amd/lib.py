@@ -141,6 +141,10 @@ SIGNATURES = {
                                        c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "dlwp_conv_transpose2d_mfma_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                                  c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "dlwp_conv2d_mfma_pack_ex_f32": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "dlwp_conv2d_dgrad_mfma_variant": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "dlwp_conv2d_dgrad_mfma_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                             c_int32, c_int32, c_void_p]),
     "dlwp_linear_packed_bytes": (c_size_t, [c_int32, c_int32]),
     "dlwp_linear_pack_f32": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "dlwp_linear_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int32, c_int32, c_int32,
@@ -172,6 +176,7 @@ SIGNATURES = {
     "dlwp_conv_transpose2d_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                             c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "dlwp_avgpool2x2_f32": (c_int32, [c_void_p, c_void_p, ctypes.c_int64, c_int32, c_int32, c_void_p]),
+    "dlwp_avgpool2x2_bwd_f32": (c_int32, [c_void_p, c_void_p, ctypes.c_int64, c_int32, c_int32, c_void_p]),
     "dlwp_conv3x3_hpx_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
                                        c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "dlwp_healpix_pad_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),

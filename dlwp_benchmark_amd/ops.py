@@ -197,20 +197,21 @@ class ConvWeights:
         self._op = op
         self._transposed = bool(transposed)
 
-    def get(self, weight: torch.Tensor) -> torch.Tensor:
-        def build():
-            cout, cin = (weight.shape[1], weight.shape[0]) if self._transposed else weight.shape[:2]
-            k = weight.shape[2]
-            lib = _lib.load()
-            nbytes = int(lib.dlwp_conv2d_mfma_packed_bytes(cout, cin, k))
-            if nbytes == 0:
-                raise _lib.DlwpError(f"{self._op}: unsupported shape cout={cout} cin={cin} k={k} for the matrix-pipe forms")
-            buf = torch.empty(nbytes // 4, dtype=torch.int32, device=weight.device)
-            _lib.launch("dlwp_conv2d_mfma_pack_f32", weight.device, weight.detach().contiguous(), cout, cin, k,
-                        int(self._transposed), buf)
-            return buf
+    def pack(self, weight: torch.Tensor) -> torch.Tensor:
+        """a fresh pack of `weight` as it lies now, outside the cache (one launch, one allocation)"""
+        cout, cin = (weight.shape[1], weight.shape[0]) if self._transposed else weight.shape[:2]
+        k = weight.shape[2]
+        lib = _lib.load()
+        nbytes = int(lib.dlwp_conv2d_mfma_packed_bytes(cout, cin, k))
+        if nbytes == 0:
+            raise _lib.DlwpError(f"{self._op}: unsupported shape cout={cout} cin={cin} k={k} for the matrix-pipe forms")
+        buf = torch.empty(nbytes // 4, dtype=torch.int32, device=weight.device)
+        _lib.launch("dlwp_conv2d_mfma_pack_f32", weight.device, weight.detach().contiguous(), cout, cin, k,
+                    int(self._transposed), buf)
+        return buf
 
-        return self._derived.get(source_key(weight), build)
+    def get(self, weight: torch.Tensor) -> torch.Tensor:
+        return self._derived.get(source_key(weight), lambda: self.pack(weight))
 
 
 def conv3x3_weights(weight: torch.Tensor) -> ConvWeights:
@@ -376,17 +377,29 @@ def groupnorm_act_backward(x: torch.Tensor, stats: torch.Tensor, weight: Optiona
     return dx, dw, db
 
 
+def _conv_pack(weight: torch.Tensor, transposed: bool, cached: bool) -> torch.Tensor:
+    """the matrix-pipe pack of a convolution weight: from the cache that belongs to the tensor, or (cached False) made now.
+    The training step packs per call, as linear_raw does: its parameters are also written by launches that move no version
+    counter (optim.FusedAdamW, ExponentialMovingAverage) and inside replayed step graphs, where a cached pack would go stale
+    without a sign; a pack launch made per call is part of the captured step."""
+    if cached:
+        return conv2d_weights(weight, transposed).get(weight)
+    return ConvWeights("conv2d", transposed).pack(weight)
+
+
 def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], stride: int = 1, padding: int = 0,
-           pre_act: int = 0, act: int = 0, resid: Optional[torch.Tensor] = None, form: str = "direct") -> torch.Tensor:
+           pre_act: int = 0, act: int = 0, resid: Optional[torch.Tensor] = None, form: str = "direct",
+           cached: bool = True) -> torch.Tensor:
     """zero-padded Conv2d (square kernel / stride / padding): the strided and 1x1 convolutions of unet.py:583-584, :879, :450.
     `form` (CONV_FORMS): "direct" the one-thread-per-output kernel; "bf16x6" / "bf16" dlwp_conv2d_mfma_f32 (k <= 4, stride 1 or 2,
     padding < k; anything else raises.  Inference only: with gradients wanted every form runs training.conv2d -- the library's
-    forward and input gradient, the weight and bias gradient on dlwp_conv2d_wgrad_f32 under DLWP_CONV_WGRAD)."""
+    forward and input gradient, under DLWP_CONV_DGRAD=hip the "bf16x6" kernel and dlwp_conv2d_dgrad_mfma_f32; the weight and
+    bias gradient on dlwp_conv2d_wgrad_f32 under DLWP_CONV_WGRAD).  `cached` False: the pack is made in this call (_conv_pack)."""
     _conv_form(form)
     for t, n in ((x, "x"), (weight, "weight"), (resid, "resid")):
         _lib.require_cuda_tensor(t, n)
     from . import training as _T
-    if _T.wants_grad(x, weight, bias, resid):       # library forward and input gradient, dlwp_conv2d_wgrad_f32 (training.py)
+    if _T.wants_grad(x, weight, bias, resid):       # DLWP_CONV_DGRAD: library or HIP forward and input gradient (training.py)
         return _T.conv2d(x, weight, bias, resid, int(stride), int(padding), int(pre_act), int(act))
     owner = weight          # the pack belongs to the caller's tensor, not to a contiguous copy made below
     x, weight = x.contiguous(), weight.contiguous()
@@ -399,7 +412,7 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], 
         raise _lib.DlwpError("conv2d: resid must be contiguous and shaped like the output")
     y = torch.empty(n, cout, oh, ow, device=x.device, dtype=torch.float32)
     if form != "direct":
-        packed = conv2d_weights(owner).get(owner)
+        packed = _conv_pack(owner, False, cached)
         _lib.launch("dlwp_conv2d_mfma_f32", x.device, x, packed, _contig(bias), resid, y, n, cin, h, w, cout, k, int(stride),
                     int(padding), int(pre_act), int(act), CONV_FORMS.index(form) - 1)
         return y
@@ -409,15 +422,16 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], 
 
 
 def conv_transpose2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], stride: int, padding: int = 0,
-                     act: int = 0, form: str = "direct") -> torch.Tensor:
+                     act: int = 0, form: str = "direct", cached: bool = True) -> torch.Tensor:
     """ConvTranspose2d (weight [cin, cout, k, k]; unet.py:523 2x2 s2, :719 4x4 s2 p1).  `form` (CONV_FORMS): "direct" the
     one-thread-per-output kernel; "bf16x6" / "bf16" dlwp_conv_transpose2d_mfma_f32 (exactly those two geometries; anything else
-    raises.  Inference only: with gradients wanted every form runs training.conv_transpose2d, as conv2d does)."""
+    raises.  Inference only: with gradients wanted every form runs training.conv_transpose2d, as conv2d does).  `cached` as
+    conv2d's."""
     _conv_form(form)
     _lib.require_cuda_tensor(x, "x")
     _lib.require_cuda_tensor(weight, "weight")
     from . import training as _T
-    if _T.wants_grad(x, weight, bias):              # library forward and input gradient, dlwp_conv2d_wgrad_f32 (training.py)
+    if _T.wants_grad(x, weight, bias):              # DLWP_CONV_DGRAD: library or HIP forward and input gradient (training.py)
         return _T.conv_transpose2d(x, weight, bias, int(stride), int(padding), int(act))
     owner = weight
     x, weight = x.contiguous(), weight.contiguous()
@@ -428,7 +442,7 @@ def conv_transpose2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch
     oh, ow = (h - 1) * stride - 2 * padding + k, (w - 1) * stride - 2 * padding + k
     y = torch.empty(n, cout, oh, ow, device=x.device, dtype=torch.float32)
     if form != "direct":
-        packed = conv2d_weights(owner, transposed=True).get(owner)
+        packed = _conv_pack(owner, True, cached)
         _lib.launch("dlwp_conv_transpose2d_mfma_f32", x.device, x, packed, _contig(bias), y, n, cin, h, w, cout, k, int(stride),
                     int(padding), int(act), CONV_FORMS.index(form) - 1)
         return y
@@ -438,15 +452,135 @@ def conv_transpose2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch
 
 
 def avgpool2x2(x: torch.Tensor) -> torch.Tensor:
-    """AvgPool2d(kernel_size=2, stride=2) (unet.py:450)."""
+    """AvgPool2d(kernel_size=2, stride=2) (unet.py:450).  With a gradient wanted: F.avg_pool2d, under DLWP_CONV_DGRAD=hip this
+    kernel and dlwp_avgpool2x2_bwd_f32 (training._AvgPool2x2Fn)."""
     _lib.require_cuda_tensor(x, "x")
     if torch.is_grad_enabled() and x.requires_grad:
+        from . import training as _T
+        if _T.conv_dgrad_uses_hip() and x.dtype == torch.float32 and x.dim() == 4 and min(x.shape[2:]) >= 2:
+            return _T.avgpool2x2(x)                 # this kernel forward, dlwp_avgpool2x2_bwd_f32 backward
         return torch.nn.functional.avg_pool2d(x, 2)
     x = x.contiguous()
     n, c, h, w = x.shape
     y = torch.empty(n, c, h // 2, w // 2, device=x.device, dtype=torch.float32)
     _lib.launch("dlwp_avgpool2x2_f32", x.device, x, y, n * c, h, w)
     return y
+
+
+def avgpool2x2_backward(gy: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    """The adjoint of avgpool2x2 on an input of h x w: gy [N, C, h // 2, w // 2] -> dx [N, C, h, w], dx[2i + u][2j + v] =
+    0.25 gy[i][j], a trailing odd row or column 0 (dlwp_avgpool2x2_bwd_f32; every element is written)."""
+    _lib.require_cuda_tensor(gy, "gy")
+    gy = gy.contiguous()
+    n, c, oh, ow = gy.shape
+    h, w = int(h), int(w)
+    if (oh, ow) != (h // 2, w // 2) or min(oh, ow) < 1:
+        raise _lib.DlwpError(f"avgpool2x2_backward: gy {tuple(gy.shape)} is not the pooled map of {h} x {w}")
+    dx = torch.empty(n, c, h, w, device=gy.device, dtype=torch.float32)
+    if dx.numel():
+        _lib.launch("dlwp_avgpool2x2_bwd_f32", gy.device, gy, dx, n * c, h, w)
+    return dx
+
+
+class ConvAdjointWeights:
+    """A Conv2d weight [cout, cin, k, k] packed for its input gradient (dlwp_conv2d_dgrad_mfma_f32): the channels exchanged,
+    k_packed >= k taps per axis, the taps reversed or not -- what dlwp_conv2d_dgrad_mfma_variant names for the layer's stride.
+    A buffer of its own beside the forward pack of the same tensor, re-derived by ConvWeights' rule."""
+
+    def __init__(self, k_packed: int, flip: bool):
+        self._derived = Derived(eager_only="conv2d_input_grad")
+        self._k_packed, self._flip = int(k_packed), bool(flip)
+
+    def pack(self, weight: torch.Tensor) -> torch.Tensor:
+        """a fresh adjoint pack of `weight` as it lies now, outside the cache"""
+        cout, cin, k = weight.shape[:3]
+        nbytes = int(_lib.load().dlwp_conv2d_mfma_packed_bytes(cin, cout, self._k_packed))
+        if nbytes == 0:
+            raise _lib.DlwpError(f"conv2d_input_grad: unsupported shape cout={cout} cin={cin} k={k} for the matrix-pipe forms")
+        buf = torch.empty(nbytes // 4, dtype=torch.int32, device=weight.device)
+        _lib.launch("dlwp_conv2d_mfma_pack_ex_f32", weight.device, weight.detach().contiguous(), cin, cout, k,
+                    self._k_packed, 1, int(self._flip), buf)
+        return buf
+
+    def get(self, weight: torch.Tensor) -> torch.Tensor:
+        return self._derived.get(source_key(weight), lambda: self.pack(weight))
+
+
+def conv2d_adjoint_weights(weight: torch.Tensor, k_packed: int, flip: bool) -> ConvAdjointWeights:
+    """The adjoint-pack cache of conv2d_input_grad that belongs to `weight`: a slot per (k_packed, flip), none shared with
+    conv2d_weights."""
+    return derived_for(weight, ("conv2d_adjoint", int(k_packed), bool(flip)), lambda: ConvAdjointWeights(k_packed, flip))
+
+
+def _conv2d_dgrad_variant(batch, cin, cout, h, w, k, stride, padding) -> int:
+    args = [int(v) for v in (batch, cin, cout, h, w, k, stride, padding)]
+    if min(args[:7]) < 1 or args[7] < 0 or max(args) >= 1 << 31:
+        return 0
+    return int(_lib.load().dlwp_conv2d_dgrad_mfma_variant(*args))
+
+
+def conv2d_input_grad_supported(batch: int, cin: int, cout: int, h: int, w: int, k: int, stride: int, padding: int) -> bool:
+    """whether dlwp_conv2d_dgrad_mfma_f32 takes the input gradient of Conv2d(cin -> cout, k, stride, padding) on [batch, cin,
+    h, w] (the launcher's own checks; its envelope: include/dlwp_hip.h); needs the library, not a GPU"""
+    return _conv2d_dgrad_variant(batch, cin, cout, h, w, k, stride, padding) != 0
+
+
+def conv2d_input_grad(gz: torch.Tensor, weight: torch.Tensor, x_shape, stride: int, padding: int,
+                      out: Optional[torch.Tensor] = None, cached: bool = True) -> torch.Tensor:
+    """The input gradient of conv2d: gz [N, cout, SH, SW], the gradient of the convolution's output, and the layer's weight
+    [cout, cin, k, k] -> dx of x_shape = [N, cin, H, W] on dlwp_conv2d_dgrad_mfma_f32 (fp32-grade, every element written, reruns
+    bit-identical).  `out`: a contiguous fp32 tensor of x_shape to write instead of a new one (any 4-byte alignment).  A geometry
+    outside the envelope raises; conv2d_input_grad_supported asks first.  `cached` False: the adjoint pack is made in this call
+    from the weight as it lies (what the training step does, see _conv_pack)."""
+    _lib.require_cuda_tensor(gz, "gz")
+    _lib.require_cuda_tensor(weight, "weight")
+    gz = gz.contiguous()
+    n, cin, h, w = (int(v) for v in x_shape)
+    if weight.dim() != 4 or weight.shape[2] != weight.shape[3] or weight.shape[1] != cin:
+        raise _lib.DlwpError(f"conv2d_input_grad: weight {tuple(weight.shape)} does not match an input of {cin} channels")
+    cout, _, k, _ = weight.shape
+    stride, padding = int(stride), int(padding)
+    variant = _conv2d_dgrad_variant(n, cin, cout, h, w, k, stride, padding)
+    if variant == 0:
+        raise _lib.DlwpError(f"conv2d_input_grad: no HIP kernel for {cin} <- {cout} channels on {n} x {h} x {w}, k={k} "
+                             f"stride={stride} padding={padding}")
+    if tuple(gz.shape) != (n, cout, *_conv2d_out_hw(h, w, k, stride, padding, False)):
+        raise _lib.DlwpError(f"conv2d_input_grad: gz {tuple(gz.shape)} is not the output map of {tuple(x_shape)} under k={k} "
+                             f"stride={stride} padding={padding}")
+    k_packed, flip = variant >> 12, not (variant >> 10) & 1
+    packed = (conv2d_adjoint_weights(weight, k_packed, flip).get(weight) if cached
+              else ConvAdjointWeights(k_packed, flip).pack(weight))
+    dx = out if out is not None else torch.empty(n, cin, h, w, device=gz.device, dtype=torch.float32)
+    if out is not None and (tuple(out.shape) != (n, cin, h, w) or out.dtype != torch.float32 or not out.is_contiguous() or
+                            out.device != gz.device):
+        raise _lib.DlwpError(f"conv2d_input_grad: out must be a contiguous fp32 tensor of {(n, cin, h, w)} on {gz.device}")
+    _lib.launch("dlwp_conv2d_dgrad_mfma_f32", gz.device, gz, packed, dx, n, cin, h, w, cout, k, stride, padding)
+    return dx
+
+
+def conv_transpose2d_input_grad_supported(batch: int, cin: int, cout: int, sh: int, sw: int, k: int, stride: int,
+                                          padding: int) -> bool:
+    """whether conv_transpose2d_input_grad takes gz [batch, cout, sh, sw]: the envelope of dlwp_conv2d_mfma_f32 (k <= 4, stride
+    1 or 2, padding < k)"""
+    args = [int(v) for v in (batch, sh, sw, cin, k, stride, padding)]
+    if min(args[:6]) < 1 or args[6] < 0 or int(cout) < 1 or max(*args, int(cout)) >= 1 << 31:
+        return False
+    lib = _lib.load()
+    return lib.dlwp_conv2d_mfma_variant(0, *args) != 0 and lib.dlwp_conv2d_mfma_packed_bytes(int(cin), int(cout), int(k)) > 0
+
+
+def conv_transpose2d_input_grad(gz: torch.Tensor, weight: torch.Tensor, stride: int, padding: int,
+                                cached: bool = True) -> torch.Tensor:
+    """The input gradient of conv_transpose2d: gz [N, cout, OH, OW] and the layer's weight [cin, cout, k, k] -> dx [N, cin, H,
+    W].  It is the Conv2d forward of gz with the same stride and padding and the weight read as a Conv2d weight of cin output
+    and cout input channels -- no flip, no copy: dlwp_conv2d_mfma_f32 in the "bf16x6" form on conv2d_weights(weight), the
+    untransposed pack (its own slot beside the layer's forward pack; `cached` False: made in this call)."""
+    _lib.require_cuda_tensor(gz, "gz")
+    _lib.require_cuda_tensor(weight, "weight")
+    if weight.dim() != 4 or weight.shape[1] != gz.shape[1]:
+        raise _lib.DlwpError(f"conv_transpose2d_input_grad: weight {tuple(weight.shape)} does not match gz {tuple(gz.shape)}")
+    with torch.no_grad():           # `weight` itself, not a detached alias: the pack belongs to the caller's tensor
+        return conv2d(gz.detach(), weight, None, int(stride), int(padding), form="bf16x6", cached=cached)
 
 
 def small_module(m: torch.nn.Module, x: torch.Tensor, act: int = 0, form: str = "direct") -> torch.Tensor:

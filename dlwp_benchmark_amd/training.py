@@ -554,6 +554,26 @@ def conv_wgrad_uses_hip(batch: int, c0: int, c1: int, cout: int, h: int, w: int,
     return ops.conv3x3_weight_grad_supported(batch, c0, c1, cout, h, w, hpx)
 
 
+CONV_DGRAD_MODES = ("torch", "hip")
+
+
+def conv_dgrad_mode() -> str:
+    """DLWP_CONV_DGRAD, the one switch of what the U-Net family's training step still sends to a library: the forward and
+    input gradient of the non-3x3 convolutions, the AvgPool2d(2) backward and the wide-HEALPix 3x3 input gradient.  "torch"
+    (default): the library calls conv2d_torch / conv_transpose2d_torch / conv2d_input_grad_torch, F.avg_pool2d and
+    F.conv_transpose2d.  "hip": dlwp_conv2d_mfma_f32 / dlwp_conv_transpose2d_mfma_f32 in the fp32-grade "bf16x6" form,
+    dlwp_conv2d_dgrad_mfma_f32 and dlwp_avgpool2x2_bwd_f32 -- bit-reproducible gradients, no algorithm search, no library
+    workspace; a geometry the kernels refuse takes the library call.  Read at every call; DLWP_TRAIN_TORCH_BACKWARD=1 wins."""
+    mode = os.environ.get("DLWP_CONV_DGRAD", "torch")
+    if mode not in CONV_DGRAD_MODES:
+        raise _lib.DlwpError(f"DLWP_CONV_DGRAD={mode!r}: one of {CONV_DGRAD_MODES}")
+    return mode
+
+
+def conv_dgrad_uses_hip() -> bool:
+    return conv_dgrad_mode() == "hip" and not _torch_backward_selected()
+
+
 # output channels up to which the HEALPix input gradient runs dlwp_conv3x3_hpx_bwd_data_f32; wider layers take the two-step
 # form (MIOpen transposed conv + dlwp_healpix_pad_bwd_f32), which measured faster there (DESIGN.md section 13)
 HPX_DX_DIRECT_MAX_COUT = 48
@@ -595,6 +615,63 @@ def conv2d_torch(x, weight, bias, resid, stride: int, padding: int, pre_act: int
 def conv_transpose2d_torch(x, weight, bias, stride: int, padding: int, act: int):
     """act(ConvTranspose2d(x)) with torch operators (reference unet.py:523, :719)"""
     return _ACT_FNS[int(act)](F.conv_transpose2d(x, weight, bias, stride=stride, padding=padding))
+
+
+def conv2d_input_grad_torch(gz, x, weight, stride: int, padding: int, transposed: bool = False):
+    """dx of conv2d_torch (transposed: of conv_transpose2d_torch) before the pre-activation's derivative, from gz, the gradient
+    of the convolution's output: the library call autograd makes for the plain composition (aten.convolution_backward, input
+    alone).  x gives the shape."""
+    return torch.ops.aten.convolution_backward(gz, x, weight, None, [stride, stride], [padding, padding], [1, 1],
+                                               bool(transposed), [0, 0], 1, [True, False, False])[0]
+
+
+def _unsupported_is_none(fn):
+    """fn(), or None where the library answers DLWP_ERR_UNSUPPORTED (the caller then takes the library call)"""
+    try:
+        return fn()
+    except _lib.DlwpError as e:
+        if e.status != _lib.ERR_UNSUPPORTED:
+            raise
+        return None
+
+
+def _conv2_forward_hip(x, weight, bias, resid, stride: int, padding: int, pre_act: int, transposed: bool):
+    """z = Conv2d(pre_act(x)) + bias + resid (transposed: ConvTranspose2d(x) + bias) on the matrix-pipe kernel in the "bf16x6"
+    form, pre-activation, bias and residual inside it, act = 0 so that z itself can be saved; None for a layer it refuses.
+    The weight is packed in this call, from the values it holds now (ops._conv_pack): no cached pack can go stale under an
+    optimizer that writes through raw pointers, and a captured step re-packs at every replay."""
+    if not (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 4):
+        return None
+    lib = _lib.load()
+    n, cin, h, w = x.shape
+    k = weight.shape[2]
+    cout = weight.shape[1] if transposed else weight.shape[0]
+    if max(n, cin, cout, h, w, k, stride, padding) >= 1 << 31 or not lib.dlwp_conv2d_mfma_packed_bytes(cout, cin, k) or \
+            not lib.dlwp_conv2d_mfma_variant(int(transposed), n, h, w, cout, k, stride, padding):
+        return None
+    if transposed:
+        return _unsupported_is_none(lambda: ops.conv_transpose2d(x, weight, bias, stride, padding, act=0, form="bf16x6",
+                                                                 cached=False))
+    resid = resid.contiguous() if resid is not None else None
+    return _unsupported_is_none(lambda: ops.conv2d(x, weight, bias, stride, padding, pre_act=pre_act, act=0, resid=resid,
+                                                   form="bf16x6", cached=False))
+
+
+def _conv2_input_grad_hip(gz, x_shape, weight, stride: int, padding: int, transposed: bool):
+    """the input gradient (before the pre-activation's derivative) on dlwp_conv2d_dgrad_mfma_f32, the transposed layer's on
+    dlwp_conv2d_mfma_f32; None for a layer they refuse.  The adjoint pack is made in this call, as the forward's is."""
+    if not (gz.is_cuda and gz.dtype == torch.float32 and weight.dtype == torch.float32):
+        return None
+    n, cin, h, w = x_shape
+    k = weight.shape[2]
+    if transposed:
+        cout = weight.shape[1]
+        if not ops.conv_transpose2d_input_grad_supported(n, cin, cout, gz.shape[2], gz.shape[3], k, stride, padding):
+            return None
+        return _unsupported_is_none(lambda: ops.conv_transpose2d_input_grad(gz, weight, stride, padding, cached=False))
+    if not ops.conv2d_input_grad_supported(n, cin, weight.shape[0], h, w, k, stride, padding):
+        return None
+    return _unsupported_is_none(lambda: ops.conv2d_input_grad(gz, weight, x_shape, stride, padding, cached=False))
 
 
 def conv2d_weight_grad_torch(x, gz, k: int, stride: int, padding: int, pre_act: int = 0, transposed: bool = False,
@@ -647,7 +724,8 @@ def _conv3x3_backward(ctx, grad_out):
     The post-activation derivative from z, recomputed by the forward kernel.  The input gradient: under CylinderPad (circular
     in longitude, zeros in latitude) the SAME operator with the weights transposed and flipped, dlwp_conv3x3_ex_f32 again;
     under HEALPixPadding(1) (healpix.py:69-114) dlwp_conv3x3_hpx_bwd_data_f32, the transposed 3x3 folded through the adjoint
-    of the padding table, or for wide layers the library's transposed convolution onto the padded face folded by
+    of the padding table, or for wide layers the library's transposed convolution onto the padded face (DLWP_CONV_DGRAD=hip:
+    dlwp_conv2d_dgrad_mfma_f32, the input gradient of the unpadded 3x3 on the padded face) folded by
     dlwp_healpix_pad_bwd_f32; then the pre-activation derivative.  The weight and bias gradients in one
     dlwp_conv3x3_wgrad_f32 call on the unpadded segments (DLWP_CONV_WGRAD: or conv3x3_weight_grad_torch, the correlation of a
     padded copy with the output gradient through MIOpen), the residual's gradient gz itself."""
@@ -668,7 +746,11 @@ def _conv3x3_backward(ctx, grad_out):
             if hpx and weight.shape[0] <= HPX_DX_DIRECT_MAX_COUT:
                 dxa = ops.conv3x3_hpx_backward_data(gz, weight, c0 + c1)
             elif hpx:
-                dxa = ops.healpix_pad_backward(F.conv_transpose2d(gz, weight), 1)
+                padded = None
+                if conv_dgrad_uses_hip():
+                    padded = _conv2_input_grad_hip(gz, (n, c0 + c1, h + 2, w + 2), weight, 1, 0, False)     # onto the padded face
+                dxa = ops.healpix_pad_backward(F.conv_transpose2d(gz, weight) if padded is None else padded, 1)
+                del padded              # the padded face is the largest tensor of this backward: not kept through the rest
             else:
                 dxa = ops.conv3x3(gz, weight.flip(2, 3).transpose(0, 1).contiguous(), None)
             if pre_act != 0:
@@ -688,7 +770,8 @@ def _conv3x3_backward(ctx, grad_out):
 
 def _conv2_backward(ctx, grad_out, transposed: bool):
     """(dx, dw, db, dresid) of _Conv2dFn / _ConvTranspose2dFn: the post-activation derivative from the saved z, the input
-    gradient by the library call autograd makes for the plain composition (aten.convolution_backward, input alone) followed by
+    gradient by the library call autograd makes for the plain composition (conv2d_input_grad_torch; DLWP_CONV_DGRAD=hip:
+    dlwp_conv2d_dgrad_mfma_f32, the transposed layer's dlwp_conv2d_mfma_f32, where they take the layer) followed by
     the pre-activation derivative, the weight and bias gradients in one dlwp_conv2d_wgrad_f32 call on x as it lies
     (DLWP_CONV_WGRAD: or conv2d_weight_grad_torch), the residual's gradient gz itself."""
     stride, padding, pre_act, act = ctx.cfg
@@ -701,8 +784,9 @@ def _conv2_backward(ctx, grad_out, transposed: bool):
     with torch.no_grad():
         gz = _act_backward(z, grad_out.contiguous(), act).contiguous()
         if need_x:
-            dxa = torch.ops.aten.convolution_backward(gz, x, weight, None, [stride, stride], [padding, padding], [1, 1],
-                                                      transposed, [0, 0], 1, [True, False, False])[0]
+            dxa = _conv2_input_grad_hip(gz, x.shape, weight, stride, padding, transposed) if conv_dgrad_uses_hip() else None
+            if dxa is None:
+                dxa = conv2d_input_grad_torch(gz, x, weight, stride, padding, transposed)
             dx = _act_backward(x, dxa, pre_act)
         if need_w or need_b:
             n, cin, h, w = x.shape
@@ -717,18 +801,21 @@ def _conv2_backward(ctx, grad_out, transposed: bool):
 
 
 class _Conv2dFn(torch.autograd.Function):
-    """ops.conv2d under autograd: the forward is conv2d_torch's operators (values bit for bit the plain composition's); saved
-    are x, weight, bias, resid and -- only with a post-activation -- the convolution's output z.  Backward: _conv2_backward."""
+    """ops.conv2d under autograd: the forward is conv2d_torch's operators (values bit for bit the plain composition's), under
+    DLWP_CONV_DGRAD=hip dlwp_conv2d_mfma_f32 ("bf16x6") followed by training.activation's kernel; saved are x, weight, bias,
+    resid and -- only with a post-activation -- the convolution's output z.  Backward: _conv2_backward."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, resid, stride, padding, pre_act, act):
         ctx.cfg = (stride, padding, pre_act, act)
         with torch.no_grad():
-            z = F.conv2d(_ACT_FNS[pre_act](x), weight, bias, stride=stride, padding=padding)
-            if resid is not None:
-                z = z + resid
+            z = _conv2_forward_hip(x, weight, bias, resid, stride, padding, pre_act, False) if conv_dgrad_uses_hip() else None
+            y = None
+            if z is None:
+                z = conv2d_torch(x, weight, bias, resid, stride, padding, pre_act, 0)
+                y = _ACT_FNS[act](z)
             ctx.save_for_backward(x, weight, bias, resid, z if act != 0 else None)
-            return _ACT_FNS[act](z)
+            return y if y is not None else (z if act == 0 else activation(z, act))
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -742,9 +829,13 @@ class _ConvTranspose2dFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias, stride, padding, act):
         ctx.cfg = (stride, padding, 0, act)
         with torch.no_grad():
-            z = F.conv_transpose2d(x, weight, bias, stride=stride, padding=padding)
+            z = _conv2_forward_hip(x, weight, bias, None, stride, padding, 0, True) if conv_dgrad_uses_hip() else None
+            y = None
+            if z is None:
+                z = conv_transpose2d_torch(x, weight, bias, stride, padding, 0)
+                y = _ACT_FNS[act](z)
             ctx.save_for_backward(x, weight, bias, None, z if act != 0 else None)
-            return _ACT_FNS[act](z)
+            return y if y is not None else (z if act == 0 else activation(z, act))
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -766,6 +857,24 @@ def conv_transpose2d(x, weight, bias, stride: int, padding: int, act: int):
     if _plain_conv2(weight):
         return conv_transpose2d_torch(x, weight, bias, stride, padding, act)
     return _ConvTranspose2dFn.apply(x, weight, bias, stride, padding, act)
+
+
+class _AvgPool2x2Fn(torch.autograd.Function):
+    """AvgPool2d(2) with HIP in both directions: dlwp_avgpool2x2_f32 forward, dlwp_avgpool2x2_bwd_f32 backward"""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.hw = tuple(x.shape[2:])
+        with torch.no_grad():
+            return ops.avgpool2x2(x.detach())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return ops.avgpool2x2_backward(grad_out, *ctx.hw)
+
+
+def avgpool2x2(x):
+    return _AvgPool2x2Fn.apply(x)
 
 
 def groupnorm_act_backward_torch(x, mean, rstd, gamma, beta, gy, groups: int, act: int):

@@ -449,6 +449,35 @@ int32_t dlwp_conv_transpose2d_mfma_f32(const float* x_dev, const void* packed_de
                                        int32_t batch, int32_t cin, int32_t height, int32_t width, int32_t cout, int32_t k,
                                        int32_t stride, int32_t pad, int32_t act, int32_t form, void* stream);
 
+/* The input gradient of the zero-padded Conv2d(cin -> cout, k, stride, pad) on the same kernel, form "bf16x6" (the gradient of
+ * the training step's loss.backward(), scripts/train.py:271, through unet.py:450, :533, :583-584, :879-881):
+ *   dx[b, ci, ih, iw] = sum_{co, kh, kw : ih = stride oh - pad + kh, iw = stride ow - pad + kw} weight[co, ci, kh, kw] gz[b, co, oh, ow]
+ * gz_dev [batch, cout, SH, SW] with SH = (height + 2 pad - k) / stride + 1 (SW alike), dx_dev [batch, cin, height, width] at any
+ * 4-byte offset.  EVERY element of dx is written: rows and columns that no output read (k2 s2 on an odd map, the holes of a
+ * 1x1 s2) are computed zeros, no memset is needed.
+ *   stride 1: the Conv2d forward of gz with padding k - 1 - pad; the pack has the channels exchanged and both tap axes reversed.
+ *   stride 2: the parity form of the transposed layer on the GEMM pixel grid ceil(height / 2) x ceil(width / 2), an odd k
+ *             zero-extended to k + 1 at the high tap index, stores cropped to height x width.  k 1 or 2 take pad 0, k 3 or 4
+ *             pad 0, 1 or 2.
+ * Anything else -- k > 4, stride > 2, pad >= k, the remaining stride-2 paddings, shapes whose per-sample offsets leave 32 bits --
+ * returns DLWP_ERR_UNSUPPORTED before any launch.
+ * dlwp_conv2d_mfma_pack_ex_f32 is dlwp_conv2d_mfma_pack_f32 with the two further modes: a pack of k_packed x k_packed taps
+ * (k_packed >= k; dlwp_conv2d_mfma_packed_bytes(cout, cin, k_packed) bytes) whose taps at index k and above are zero, and
+ * flip != 0: pack tap (th, tw) holds weight tap (k - 1 - th, k - 1 - tw).  cout and cin are the GEMM's output and input
+ * channels; exchange != 0 reads the tensor as [cin, cout, k, k].  The adjoint pack of a Conv2d weight [cout, cin, k, k] is
+ * pack_ex(weight, cin, cout, k, k_packed, 1, flip), with k_packed and flip from dlwp_conv2d_dgrad_mfma_variant.
+ * dlwp_conv2d_dgrad_mfma_variant runs the launcher's own checks: 0 for what it refuses, otherwise 4096 * k_packed + 1024 * policy
+ * (0: stride 1, the reversed pack; 1: stride 2, the parity form, unreversed) + 16 * fragment width + output fragments per
+ * workgroup.  The ConvTranspose2d input gradient needs no entry: it is dlwp_conv2d_mfma_f32 on gz with the [cin, cout, k, k]
+ * weight packed as a Conv2d weight of cin output and cout input channels. */
+int32_t dlwp_conv2d_mfma_pack_ex_f32(const float* weight_dev, int32_t cout, int32_t cin, int32_t k, int32_t k_packed,
+                                     int32_t exchange, int32_t flip, void* packed_dev, void* stream);
+int32_t dlwp_conv2d_dgrad_mfma_variant(int32_t batch, int32_t cin, int32_t cout, int32_t height, int32_t width, int32_t k,
+                                       int32_t stride, int32_t pad);
+int32_t dlwp_conv2d_dgrad_mfma_f32(const float* gz_dev, const void* packed_dev, float* dx_dev, int32_t batch, int32_t cin,
+                                   int32_t height, int32_t width, int32_t cout, int32_t k, int32_t stride, int32_t pad,
+                                   void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * fp32 Linear layers on the bf16 matrix pipe with the block's pointwise work fused (csrc/linear.hip): the qkv / proj /
  * fc1 / fc2 Linears, GELU and residual adds of the Swin and Pangu blocks (swin_transformer.py:21-39, :107-120, :254-262;
@@ -503,6 +532,9 @@ int32_t dlwp_conv_transpose2d_f32(const float* x_dev, const float* weight_dev, c
                                   int32_t cin, int32_t height, int32_t width, int32_t cout, int32_t k, int32_t stride,
                                   int32_t pad, int32_t act, void* stream);
 int32_t dlwp_avgpool2x2_f32(const float* x_dev, float* y_dev, int64_t planes, int32_t height, int32_t width, void* stream);
+/* its adjoint: dx[2i + u][2j + v] = 0.25 gy[i][j] for gy_dev [planes, height / 2, width / 2]; every element of dx_dev [planes,
+ * height, width] is written, a trailing odd row or column with 0 */
+int32_t dlwp_avgpool2x2_bwd_f32(const float* gy_dev, float* dx_dev, int64_t planes, int32_t height, int32_t width, void* stream);
 
 /* GroupNorm + activation for training (csrc/groupnorm_bwd.hip): unet.py:739 (+ GELU :761), :887-888 under the
  * `loss.backward()` of scripts/train.py:271.  With v = xh gamma_c + beta_c, xh = (x - mean) rstd, y = act(v):

@@ -1,5 +1,5 @@
 // Host-side check of the argument checks of csrc/conv_mfma.hip: a stand-alone program that calls the packed-size and variant
-// entries and the three launch entries with bad and oversized shapes.  Every such call returns before any launch, so the
+// entries, the three launch entries and the input-gradient entries with bad and oversized shapes.  Every such call returns before any launch, so the
 // program needs no GPU; build it with the host sanitizers and run it directly:
 //
 //   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
@@ -150,6 +150,74 @@ int main() {
   EXPECT(c3(1, 4, 0, 1, 2, big, 0, nullptr), DLWP_ERR_UNSUPPORTED);               // output channels
   EXPECT(c3(1, 1 << 20, 0, 4, 4, 1 << 20, 0, nullptr), DLWP_ERR_UNSUPPORTED);     // pack of 2 GiB and more
   EXPECT(c3(big, big, big, big, big, big, 1, nullptr), DLWP_ERR_UNSUPPORTED);
+
+  // the Conv2d input gradient: the variant query runs the launcher's own checks, the entry returns before any launch
+  auto dv = [&](int32_t batch, int32_t cin, int32_t cout, int32_t H, int32_t W, int32_t k, int32_t s, int32_t p) {
+    return dlwp_conv2d_dgrad_mfma_variant(batch, cin, cout, H, W, k, s, p);
+  };
+  auto dg = [&](int32_t batch, int32_t cin, int32_t H, int32_t W, int32_t cout, int32_t k, int32_t s, int32_t p) {
+    return dlwp_conv2d_dgrad_mfma_f32(x, pk, x, batch, cin, H, W, cout, k, s, p, nullptr);
+  };
+  EXPECT(dv(2, 6, 4, 8, 16, 3, 2, 1), 4096 * 4 + 1024 + 16 * 8 + 1);              // 3x3 s2 p1: the 4x4 window, parity form
+  EXPECT(dv(1, 3, 2, 5, 7, 2, 2, 0), 4096 * 2 + 1024 + 16 * 8 + 1);
+  EXPECT(dv(1, 3, 2, 5, 7, 1, 2, 0), 4096 * 2 + 1024 + 16 * 8 + 1);               // 1x1 s2: the 2x2 window
+  EXPECT(dv(1, 2, 3, 8, 16, 3, 1, 1), 4096 * 3 + 16 * 16 + 1);                    // stride 1: the reversed pack, ZeroPadWindow<8>
+  EXPECT(dv(64, 208, 8, 16, 32, 4, 2, 1), 4096 * 4 + 1024 + 16 * 16 + 4);
+  EXPECT(dv(1, 3, 2, 6, 9, 3, 2, 0) > 0, 1);                                      // what the 4x4 window holds as well
+  EXPECT(dv(1, 3, 2, 6, 9, 4, 2, 2) > 0, 1);
+  EXPECT(dv(0, 3, 2, 8, 8, 1, 1, 0), 0);                                          // bad shapes
+  EXPECT(dv(1, 0, 2, 8, 8, 1, 1, 0), 0);
+  EXPECT(dv(1, 3, -2, 8, 8, 1, 1, 0), 0);
+  EXPECT(dv(1, 3, 2, 0, 8, 1, 1, 0), 0);
+  EXPECT(dv(1, 3, 2, 8, 8, 0, 1, 0), 0);
+  EXPECT(dv(1, 3, 2, 8, 8, 3, 0, 1), 0);
+  EXPECT(dv(1, 3, 2, 8, 8, 3, 1, -1), 0);
+  EXPECT(dv(1, 3, 2, 2, 2, 4, 1, 0), 0);                                          // empty output
+  EXPECT(dv(1, 3, 2, 8, 8, 4, 2, 3), 0);                                          // geometry
+  EXPECT(dv(1, 3, 2, 8, 8, 2, 2, 1), 0);
+  EXPECT(dv(1, 3, 2, 8, 8, 1, 2, 1), 0);
+  EXPECT(dv(1, 3, 2, 8, 8, 5, 1, 2), 0);
+  EXPECT(dv(1, 3, 2, 8, 8, 3, 3, 1), 0);
+  EXPECT(dv(65536, 3, 2, 8, 8, 3, 2, 1), 0);                                      // batch over the grid
+  EXPECT(dv(1, 3, 2, 32768, 32768, 3, 2, 1), 0);                                  // 32-bit offsets inside a sample
+  EXPECT(dv(1, 3, 2, big, big, 4, 2, 1), 0);                                      // ceil(H / 2) of INT_MAX: no H + 1 in int
+  EXPECT(dv(1, 3, 2, big, 1, 1, 2, 0), 0);
+  EXPECT(dv(1, 3, 2, 1, big, 2, 2, 0), 0);
+  EXPECT(dv(1, 3, 2, big, big, 3, 1, 1), 0);
+  EXPECT(dv(1, big, 2, 1, 1, 1, 1, 0), 0);                                        // channels
+  EXPECT(dv(1, 3, big, 1, 1, 1, 1, 0), 0);
+  EXPECT(dv(1, 1 << 20, 1 << 20, 4, 4, 1, 1, 0), 0);                              // pack of 2 GiB and more
+  EXPECT(dv(big, big, big, big, big, 4, 2, 2), 0);
+  EXPECT(dv(1, 1, 2, 8000, 8000, 4, 2, 1) > 0, 1);                                // large maps inside the 32-bit offsets
+  EXPECT(dv(1, 1, 2, 8001, 7999, 3, 2, 1) > 0, 1);
+  EXPECT(dv(1, 3, 2, 46000, 46000, 4, 2, 1), 0);                                  // 3 x 46000^2 elements per sample of dx
+
+  EXPECT(dlwp_conv2d_dgrad_mfma_f32(nullptr, pk, x, 1, 3, 8, 8, 2, 3, 2, 1, nullptr), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(dlwp_conv2d_dgrad_mfma_f32(x, nullptr, x, 1, 3, 8, 8, 2, 3, 2, 1, nullptr), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(dlwp_conv2d_dgrad_mfma_f32(x, pk, nullptr, 1, 3, 8, 8, 2, 3, 2, 1, nullptr), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(dg(0, 3, 8, 8, 2, 3, 2, 1), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(dg(1, 3, 8, -8, 2, 3, 2, 1), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(dg(1, 3, 8, 8, 2, 3, 2, -1), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(dg(1, 3, 2, 2, 2, 4, 1, 0), DLWP_ERR_UNSUPPORTED);                       // no output pixel: outside the envelope
+  EXPECT(dg(1, 3, 8, 8, 2, 4, 2, 3), DLWP_ERR_UNSUPPORTED);
+  EXPECT(dg(1, 3, 8, 8, 2, 2, 2, 1), DLWP_ERR_UNSUPPORTED);
+  EXPECT(dg(1, 3, 8, 8, 2, 5, 1, 2), DLWP_ERR_UNSUPPORTED);
+  EXPECT(dg(1, 3, 8, 8, 2, 3, 3, 1), DLWP_ERR_UNSUPPORTED);
+  EXPECT(dg(65536, 3, 8, 8, 2, 3, 2, 1), DLWP_ERR_UNSUPPORTED);
+  EXPECT(dg(1, 3, 32768, 32768, 2, 3, 2, 1), DLWP_ERR_UNSUPPORTED);
+  EXPECT(dg(1, 3, big, big, 2, 4, 2, 1), DLWP_ERR_UNSUPPORTED);
+  EXPECT(dg(1, 3, big, big, 2, 1, 2, 0), DLWP_ERR_UNSUPPORTED);
+  EXPECT(dg(1, 3, big, 1, 2, 3, 1, 1), DLWP_ERR_UNSUPPORTED);
+  EXPECT(dg(1, big, 1, 1, 2, 1, 1, 0), DLWP_ERR_UNSUPPORTED);
+  EXPECT(dg(1, 3, 1, 1, big, 1, 1, 0), DLWP_ERR_UNSUPPORTED);
+  EXPECT(dg(1, 1 << 20, 4, 4, 1 << 20, 1, 1, 0), DLWP_ERR_UNSUPPORTED);
+  EXPECT(dg(big, big, big, big, big, 4, 2, 2), DLWP_ERR_UNSUPPORTED);
+
+  EXPECT(dlwp_conv2d_mfma_pack_ex_f32(nullptr, 8, 8, 3, 4, 1, 0, pk, nullptr), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(dlwp_conv2d_mfma_pack_ex_f32(x, 8, 8, 3, 2, 1, 0, pk, nullptr), DLWP_ERR_INVALID_ARGUMENT);     // k_packed < k
+  EXPECT(dlwp_conv2d_mfma_pack_ex_f32(x, 8, 8, 0, 2, 1, 0, pk, nullptr), DLWP_ERR_INVALID_ARGUMENT);
+  EXPECT(dlwp_conv2d_mfma_pack_ex_f32(x, 8, 8, 4, 5, 1, 1, pk, nullptr), DLWP_ERR_UNSUPPORTED);
+  EXPECT(dlwp_conv2d_mfma_pack_ex_f32(x, big, big, 3, 4, 1, 0, pk, nullptr), DLWP_ERR_UNSUPPORTED);
 
   if (failures == 0) std::printf("ok\n");
   return failures ? 1 : 0;

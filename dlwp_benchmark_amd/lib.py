@@ -195,6 +195,8 @@ SIGNATURES = {
     "dlwp_conv2d_wgrad_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int32] * 10 + [c_void_p, c_size_t, c_void_p]),
     "dlwp_convlstm_gates_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                           c_void_p]),
+    "dlwp_convlstm_gates_bwd_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                              c_int32, c_int32, c_void_p]),
     "dlwp_layernorm_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int32, c_float, c_void_p]),
     "dlwp_layernorm_prebias_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int32, c_float,
                                              c_void_p]),

@@ -543,15 +543,24 @@ class ConvLSTM(HipBackbone):
         ctx = self.context_size
         if t_total <= ctx:
             raise _lib.DlwpError(f"need more than context_size={ctx} frames, got {t_total}")
-        dev = prognostic.device
-        hs = [torch.zeros(b, n, hgt, wid, device=dev) for n in self.hidden_sizes]
-        cs = [torch.zeros(b, n, hgt, wid, device=dev) for n in self.hidden_sizes]
+        hs, cs = self._zero_state(b, hgt, wid, prognostic.device)
+        return self._frames(constants, prescribed, prognostic, ctx, t_total, hs, cs, None)
+
+    def _zero_state(self, b, hgt, wid, dev):
+        return ([torch.zeros(b, n, hgt, wid, device=dev) for n in self.hidden_sizes],
+                [torch.zeros(b, n, hgt, wid, device=dev) for n in self.hidden_sizes])
+
+    def _frames(self, constants, prescribed, prognostic, lead, n_frames, hs, cs, prev):
+        """The loop of _rollout over `n_frames` frames: the first `lead` are teacher-forced from prognostic[:, t] and produce
+        no output, every later one continues from `prev`, the frame produced last; frame t reads prescribed[:, t].  hs, cs
+        (lists, one tensor per cell) are replaced entry by entry.  Returns the [N, n_frames - lead, Cg, H, W] trajectory."""
+        first = prognostic[:, 0] if lead else prev
+        b, cg, hgt, wid = first.shape
         grad = self._grad_mode()       # training: nothing in place, the trajectory is stacked at the end
         outs = []
-        out = None if grad else torch.empty(b, t_total - ctx, cg, hgt, wid, device=dev, dtype=torch.float32)
-        prev = None
-        for t in range(t_total):
-            prog_t = prognostic[:, t] if t < ctx else prev
+        out = None if grad else torch.empty(b, n_frames - lead, cg, hgt, wid, device=first.device, dtype=torch.float32)
+        for t in range(n_frames):
+            prog_t = prognostic[:, t] if t < lead else prev
             parts = []
             if constants is not None:
                 parts.append(constants[:, 0])
@@ -565,11 +574,11 @@ class ConvLSTM(HipBackbone):
             inc = self._decode(x)
             if grad:
                 prev = prog_t + inc
-                if t >= ctx:
+                if t >= lead:
                     outs.append(prev)
-            elif t >= ctx:
-                torch.add(prog_t, inc, out=out[:, t - ctx])
-                prev = out[:, t - ctx]
+            elif t >= lead:
+                torch.add(prog_t, inc, out=out[:, t - lead])
+                prev = out[:, t - lead]
             else:
                 prev = prog_t + inc
         return torch.stack(outs, dim=1) if grad else out
@@ -581,6 +590,75 @@ class ConvLSTM(HipBackbone):
             return self._rollout(constants, prescribed, prognostic)
         with torch.no_grad():
             return self._rollout(constants, prescribed, prognostic)
+
+    # ---- carried state: a rollout continued chunk by chunk (rollout.rollout_chunks(..., carry_state=True)) ----
+    def _fold(self, t: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
+        """an input as _frames reads it, [N, T, C, H, W] (ConvLSTMHPX folds its face axis into N)"""
+        _lib.require_cuda_tensor(t, name)
+        if t is not None and t.dim() != 5:
+            raise _lib.DlwpError(f"{name}: expected [B, T, C, H, W], got {tuple(t.shape)}")
+        return t.contiguous() if t is not None else None
+
+    def _unfold(self, out: torch.Tensor) -> torch.Tensor:
+        return out
+
+    def forward_chunk(self, constants: Optional[torch.Tensor] = None, prescribed: Optional[torch.Tensor] = None,
+                      prognostic: Optional[torch.Tensor] = None, state: Optional["ConvLSTMState"] = None, *,
+                      steps: Optional[int] = None):
+        """A rollout in pieces: (out [B, k, Cg, ...], state).  Inference only (DlwpError with .train() and autograd recording;
+        truncated BPTT through a carried state is not offered).
+
+        state=None starts a rollout: exactly `forward` on [B, ctx + k, ...] inputs (with `steps` = k given, `prognostic` may
+        hold the ctx initial frames alone: no later one is read), the same bits, and beside the trajectory the state after
+        its last frame -- every cell's h and c and the frame produced last, owned tensors (no views of `out`).
+        With a state the loop continues from it for k more steps: `prognostic` is not read (None allowed) and `prescribed`
+        holds only the next k frames; k = prescribed.shape[1], or `steps` for a model without prescribed channels.  The state
+        passed in is left as it is, so a chunk can be run again from it."""
+        if self._grad_mode():
+            raise _lib.DlwpError(f"{type(self).__name__}.forward_chunk is inference only: call it in eval() mode or under "
+                                 "torch.no_grad() (a carried state does not carry the graph of the frames before it)")
+        constants, prescribed = self._fold(constants, "constants"), self._fold(prescribed, "prescribed")
+        with torch.no_grad():
+            if state is None:
+                if prognostic is None:
+                    raise _lib.DlwpError("forward_chunk: prognostic is required where no state is given")
+                prognostic = self._fold(prognostic, "prognostic")
+                b, t_have, _, hgt, wid = prognostic.shape
+                lead = self.context_size
+                t_total = t_have if steps is None else lead + int(steps)        # with steps, the ctx initial frames suffice
+                if t_total <= lead or t_have < lead:
+                    raise _lib.DlwpError(f"need more than context_size={lead} frames, got {t_have}"
+                                         + (f" and steps = {steps}" if steps is not None else ""))
+                if prescribed is not None and prescribed.shape[1] < t_total:
+                    raise _lib.DlwpError(f"forward_chunk: prescribed holds {prescribed.shape[1]} frames, {t_total} are read")
+                hs, cs = self._zero_state(b, hgt, wid, prognostic.device)
+                prev = None
+            else:
+                if not isinstance(state, ConvLSTMState) or len(state.hs) != len(self.hidden_sizes):
+                    raise _lib.DlwpError("forward_chunk: state must be what an earlier forward_chunk of this model returned")
+                if steps is None and prescribed is None:
+                    raise _lib.DlwpError("forward_chunk: with a state and no prescribed frames, pass steps=...")
+                t_total = int(steps) if steps is not None else prescribed.shape[1]
+                if t_total < 1 or (prescribed is not None and prescribed.shape[1] != t_total):
+                    raise _lib.DlwpError(f"forward_chunk: {t_total} steps asked for, prescribed holds "
+                                         f"{None if prescribed is None else prescribed.shape[1]} frames")
+                for name, t in (("constants", constants), ("prescribed", prescribed)):
+                    if t is not None and (t.shape[0] != state.prev.shape[0] or t.shape[3:] != state.prev.shape[2:]):
+                        raise _lib.DlwpError(f"forward_chunk: {name} {tuple(t.shape)} does not fit the state's frames "
+                                             f"{tuple(state.prev.shape)}")
+                lead, prognostic = 0, None
+                hs, cs, prev = list(state.hs), list(state.cs), state.prev
+            out = self._frames(constants, prescribed, prognostic, lead, t_total, hs, cs, prev)
+            return self._unfold(out), ConvLSTMState(hs, cs, out[:, -1].clone())
+
+
+class ConvLSTMState:
+    """What ConvLSTM.forward_chunk hands from one chunk to the next: every cell's (h, c) and the frame produced last, in the
+    model's internal layout.  Opaque to callers; the tensors are owned (no views of a chunk's output) and never written."""
+    __slots__ = ("hs", "cs", "prev")
+
+    def __init__(self, hs, cs, prev):
+        self.hs, self.cs, self.prev = tuple(hs), tuple(cs), prev
 
 
 class ConvLSTMHPX(ConvLSTM):
@@ -600,15 +678,29 @@ class ConvLSTMHPX(ConvLSTM):
     def forward(self, constants: Optional[torch.Tensor] = None, prescribed: Optional[torch.Tensor] = None,
                 prognostic: torch.Tensor = None) -> torch.Tensor:
         for name, t in (("constants", constants), ("prescribed", prescribed), ("prognostic", prognostic)):
-            if t is not None:
-                _lib.require_cuda_tensor(t, name)
-                if t.dim() != 6 or t.shape[3] != 12:
-                    raise _lib.DlwpError(f"{name}: expected [B, T, C, 12, H, W], got {tuple(t.shape)}")
+            self._check_faces(t, name)
         if prognostic is None:
             raise _lib.DlwpError("prognostic is required")
-        b, t_total, cg, f, h, w = prognostic.shape
         with torch.set_grad_enabled(self._grad_mode()):
-            fold5 = lambda t: t.permute(0, 3, 1, 2, 4, 5).reshape(b * f, t.shape[1], t.shape[2], h, w).float().contiguous()
-            out = self._rollout(fold5(constants) if constants is not None else None,
-                                fold5(prescribed) if prescribed is not None else None, fold5(prognostic))
-            return out.reshape(b, f, out.shape[1], cg, h, w).permute(0, 2, 3, 1, 4, 5).contiguous()
+            out = self._rollout(self._fold(constants, "constants"), self._fold(prescribed, "prescribed"),
+                                self._fold(prognostic, "prognostic"))
+            return self._unfold(out)
+
+    @staticmethod
+    def _check_faces(t, name: str):
+        if t is not None:
+            _lib.require_cuda_tensor(t, name)
+            if t.dim() != 6 or t.shape[3] != 12:
+                raise _lib.DlwpError(f"{name}: expected [B, T, C, 12, H, W], got {tuple(t.shape)}")
+
+    def _fold(self, t: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
+        """[B, T, C, 12, H, W] -> [B * 12, T, C, H, W]: the faces fold into the batch (`_prepare_inputs` :293-305)"""
+        if t is None:
+            return None
+        self._check_faces(t, name)
+        b, tt, c, f, h, w = t.shape
+        return t.permute(0, 3, 1, 2, 4, 5).reshape(b * f, tt, c, h, w).float().contiguous()
+
+    def _unfold(self, out: torch.Tensor) -> torch.Tensor:
+        n, k, cg, h, w = out.shape
+        return out.reshape(n // 12, 12, k, cg, h, w).permute(0, 2, 3, 1, 4, 5).contiguous()

@@ -926,18 +926,47 @@ def conv2d_weight_grad(x: torch.Tensor, grad_z: torch.Tensor, k: int, stride: in
 
 
 def convlstm_gates(gates: torch.Tensor, c_prev: torch.Tensor):
+    """The ConvLSTM cell update (convlstm.py:96-109): gates [B, 4*hid, H, W] = (netin, i, f, o) before their activations and
+    c_prev [B, hid, H, W] -> (h, c), one dlwp_convlstm_gates_f32 launch.  With a gradient wanted: training.convlstm_gates,
+    this kernel forward and dlwp_convlstm_gates_bwd_f32 backward."""
     _lib.require_cuda_tensor(gates, "gates")
     _lib.require_cuda_tensor(c_prev, "c_prev")
-    if torch.is_grad_enabled() and (gates.requires_grad or c_prev.requires_grad):     # convlstm.py:96-109 with torch operators
-        netin, ig, fg, og = torch.split(gates, gates.shape[1] // 4, dim=1)
-        c_new = torch.sigmoid(fg) * c_prev + torch.sigmoid(ig) * torch.tanh(netin)
-        return torch.sigmoid(og) * torch.tanh(c_new), c_new
+    if torch.is_grad_enabled() and (gates.requires_grad or c_prev.requires_grad):
+        from . import training as _T
+        return _T.convlstm_gates(gates, c_prev)
     gates, c_prev = gates.contiguous(), c_prev.contiguous()
     b, c4, h, w = gates.shape
     hid = c4 // 4
     h_out, c_out = torch.empty_like(c_prev), torch.empty_like(c_prev)
     _lib.launch("dlwp_convlstm_gates_f32", gates.device, gates, c_prev, h_out, c_out, b, hid, h, w)
     return h_out, c_out
+
+
+def convlstm_gates_backward(gates: torch.Tensor, c_prev: torch.Tensor, dh: Optional[torch.Tensor], dc: Optional[torch.Tensor],
+                            need_c_prev: bool = True):
+    """The backward of convlstm_gates from its inputs alone (dlwp_convlstm_gates_bwd_f32: the activations are recomputed with
+    the forward's arithmetic, nothing activated is saved): (dgates [B, 4*hid, H, W], dc_prev [B, hid, H, W] or None when
+    need_c_prev is false).  dh, dc [B, hid, H, W] are the gradients of h and c; either may be None (a zero gradient, not
+    read), not both.  One launch on the current stream, no host synchronisation; reruns are bitwise identical."""
+    for t, name in ((gates, "gates"), (c_prev, "c_prev"), (dh, "dh"), (dc, "dc")):
+        _lib.require_cuda_tensor(t, name)
+    if dh is None and dc is None:
+        raise _lib.DlwpError("convlstm_gates_backward: neither dh nor dc given")
+    gates, c_prev = gates.contiguous(), c_prev.contiguous()
+    if gates.dim() != 4 or gates.shape[1] % 4 or tuple(c_prev.shape) != (gates.shape[0], gates.shape[1] // 4, *gates.shape[2:]):
+        raise _lib.DlwpError(f"convlstm_gates_backward: gates {tuple(gates.shape)} must be [B, 4*hid, H, W] and c_prev "
+                             f"{tuple(c_prev.shape)} [B, hid, H, W]")
+    for t, name in ((dh, "dh"), (dc, "dc")):
+        if t is not None and t.shape != c_prev.shape:
+            raise _lib.DlwpError(f"convlstm_gates_backward: {name} {tuple(t.shape)} is not c_prev's {tuple(c_prev.shape)}")
+    dh = dh.contiguous() if dh is not None else None
+    dc = dc.contiguous() if dc is not None else None
+    b, c4, h, w = gates.shape
+    dgates = torch.empty_like(gates)
+    dc_prev = torch.empty_like(c_prev) if need_c_prev else None
+    if dgates.numel():
+        _lib.launch("dlwp_convlstm_gates_bwd_f32", gates.device, gates, c_prev, dh, dc, dgates, dc_prev, b, c4 // 4, h, w)
+    return dgates, dc_prev
 
 
 def afno2d_mix(xf_cf: torch.Tensor, w1, b1, w2, b2, num_blocks: int, sparsity_threshold: float,

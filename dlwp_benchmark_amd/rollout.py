@@ -51,7 +51,7 @@ def rollout_into(one_step: Callable[[torch.Tensor], torch.Tensor], context_size:
 
 
 def rollout_chunks(model, constants: Optional[torch.Tensor], prescribed, prognostic: torch.Tensor, n_steps: int,
-                   chunk_steps: int, noise_scheduler=None):
+                   chunk_steps: int, noise_scheduler=None, carry_state: bool = False):
     """A rollout of any length in fixed device memory: a generator of (step_begin, out_chunk), out_chunk [B, k, Cg, ...] holding
     rollout steps [step_begin, step_begin + k), k = chunk_steps (less in the last chunk).  `out_chunk` is a view of a reused
     buffer: valid until the next iteration.
@@ -67,7 +67,14 @@ def rollout_chunks(model, constants: Optional[torch.Tensor], prescribed, prognos
     input, every later one from `out`; the FNO kernels: csrc/fno2d.hip, fno_rollout_once, the same rule).  The driver holds
     three buffers of ctx + chunk_steps frames at most, whatever n_steps is, and does not synchronise with the host.
 
-    ConvLSTM / ConvLSTMHPX carry a recurrent state that starts at frame 0 and cannot be resumed from frames: they are refused.
+    ConvLSTM / ConvLSTMHPX carry a recurrent (h, c) state that starts at frame 0 and cannot be resumed from frames: without
+    `carry_state` they are refused.  With carry_state=True the chunks are the model's own `forward_chunk`: the first one is its
+    forward over the ctx initial frames and k steps, every later one continues from the state the one before returned (every
+    cell's h and c and the last frame, 2 len(hidden_sizes) + 1 tensors), so the chunked run is bitwise the one-shot forward
+    and the driver holds one chunk of output beside that state, whatever n_steps is.  The frames of `prescribed` asked for
+    are then exactly those read: (0, ctx + k) for the first chunk, (ctx + s0, ctx + s0 + k) afterwards.  `out_chunk` is the
+    model's tensor, valid until the next iteration like the reused buffer of the other models.  A model without
+    `forward_chunk` is refused under carry_state=True.
     The diffusion backbones (DiffModernUNet, DiffMUNetHPX) need `noise_scheduler` and are refused without it; with it every
     chunk is their own forward(..., noise_scheduler=...), which draws per rollout step on per-step shapes, so a chunked run is
     bitwise the one-shot forward with a scheduler in the same state.  Other models take no scheduler."""
@@ -75,9 +82,14 @@ def rollout_chunks(model, constants: Optional[torch.Tensor], prescribed, prognos
     from .models.diffusion import DiffModernUNet
     from .models.unet import ConvLSTM
 
-    if isinstance(model, ConvLSTM):
+    carry_state = bool(carry_state)
+    if isinstance(model, ConvLSTM) and not carry_state:
         raise _lib.DlwpError(f"rollout_chunks: {type(model).__name__} carries a recurrent (h, c) state that starts at frame 0 of a "
-                             "forward and cannot be resumed from the last frames of a chunk")
+                             "forward and cannot be resumed from the last frames of a chunk: pass carry_state=True to hand the "
+                             "state from chunk to chunk (forward_chunk)")
+    if carry_state and not callable(getattr(model, "forward_chunk", None)):
+        raise _lib.DlwpError(f"rollout_chunks: carry_state=True needs a model with forward_chunk (ConvLSTM, ConvLSTMHPX); "
+                             f"{type(model).__name__} has no state to carry")
     diffusion = isinstance(model, DiffModernUNet)
     if diffusion and noise_scheduler is None:
         raise _lib.DlwpError(f"rollout_chunks: {type(model).__name__}.forward needs a noise scheduler: pass noise_scheduler=...")
@@ -108,34 +120,51 @@ def rollout_chunks(model, constants: Optional[torch.Tensor], prescribed, prognos
     dev = prognostic.device
     into = prognostic.dim() == 5 and hasattr(model, "rollout_into")      # the diffusion backbones have none
     constants = constants.contiguous() if constants is not None else None
+    presc_buf = None
+
+    def frames_of_prescribed(f0, f1):
+        """frames [f0, f1) of `prescribed`, contiguous (None without prescribed channels)"""
+        nonlocal presc_buf
+        if prescribed is None:
+            return None
+        if fixed:
+            presc = prescribed[:, f0:f1]
+            if not presc.is_contiguous():
+                if presc_buf is None:
+                    presc_buf = torch.empty(b * (ctx + kmax) * (prescribed[0, 0].numel()), device=dev, dtype=torch.float32)
+                view = presc_buf[:presc.numel()].view(presc.shape)
+                view.copy_(presc)
+                presc = view
+            return presc
+        presc = prescribed(f0, f1)
+        _lib.require_cuda_tensor(presc, "prescribed(frame_begin, frame_end)")
+        if presc is None or presc.shape[0] != b or presc.shape[1] != f1 - f0:
+            raise _lib.DlwpError(f"rollout_chunks: prescribed({f0}, {f1}) must give [{b}, {f1 - f0}, Cp, ...], got "
+                                 f"{None if presc is None else tuple(presc.shape)}")
+        return presc.contiguous()
+
+    def state_chunks():
+        state = None
+        for s0 in range(0, n_steps, kmax):
+            k = min(kmax, n_steps - s0)
+            presc = frames_of_prescribed(0, ctx + k) if s0 == 0 else frames_of_prescribed(ctx + s0, ctx + s0 + k)
+            # (forward_chunk runs under no_grad itself; nothing is held across the yield)
+            out, state = model.forward_chunk(constants=constants, prescribed=presc, prognostic=prognostic if s0 == 0 else None,
+                                             state=state, steps=k)
+            yield s0, out
+
+    if carry_state:
+        return state_chunks()
     context = prognostic.contiguous().clone()                                  # the last ctx frames produced so far
     win_buf = torch.zeros(b * (ctx + kmax) * fsz, device=dev, dtype=torch.float32)   # frames past ctx are never read
     out_buf = torch.empty(b * kmax * fsz, device=dev, dtype=torch.float32) if into else None
-    presc_buf = None
 
     def chunks():
-        nonlocal presc_buf
         for s0 in range(0, n_steps, kmax):
             k = min(kmax, n_steps - s0)
             win = win_buf[:b * (ctx + k) * fsz].view(b, ctx + k, *frame)
             win[:, :ctx].copy_(context)
-            if prescribed is None:
-                presc = None
-            elif fixed:
-                presc = prescribed[:, s0:s0 + ctx + k]
-                if not presc.is_contiguous():
-                    if presc_buf is None:
-                        presc_buf = torch.empty(b * (ctx + kmax) * (prescribed[0, 0].numel()), device=dev, dtype=torch.float32)
-                    view = presc_buf[:presc.numel()].view(presc.shape)
-                    view.copy_(presc)
-                    presc = view
-            else:
-                presc = prescribed(s0, s0 + ctx + k)
-                _lib.require_cuda_tensor(presc, "prescribed(frame_begin, frame_end)")
-                if presc is None or presc.shape[0] != b or presc.shape[1] != ctx + k:
-                    raise _lib.DlwpError(f"rollout_chunks: prescribed({s0}, {s0 + ctx + k}) must give [{b}, {ctx + k}, Cp, ...], got "
-                                         f"{None if presc is None else tuple(presc.shape)}")
-                presc = presc.contiguous()
+            presc = frames_of_prescribed(s0, s0 + ctx + k)
             with torch.no_grad():           # not held across the yield: the consumer keeps its own grad mode
                 if into:
                     out = out_buf[:b * k * fsz].view(b, k, *frame)

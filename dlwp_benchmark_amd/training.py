@@ -1,8 +1,8 @@
 """The hot kernels under autograd (reference scripts/train.py:263-271 runs `loss.backward()` through the
 backbone): one autograd Function per kernel family, each with a HIP forward and a HIP backward, and the entry points the
 ops call when a gradient is wanted (`wants_grad`).  First the spectral convolution, then window and global attention,
-the AFNO filter, HEALPix padding, the cylinder / HEALPix 3x3 convolution, Conv2d and ConvTranspose2d, GroupNorm, Linear,
-MeshGraphNet and GraphCastNet.
+the AFNO filter, HEALPix padding, the cylinder / HEALPix 3x3 convolution, Conv2d and ConvTranspose2d, the ConvLSTM cell,
+GroupNorm, Linear, MeshGraphNet and GraphCastNet.
 
 Every family but the spectral one also has a torch form: the same operator in plain torch operators (a restatement of
 the reference arithmetic that imports nothing from the oracle).  Autograd of that form is the cross-check of the HIP
@@ -37,6 +37,7 @@ from typing import Optional, Sequence
 
 import torch
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import healpix as _hpx
 from . import lib as _lib
@@ -875,6 +876,75 @@ class _AvgPool2x2Fn(torch.autograd.Function):
 
 def avgpool2x2(x):
     return _AvgPool2x2Fn.apply(x)
+
+
+def convlstm_gates_torch(gates, c_prev):
+    """The ConvLSTM cell update (reference convlstm.py:96-109) with torch operators, on any device and dtype: (h, c) from
+    gates [B, 4*hid, H, W] = (netin, i, f, o) before their activations and c_prev [B, hid, H, W]."""
+    netin, ig, fg, og = torch.split(gates, gates.shape[1] // 4, dim=1)
+    c_new = torch.sigmoid(fg) * c_prev + torch.sigmoid(ig) * torch.tanh(netin)
+    return torch.sigmoid(og) * torch.tanh(c_new), c_new
+
+
+def convlstm_gates_backward_torch(gates, c_prev, dh, dc):
+    """The backward of convlstm_gates_torch from its inputs alone, as plain torch operators on any device and dtype: what
+    dlwp_convlstm_gates_bwd_f32 computes (csrc/convlstm_cell.hpp), term by term.  dh, dc: the gradients of h and c, either
+    None (zero).
+
+        si, sf, so = sigma(i), sigma(f), sigma(o)      tn = tanh(netin)     c = sf c_prev + si tn     tc = tanh(c)
+        dct      = dc + dh so (1 - tc^2)
+        d_o      = dh tc so (1 - so)          d_f = dct c_prev sf (1 - sf)
+        d_i      = dct tn si (1 - si)         d_netin = dct si (1 - tn^2)
+        dc_prev  = dct sf
+
+    Returns (dgates in the gate order of `gates`, dc_prev)."""
+    if dh is None and dc is None:
+        raise _lib.DlwpError("convlstm_gates_backward_torch: neither dh nor dc given")
+    netin, ig, fg, og = torch.split(gates, gates.shape[1] // 4, dim=1)
+    dh = torch.zeros_like(c_prev) if dh is None else dh
+    dc = torch.zeros_like(c_prev) if dc is None else dc
+    si, sf, so, tn = torch.sigmoid(ig), torch.sigmoid(fg), torch.sigmoid(og), torch.tanh(netin)
+    tc = torch.tanh(sf * c_prev + si * tn)
+    dct = dc + dh * so * (1.0 - tc * tc)
+    d_o = dh * tc * so * (1.0 - so)
+    d_f = dct * c_prev * sf * (1.0 - sf)
+    d_i = dct * tn * si * (1.0 - si)
+    d_n = dct * si * (1.0 - tn * tn)
+    return torch.cat([d_n, d_i, d_f, d_o], dim=1), dct * sf
+
+
+class _ConvLstmGatesFn(torch.autograd.Function):
+    """The ConvLSTM cell update on HIP in both directions: dlwp_convlstm_gates_f32 (the inference kernel: h and c bit for bit
+    what eval() computes) and dlwp_convlstm_gates_bwd_f32.  Saved for the backward: gates and c_prev, the forward's inputs --
+    no activated plane (the torch chain keeps six per cell and frame).  A gradient autograd does not have (the last frame's
+    c) stays None and reaches the kernel as a null pointer; dc_prev is not computed where c_prev takes no gradient (the first
+    frame's state is a constant zero)."""
+
+    @staticmethod
+    def forward(ctx, gates, c_prev):
+        gates, c_prev = gates.contiguous(), c_prev.contiguous()
+        ctx.save_for_backward(gates, c_prev)
+        ctx.set_materialize_grads(False)
+        with torch.no_grad():
+            return ops.convlstm_gates(gates.detach(), c_prev.detach())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dh, dc):
+        gates, c_prev = ctx.saved_tensors
+        need_g, need_c = ctx.needs_input_grad
+        if (dh is None and dc is None) or not (need_g or need_c):
+            return None, None
+        dgates, dc_prev = ops.convlstm_gates_backward(gates, c_prev, dh, dc, need_c_prev=need_c)
+        return (dgates if need_g else None), dc_prev
+
+
+def convlstm_gates(gates, c_prev):
+    """differentiable ConvLSTM cell update (h, c): HIP forward and HIP backward; under DLWP_TRAIN_TORCH_BACKWARD=1, and for
+    tensors that are not fp32 on the GPU, convlstm_gates_torch, left to autograd"""
+    if _torch_backward_selected() or not (gates.is_cuda and gates.dtype == torch.float32 and c_prev.dtype == torch.float32):
+        return convlstm_gates_torch(gates, c_prev)
+    return _ConvLstmGatesFn.apply(gates, c_prev)
 
 
 def groupnorm_act_backward_torch(x, mean, rstd, gamma, beta, gy, groups: int, act: int):

@@ -671,6 +671,21 @@ int32_t dlwp_convlstm_gates_f32(const float* gates_dev, const float* c_prev_dev,
                                 float* c_out_dev, int32_t batch, int32_t hidden, int32_t height,
                                 int32_t width, void* stream);
 
+/* Backward of dlwp_convlstm_gates_f32 (csrc/convlstm_bwd.hip; the forward it differentiates: models/convlstm/convlstm.py:96-109,
+ * under scripts/train.py:271).  From the forward's INPUTS alone -- gates_dev [B, 4*hidden, H, W] (netin, igate, fgate, ogate,
+ * pre-activation) and c_prev_dev [B, hidden, H, W]; the activations, c and tanh(c) are recomputed with the forward's arithmetic:
+ *   si, sf, so = sigma(i), sigma(f), sigma(o)     tn = tanh(netin)     c = sf c_prev + si tn     tc = tanh(c)
+ *   dct = dc + dh so (1 - tc^2)
+ *   d_o = dh tc so (1 - so)     d_f = dct c_prev sf (1 - sf)     d_i = dct tn si (1 - si)     d_netin = dct si (1 - tn^2)
+ *   dc_prev = dct sf
+ * dh_dev, dc_dev [B, hidden, H, W]: the gradients of h_out and c_out; either may be NULL (a zero gradient, not read; results are
+ * those of a zero tensor bit for bit), both NULL is DLWP_ERR_INVALID_ARGUMENT.  dgates_dev [B, 4*hidden, H, W]: every element
+ * written; dc_prev_dev [B, hidden, H, W] or NULL (not wanted, not stored).  Outputs may not alias inputs or each other.  One
+ * launch on `stream`, one writer per element, no atomics, no workspace: reruns are bitwise identical. */
+int32_t dlwp_convlstm_gates_bwd_f32(const float* gates_dev, const float* c_prev_dev, const float* dh_dev, const float* dc_dev,
+                                    float* dgates_dev, float* dc_prev_dev, int32_t batch, int32_t hidden, int32_t height,
+                                    int32_t width, void* stream);
+
 /* LayerNorm over the last dimension of a token-major tensor x_dev [rows, channels] (channels % 4 == 0,
  * <= 2048): y = (x - mean) * rsqrt(var + eps) * gamma + beta, biased variance (torch.nn.LayerNorm).
  * Reference call sites: models/fourcastnet/fourcastnet.py:180-193, models/swintransformer/

@@ -297,6 +297,16 @@ SIGNATURES = {
                                                  c_void_p]),
     "dlwp_ddpm_step_members_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int32, c_int32,
                                              POINTER(ctypes.c_double), ctypes.c_int64, ctypes.c_int64, c_void_p]),
+    "dlwp_dataset_grid_blocks": (c_int32, []),
+    "dlwp_dataset_gather_f32": (c_int32, [c_void_p, ctypes.c_int64, c_int32, ctypes.c_int64, c_void_p, c_void_p, c_int32, c_int32,
+                                          c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
+                                          c_float, ctypes.c_int64, ctypes.c_int64, c_void_p]),
+    "dlwp_dataset_stats_workspace_bytes": (c_size_t, [c_int32]),
+    "dlwp_dataset_stats_f64": (c_int32, [c_void_p, ctypes.c_int64, c_int32, ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p,
+                                         c_void_p, c_size_t, c_void_p]),
+    "dlwp_dataset_group_mean_f32": (c_int32, [c_void_p, ctypes.c_int64, c_int32, ctypes.c_int64, c_void_p, c_void_p,
+                                              ctypes.c_int64, c_int32, c_void_p, c_void_p]),
+    "dlwp_coarsen_mean_f32": (c_int32, [c_void_p, c_void_p, ctypes.c_int64, c_int32, c_int32, c_int32, c_void_p]),
 }
 
 _lib = None

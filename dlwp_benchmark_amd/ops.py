@@ -2368,3 +2368,122 @@ def refiner_pair(prognostic: torch.Tensor, target: torch.Tensor, context_size: i
     _lib.launch("dlwp_refiner_pair_f32", target.device, target, frame, noise, y_noised, v_target, b, faces, c, plane, t_bs, p_bs,
                 float(sqrt_abar), float(sqrt_1m_abar), _i64(seed), _noise_offset(offset))
     return y_noised, v_target
+
+
+# ---- the device-resident dataset (csrc/dataset.hip; data.DeviceWeatherDataset drives these) ------------------------------------
+def dataset_grid_blocks() -> int:
+    """workgroups of a full grid of the dataset kernels: above it (in tiles of 1024 plane elements) the strided loop runs"""
+    return int(_lib.load().dlwp_dataset_grid_blocks())
+
+
+def _dataset_store(store: torch.Tensor, what: str):
+    _lib.require_cuda_tensor(store, "store")
+    if store.dim() != 3 or not store.is_contiguous() or store.numel() == 0:
+        raise _lib.DlwpError(f"{what}: the store must be a contiguous, non-empty [T, V, plane] tensor (got {tuple(store.shape)})")
+    return int(store.shape[0]), int(store.shape[1]), int(store.shape[2])
+
+
+def _dataset_int32(t: torch.Tensor, shape, device, name: str, what: str):
+    if not isinstance(t, torch.Tensor) or t.device != device or t.dtype != torch.int32 or not t.is_contiguous() \
+            or tuple(t.shape) != tuple(shape):
+        raise _lib.DlwpError(f"{what}: {name} must be a contiguous int32 tensor {tuple(shape)} on the store's device")
+    return t
+
+
+def _dataset_out(out, shape, device, name: str, what: str):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    _lib.require_cuda_tensor(out, name)
+    if tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != device:
+        raise _lib.DlwpError(f"{what}: {name} must be a contiguous float32 tensor {tuple(shape)} on the store's device "
+                             f"(got {tuple(out.shape)})")
+    return out
+
+
+def dataset_gather(store: torch.Tensor, frames: torch.Tensor, prog_table: Optional[torch.Tensor],
+                   pres_table: Optional[torch.Tensor], context: int, normalize: bool, noise: float = 0.0,
+                   items: Optional[torch.Tensor] = None, seed: int = 0, offset: int = 0, prescribed: Optional[torch.Tensor] = None,
+                   prognostic: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None,
+                   want_prognostic: bool = True, want_target: bool = True):
+    """One batch from the resident store in one launch (dlwp_dataset_gather_f32; the reference: WeatherBenchDataset.__getitem__ +
+    default_collate, data/datasets/datasets.py:330-416).  store [T, V, plane] float32; frames int32 [B, S + 1] store time indices
+    (-1: no such frame); the channel tables int32 [n, 4] = {source variable, mean bits, std bits, NaN-fill flag} (None: no such
+    channels); items int32 [B] (the noise member of each sample; needed with noise != 0).  Returns (prescribed [B, S, P, plane] or
+    None, prognostic [B, S, C, plane] or None, target [B, S - context, C, plane] or None); the three may be caller-supplied
+    contiguous buffers.  Everything is read from device memory when the launch executes."""
+    what = "dataset_gather"
+    n_times, n_vars, plane = _dataset_store(store, what)
+    dev = store.device
+    if not isinstance(frames, torch.Tensor) or frames.dim() != 2 or frames.shape[1] < 2 or frames.shape[0] < 1:
+        raise _lib.DlwpError(f"{what}: frames must be [B, S + 1] with S >= 1")
+    b, s = int(frames.shape[0]), int(frames.shape[1]) - 1
+    _dataset_int32(frames, (b, s + 1), dev, "frames", what)
+    context = int(context)
+    if not 0 <= context <= s:
+        raise _lib.DlwpError(f"{what}: context {context} outside [0, {s}]")
+    c = int(prog_table.shape[0]) if prog_table is not None else 0
+    p = int(pres_table.shape[0]) if pres_table is not None else 0
+    if c:
+        _dataset_int32(prog_table, (c, 4), dev, "prog_table", what)
+    if p:
+        _dataset_int32(pres_table, (p, 4), dev, "pres_table", what)
+    noise = float(noise)
+    if noise != 0.0 and c and want_prognostic:
+        if items is None:
+            raise _lib.DlwpError(f"{what}: noise needs the dataset item of every sample")
+        _dataset_int32(items, (b,), dev, "items", what)
+    pres = _dataset_out(prescribed, (b, s, p, plane), dev, "prescribed", what) if p else None
+    prog = _dataset_out(prognostic, (b, s, c, plane), dev, "prognostic", what) if c and want_prognostic else None
+    tar = _dataset_out(target, (b, s - context, c, plane), dev, "target", what) if c and want_target and context < s else None
+    if pres is None and prog is None and tar is None:
+        return None, None, None
+    _lib.launch("dlwp_dataset_gather_f32", dev, store, n_times, n_vars, plane, frames, items if noise != 0.0 else None, b, s,
+                context, prog_table if c else None, c, pres_table if p else None, p, pres, prog, tar, int(bool(normalize)),
+                noise, _i64(seed), _noise_offset(offset))
+    return pres, prog, tar
+
+
+def dataset_stats(store: torch.Tensor, frames: torch.Tensor) -> torch.Tensor:
+    """float64 [V, 3] = {count of non-NaN values, their sum, the sum of squared deviations from sum / count} per variable over
+    the listed frames (dlwp_dataset_stats_f64; the reference: compute_statistics, datasets.py:419-453).  Repeated calls give the
+    same bits."""
+    what = "dataset_stats"
+    n_times, n_vars, plane = _dataset_store(store, what)
+    if not isinstance(frames, torch.Tensor) or frames.dim() != 1 or frames.numel() == 0:
+        raise _lib.DlwpError(f"{what}: frames must be a non-empty list of time indices")
+    _dataset_int32(frames, (frames.numel(),), store.device, "frames", what)
+    out = torch.empty((n_vars, 3), dtype=torch.float64, device=store.device)
+    nbytes = int(_lib.load().dlwp_dataset_stats_workspace_bytes(n_vars))
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=store.device)
+    _lib.launch("dlwp_dataset_stats_f64", store.device, store, n_times, n_vars, plane, frames, frames.numel(), out, ws, nbytes)
+    return out
+
+
+def dataset_group_mean(store: torch.Tensor, frames: torch.Tensor, groups: torch.Tensor, n_groups: int) -> torch.Tensor:
+    """[G, V, plane]: the mean of the non-NaN values of every group of frames (dlwp_dataset_group_mean_f32; the reference:
+    groupby(time.dt.month).mean(), climatology.py:41), NaN where a group has none.  groups int32 per listed frame; a value
+    outside [0, G) skips the frame."""
+    what = "dataset_group_mean"
+    n_times, n_vars, plane = _dataset_store(store, what)
+    if not isinstance(frames, torch.Tensor) or frames.dim() != 1 or frames.numel() == 0 or int(n_groups) < 1:
+        raise _lib.DlwpError(f"{what}: frames must be a non-empty list of time indices and n_groups >= 1")
+    _dataset_int32(frames, (frames.numel(),), store.device, "frames", what)
+    _dataset_int32(groups, (frames.numel(),), store.device, "groups", what)
+    out = torch.empty((int(n_groups), n_vars, plane), dtype=torch.float32, device=store.device)
+    _lib.launch("dlwp_dataset_group_mean_f32", store.device, store, n_times, n_vars, plane, frames, groups, frames.numel(),
+                int(n_groups), out)
+    return out
+
+
+def coarsen_mean(x: torch.Tensor, k: int) -> torch.Tensor:
+    """k x k block means over the last two dimensions, NaN skipped (dlwp_coarsen_mean_f32; the reference:
+    ds.coarsen(lat=k, lon=k).mean(), datasets.py:303-305).  Both dimensions must be multiples of k."""
+    _lib.require_cuda_tensor(x, "x")
+    k = int(k)
+    if x.dim() < 2 or x.numel() == 0 or k < 1 or x.shape[-2] % k or x.shape[-1] % k:
+        raise _lib.DlwpError(f"coarsen_mean: the last two dimensions of {tuple(x.shape)} must be multiples of k = {k}")
+    x = x.contiguous()
+    h, w = int(x.shape[-2]), int(x.shape[-1])
+    out = torch.empty(tuple(x.shape[:-2]) + (h // k, w // k), dtype=torch.float32, device=x.device)
+    _lib.launch("dlwp_coarsen_mean_f32", x.device, x, out, x.numel() // (h * w), h, w, k)
+    return out

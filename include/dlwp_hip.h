@@ -1246,6 +1246,56 @@ int32_t dlwp_ddpm_step_members_f32(const float* sample_dev, const float* model_o
                                    float* out_dev, int64_t n_per_member, int32_t members, int32_t first_member,
                                    const double coef[4], int64_t seed, int64_t offset, void* stream);
 
+/* The device-resident WeatherBench dataset (csrc/dataset.hip; data.DeviceWeatherDataset drives these).  The fields are ONE
+ * float32 store_dev [n_times, n_vars, plane], contiguous: time first, variables with levels flattened into n_vars by the host,
+ * plane = H W on a lat-lon grid and 12 n n on HEALPix.  The store may hold more than 2^31 elements: every offset into it is
+ * 64-bit; a time index is an int32.  256 threads per workgroup, a thread per 4 consecutive plane elements, a workgroup per tile
+ * of 256 such units of one plane, the grid capped at dlwp_dataset_grid_blocks() workgroups and strided above; 16-byte accesses
+ * where plane % 4 == 0 and the pointer in question is 16-byte aligned, 4-byte ones of the same elements otherwise.  No atomics;
+ * no entry point allocates, synchronises or reads a device value on the host.  A frame index outside [0, n_times) is never
+ * dereferenced. */
+int32_t dlwp_dataset_grid_blocks(void);
+/* One batch of WeatherBenchDataset.__getitem__ + default_collate (reference data/datasets/datasets.py:330-416) in one launch.
+ *   frames_dev      int32 [batch, seq + 1]: the store time index of every frame of every window, -1 = no such frame
+ *   items_dev       int32 [batch]: the dataset item of every sample = the member of its noise stream; read only with noise != 0
+ *   *_table_dev     int32 [n, 4], 16-byte aligned: {source variable, mean as fp32 bits, std as fp32 bits, replace-NaN-by-0 flag}
+ *   prescribed_dev  [batch, seq, n_pres, plane]            = frames 0 .. seq - 1 (:345, :371, :375); may be null
+ *   prognostic_dev  [batch, seq, n_prog, plane]            = frames 0 .. seq - 1, plus noise eps (:384-403, :414); may be null
+ *   target_dev      [batch, seq - context, n_prog, plane]  = frames 1 + context .. seq, never noised (:413, :416); may be null
+ * A value is (x - mean) / std with two correctly rounded fp32 operations when `normalize` (else x), then 0 where it is NaN and
+ * the channel's flag is set (:397, :401); a frame -1 is zeros (:405-409).  Frame j of a window is loaded ONCE and serves
+ * prognostic[:, j] and target[:, j - 1 - context]; a frame no output asks for is not loaded.  eps for sample b is the member
+ * stream (seed, member = items_dev[b], offset) of dlwp_philox_normal_members_f32 over the sample's own [seq, n_prog, plane]
+ * elements, evaluated in the kernel: prognostic = x + noise eps (an fp32 product, then an fp32 sum).  All pointers are device
+ * memory read at execution time: a recorded launch follows a frame table that is overwritten in place. */
+int32_t dlwp_dataset_gather_f32(const float* store_dev, int64_t n_times, int32_t n_vars, int64_t plane,
+                                const int32_t* frames_dev, const int32_t* items_dev, int32_t batch, int32_t seq,
+                                int32_t context, const int32_t* prog_table_dev, int32_t n_prog, const int32_t* pres_table_dev,
+                                int32_t n_pres, float* prescribed_dev, float* prognostic_dev, float* target_dev,
+                                int32_t normalize, float noise, int64_t seed, int64_t offset, void* stream);
+/* compute_statistics (datasets.py:419-453; xarray's .mean() / .std() skip NaN, .std() has ddof 0) over the frames
+ * frames_dev int32 [n_frames] (the used times after the timedelta stride, :291).  out_dev double [n_vars, 3] = {count of non-NaN
+ * values, their sum, the sum of squared deviations from sum / count}: mean = sum / count and std = sqrt(ssd / count) are the
+ * caller's.  Two passes over the resident store, four launches on `stream`; every add is fp64, each pass writes 128 workgroup
+ * partials per variable into the workspace and one thread adds them in workgroup order: repeated calls give the same bits. */
+size_t dlwp_dataset_stats_workspace_bytes(int32_t n_vars);
+int32_t dlwp_dataset_stats_f64(const float* store_dev, int64_t n_times, int32_t n_vars, int64_t plane, const int32_t* frames_dev,
+                               int64_t n_frames, double* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* groupby(...).mean() over time (the monthly climatology of climatology.py:41 and scripts/build_baselines.py:64).
+ * groups_dev int32 [n_frames]: the group 0 .. n_groups - 1 of every listed frame, any other value = skip.
+ * out_dev [n_groups, n_vars, plane]: the mean of the group's non-NaN values per element, summed in fp64 in list order by the one
+ * thread that owns the element, divided in fp64 and rounded to fp32 once; NaN where the group has no value.  Each stored value
+ * of a listed frame is read once. */
+int32_t dlwp_dataset_group_mean_f32(const float* store_dev, int64_t n_times, int32_t n_vars, int64_t plane,
+                                    const int32_t* frames_dev, const int32_t* groups_dev, int64_t n_frames, int32_t n_groups,
+                                    float* out_dev, void* stream);
+/* ds.coarsen(lat=k, lon=k).mean() (datasets.py:303-305): in_dev [planes, height, width] -> out_dev [planes, height / k,
+ * width / k], the mean of the non-NaN values of each k x k block (NaN for a block without one), summed in fp64 in row-major
+ * block order and rounded to fp32 once.  height and width must be multiples of k (xarray's boundary="exact").  16-byte accesses
+ * for k = 2, 4 where width / k % 4 == 0 and both pointers are 16-byte aligned. */
+int32_t dlwp_coarsen_mean_f32(const float* in_dev, float* out_dev, int64_t planes, int32_t height, int32_t width, int32_t k,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

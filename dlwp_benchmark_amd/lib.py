@@ -307,6 +307,12 @@ SIGNATURES = {
     "dlwp_dataset_group_mean_f32": (c_int32, [c_void_p, ctypes.c_int64, c_int32, ctypes.c_int64, c_void_p, c_void_p,
                                               ctypes.c_int64, c_int32, c_void_p, c_void_p]),
     "dlwp_coarsen_mean_f32": (c_int32, [c_void_p, c_void_p, ctypes.c_int64, c_int32, c_int32, c_int32, c_void_p]),
+    # spherical harmonic transforms + Driscoll-Healy channel mix (csrc/sht.hip)
+    "dlwp_sht_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "dlwp_isht_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "dlwp_sph_mix_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "dlwp_sph_mix_packed_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "dlwp_sph_mix_pack_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
 }
 
 _lib = None

@@ -9,6 +9,7 @@ as `models` or import from here directly.
 from .fno import FNO2DModule, TFNO2DModule
 from .fourcastnet import AFNONet, FourCastNet
 from .pangu import PanguWeather
+from .sfno import SFNO2DModule
 from .spectral import SpectralConv2d
 from .swin import SwinTransformer, SwinTransformerHPX
 from .diffusion import DiffModernUNet, DiffMUNetHPX
@@ -16,5 +17,5 @@ from .graphcast import GraphCastNet
 from .mgn import MeshGraphNet
 from .unet import ConvLSTM, ConvLSTMHPX, HEALPixLayer, HEALPixPadding, ModernUNet, MUNetHPX, UNet, UNetHPX
 
-__all__ = ["DiffModernUNet", "DiffMUNetHPX", "FNO2DModule", "TFNO2DModule", "ConvLSTMHPX", "ModernUNet", "FourCastNet", "AFNONet", "GraphCastNet", "MeshGraphNet", "PanguWeather", "SpectralConv2d", "SwinTransformer", "SwinTransformerHPX", "UNet",
+__all__ = ["DiffModernUNet", "DiffMUNetHPX", "FNO2DModule", "TFNO2DModule", "SFNO2DModule", "ConvLSTMHPX", "ModernUNet", "FourCastNet", "AFNONet", "GraphCastNet", "MeshGraphNet", "PanguWeather", "SpectralConv2d", "SwinTransformer", "SwinTransformerHPX", "UNet",
            "UNetHPX", "MUNetHPX", "ConvLSTM", "HEALPixPadding", "HEALPixLayer"]

@@ -2487,3 +2487,103 @@ def coarsen_mean(x: torch.Tensor, k: int) -> torch.Tensor:
     out = torch.empty(tuple(x.shape[:-2]) + (h // k, w // k), dtype=torch.float32, device=x.device)
     _lib.launch("dlwp_coarsen_mean_f32", x.device, x, out, x.numel() // (h * w), h, w, k)
     return out
+
+
+# ---- spherical harmonic transforms and the Driscoll-Healy channel mix (csrc/sht.hip; host tables: sphere.py) -----------------
+def _complex_pairs(c: torch.Tensor, name: str) -> torch.Tensor:
+    """the contiguous float32 [..., 2] buffer behind a complex64 tensor (what the kernels take)"""
+    if not isinstance(c, torch.Tensor) or c.dtype != torch.complex64:
+        raise _lib.DlwpError(f"{name} must be a complex64 tensor (got {getattr(c, 'dtype', type(c))})")
+    pairs = torch.view_as_real(c.contiguous())
+    _lib.require_cuda_tensor(pairs, name)
+    return pairs
+
+
+def sht(x: torch.Tensor, grid: str = "legendre-gauss", lmax: Optional[int] = None, mmax: Optional[int] = None) -> torch.Tensor:
+    """Real spherical harmonic transform of fields [..., nlat, nlon] on `grid` ("legendre-gauss" or "equiangular", row 0 the
+    northernmost latitude) -> complex64 [..., lmax, mmax], orthonormal with the Condon-Shortley phase (the conventions of
+    sphere.py; dlwp_sht_f32).  lmax defaults to nlat, mmax to min(lmax, nlon / 2 + 1).  Entries with l < m are zero.  With a
+    gradient wanted the same kernel runs inside training.sht, whose backward differentiates training.sht_torch."""
+    from . import sphere as _sph
+
+    _lib.require_cuda_tensor(x, "x")
+    if x.dim() < 2:
+        raise _lib.DlwpError(f"sht: expected fields [..., nlat, nlon], got shape {tuple(x.shape)}")
+    nlat, nlon = int(x.shape[-2]), int(x.shape[-1])
+    lmax = nlat if lmax is None else int(lmax)
+    mmax = min(lmax, nlon // 2 + 1) if mmax is None else int(mmax)
+    tab = _sph.device_tables(grid, nlat, nlon, lmax, mmax, x.device)
+    from . import training as _T
+    if _T.wants_grad(x):
+        return _T.sht(x, tab)
+    lead = tuple(x.shape[:-2])
+    planes = math.prod(lead)
+    out = torch.empty(lead + (lmax, mmax, 2), device=x.device, dtype=torch.float32)
+    if planes:
+        _lib.launch("dlwp_sht_f32", x.device, x.contiguous(), tab.wleg, tab.tw, out, planes, nlat, nlon, lmax, mmax)
+    return torch.view_as_complex(out)
+
+
+def isht(c: torch.Tensor, grid: str, nlat: int, nlon: int) -> torch.Tensor:
+    """The inverse of `sht`: complex64 coefficients [..., lmax, mmax] -> fields [..., nlat, nlon] on `grid` (dlwp_isht_f32).
+    Entries with l < m are not read; the imaginary parts of m = 0 and m = nlon / 2 are ignored, as irfft ignores them."""
+    from . import sphere as _sph
+
+    pairs = _complex_pairs(c, "c")
+    if c.dim() < 2:
+        raise _lib.DlwpError(f"isht: expected coefficients [..., lmax, mmax], got shape {tuple(c.shape)}")
+    lmax, mmax = int(c.shape[-2]), int(c.shape[-1])
+    nlat, nlon = int(nlat), int(nlon)
+    tab = _sph.device_tables(grid, nlat, nlon, lmax, mmax, c.device)
+    from . import training as _T
+    if _T.wants_grad(c):
+        return _T.isht(c, tab)
+    lead = tuple(c.shape[:-2])
+    planes = math.prod(lead)
+    out = torch.empty(lead + (nlat, nlon), device=c.device, dtype=torch.float32)
+    if planes:
+        _lib.launch("dlwp_isht_f32", c.device, pairs, tab.leg, tab.tw, out, planes, nlat, nlon, lmax, mmax)
+    return out
+
+
+class SphMixWeights:
+    """A Driscoll-Healy weight ([cin, cout, lmax, 2] pairs) re-laid degree-major, [lmax, cin, cout, 2], the layout
+    dlwp_sph_mix_packed_f32 reads in long runs; re-packed on the device whenever the source has been written to -- the derivation
+    rule of ConvWeights, with the same rule for graph captures."""
+
+    def __init__(self):
+        self._derived = Derived(eager_only="sph_mix")
+
+    @staticmethod
+    def pack(pairs: torch.Tensor) -> torch.Tensor:
+        ci, co, lmax = (int(s) for s in pairs.shape[:3])
+        buf = torch.empty(lmax, ci, co, 2, dtype=torch.float32, device=pairs.device)
+        _lib.launch("dlwp_sph_mix_pack_f32", pairs.device, pairs, buf, ci, co, lmax)
+        return buf
+
+    def get(self, owner: torch.Tensor, pairs: torch.Tensor) -> torch.Tensor:
+        return self._derived.get(source_key(owner), lambda: self.pack(pairs))
+
+
+def sph_mix(c: torch.Tensor, weight: torch.Tensor, owner: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Driscoll-Healy spectral convolution: out[b, o, l, m] = sum_i c[b, i, l, m] * weight[i, o, l] for m <= l, zero above the
+    diagonal whatever c holds there.  c complex64 [B, Ci, lmax, mmax], weight complex64 [Ci, Co, lmax].  `owner`: the tensor the
+    caller keeps alive that `weight` is (a view of) -- a module's Parameter; with it the degree-major pack of the weight is cached
+    on that tensor (SphMixWeights) and dlwp_sph_mix_packed_f32 runs, the fast form; without it dlwp_sph_mix_f32 reads the weight as
+    it lies.  Both give the same bits.  With a gradient wanted: training.sph_mix."""
+    cp, wp = _complex_pairs(c, "c"), _complex_pairs(weight, "weight")
+    if c.dim() != 4 or weight.dim() != 3 or weight.shape[0] != c.shape[1] or weight.shape[2] != c.shape[2]:
+        raise _lib.DlwpError(f"sph_mix: c {tuple(c.shape)} [B, Ci, lmax, mmax] and weight {tuple(weight.shape)} [Ci, Co, lmax] "
+                             "do not match")
+    from . import training as _T
+    if _T.wants_grad(c, weight):
+        return _T.sph_mix(c, weight)
+    b, ci, lmax, mmax = (int(s) for s in c.shape)
+    co = int(weight.shape[1])
+    out = torch.empty(b, co, lmax, mmax, 2, device=c.device, dtype=torch.float32)
+    if b and owner is not None:
+        packed = derived_for(owner, "sph_mix", SphMixWeights).get(owner, wp)
+        _lib.launch("dlwp_sph_mix_packed_f32", c.device, cp, packed, out, b, ci, co, lmax, mmax)
+    elif b:
+        _lib.launch("dlwp_sph_mix_f32", c.device, cp, wp, out, b, ci, co, lmax, mmax)
+    return torch.view_as_complex(out)

@@ -32,6 +32,7 @@ the GPU in training mode.
 """
 import ctypes
 import functools
+import math
 import os
 from typing import Optional, Sequence
 
@@ -1547,3 +1548,100 @@ def mse_loss(x, target, weight=None):
     if target.requires_grad or (weight is not None and weight.requires_grad):
         raise _lib.DlwpError("mse_loss: only the input can require a gradient")
     return _MseLossFn.apply(x, target, weight)
+
+
+# ---- spherical harmonic transforms and the Driscoll-Healy mix (models/sfno.py; csrc/sht.hip forward) -------------------------
+# HIP backward kernels for these three are out of scope: the backward of each Function differentiates
+# the torch form beside it, which computes the same thing from the SAME fp32 device tables (sphere.device_tables).
+def _real_einsum_complex(eq: str, table: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
+    """einsum of a real table with a complex tensor, part by part (einsum wants one dtype)"""
+    return torch.complex(torch.einsum(eq, table, z.real), torch.einsum(eq, table, z.imag))
+
+
+def sht_torch(x: torch.Tensor, tab) -> torch.Tensor:
+    """what dlwp_sht_f32 computes, with torch operators: 2 pi rfft(norm="forward")[..., :mmax], then the contraction over
+    latitude with tab.wleg [nlat, lmax, mmax]"""
+    xf = torch.fft.rfft(x, dim=-1, norm="forward")[..., :tab.mmax] * (2.0 * math.pi)
+    return _real_einsum_complex("klm,...km->...lm", tab.wleg, xf)
+
+
+def isht_torch(c: torch.Tensor, tab) -> torch.Tensor:
+    """what dlwp_isht_f32 computes: the contraction over l >= m with tab.leg [lmax, nlat, mmax] (the other triangle of c is
+    masked out, not multiplied by the table's zeros), the imaginary parts of m = 0 and m = nlon / 2 dropped,
+    irfft(n=nlon, norm="forward")"""
+    lmax, mmax, nlon = tab.lmax, tab.mmax, tab.nlon
+    keep = torch.ones(lmax, mmax, device=c.device).tril().bool()
+    xf = _real_einsum_complex("lkm,...lm->...km", tab.leg, torch.where(keep, c, torch.zeros((), dtype=c.dtype, device=c.device)))
+    real_only = torch.zeros(mmax, dtype=torch.bool, device=c.device)
+    real_only[0] = True
+    if nlon // 2 < mmax:
+        real_only[nlon // 2] = True
+    xf = torch.complex(xf.real, torch.where(real_only, torch.zeros((), device=c.device), xf.imag))
+    if mmax < nlon // 2 + 1:        # the columns m >= mmax are zero
+        xf = torch.cat([xf, torch.zeros(*xf.shape[:-1], nlon // 2 + 1 - mmax, dtype=xf.dtype, device=xf.device)], dim=-1)
+    return torch.fft.irfft(xf, n=nlon, dim=-1, norm="forward")
+
+
+def sph_mix_torch(c: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """what dlwp_sph_mix_f32 computes: einsum over the input channels per degree, entries above the diagonal (m > l) neither
+    read nor written (zero)"""
+    keep = torch.ones(c.shape[-2], c.shape[-1], device=c.device).tril().bool()
+    zero = torch.zeros((), dtype=c.dtype, device=c.device)
+    return torch.where(keep, torch.einsum("bilm,iol->bolm", torch.where(keep, c, zero), weight), zero)
+
+
+class _ShtFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, tab):
+        ctx.tab = tab
+        ctx.save_for_backward(x)
+        with torch.no_grad():
+            return ops.sht(x.detach(), tab.grid, tab.lmax, tab.mmax)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (x,) = ctx.saved_tensors
+        g, = _grad_of_torch_form(lambda t: sht_torch(t, ctx.tab), (x,), (True,), grad_out)
+        return g, None
+
+
+class _IshtFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, c, tab):
+        ctx.tab = tab
+        ctx.save_for_backward(c)
+        with torch.no_grad():
+            return ops.isht(c.detach(), tab.grid, tab.nlat, tab.nlon)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (c,) = ctx.saved_tensors
+        g, = _grad_of_torch_form(lambda t: isht_torch(t, ctx.tab), (c,), (True,), grad_out)
+        return g, None
+
+
+class _SphMixFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, c, weight):
+        ctx.save_for_backward(c, weight)
+        with torch.no_grad():
+            return ops.sph_mix(c.detach(), weight.detach())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return tuple(_grad_of_torch_form(sph_mix_torch, ctx.saved_tensors, ctx.needs_input_grad, grad_out))
+
+
+def sht(x, tab):
+    """differentiable ops.sht: HIP forward, backward by autograd of sht_torch"""
+    return _ShtFn.apply(x, tab)
+
+
+def isht(c, tab):
+    """differentiable ops.isht: HIP forward, backward by autograd of isht_torch"""
+    return _IshtFn.apply(c, tab)
+
+
+def sph_mix(c, weight):
+    """differentiable ops.sph_mix: HIP forward, backward by autograd of sph_mix_torch"""
+    return _SphMixFn.apply(c, weight)

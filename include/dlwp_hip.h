@@ -1296,6 +1296,40 @@ int32_t dlwp_dataset_group_mean_f32(const float* store_dev, int64_t n_times, int
 int32_t dlwp_coarsen_mean_f32(const float* in_dev, float* out_dev, int64_t planes, int32_t height, int32_t width, int32_t k,
                               void* stream);
 
+/* Real spherical harmonic transforms and the per-degree channel mix of the SFNO backbone (csrc/sht.hip; the reference reaches
+ * them through torch_harmonics from models/fno/fno.py:183-200 -- PARITY UNPINNED, the conventions are those of
+ * dlwp_benchmark_amd/sphere.py and DESIGN.md section 35).  All tables are fp32, made on the host (sphere.device_tables):
+ *   wleg_dev [nlat][lmax][mmax] = P[m, l, k] w_k,  leg_dev [lmax][nlat][mmax] = P[m, l, k]  (zero for l < m, never read there),
+ *   tw_dev [nlon][2] = (cos, -sin)(2 pi t / nlon), indexed by (j m) mod nlon: no transcendental runs on the device.
+ * Envelope: 2 <= nlat <= 256, 2 <= nlon <= 512 and even, 1 <= lmax <= nlat, 1 <= mmax <= nlon / 2 + 1, planes >= 1 (64-bit);
+ * DLWP_ERR_UNSUPPORTED outside it.  One launch each on `stream`, fixed summation order, no atomics: a call repeated gives the
+ * same bits.  Outputs may not alias inputs.
+ *
+ * dlwp_sht_f32:   x_dev [planes, nlat, nlon] -> coeffs_dev [planes, lmax, mmax, 2] (re, im):
+ *   X[k][m] = (2 pi / nlon) sum_j x[k][j] tw[(j m) mod nlon],   c[l][m] = sum_k wleg[k][l][m] X[k][m]   (l >= m; zero below)
+ * dlwp_isht_f32:  coeffs_dev [planes, lmax, mmax, 2] -> y_dev [planes, nlat, nlon]:
+ *   X[k][m] = f_m sum_{l >= m} leg[l][k][m] c[l][m]  with f_m = 1 for m = 0 and m = nlon / 2 (imaginary part dropped), else 2,
+ *   y[k][j] = sum_m Re(X[k][m]) tw[(j m) mod nlon].re + Im(X[k][m]) tw[(j m) mod nlon].im   -- irfft(n = nlon, norm = "forward")
+ *   Entries of coeffs_dev with l < m are not read. */
+int32_t dlwp_sht_f32(const float* x_dev, const float* wleg_dev, const float* tw_dev, float* coeffs_dev, int64_t planes,
+                     int32_t nlat, int32_t nlon, int32_t lmax, int32_t mmax, void* stream);
+int32_t dlwp_isht_f32(const float* coeffs_dev, const float* leg_dev, const float* tw_dev, float* y_dev, int64_t planes,
+                      int32_t nlat, int32_t nlon, int32_t lmax, int32_t mmax, void* stream);
+/* Driscoll-Healy spectral convolution: c_out[b][o][l][m] = sum_i c_in[b][i][l][m] * weight[i][o][l] (complex) for
+ * m <= min(l, mmax - 1); every other entry of c_out is written as zero and no entry of c_in with m > l is read.
+ *   c_in_dev [batch, cin, lmax, mmax, 2], weight_dev [cin, cout, lmax, 2], c_out_dev [batch, cout, lmax, mmax, 2].
+ * Per degree l a complex GEMM with rows (b, m <= l), K = cin, N = cout on the exact-fp32 matrix instruction
+ * (v_mfma_f32_16x16x4_f32), products summed in the order i = 0, 1, ...  Any batch, cin, cout >= 1 with batch * mmax < 2^24,
+ * 1 <= lmax, mmax <= 1024. */
+int32_t dlwp_sph_mix_f32(const float* c_in_dev, const float* weight_dev, float* c_out_dev, int32_t batch, int32_t cin,
+                         int32_t cout, int32_t lmax, int32_t mmax, void* stream);
+/* The same product from the weight re-laid degree-major, packed_dev [lmax, cin, cout, 2], which dlwp_sph_mix_pack_f32 makes from
+ * weight_dev [cin, cout, lmax, 2] (one transposing launch).  The parameter layout costs a workgroup a 128-byte line per 8 bytes
+ * it uses; the packed one is read in 512-byte runs.  Same arithmetic in the same order: the two entry points give the same bits. */
+int32_t dlwp_sph_mix_packed_f32(const float* c_in_dev, const float* packed_dev, float* c_out_dev, int32_t batch, int32_t cin,
+                                int32_t cout, int32_t lmax, int32_t mmax, void* stream);
+int32_t dlwp_sph_mix_pack_f32(const float* weight_dev, float* packed_dev, int32_t cin, int32_t cout, int32_t lmax, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2503,7 +2503,7 @@ def sht(x: torch.Tensor, grid: str = "legendre-gauss", lmax: Optional[int] = Non
     """Real spherical harmonic transform of fields [..., nlat, nlon] on `grid` ("legendre-gauss" or "equiangular", row 0 the
     northernmost latitude) -> complex64 [..., lmax, mmax], orthonormal with the Condon-Shortley phase (the conventions of
     sphere.py; dlwp_sht_f32).  lmax defaults to nlat, mmax to min(lmax, nlon / 2 + 1).  Entries with l < m are zero.  With a
-    gradient wanted the same kernel runs inside training.sht, whose backward differentiates training.sht_torch."""
+    gradient wanted the same kernel runs inside training.sht, whose backward is `sht_backward`."""
     from . import sphere as _sph
 
     _lib.require_cuda_tensor(x, "x")
@@ -2587,3 +2587,94 @@ def sph_mix(c: torch.Tensor, weight: torch.Tensor, owner: Optional[torch.Tensor]
     elif b:
         _lib.launch("dlwp_sph_mix_f32", c.device, cp, wp, out, b, ci, co, lmax, mmax)
     return torch.view_as_complex(out)
+
+
+def sht_backward(g: torch.Tensor, grid: str, nlat: int, nlon: int) -> torch.Tensor:
+    """The adjoint of `sht`: the cotangent g complex64 [..., lmax, mmax] of a spectrum -> the gradient [..., nlat, nlon] of the
+    field it was transformed from (dlwp_sht_bwd_f32: the inverse transform's kernel over the forward's table wleg, every column
+    weighted 2 pi / nlon).  Entries of g with l < m are not read."""
+    from . import sphere as _sph
+
+    pairs = _complex_pairs(g, "g")
+    if g.dim() < 2:
+        raise _lib.DlwpError(f"sht_backward: expected a cotangent [..., lmax, mmax], got shape {tuple(g.shape)}")
+    lmax, mmax = int(g.shape[-2]), int(g.shape[-1])
+    nlat, nlon = int(nlat), int(nlon)
+    tab = _sph.device_tables(grid, nlat, nlon, lmax, mmax, g.device)
+    lead = tuple(g.shape[:-2])
+    planes = math.prod(lead)
+    out = torch.empty(lead + (nlat, nlon), device=g.device, dtype=torch.float32)
+    if planes:
+        _lib.launch("dlwp_sht_bwd_f32", g.device, pairs, tab.wleg, tab.tw, out, planes, nlat, nlon, lmax, mmax)
+    return out
+
+
+def isht_backward(gy: torch.Tensor, grid: str, lmax: int, mmax: int) -> torch.Tensor:
+    """The adjoint of `isht`: the cotangent gy [..., nlat, nlon] of a field -> the gradient complex64 [..., lmax, mmax] of the
+    coefficients it was synthesised from, in torch's convention dL/dRe + i dL/dIm (dlwp_isht_bwd_f32: the forward transform's
+    kernel over the inverse's table leg, the columns weighted as irfft weights them).  Exactly zero for l < m."""
+    from . import sphere as _sph
+
+    _lib.require_cuda_tensor(gy, "gy")
+    if gy.dim() < 2:
+        raise _lib.DlwpError(f"isht_backward: expected a cotangent [..., nlat, nlon], got shape {tuple(gy.shape)}")
+    nlat, nlon = int(gy.shape[-2]), int(gy.shape[-1])
+    lmax, mmax = int(lmax), int(mmax)
+    tab = _sph.device_tables(grid, nlat, nlon, lmax, mmax, gy.device)
+    lead = tuple(gy.shape[:-2])
+    planes = math.prod(lead)
+    out = torch.empty(lead + (lmax, mmax, 2), device=gy.device, dtype=torch.float32)
+    if planes:
+        _lib.launch("dlwp_isht_bwd_f32", gy.device, gy.contiguous(), tab.leg, tab.tw, out, planes, nlat, nlon, lmax, mmax)
+    return torch.view_as_complex(out)
+
+
+# The two candidates of each half of the mix backward (tools/bench_sht.py times both; DESIGN.md section 35.7 has the figures and
+# says why these stand):  dgrad "in_place" reads the parameter conjugate-transposed inside the mix kernel, "packed" first makes
+# the degree-major image of the conjugate transpose -- per call, from the values the weight holds NOW (it changes every step:
+# the rule of _conv2_forward_hip; no Derived cache);  wgrad "direct" stores into the parameter layout, "packed" stores
+# degree-major into a scratch buffer and transposes it back.  Each pair gives the same bits.  Measured at the config's width
+# (32 x 64, E 256, B 16): dgrad 0.089 ms packed against 0.104 in place; wgrad 0.108 ms direct against 0.111 through the scratch.
+SPH_MIX_DGRAD = "packed"
+SPH_MIX_WGRAD = "direct"
+
+
+def sph_mix_backward(c_in: torch.Tensor, weight: torch.Tensor, g: torch.Tensor, need_c: bool = True, need_w: bool = True,
+                     dgrad: Optional[str] = None, wgrad: Optional[str] = None):
+    """The backward of `sph_mix` for the cotangent g complex64 [B, Co, lmax, mmax] of its output: (gc_in | None, gw | None).
+    gc_in[b, i, l, m] = sum_o g[b, o, l, m] conj(weight[i, o, l]) for m <= l, zero above the diagonal (complex64 [B, Ci, lmax, mmax]);
+    gw[i, o, l] = sum_b sum_{m <= l} conj(c_in[b, i, l, m]) g[b, o, l, m] (complex64 [Ci, Co, lmax]).  Entries above the diagonal
+    of c_in and g are not read.  `dgrad` / `wgrad` choose between the candidates above (default SPH_MIX_DGRAD / SPH_MIX_WGRAD)."""
+    cp, wp, gp = _complex_pairs(c_in, "c_in"), _complex_pairs(weight, "weight"), _complex_pairs(g, "g")
+    if (c_in.dim() != 4 or weight.dim() != 3 or g.dim() != 4 or weight.shape[0] != c_in.shape[1] or weight.shape[2] != c_in.shape[2]
+            or tuple(g.shape) != (c_in.shape[0], weight.shape[1], c_in.shape[2], c_in.shape[3])):
+        raise _lib.DlwpError(f"sph_mix_backward: c_in {tuple(c_in.shape)} [B, Ci, lmax, mmax], weight {tuple(weight.shape)} "
+                             f"[Ci, Co, lmax] and g {tuple(g.shape)} [B, Co, lmax, mmax] do not match")
+    dgrad, wgrad = dgrad or SPH_MIX_DGRAD, wgrad or SPH_MIX_WGRAD
+    if dgrad not in ("packed", "in_place") or wgrad not in ("packed", "direct"):
+        raise _lib.DlwpError(f"sph_mix_backward: dgrad {dgrad!r} ('packed' or 'in_place'), wgrad {wgrad!r} ('packed' or 'direct')")
+    b, ci, lmax, mmax = (int(s) for s in c_in.shape)
+    co = int(weight.shape[1])
+    dev = c_in.device
+    gc = gw = None
+    if need_c:
+        gc = torch.empty(b, ci, lmax, mmax, 2, device=dev, dtype=torch.float32)
+        if b and dgrad == "packed":
+            packed = torch.empty(lmax, co, ci, 2, device=dev, dtype=torch.float32)
+            _lib.launch("dlwp_sph_mix_pack_adjoint_f32", dev, wp, packed, ci, co, lmax)
+            _lib.launch("dlwp_sph_mix_packed_f32", dev, gp, packed, gc, b, co, ci, lmax, mmax)
+        elif b:
+            _lib.launch("dlwp_sph_mix_dgrad_f32", dev, gp, wp, gc, b, ci, co, lmax, mmax)
+        gc = torch.view_as_complex(gc)
+    if need_w:
+        gw = torch.empty(ci, co, lmax, 2, device=dev, dtype=torch.float32)
+        if not b:
+            gw.zero_()
+        elif wgrad == "packed":
+            scratch = torch.empty(lmax, ci, co, 2, device=dev, dtype=torch.float32)
+            _lib.launch("dlwp_sph_mix_wgrad_packed_f32", dev, cp, gp, scratch, b, ci, co, lmax, mmax)
+            _lib.launch("dlwp_sph_mix_unpack_f32", dev, scratch, gw, ci, co, lmax)
+        else:
+            _lib.launch("dlwp_sph_mix_wgrad_f32", dev, cp, gp, gw, b, ci, co, lmax, mmax)
+        gw = torch.view_as_complex(gw)
+    return gc, gw

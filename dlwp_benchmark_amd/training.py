@@ -1550,9 +1550,11 @@ def mse_loss(x, target, weight=None):
     return _MseLossFn.apply(x, target, weight)
 
 
-# ---- spherical harmonic transforms and the Driscoll-Healy mix (models/sfno.py; csrc/sht.hip forward) -------------------------
-# HIP backward kernels for these three are out of scope: the backward of each Function differentiates
-# the torch form beside it, which computes the same thing from the SAME fp32 device tables (sphere.device_tables).
+# ---- spherical harmonic transforms and the Driscoll-Healy mix (models/sfno.py; csrc/sht.hip forward and backward) ------------
+# Each Function runs its HIP backward: the adjoint of a transform is the other transform's kernel over
+# the same table, the mix has an input- and a weight-gradient kernel.  The torch form beside each computes the same thing from
+# the SAME fp32 device tables (sphere.device_tables); it is differentiated under DLWP_TRAIN_TORCH_BACKWARD=1 and where a kernel
+# answers "unsupported".
 def _real_einsum_complex(eq: str, table: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
     """einsum of a real table with a complex tensor, part by part (einsum wants one dtype)"""
     return torch.complex(torch.einsum(eq, table, z.real), torch.einsum(eq, table, z.imag))
@@ -1590,37 +1592,65 @@ def sph_mix_torch(c: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     return torch.where(keep, torch.einsum("bilm,iol->bolm", torch.where(keep, c, zero), weight), zero)
 
 
+def _hip_backward_or_none(run):
+    """what `run` returns -- a HIP backward -- or None where the torch form is to be differentiated: under
+    DLWP_TRAIN_TORCH_BACKWARD=1, and where the kernel answers DLWP_ERR_UNSUPPORTED.  Any other error raises."""
+    if _torch_backward_selected():
+        return None
+    try:
+        with torch.no_grad():
+            return run()
+    except _lib.DlwpError as e:
+        if e.status != _lib.ERR_UNSUPPORTED:
+            raise
+    return None
+
+
 class _ShtFn(torch.autograd.Function):
+    """ops.sht forward, dlwp_sht_bwd_f32 backward.  Nothing is saved: the transform is linear, its backward needs the
+    cotangent and the tables only (the torch-form branch differentiates at a zero field of the input's shape)."""
+
     @staticmethod
     def forward(ctx, x, tab):
         ctx.tab = tab
-        ctx.save_for_backward(x)
+        ctx.in_shape = tuple(x.shape)
         with torch.no_grad():
             return ops.sht(x.detach(), tab.grid, tab.lmax, tab.mmax)
 
     @staticmethod
     def backward(ctx, grad_out):
-        (x,) = ctx.saved_tensors
-        g, = _grad_of_torch_form(lambda t: sht_torch(t, ctx.tab), (x,), (True,), grad_out)
+        tab = ctx.tab
+        g = _hip_backward_or_none(lambda: ops.sht_backward(grad_out.contiguous(), tab.grid, tab.nlat, tab.nlon))
+        if g is None:
+            zero = torch.zeros(ctx.in_shape, device=grad_out.device, dtype=torch.float32)
+            g, = _grad_of_torch_form(lambda t: sht_torch(t, tab), (zero,), (True,), grad_out)
         return g, None
 
 
 class _IshtFn(torch.autograd.Function):
+    """ops.isht forward, dlwp_isht_bwd_f32 backward; nothing saved, as _ShtFn"""
+
     @staticmethod
     def forward(ctx, c, tab):
         ctx.tab = tab
-        ctx.save_for_backward(c)
+        ctx.in_shape = tuple(c.shape)
         with torch.no_grad():
             return ops.isht(c.detach(), tab.grid, tab.nlat, tab.nlon)
 
     @staticmethod
     def backward(ctx, grad_out):
-        (c,) = ctx.saved_tensors
-        g, = _grad_of_torch_form(lambda t: isht_torch(t, ctx.tab), (c,), (True,), grad_out)
+        tab = ctx.tab
+        g = _hip_backward_or_none(lambda: ops.isht_backward(grad_out.contiguous(), tab.grid, tab.lmax, tab.mmax))
+        if g is None:
+            zero = torch.zeros(ctx.in_shape, device=grad_out.device, dtype=torch.complex64)
+            g, = _grad_of_torch_form(lambda t: isht_torch(t, tab), (zero,), (True,), grad_out)
         return g, None
 
 
 class _SphMixFn(torch.autograd.Function):
+    """ops.sph_mix forward; backward the mix kernel over the conjugate-transposed weight (input gradient) and
+    dlwp_sph_mix_wgrad_f32 (weight gradient), each only where needs_input_grad asks for it.  Saved: c and weight."""
+
     @staticmethod
     def forward(ctx, c, weight):
         ctx.save_for_backward(c, weight)
@@ -1629,19 +1659,26 @@ class _SphMixFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        return tuple(_grad_of_torch_form(sph_mix_torch, ctx.saved_tensors, ctx.needs_input_grad, grad_out))
+        c, weight = ctx.saved_tensors
+        need_c, need_w = ctx.needs_input_grad
+        if not (need_c or need_w):
+            return None, None
+        grads = _hip_backward_or_none(lambda: ops.sph_mix_backward(c, weight, grad_out.contiguous(), need_c, need_w))
+        if grads is None:
+            grads = _grad_of_torch_form(sph_mix_torch, (c, weight), (need_c, need_w), grad_out)
+        return tuple(grads)
 
 
 def sht(x, tab):
-    """differentiable ops.sht: HIP forward, backward by autograd of sht_torch"""
+    """differentiable ops.sht: HIP forward and HIP backward (the torch form under DLWP_TRAIN_TORCH_BACKWARD=1)"""
     return _ShtFn.apply(x, tab)
 
 
 def isht(c, tab):
-    """differentiable ops.isht: HIP forward, backward by autograd of isht_torch"""
+    """differentiable ops.isht: HIP forward and HIP backward (the torch form under DLWP_TRAIN_TORCH_BACKWARD=1)"""
     return _IshtFn.apply(c, tab)
 
 
 def sph_mix(c, weight):
-    """differentiable ops.sph_mix: HIP forward, backward by autograd of sph_mix_torch"""
+    """differentiable ops.sph_mix: HIP forward and HIP backward (the torch form under DLWP_TRAIN_TORCH_BACKWARD=1)"""
     return _SphMixFn.apply(c, weight)

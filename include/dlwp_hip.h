@@ -1330,6 +1330,42 @@ int32_t dlwp_sph_mix_packed_f32(const float* c_in_dev, const float* packed_dev, 
                                 int32_t cout, int32_t lmax, int32_t mmax, void* stream);
 int32_t dlwp_sph_mix_pack_f32(const float* weight_dev, float* packed_dev, int32_t cin, int32_t cout, int32_t lmax, void* stream);
 
+/* The backwards of the three operators above (training of the SFNO backbone; the reference differentiates torch_harmonics from
+ * models/fno/fno.py:183-200 by autograd).  Gradients of complex tensors follow torch's convention g = dL/dRe + i dL/dIm.  Each
+ * transform's adjoint is the OTHER transform's kernel over the table its forward reads, with the table strides exchanged: the
+ * same envelope, tiling and LDS budget as the forward, fixed summation order, no atomics.
+ * dlwp_sht_bwd_f32:   g_dev [planes, lmax, mmax, 2] (the cotangent of the spectrum) -> gx_dev [planes, nlat, nlon]:
+ *   Y[k][m] = (2 pi / nlon) sum_{l >= m} wleg[k][l][m] g[l][m],   gx[k][j] = sum_m Re(Y) tw[(j m) mod nlon].re + Im(Y) tw[..].im
+ *   Entries of g_dev with l < m are not read.
+ * dlwp_isht_bwd_f32:  gy_dev [planes, nlat, nlon] -> gc_dev [planes, lmax, mmax, 2]:
+ *   Z[k][m] = f_m sum_j gy[k][j] tw[(j m) mod nlon]  (f_m as in dlwp_isht_f32, imaginary part zero where f_m = 1),
+ *   gc[l][m] = sum_k leg[l][k][m] Z[k][m]  (l >= m; written as zero below). */
+int32_t dlwp_sht_bwd_f32(const float* g_dev, const float* wleg_dev, const float* tw_dev, float* gx_dev, int64_t planes,
+                         int32_t nlat, int32_t nlon, int32_t lmax, int32_t mmax, void* stream);
+int32_t dlwp_isht_bwd_f32(const float* gy_dev, const float* leg_dev, const float* tw_dev, float* gc_dev, int64_t planes,
+                          int32_t nlat, int32_t nlon, int32_t lmax, int32_t mmax, void* stream);
+/* Input gradient of dlwp_sph_mix_f32: gc_in[b][i][l][m] = sum_o g[b][o][l][m] conj(weight[i][o][l]) for m <= min(l, mmax - 1), zero
+ * above; entries of g_dev above the diagonal are not read.  The forward kernel with the weight read conjugate-transposed in place.
+ *   g_dev [batch, cout, lmax, mmax, 2], weight_dev [cin, cout, lmax, 2], gc_in_dev [batch, cin, lmax, mmax, 2].
+ * dlwp_sph_mix_pack_adjoint_f32 makes the degree-major image of the conjugate transpose, packed_dev [lmax, cout, cin, 2], with
+ * which dlwp_sph_mix_packed_f32(g_dev, packed_dev, gc_in_dev, batch, cout, cin, ...) gives the same bits. */
+int32_t dlwp_sph_mix_dgrad_f32(const float* g_dev, const float* weight_dev, float* gc_in_dev, int32_t batch, int32_t cin,
+                               int32_t cout, int32_t lmax, int32_t mmax, void* stream);
+int32_t dlwp_sph_mix_pack_adjoint_f32(const float* weight_dev, float* packed_dev, int32_t cin, int32_t cout, int32_t lmax,
+                                      void* stream);
+/* Weight gradient of dlwp_sph_mix_f32: gw[i][o][l] = sum_b sum_{m <= min(l, mmax - 1)} conj(c_in[b][i][l][m]) g[b][o][l][m]; entries
+ * of either operand above the diagonal are not read.  Per degree a complex GEMM with M = cin, N = cout, K = batch * rows_l on
+ * v_mfma_f32_16x16x4_f32, summed over k = (b, m) in ascending order in one accumulator chain (no split-K, no atomics).
+ *   c_in_dev [batch, cin, lmax, mmax, 2], g_dev [batch, cout, lmax, mmax, 2], gw_dev [cin, cout, lmax, 2].
+ * dlwp_sph_mix_wgrad_packed_f32 writes the same values degree-major, gw_packed_dev [lmax, cin, cout, 2], and
+ * dlwp_sph_mix_unpack_f32 (the inverse of dlwp_sph_mix_pack_f32) transposes them into the parameter layout.  The envelope of
+ * all of these is that of dlwp_sph_mix_f32. */
+int32_t dlwp_sph_mix_wgrad_f32(const float* c_in_dev, const float* g_dev, float* gw_dev, int32_t batch, int32_t cin, int32_t cout,
+                               int32_t lmax, int32_t mmax, void* stream);
+int32_t dlwp_sph_mix_wgrad_packed_f32(const float* c_in_dev, const float* g_dev, float* gw_packed_dev, int32_t batch, int32_t cin,
+                                      int32_t cout, int32_t lmax, int32_t mmax, void* stream);
+int32_t dlwp_sph_mix_unpack_f32(const float* packed_dev, float* weight_dev, int32_t cin, int32_t cout, int32_t lmax, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,22 @@ Per (op, shape) one JSON line:
 that reads the parameter as it lies.  The step is timed with the 1x1 convolutions in both forms of
 HipBackbone.set_aux_conv_form ("direct", "bf16x6").
 
-Usage: python tools/bench_sht.py [--reps 15] [--inner 20] [--warmup 3] [--out FILE]
+
+--part backward (or all) adds the backwards, by the same method at the two legendre-gauss shapes:
+  sht_backward, isht_backward                   ops.* against the backward of the torch form (training._grad_of_torch_form of
+                                                sht_torch / isht_torch: what the Functions ran before they had kernels)
+  sph_mix_dgrad {packed, in_place}              the two candidates of the input gradient: a per-call degree-major pack of the
+                                                conjugate transpose + the packed kernel, or the weight read in place
+  sph_mix_wgrad {packed, direct}                the two candidates of the weight gradient's store: degree-major scratch + transpose
+                                                back, or straight into the parameter layout
+  sfno_train_step                               forward + backward of the 4-block network (MLP, big skip, pos_embed), "hip": the HIP
+                                                backwards of the three ops; "torch": `switch` "env" is DLWP_TRAIN_TORCH_BACKWARD=1
+                                                (read at every call: the two alternate in one process; it also turns the
+                                                convolutions into the plain composition), `switch` "three_ops" sends ONLY the
+                                                three ops to their torch forms.  conv_dgrad: DLWP_CONV_DGRAD of the run
+                                                ("hip": the bf16x6 matrix-pipe convolutions).  peak_mb_*: max_memory_allocated of one step.
+
+Usage: python tools/bench_sht.py [--part forward|backward|all] [--reps 15] [--inner 20] [--warmup 3] [--out FILE]
 """
 import argparse
 import json
@@ -74,6 +89,7 @@ def main():
     ap.add_argument("--inner", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--part", default="all", choices=("forward", "backward", "all"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_sht: no GPU; a timing taken anywhere else says nothing")
@@ -112,8 +128,76 @@ def main():
         print(json.dumps(line), flush=True)
         lines.append(line)
 
+    def peak_mb(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        fn()
+        torch.cuda.synchronize()
+        return round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)
+
+    def backward_part(grid, nlat, nlon, embed, batch):
+        modes = min(nlat, nlon // 2)
+        shape = {"grid": grid, "nlat": nlat, "nlon": nlon, "embed": embed, "batch": batch, "modes": modes}
+        tab = S.device_tables(grid, nlat, nlon, modes, modes, dev)
+        gen = torch.Generator(device=dev).manual_seed(nlat + 1)
+        x = torch.randn(batch, embed, nlat, nlon, device=dev, generator=gen)
+        gy = torch.randn(batch, embed, nlat, nlon, device=dev, generator=gen)
+        c = ops.sht(x, grid, modes, modes)
+        g = ops.sht(gy, grid, modes, modes)
+        w = torch.view_as_complex(torch.randn(embed, embed, modes, 2, device=dev, generator=gen) / embed ** 0.5)
+        planes = batch * embed
+        field, spec, wbytes = planes * nlat * nlon * 4, planes * modes * modes * 8, embed * embed * modes * 8
+        gflop = round(8 * batch * embed * embed * modes * (modes + 1) / 2 / 1e9, 3)
+        torch_form = T._grad_of_torch_form
+        measure("sht_backward", shape, lambda: ops.sht_backward(g, grid, nlat, nlon),
+                lambda: torch_form(lambda t: T.sht_torch(t, tab), (x,), (True,), g)[0], field + spec)
+        measure("isht_backward", shape, lambda: ops.isht_backward(gy, grid, modes, modes),
+                lambda: torch_form(lambda t: T.isht_torch(t, tab), (c,), (True,), gy)[0], field + spec)
+        for cand in ("packed", "in_place"):
+            measure("sph_mix_dgrad", shape, lambda: ops.sph_mix_backward(c, w, g, True, False, dgrad=cand)[0],
+                    lambda: torch_form(T.sph_mix_torch, (c, w), (True, False), g)[0], 2 * spec + wbytes, candidate=cand, gflop=gflop)
+        for cand in ("packed", "direct"):
+            measure("sph_mix_wgrad", shape, lambda: ops.sph_mix_backward(c, w, g, False, True, wgrad=cand)[1],
+                    lambda: torch_form(T.sph_mix_torch, (c, w), (False, True), g)[1], 2 * spec + wbytes, candidate=cand, gflop=gflop)
+        del x, gy, c, g, w
+        model = SFNO2DModule(height=nlat, width=nlon, grid=grid, num_layers=4, scale_factor=1, embed_dim=embed, big_skip=True,
+                             pos_embed=True, use_mlp=True)
+        fill_state_dict(model, std_fn=lambda n, s: 0.7 / s[0] ** 0.5 if n.endswith("filter.weight") else None)
+        model = model.to(dev).train()
+        xin = torch.randn(batch, model.in_channels, nlat, nlon, device=dev, generator=gen)
+        hip_or_none = T._hip_backward_or_none
+
+        def step(torch_backward: str, three_ops_torch: bool = False):
+            os.environ["DLWP_TRAIN_TORCH_BACKWARD"] = torch_backward
+            T._hip_backward_or_none = (lambda run: None) if three_ops_torch else hip_or_none
+            try:
+                with torch.enable_grad():
+                    model.zero_grad(set_to_none=True)
+                    model.sfno(xin).square().mean().backward()
+            finally:
+                os.environ["DLWP_TRAIN_TORCH_BACKWARD"] = "0"
+                T._hip_backward_or_none = hip_or_none
+            return model.sfno.blocks[1].filter.filter.weight.grad
+
+        for conv_dgrad in ("torch", "hip"):
+            os.environ["DLWP_CONV_DGRAD"] = conv_dgrad
+            for switch, tor in (("env", lambda: step("1")), ("three_ops", lambda: step("0", True))):
+                try:
+                    measure("sfno_train_step", shape, lambda: step("0"), tor, 0, switch=switch, conv_dgrad=conv_dgrad,
+                            peak_mb_hip=peak_mb(lambda: step("0")), peak_mb_torch=peak_mb(tor))
+                except DlwpError as e:
+                    print(json.dumps({"op": "sfno_train_step", **shape, "switch": switch, "conv_dgrad": conv_dgrad, "error": str(e)}),
+                          flush=True)
+        os.environ.pop("DLWP_CONV_DGRAD", None)
+        del model
+        torch.cuda.empty_cache()
+
     with torch.no_grad():
         for grid, nlat, nlon, embed, batch in SHAPES:
+            if args.part in ("backward", "all") and grid == "legendre-gauss":
+                backward_part(grid, nlat, nlon, embed, batch)
+            if args.part == "backward":
+                continue
             modes = min(nlat, nlon // 2)
             shape = {"grid": grid, "nlat": nlat, "nlon": nlon, "embed": embed, "batch": batch, "modes": modes}
             tab = S.device_tables(grid, nlat, nlon, modes, modes, dev)

@@ -550,6 +550,19 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
   do {                                                                                                 \
     if (p.trace && tid == p.trace_tid && n_stamp < 64) p.trace[blockIdx.x * 64 + n_stamp++] = __builtin_amdgcn_s_memrealtime(); \
   } while (0)
+  // Polls of a hand-off: the traced wave leaves the poll issue that delivered its block (1 = the first; the last block of the
+  // phase counts) in bits 56-63 of the slot of the phase's closing stamp, which is then OR-ed in (the 100 MHz counter does not
+  // reach those bits; the buffer is zeroed before the launch; tools/trunk_trace.py).  Nothing is carried in registers.
+  // Counted in the step kernel only: in the plain trunk the two extra stores cost <4, 32, true> eight more spilled dwords.
+#define DLWP_STAMP_POLLS(n)                                                                            \
+  do {                                                                                                 \
+    if (STEP && p.trace && tid == p.trace_tid && n_stamp < 64)                                         \
+      p.trace[blockIdx.x * 64 + n_stamp] = (unsigned long long)((n) < 255 ? (n) : 255) << 56;          \
+  } while (0)
+#define DLWP_STAMP_OR()                                                                                \
+  do {                                                                                                 \
+    if (p.trace && tid == p.trace_tid && n_stamp < 64) p.trace[blockIdx.x * 64 + n_stamp++] |= __builtin_amdgcn_s_memrealtime(); \
+  } while (0)
   DLWP_STAMP();
 
   for (int l = 0; l < p.L; ++l) {
@@ -643,11 +656,17 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
     }
     if (!LL) trunk_group_wait(ctr, target, s_fail, p.spin_limit);
     DLWP_STAMP();
-    {   // weights of the wave's second mode: requested now, they arrive while the partials are awaited
-      const int m = m_lo + wave + ROWS;
-      const float2* w = p.wt[l] + ((long long)(m < m_hi ? m : 0) * C + (lane >> 5) * 16) * C + (lane & 31);
+    // weights of the wave's second mode: requested now, they arrive while the partials are awaited.  Only by a wave that
+    // has one (wave-uniform; at the headline shape three of a workgroup's eight): the requests stand in front of the poll
+    // in the same in-order vmcnt.  The other waves' registers are zeroed, never read: left undefined they cost the headline
+    // instantiation its spill-free allocation (DESIGN.md section 4.6 "hand-off polls")
+    if (const int m = m_lo + wave + ROWS; m < m_hi) {
+      const float2* w = p.wt[l] + ((long long)m * C + (lane >> 5) * 16) * C + (lane & 31);
 #pragma unroll
       for (int cc = 0; cc < 16; ++cc) wreg[1][cc] = w[cc * C];
+    } else {
+#pragma unroll
+      for (int cc = 0; cc < 16; ++cc) wreg[1][cc] = float2{0.f, 0.f};
     }
     // ---- P2: channel mixing of this workgroup's share of the modes, two modes per pass.
     // lane (q4 = lane >> 4, quad = lane & 15) fetches floats 4 quad..4 quad+3 of the partials q4, q4+4, ...
@@ -678,6 +697,7 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
             __builtin_amdgcn_s_sleep(2);
             ld4_sc1_x4(xp_grp, oa0, oa1, obo0, obo1, v0, v1, v2, v3);
           }
+          DLWP_STAMP_POLLS(tries + 1);
           // re-arm what was consumed (this wave is the only reader of these modes' partials)
           const f32x4 sent4 = {__uint_as_float(kSentinel), __uint_as_float(kSentinel), __uint_as_float(kSentinel),
                                __uint_as_float(kSentinel)};
@@ -739,7 +759,7 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
       }
       wave_lds_fence();
     }
-    DLWP_STAMP();
+    DLWP_STAMP_OR();
     target += (unsigned)G;
     if (!LL) trunk_group_barrier(ctr, target, s_fail, p.spin_limit);
     DLWP_STAMP();
@@ -769,6 +789,7 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
             __builtin_amdgcn_s_sleep(2);
             ld4_sc1_x4(ob, o[0], o[1], o[2], o[3], v0, v1, v2, v3);
           }
+          DLWP_STAMP_POLLS(tries + 1);
         }
         if (LL && l == 0 && st == 0 && wave == 0 && ky == 0) {
           // O of layer 0 has arrived, so every workgroup of the group has run and published its XCC id: does the
@@ -811,7 +832,7 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
       wave_lds_fence();   // the transpose tile is reused for the next ky
     }
     lds_barrier();
-    DLWP_STAMP();
+    DLWP_STAMP_OR();
     // ---- the row itself
     if constexpr (F16) {
       // inverse W-DFT, f16x3: A = Z[o = 16 ot + j][k' = 8g .. 8g+7] (lane groups 2, 3 carry zeros: K = 16 of 32)
@@ -903,6 +924,8 @@ __global__ __launch_bounds__(64 * ROWS, 2) void fno_trunk_kernel(const TrunkPara
   }
   DLWP_STAMP();
 #undef DLWP_STAMP
+#undef DLWP_STAMP_POLLS
+#undef DLWP_STAMP_OR
   if (*s_fail) {
     // loud failure: the host reads this word after the launch (DLWP_ERR_TIMEOUT / re-run on the unfused kernels)
     if (tid == 0 && p.fail_word) {

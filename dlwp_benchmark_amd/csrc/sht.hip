@@ -25,32 +25,18 @@
 //                   M = cin, N = cout, K = batch * rows_l on the same matrix instruction.  See the kernel.
 //
 // Every sum runs in a fixed order in one thread (or one accumulator chain of the matrix pipe): no atomics, the same bits twice.
+// The two stages of sht_kernel are device functions of sht_stages.hpp, which sph_power.hip (power spectra without the
+// coefficients ever reaching memory) runs as well.
 #include <algorithm>
 
-#include "common.hpp"
+#include "sht_stages.hpp"
 
 namespace dlwp {
 namespace sht {
 
-constexpr int kThreads = 256;
 constexpr int kMaxPlanes = 4;                // planes of a workgroup, which share every table load: 4, 2 or 1 (chosen per shape in dlwp_sht_f32)
-constexpr size_t kLdsBudget = 52 * 1024;     // three workgroups per compute unit (160 KB)
-
-// Each transform's backward is the OTHER kernel over the table its forward reads (both are linear: the adjoint of "DFT, then
-// contract over latitude" is "contract over degree, then DFT back").  What differs between a kernel's two uses is carried by
-// two small arguments, not by a second copy of the kernel:
-//   TableStrides  where the Legendre table keeps (row k, degree l) for column m: wleg is [k][l][m], leg is [l][k][m].  m is the
-//                 fastest index of both, so the lanes of a wave (consecutive m) read consecutive floats either way.
-//   ColumnFactor  what multiplies column m between the two stages: the quadrature's 2 pi / nlon (forward sht and the adjoint of
-//                 sht), or irfft's Hermitian weights -- 1 for the self-conjugate columns m = 0 and 2 m = nlon, whose imaginary
-//                 parts are dropped, 2 for the others (isht and the adjoint of isht).
-struct TableStrides {
-  size_t row, degree;
-};
-struct ColumnFactor {
-  float self_conjugate, other;
-  bool drop_imag;             // zero the imaginary part of the self-conjugate columns
-};
+// kThreads, kLdsBudget, TableStrides / ColumnFactor, the two stages of the forward transform, fit_tiles and check_transform:
+// sht_stages.hpp (sph_power.hip runs the same two stages).
 
 // ---- sht, and the adjoint of isht (x: the cotangent of the field, wleg: the table `leg`) ------------------------------------
 // LDS: tw [nlon] float2 | X [kPlanes][nlat][mt] float2 | xs [kPlanes][rt][nlon] float
@@ -78,51 +64,13 @@ __global__ __launch_bounds__(kThreads) void sht_kernel(const float* __restrict__
       for (int e = tid; e < rn * nlon; e += kThreads) xs[p * rt * nlon + e] = p < np ? src[e] : 0.f;
     }
     __syncthreads();
-    for (int it = tid; it < rn * mn; it += kThreads) {
-      const int kk = it / mn, mm = it - kk * mn, m = m0 + mm;
-      float ar[kPlanes], ai[kPlanes];
-#pragma unroll
-      for (int p = 0; p < kPlanes; ++p) ar[p] = ai[p] = 0.f;
-      const float* row = xs + kk * nlon;
-      int idx = 0;            // (j m) mod nlon; m < nlon, so one subtraction wraps it
-#pragma unroll 4
-      for (int j = 0; j < nlon; ++j) {
-        const float2 w = tws[idx];
-        idx += m;
-        if (idx >= nlon) idx -= nlon;
-#pragma unroll
-        for (int p = 0; p < kPlanes; ++p) {
-          const float v = row[p * rt * nlon + j];
-          ar[p] = fmaf(v, w.x, ar[p]);
-          ai[p] = fmaf(v, w.y, ai[p]);
-        }
-      }
-      const bool self_conjugate = m == 0 || 2 * m == nlon;      // only the adjoint of isht tells them apart
-      const float f = self_conjugate ? cf.self_conjugate : cf.other;
-#pragma unroll
-      for (int p = 0; p < kPlanes; ++p)
-        Xs[(p * nlat + k0 + kk) * mt + mm] = float2{ar[p] * f, self_conjugate && cf.drop_imag ? 0.f : ai[p] * f};
-    }
+    dft_rows<kPlanes>(xs, tws, Xs, tid, k0, rn, m0, mn, nlat, nlon, mt, rt, cf);
   }
   __syncthreads();
   for (int it = tid; it < lmax * mn; it += kThreads) {
     const int l = it / mn, mm = it - l * mn, m = m0 + mm;
     float ar[kPlanes], ai[kPlanes];
-#pragma unroll
-    for (int p = 0; p < kPlanes; ++p) ar[p] = ai[p] = 0.f;
-    if (l >= m) {
-      const float* wp = wleg + l * ts.degree + m;
-#pragma unroll 4
-      for (int k = 0; k < nlat; ++k) {
-        const float w = wp[k * ts.row];
-#pragma unroll
-        for (int p = 0; p < kPlanes; ++p) {
-          const float2 v = Xs[(p * nlat + k) * mt + mm];
-          ar[p] = fmaf(w, v.x, ar[p]);
-          ai[p] = fmaf(w, v.y, ai[p]);
-        }
-      }
-    }
+    legendre_column<kPlanes>(Xs, wleg, ts, l, m, mm, nlat, mt, ar, ai);
 #pragma unroll
     for (int p = 0; p < kPlanes; ++p)
       if (p < np) coeffs[((p0 + p) * lmax + l) * (long long)mmax + m] = float2{ar[p], ai[p]};
@@ -202,19 +150,6 @@ __global__ __launch_bounds__(kThreads) void isht_kernel(const float2* __restrict
 #pragma unroll
     for (int p = 0; p < kPlanes; ++p)
       if (p < np) y[((p0 + p) * nlat + k0 + kk) * (long long)nlon + j] = acc[p];
-  }
-}
-
-// the two tile extents of a transform kernel: start from "everything in one tile" and halve the larger LDS array until the
-// workgroup fits the budget.  a_unit / b_unit: bytes of the two arrays per unit of their extent.
-static bool fit_tiles(size_t fixed, size_t a_unit, int& a, size_t b_unit, int& b, size_t& bytes) {
-  for (;;) {
-    bytes = fixed + a_unit * a + b_unit * b;
-    if (bytes <= kLdsBudget) return true;
-    if (a_unit * a >= b_unit * b && a > 1) a = (a + 1) / 2;
-    else if (b > 1) b = (b + 1) / 2;
-    else if (a > 1) a = (a + 1) / 2;
-    else return false;
   }
 }
 
@@ -449,17 +384,6 @@ __global__ __launch_bounds__(kThreads) void sph_mix_wgrad_kernel(const float2* _
       if (o < co) gw[kDegreeMajor ? ((size_t)l * ci + i) * co + o : ((size_t)i * co + o) * lmax + l] = float2{accR[c][rr], accI[c][rr]};
     }
   }
-}
-
-static int32_t check_transform(const void* a, const void* b, const void* c, const void* d, int64_t planes, int32_t nlat,
-                               int32_t nlon, int32_t lmax, int32_t mmax) {
-  DLWP_REQUIRE(a && b && c && d, DLWP_ERR_INVALID_ARGUMENT, "null argument");
-  DLWP_REQUIRE(planes >= 1, DLWP_ERR_INVALID_ARGUMENT, "planes must be at least 1");
-  DLWP_REQUIRE(nlat >= 2 && nlat <= 256 && nlon >= 2 && nlon <= 512 && nlon % 2 == 0 && lmax >= 1 && lmax <= nlat && mmax >= 1 &&
-                   mmax <= nlon / 2 + 1,
-               DLWP_ERR_UNSUPPORTED, "spherical transform outside the envelope: nlat %d (2..256), nlon %d (even, 2..512), lmax %d "
-               "(1..nlat), mmax %d (1..nlon / 2 + 1)", nlat, nlon, lmax, mmax);
-  return DLWP_OK;
 }
 
 }  // namespace sht

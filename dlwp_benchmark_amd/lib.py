@@ -321,6 +321,12 @@ SIGNATURES = {
     "dlwp_sph_mix_wgrad_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "dlwp_sph_mix_wgrad_packed_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "dlwp_sph_mix_unpack_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    # spherical power spectra of a rollout and its targets (csrc/sph_power.hip)
+    "dlwp_sph_power_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "dlwp_sph_power_sums_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                          c_int32, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
+    "dlwp_sph_power_sums_acc_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                              c_int32, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

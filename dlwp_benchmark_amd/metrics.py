@@ -19,7 +19,11 @@ ensemble_forecast): RMSE of the ensemble mean, spread, spread / skill, CRPS and 
 through dlwp_ensemble_sums_acc_f32 (csrc/ensemble_scores.hip).  The reference has only a commented sketch of it
 (scripts/train.py:352-371): PARITY UNPINNED.
 
-All four classes also take HEALPix rollouts [B, K, C, 12, n, n] when they are given the longitudes of the lat-lon grid beside its
+`SphericalSpectrumMetrics` reduces a rollout and its targets to the power per total wavenumber l of forecast, truth and error
+and to their spectral coherence, through one fused spherical-harmonic transform-and-reduce kernel (csrc/sph_power.hip; DESIGN.md
+section 36).  The reference has no spherical spectrum: PARITY UNPINNED.
+
+All five classes also take HEALPix rollouts [B, K, C, 12, n, n] when they are given the longitudes of the lat-lon grid beside its
 latitudes: the reference remaps inits, outputs and targets to lat-lon before every metric (scripts/evaluate.py:298-303,
 scripts/train.py:430-441), on the host; here `ops.healpix_to_latlon` does it on the device, a chunk of samples at a time into one
 reused workspace, and the sums accumulate through the `*_acc` entry points.
@@ -489,6 +493,115 @@ class ZonalSpectrumMetrics(_HealpixInput):
         energy = s / (n_samples * self.height)
         log_ratio = torch.log((energy[0] + MELR_EPS) / (energy[1] + MELR_EPS))
         return {"energy_pred": energy[0], "energy_true": energy[1], "log_ratio": log_ratio, "melr": log_ratio.mean(dim=-1)}
+
+
+class SphericalSpectrumMetrics(_HealpixInput):
+    """Power per total wavenumber l of a rollout [B, K, C, nlat, nlon], of its targets and of their difference, and the
+    spectral coherence between rollout and target, on `grid` ("legendre-gauss", "equiangular" or "equiangular-centred": the
+    cell-centred lat-lon grids of the data, healpix.reference_grid), reduced on the device by one fused transform-and-reduce
+    kernel (ops.sph_power_sums, dlwp_sph_power_sums_f32).  The reference has no spherical spectrum: PARITY
+    UNPINNED, the definitions are those of sphere.py -- orthonormal harmonics, Condon-Shortley phase, row 0 the northernmost.
+
+    With c = sht(x) and f_m = 1 for m = 0 and 2 m = nlon, else 2:  power(x)[l] = sum_{m <= l} f_m |c[l, m]|^2 and
+    cross(x, y)[l] = sum_{m <= l} f_m Re(c_x conj c_y); the sums are [4, K, C, lmax] over the samples: power(out), power(target),
+    power(out - target) -- the difference formed in the field domain, where a forecast close to its truth keeps its accuracy --
+    and cross(out, target).  With an exact quadrature and a band-limited field the degrees of power(x) add up to the integral
+    of x^2 over the sphere, so `finalize` divides by 4 pi n_samples: the degrees of a spectrum add up to the mean square.
+    lmax defaults to nlat, mmax to min(lmax, nlon / 2 + 1); on the two equiangular grids the quadrature is exact only for
+    l + l' <= nlat - 1, so lmax = nlat / 2 is the largest without aliasing.
+
+    A north-south flip of BOTH inputs on a symmetric grid changes none of the four sums (only the signs of the coefficients
+    with odd l - m change): WeatherBench stores south first, and may be scored as stored.
+
+    With `lons_deg` (nlon longitudes) HEALPix rollouts [B, K, C, 12, n, n] are taken too: they are remapped to
+    (sphere.latitudes_deg(grid, nlat), lons_deg) on the device in chunks of samples whose lat-lon copies stay within
+    `max_workspace_bytes`, and accumulated; without it they are refused.  The target grid is free there: "legendre-gauss" is
+    the one to take, its quadrature is exact up to lmax = nlat."""
+
+    def __init__(self, grid: str, nlat: int, nlon: int, lmax: Optional[int] = None, mmax: Optional[int] = None, group=None,
+                 lons_deg=None, max_workspace_bytes: int = DEFAULT_WORKSPACE_BYTES):
+        from . import sphere as _sph
+
+        self.grid, self.nlat, self.nlon = grid, int(nlat), int(nlon)
+        self.lmax = self.nlat if lmax is None else int(lmax)
+        self.mmax = min(self.lmax, self.nlon // 2 + 1) if mmax is None else int(mmax)
+        _sph.check_range(self.nlat, self.nlon, self.lmax, self.mmax)
+        self._init_remap(_sph.latitudes_deg(grid, self.nlat), lons_deg, max_workspace_bytes)
+        if self._lons is not None and len(self._lons) != self.nlon:
+            raise _lib.DlwpError(f"spherical spectrum: {len(self._lons)} longitudes in lons_deg, nlon = {self.nlon}")
+        self.group = group
+        self._ws = {}    # device -> workspaces, the last one the largest and the one in use
+
+    def _workspace(self, dev, shape):
+        """One workspace per device that only grows (ZonalSpectrumMetrics._workspace: a recorded step keeps its address)."""
+        from . import ops as _ops
+
+        n = _ops.sph_power_workspace_bytes(shape, self.lmax, self.mmax)
+        bufs = self._ws.setdefault(str(dev), [])
+        if not bufs or bufs[-1].numel() < n:
+            bufs.append(torch.empty(max(n, 2 * bufs[-1].numel()) if bufs else n, dtype=torch.uint8, device=dev))
+        return bufs[-1]
+
+    def sums(self, out: torch.Tensor, target: torch.Tensor, into: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """double [4, K, C, lmax] sums over this rank's samples (see the class; dlwp_sph_power_sums_f32).  `into`: a
+        [4, K, C, lmax] double tensor of running sums the new ones are ADDED to (dlwp_sph_power_sums_acc_f32); it is returned.  A
+        HEALPix rollout [B, K, C, 12, n, n] (see `lons_deg`) is remapped chunk by chunk and summed into zero-initialised (or
+        `into`) sums: the chain of every sum runs over the samples in order, so the chunk size does not change a bit."""
+        from . import ops as _ops
+
+        _lib.require_cuda_tensor(out, "out")
+        _lib.require_cuda_tensor(target, "target")
+        if out.dim() == 6 and self._lons is not None:
+            self._require_remap(out, target)
+            sums = into if into is not None else torch.zeros(4, out.shape[1], out.shape[2], self.lmax, dtype=torch.float64,
+                                                             device=out.device)
+            for o, t in self._remapped_chunks(out, target):
+                self.sums(o, t, into=sums)
+            return sums
+        if out.dim() != 5:
+            raise _lib.DlwpError(f"spherical spectrum: expected a lat-lon rollout [B, K, C, nlat, nlon], got {out.dim()}-D shape "
+                                 f"{tuple(out.shape)} (a HEALPix rollout [B, K, C, 12, n, n] is remapped to lat-lon only when the "
+                                 "metric is built with `lons_deg`)")
+        if tuple(out.shape[-2:]) != (self.nlat, self.nlon):
+            raise _lib.DlwpError(f"spherical spectrum: a {out.shape[-2]}x{out.shape[-1]} rollout, the metric was built for "
+                                 f"{self.nlat}x{self.nlon}")
+        if target.shape != out.shape:
+            raise _lib.DlwpError(f"target shape {tuple(target.shape)} != output shape {tuple(out.shape)}")
+        return _ops.sph_power_sums(out, target, self.grid, self.lmax, self.mmax, into=into,
+                                   workspace=self._workspace(out.device, out.shape))
+
+    def __call__(self, out: torch.Tensor, target: torch.Tensor, world_size: int = 1):
+        """Spectra, coherence and log ratio over ALL ranks' samples (see finalize)."""
+        return self.finalize(self.sums(out, target), float(out.shape[0]), world_size)
+
+    def finalize(self, s: torch.Tensor, n_samples: float, world_size: int = 1):
+        """Scores from accumulated sums: `s` = this rank's [4, K, C, lmax] sums (of one batch or added up over many),
+        n_samples = how many samples went into them.  With world_size > 1 ONE all-reduce moves the sums and the sample count
+        (shards may differ in size).  With P = s / (4 pi n) returns, in float64,
+          "power_pred", "power_true", "power_error"  [K, C, lmax]   P[0], P[1], P[2]
+          "coherence"  [K, C, lmax]   s[3] / sqrt(s[0] s[1]), 0 where the product is 0
+          "log_ratio"  [K, C, lmax]   ln((power_pred + 1e-10) / (power_true + 1e-10))   (MELR_EPS)
+          "selr"       [K, C]         the mean of log_ratio over l."""
+        if world_size > 1:
+            import torch.distributed as dist
+
+            host = dist.get_backend(self.group) != "nccl"
+            dev = s.device
+            buf = torch.empty(s.numel() + 1, dtype=torch.float64, device=dev)
+            buf[:-1].copy_(s.flatten())
+            buf[-1:].fill_(n_samples)   # the count travels with the sums
+            if host:
+                buf = buf.cpu()
+            dist.all_reduce(buf, group=self.group)
+            buf = buf.to(dev)
+            s, n_samples = buf[:-1].view_as(s), buf[-1:]
+        power = s[:3] / (n_samples * (4.0 * math.pi))
+        prod = s[0] * s[1]
+        coherence = torch.where(prod > 0, s[3] / torch.sqrt(torch.where(prod > 0, prod, torch.ones_like(prod))),
+                                torch.zeros_like(prod))
+        log_ratio = torch.log((power[0] + MELR_EPS) / (power[1] + MELR_EPS))
+        return {"power_pred": power[0], "power_true": power[1], "power_error": power[2], "coherence": coherence,
+                "log_ratio": log_ratio, "selr": log_ratio.mean(dim=-1)}
 
 
 def ensemble_scores(sums: torch.Tensor, ranks: torch.Tensor, count: torch.Tensor, members: int, cells: int):

@@ -2629,6 +2629,59 @@ def isht_backward(gy: torch.Tensor, grid: str, lmax: int, mmax: int) -> torch.Te
     return torch.view_as_complex(out)
 
 
+def sph_power_workspace_bytes(shape, lmax: int, mmax: int) -> int:
+    """bytes of the partials dlwp_sph_power_sums_f32 needs for a rollout of `shape` [B, K, C, nlat, nlon] (at least 8)"""
+    b, k, c, nlat, nlon = (int(s) for s in shape)
+    return max(int(_lib.load().dlwp_sph_power_workspace_bytes(b, k, c, nlat, nlon, int(lmax), int(mmax))), 8)
+
+
+def sph_power_sums(out: torch.Tensor, target: torch.Tensor, grid: str = "legendre-gauss", lmax: Optional[int] = None,
+                   mmax: Optional[int] = None, into: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Spherical power spectrum sums of a rollout and its targets, both [B, K, C, nlat, nlon] float32 on `grid` (row 0 the
+    northernmost latitude) -> double [4, K, C, lmax], summed over b:  0 power(out), 1 power(target), 2 power(out - target) with the
+    difference formed in the field domain, 3 cross(out, target), where with c = sht(x) (the conventions of `sht`)
+      power(x)[l] = sum_{m <= min(l, mmax - 1)} f_m |c[l, m]|^2,   cross(x, y)[l] = sum_m f_m Re(c_x[l, m] conj(c_y[l, m])),
+    f_m = 1 for m = 0 and 2 m = nlon (imaginary part dropped), else 2.  One fused transform-and-reduce kernel and one combining
+    launch (dlwp_sph_power_sums_f32): no coefficient is written to memory.  lmax defaults to nlat, mmax to min(lmax, nlon / 2 + 1).
+    `into`: a [4, K, C, lmax] double tensor of running sums the new ones are ADDED to (dlwp_sph_power_sums_acc_f32: a batch cut
+    anywhere gives the bits of the one-shot call); it is returned.  `workspace`: a uint8 tensor of at least
+    sph_power_workspace_bytes(...) to use instead of one from torch's allocator (metrics.SphericalSpectrumMetrics keeps one).
+    A north-south flip of BOTH inputs on a symmetric grid changes none of the four sums (only the signs of the coefficients
+    with odd l - m change), so south-first data such as WeatherBench's may be passed as it is stored."""
+    from . import sphere as _sph
+
+    _lib.require_cuda_tensor(out, "out")
+    _lib.require_cuda_tensor(target, "target")
+    if out.dim() != 5:
+        raise _lib.DlwpError(f"sph_power_sums: expected a lat-lon rollout [B, K, C, nlat, nlon], got {out.dim()}-D shape "
+                             f"{tuple(out.shape)}")
+    if target.shape != out.shape:
+        raise _lib.DlwpError(f"target shape {tuple(target.shape)} != output shape {tuple(out.shape)}")
+    if target.device != out.device:
+        raise _lib.DlwpError(f"target is on {target.device}, output on {out.device}: both must be on one device")
+    b, k, c, nlat, nlon = (int(s) for s in out.shape)
+    if b < 1 or k < 1 or c < 1:
+        raise _lib.DlwpError(f"sph_power_sums: empty rollout {tuple(out.shape)}")
+    lmax = nlat if lmax is None else int(lmax)
+    mmax = min(lmax, nlon // 2 + 1) if mmax is None else int(mmax)
+    dev = out.device
+    tab = _sph.device_tables(grid, nlat, nlon, lmax, mmax, dev)
+    if into is not None:
+        if not isinstance(into, torch.Tensor) or not into.is_cuda:
+            raise _lib.DlwpError("running sums must be a tensor on an MI355X device")
+        if tuple(into.shape) != (4, k, c, lmax) or into.dtype != torch.float64 or not into.is_contiguous() or into.device != dev:
+            raise _lib.DlwpError(f"running sums must be a contiguous double [4, {k}, {c}, {lmax}] tensor on {dev}")
+    need = sph_power_workspace_bytes(out.shape, lmax, mmax)
+    if workspace is None:
+        workspace = _lib.workspace(need, dev)
+    elif workspace.dtype != torch.uint8 or workspace.device != dev or workspace.numel() < need:
+        raise _lib.DlwpError(f"workspace must be a uint8 tensor of at least {need} bytes on {dev}")
+    sums = into if into is not None else torch.empty(4, k, c, lmax, dtype=torch.float64, device=dev)
+    _lib.launch("dlwp_sph_power_sums_acc_f32" if into is not None else "dlwp_sph_power_sums_f32", dev, out.contiguous(),
+                target.contiguous(), tab.wleg, tab.tw, sums, b, k, c, nlat, nlon, lmax, mmax, workspace, workspace.numel())
+    return sums
+
+
 # The two candidates of each half of the mix backward (tools/bench_sht.py times both; DESIGN.md section 35.7 has the figures and
 # says why these stand):  dgrad "in_place" reads the parameter conjugate-transposed inside the mix kernel, "packed" first makes
 # the degree-major image of the conjugate transpose -- per call, from the values the weight holds NOW (it changes every step:

@@ -21,13 +21,22 @@ import numpy as np
 
 from . import lib as _lib
 
-GRIDS = ("legendre-gauss", "equiangular")
+GRIDS = ("legendre-gauss", "equiangular", "equiangular-centred")
 MAX_NLAT = 256       # the envelope of the kernels (include/dlwp_hip.h)
 MAX_NLON = 512
 
 
 def quadrature(grid: str, nlat: int):
-    """(theta, w): colatitudes in radians, ascending, and the weights of the integral over cos(theta) (they sum to 2)."""
+    """(theta, w): colatitudes in radians, ascending, and the weights of the integral over cos(theta) (they sum to 2).
+
+    "legendre-gauss": the Gauss nodes; exact for polynomials of degree <= 2 nlat - 1, so the Legendre functions are
+    orthonormal under it for l + l' <= 2 nlat - 1: every lmax <= nlat.
+    "equiangular": Clenshaw-Curtis on theta_j = pi j / (nlat - 1), poles included; exact for degree <= nlat - 1 only, so
+    orthonormality holds for l + l' <= nlat - 1.
+    "equiangular-centred": the cell-centred grid theta_j = pi (j + 1/2) / nlat (no pole; the lat-lon grids of the reference data,
+    healpix.reference_grid) with Fejer's first rule, w_j = (2 / nlat) (1 - 2 sum_{k=1}^{nlat // 2} cos(2 k theta_j) / (4 k^2 - 1)).
+    The weights are positive; the rule is exact for degree <= nlat - 1, so, as on "equiangular", orthonormality holds for
+    l + l' <= nlat - 1 only: spectra of fields band-limited below nlat / 2 are exact with lmax = nlat / 2, above that they alias."""
     nlat = int(nlat)
     if grid == "lobatto":
         raise NotImplementedError("grid='lobatto' is not supported (no shipped config uses it)")
@@ -38,6 +47,12 @@ def quadrature(grid: str, nlat: int):
     if grid == "legendre-gauss":
         x, w = np.polynomial.legendre.leggauss(nlat)       # x ascending: south to north
         return np.arccos(x[::-1]).copy(), w[::-1].copy()
+    if grid == "equiangular-centred":
+        theta = math.pi * (np.arange(nlat, dtype=np.float64) + 0.5) / nlat
+        w = np.ones(nlat, dtype=np.float64)
+        for k in range(1, nlat // 2 + 1):
+            w -= 2.0 / (4.0 * k * k - 1.0) * np.cos(2.0 * k * theta)
+        return theta, w * (2.0 / nlat)
     # Clenshaw-Curtis on theta_j = pi j / (nlat - 1), poles included
     n = nlat - 1
     theta = math.pi * np.arange(nlat, dtype=np.float64) / n
@@ -48,6 +63,12 @@ def quadrature(grid: str, nlat: int):
     c = np.full(nlat, 2.0)
     c[0] = c[-1] = 1.0
     return theta, c * w / n
+
+
+def latitudes_deg(grid: str, nlat: int) -> np.ndarray:
+    """the latitudes of the grid's rows in degrees, 90 - theta: row 0 the northernmost"""
+    theta, _ = quadrature(grid, nlat)
+    return 90.0 - np.degrees(theta)
 
 
 def legendre(mmax: int, lmax: int, theta) -> np.ndarray:

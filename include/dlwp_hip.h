@@ -1315,6 +1315,29 @@ int32_t dlwp_sht_f32(const float* x_dev, const float* wleg_dev, const float* tw_
                      int32_t nlat, int32_t nlon, int32_t lmax, int32_t mmax, void* stream);
 int32_t dlwp_isht_f32(const float* coeffs_dev, const float* leg_dev, const float* tw_dev, float* y_dev, int64_t planes,
                       int32_t nlat, int32_t nlon, int32_t lmax, int32_t mmax, void* stream);
+/* Spherical power spectra of a rollout and its targets (csrc/sph_power.hip; the reference has no
+ * spherical spectrum -- PARITY UNPINNED).  out_dev, target_dev [b, k, c, nlat, nlon] fp32, contiguous; wleg_dev, tw_dev: the
+ * forward tables of dlwp_sht_f32, in its envelope (DLWP_ERR_UNSUPPORTED outside it).  With c = sht(x) and f_m = 1 for m = 0 and
+ * 2 m = nlon (the imaginary part of c is dropped there, as dlwp_isht_f32 ignores it), f_m = 2 otherwise,
+ *   power(x)[l] = sum_{m <= min(l, mmax - 1)} f_m |c[l][m]|^2,   cross(x, y)[l] = sum_m f_m Re(c_x[l][m] conj c_y[l][m]).
+ * sums_dev: double [4, k, c, lmax], written by the call (dlwp_sph_power_sums_f32) or added to (dlwp_sph_power_sums_acc_f32):
+ *   0: sum_b power(out)   1: sum_b power(target)   2: sum_b power(out - target)   3: sum_b cross(out, target)
+ * The difference of index 2 is formed in the FIELD domain, in fp32, before it is transformed.  A north-south flip of both
+ * inputs on a symmetric grid changes none of the four.  fp32 transforms (the two stages of dlwp_sht_f32; no coefficient is
+ * written to memory), fp64 from the squares on.  First launch: one fp64 partial per ((b, k, c), m tile, quantity, l) into the
+ * workspace, the terms of a degree added over the tile's m in ascending order; second launch: one thread per (quantity, k, c, l)
+ * adds the partials in one chain, b ascending and m tiles ascending inside a b, starting from zero or (_acc) from what sums_dev
+ * holds -- a batch cut anywhere and fed through _acc gives the bits of the one-shot call.  The tiling depends on (nlat, nlon,
+ * lmax, mmax) alone.  No atomics, no host synchronisation; tw_dev, sums_dev and workspace_dev 8-byte aligned.
+ *   dlwp_sph_power_workspace_bytes: the partials (0 for a shape outside the envelope); a smaller workspace returns
+ *   DLWP_ERR_WORKSPACE. */
+size_t dlwp_sph_power_workspace_bytes(int32_t b, int32_t k, int32_t c, int32_t nlat, int32_t nlon, int32_t lmax, int32_t mmax);
+int32_t dlwp_sph_power_sums_f32(const float* out_dev, const float* target_dev, const float* wleg_dev, const float* tw_dev,
+                                double* sums_dev, int32_t b, int32_t k, int32_t c, int32_t nlat, int32_t nlon, int32_t lmax,
+                                int32_t mmax, void* workspace_dev, size_t workspace_bytes, void* stream);
+int32_t dlwp_sph_power_sums_acc_f32(const float* out_dev, const float* target_dev, const float* wleg_dev, const float* tw_dev,
+                                    double* sums_dev, int32_t b, int32_t k, int32_t c, int32_t nlat, int32_t nlon, int32_t lmax,
+                                    int32_t mmax, void* workspace_dev, size_t workspace_bytes, void* stream);
 /* Driscoll-Healy spectral convolution: c_out[b][o][l][m] = sum_i c_in[b][i][l][m] * weight[i][o][l] (complex) for
  * m <= min(l, mmax - 1); every other entry of c_out is written as zero and no entry of c_in with m > l is read.
  *   c_in_dev [batch, cin, lmax, mmax, 2], weight_dev [cin, cout, lmax, 2], c_out_dev [batch, cout, lmax, mmax, 2].

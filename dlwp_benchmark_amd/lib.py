@@ -383,6 +383,15 @@ def require_cuda_tensor(t, name: str):
         raise DlwpError(f"{name} must be float32 (got {t.dtype})")
 
 
+def require_running_sums(into, shape, device):
+    """`into`: the running sums an `*_acc` entry point adds to, a contiguous double tensor of `shape` on `device`."""
+    import torch
+
+    if (not isinstance(into, torch.Tensor) or not into.is_cuda or tuple(into.shape) != tuple(shape) or into.dtype != torch.float64
+            or not into.is_contiguous() or into.device != device):
+        raise DlwpError(f"running sums must be a contiguous double {list(shape)} tensor on the MI355X device {device}")
+
+
 def stream_ptr():
     import torch
 

@@ -23,8 +23,10 @@ through dlwp_ensemble_sums_acc_f32 (csrc/ensemble_scores.hip).  The reference ha
 and to their spectral coherence, through one fused spherical-harmonic transform-and-reduce kernel (csrc/sph_power.hip; DESIGN.md
 section 36).  The reference has no spherical spectrum: PARITY UNPINNED.
 
-All five classes also take HEALPix rollouts [B, K, C, 12, n, n] when they are given the longitudes of the lat-lon grid beside its
-latitudes: the reference remaps inits, outputs and targets to lat-lon before every metric (scripts/evaluate.py:298-303,
+The five classes differ in their kernel and their scores; everything around them is `_Scorer`'s, defined once: the checks on an
+(out, target) pair, the device copies of host constants, the kernel workspace, the cross-rank all-reduce, and HEALPix input.
+All five take HEALPix rollouts [B, K, C, 12, n, n] when they are given the longitudes of the lat-lon grid beside its latitudes:
+the reference remaps inits, outputs and targets to lat-lon before every metric (scripts/evaluate.py:298-303,
 scripts/train.py:430-441), on the host; here `ops.healpix_to_latlon` does it on the device, a chunk of samples at a time into one
 reused workspace, and the sums accumulate through the `*_acc` entry points.
 """
@@ -45,98 +47,153 @@ def latitude_weights(lats_deg: torch.Tensor) -> torch.Tensor:
 DEFAULT_WORKSPACE_BYTES = 256 << 20
 
 
-class _HealpixInput:
-    """What the metric classes share for HEALPix rollouts [B, K, C, 12, n, n]: the target grid and one workspace per device
-    that holds a chunk of samples of `out` and of `target` remapped to lat-lon, within `max_workspace_bytes`."""
+class _Scorer:
+    """What the metric classes share.  `constants`: host tensors (or None) the kernel reads, copied to a device on first use.
+    `lons_deg`: the longitudes of the lat-lon grid; with them HEALPix input is remapped to (lats_deg, lons_deg) on the device in
+    chunks of samples whose lat-lon copies stay within `max_workspace_bytes`, without them it is refused."""
 
-    def _init_remap(self, lats_deg, lons_deg, max_workspace_bytes):
+    def __init__(self, lats_deg, lons_deg, max_workspace_bytes, group, constants=()):
         self._lats = torch.as_tensor(lats_deg).detach().double().cpu().reshape(-1).numpy()
         self._lons = None if lons_deg is None else torch.as_tensor(lons_deg).detach().double().cpu().reshape(-1).numpy()
         self.max_workspace_bytes = int(max_workspace_bytes)
-        self._remap_ws = {}   # device -> float32 workspace, grown when a shape needs more
+        self.group = group
+        self._constants = tuple(constants)
+        self._dev = {}        # device -> the constants on it
+        self._ws = {}         # device -> kernel workspaces, the last one the largest and the one in use
+        self._remap_ws = {}   # device -> float32 remap workspace, replaced when a shape needs more
 
-    def _require_remap(self, out, target):
-        if self._lons is None:
-            raise _lib.DlwpError(f"got a {out.dim()}-D rollout {tuple(out.shape)}: a HEALPix rollout [B, K, C, 12, n, n] is remapped "
-                                 "to lat-lon only when the metric is built with `lons_deg` (the longitudes of the lat-lon grid)")
-        _lib.require_cuda_tensor(out, "out")
-        _lib.require_cuda_tensor(target, "target")
+    def _on(self, dev):
+        """The constants on `dev`, in the order given to __init__ (None stays None), copied once."""
+        key = str(dev)
+        if key not in self._dev:
+            self._dev[key] = tuple(t.to(dev).contiguous() if t is not None else None for t in self._constants)
+        return self._dev[key]
+
+    def _workspace(self, dev, nbytes):
+        """One kernel workspace per device, shared by every shape: a shape that needs more replaces it by one at least twice as
+        large.  The replaced ones stay allocated because a recorded step (sharding.CapturedStep) keeps the address it was
+        recorded with; with the doubling they add up to less than the one in use."""
+        n = max(int(nbytes), 8)
+        bufs = self._ws.setdefault(str(dev), [])
+        if not bufs or bufs[-1].numel() < n:
+            bufs.append(torch.empty(max(n, 2 * bufs[-1].numel()) if bufs else n, dtype=torch.uint8, device=dev))
+        return bufs[-1]
+
+    def _pair_shape(self, out, target, name="out", lead=""):
+        """(B, K, C, H, W) of two tensors of one shape: lat-lon [B, K, C, H, W], or HEALPix [B, K, C, 12, n, n] when the metric
+        has longitudes, with the H, W of its grid.  Looks at no device, so a caller may put host-side checks of its own next.
+        `name`, `lead`: what the caller's argument is called and the dimensions it has in front of these (EnsembleMetrics
+        passes a member of `ens` and "M, "), for the messages."""
+        if not isinstance(out, torch.Tensor) or not isinstance(target, torch.Tensor):
+            raise _lib.DlwpError(f"{name} and target must be tensors")
         if target.shape != out.shape:
-            raise _lib.DlwpError(f"target shape {tuple(target.shape)} != output shape {tuple(out.shape)}")
-        if target.device != out.device:
-            raise _lib.DlwpError(f"target is on {target.device}, output on {out.device}: both must be on one device")
+            raise _lib.DlwpError(f"target shape {tuple(target.shape)} != {'member' if lead else 'output'} shape "
+                                 f"{tuple(out.shape)}")
+        if out.dim() == 5:
+            return tuple(out.shape)
+        if out.dim() == 6 and self._lons is not None:
+            return tuple(out.shape[:3]) + (len(self._lats), len(self._lons))
+        raise _lib.DlwpError(f"expected lat-lon `{name}` [{lead}B, K, C, H, W], got {'members of ' if lead else ''}{out.dim()}-D "
+                             f"shape {tuple(out.shape)}: HEALPix input [{lead}B, K, C, 12, n, n] is remapped to lat-lon only when "
+                             "the metric is built with `lons_deg` (the longitudes of the lat-lon grid)")
 
-    def _remapped_chunks(self, out, target):
-        """Yields (out, target) as lat-lon [m, K, C, H, W] views of the workspace, m samples at a time, in sample order.  A
-        pair is valid until the next one is asked for."""
+    @staticmethod
+    def _pair_device(out, target, name="out"):
+        """The one MI355X device both float32 tensors are on."""
+        _lib.require_cuda_tensor(out, name)
+        _lib.require_cuda_tensor(target, "target")
+        if target.device != out.device:
+            raise _lib.DlwpError(f"target is on {target.device}, {name} on {out.device}: both must be on one device")
+        return out.device
+
+    def _check_pair(self, out, target, name="out", lead=""):
+        shape = self._pair_shape(out, target, name, lead)
+        self._pair_device(out, target, name)
+        return shape
+
+    def _remapped_chunks(self, *tensors):
+        """Yields the sample-major HEALPix tensors [B, K, C, 12, n, n] as lat-lon [m, K, C, H, W] views of the workspace, one per
+        tensor in the order given, m samples at a time in sample order: max_workspace_bytes // (4 x tensors x floats per sample)
+        of them, every tensor's share of a sample in the same chunk.  The views are valid until the next ones are asked for.
+        Layout, which callers may rely on: the views of one chunk lie one fixed distance apart in the workspace, in the order
+        given, so the first M of them are one block of M planes `views[1].storage_offset() - views[0].storage_offset()` floats
+        apart (what dlwp_ensemble_sums_acc_f32 takes as its members).
+        The workspace is exactly as large as the shape needs and is REPLACED by a larger one when a later shape needs more --
+        `max_workspace_bytes` bounds it, which doubling would not respect -- so a recorded step (sharding.CapturedStep), which
+        keeps the address it was recorded with, must not see a growing HEALPix shape."""
         from . import ops as _ops
 
-        b, k, c = out.shape[:3]
+        b, k, c = tensors[0].shape[:3]
         h, w = len(self._lats), len(self._lons)
+        n = len(tensors)
         per = k * c * h * w                                    # floats of one sample of one tensor
-        chunk = min(b, self.max_workspace_bytes // (8 * per)) if per else b
+        chunk = min(b, self.max_workspace_bytes // (4 * n * per)) if per else b
         if chunk < 1:
-            raise _lib.DlwpError(f"max_workspace_bytes = {self.max_workspace_bytes} does not hold one sample of the rollout and "
-                                 f"of the target on the {h}x{w} grid ({8 * per} bytes)")
-        key = str(out.device)
-        buf = self._remap_ws.get(key)
-        if buf is None or buf.numel() < 2 * chunk * per:
-            buf = self._remap_ws[key] = torch.empty(2 * chunk * per, dtype=torch.float32, device=out.device)
+            raise _lib.DlwpError(f"max_workspace_bytes = {self.max_workspace_bytes} does not hold one sample of the {n} tensors "
+                                 f"on the {h}x{w} grid ({4 * n * per} bytes)")
+        dev = tensors[0].device
+        buf = self._remap_ws.get(str(dev))
+        if buf is None or buf.numel() < n * chunk * per:
+            buf = self._remap_ws[str(dev)] = torch.empty(n * chunk * per, dtype=torch.float32, device=dev)
         for b0 in range(0, b, chunk):
             m = min(chunk, b - b0)
-            o = buf[:m * per].view(m, k, c, h, w)
-            t = buf[chunk * per:chunk * per + m * per].view(m, k, c, h, w)
-            _ops.healpix_to_latlon(out[b0:b0 + m], self._lats, self._lons, out=o)
-            _ops.healpix_to_latlon(target[b0:b0 + m], self._lats, self._lons, out=t)
-            yield o, t
+            views = [buf[i * chunk * per:i * chunk * per + m * per].view(m, k, c, h, w) for i in range(n)]
+            for x, v in zip(tensors, views):
+                _ops.healpix_to_latlon(x[b0:b0 + m], self._lats, self._lons, out=v)
+            yield views
+
+    def _healpix_sums(self, out, target, into, shape):
+        """`sums` of a HEALPix pair: remapped chunk by chunk and summed into `into`, or into zero-initialised sums of `shape`."""
+        sums = into if into is not None else torch.zeros(shape, dtype=torch.float64, device=out.device)
+        for o, t in self._remapped_chunks(out, target):
+            self.sums(o, t, into=sums)
+        return sums
+
+    def _reduce(self, buf):
+        """A 1-D double tensor summed over the ranks of `self.group`, on the device it came from: it travels through the host
+        unless the group's backend is nccl."""
+        import torch.distributed as dist
+
+        dev = buf.device
+        if dist.get_backend(self.group) != "nccl":
+            buf = buf.cpu()
+        dist.all_reduce(buf, group=self.group)
+        return buf.to(dev)
+
+    def _reduce_sums(self, s, n_samples):
+        """(sums, sample count) over all ranks in ONE all-reduce: the count travels with the sums (shards may differ in size)."""
+        buf = torch.empty(s.numel() + 1, dtype=torch.float64, device=s.device)
+        buf[:-1].copy_(s.flatten())
+        buf[-1:].fill_(n_samples)
+        buf = self._reduce(buf)
+        return buf[:-1].view_as(s), buf[-1:]
 
 
-class RolloutMetrics(_HealpixInput):
+class RolloutMetrics(_Scorer):
     def __init__(self, lats_deg: torch.Tensor, std: Optional[torch.Tensor] = None,
                  climatology: Optional[torch.Tensor] = None, group=None, lons_deg=None,
                  max_workspace_bytes: int = DEFAULT_WORKSPACE_BYTES):
         """`lons_deg`: the longitudes of the lat-lon grid; with them `sums` and `__call__` also take HEALPix rollouts
         [B, K, C, 12, n, n], remapped to (lats_deg, lons_deg) on the device in chunks of samples whose lat-lon copies stay within
         `max_workspace_bytes`.  Climatology and latitude weights are lat-lon either way."""
-        self._init_remap(lats_deg, lons_deg, max_workspace_bytes)
         self.latw = latitude_weights(lats_deg)
         self.std = std.float() if std is not None else None
         self.clim = climatology.float() if climatology is not None else None
-        self.group = group
-        self._dev = {}   # device -> (latw, std, clim) copies made once
-
-    def _on(self, dev):
-        key = str(dev)
-        if key not in self._dev:
-            self._dev[key] = (self.latw.to(dev).contiguous(),
-                              self.std.to(dev).contiguous() if self.std is not None else None,
-                              self.clim.to(dev).contiguous() if self.clim is not None else None)
-        return self._dev[key]
+        super().__init__(lats_deg, lons_deg, max_workspace_bytes, group, (self.latw, self.std, self.clim))
 
     def sums(self, out: torch.Tensor, target: torch.Tensor, into: Optional[torch.Tensor] = None) -> torch.Tensor:
         """double [4, K, C] sums of this rank's samples (see dlwp_weighted_error_sums_f32).  `into`: a [4, K, C] double tensor
         of running sums the new ones are ADDED to (dlwp_weighted_error_sums_acc_f32: one launch per batch, no zero-fill, no add
         kernel); it is returned.  A HEALPix rollout [B, K, C, 12, n, n] (see `lons_deg`) is remapped chunk by chunk and summed
         into zero-initialised (or `into`) sums."""
-        if isinstance(out, torch.Tensor) and out.dim() == 6:
-            self._require_remap(out, target)
-            sums = into if into is not None else torch.zeros(4, out.shape[1], out.shape[2], dtype=torch.float64, device=out.device)
-            for o, t in self._remapped_chunks(out, target):
-                self.sums(o, t, into=sums)
-            return sums
-        _lib.require_cuda_tensor(out, "out")
-        _lib.require_cuda_tensor(target, "target")
+        b, k, c, h, w = self._check_pair(out, target)
+        if out.dim() == 6:
+            return self._healpix_sums(out, target, into, (4, k, c))
         out, target = out.contiguous(), target.contiguous()
-        b, k, c, h, w = out.shape
-        if target.shape != out.shape:
-            raise _lib.DlwpError(f"target shape {tuple(target.shape)} != output shape {tuple(out.shape)}")
         dev = out.device
         latw, std, clim = self._on(dev)
         if into is not None:
-            if not isinstance(into, torch.Tensor) or not into.is_cuda:
-                raise _lib.DlwpError("running sums must be a tensor on an MI355X device")
-            if tuple(into.shape) != (4, k, c) or into.dtype != torch.float64 or not into.is_contiguous() or into.device != dev:
-                raise _lib.DlwpError(f"running sums must be a contiguous double [4, {k}, {c}] tensor on {dev}")
+            _lib.require_running_sums(into, (4, k, c), dev)
         sums = into if into is not None else torch.empty(4, k, c, dtype=torch.float64, device=dev)
         _lib.launch("dlwp_weighted_error_sums_acc_f32" if into is not None else "dlwp_weighted_error_sums_f32", dev, out, target,
                     clim, latw, std, sums, b, k, c, h, w)
@@ -153,18 +210,7 @@ class RolloutMetrics(_HealpixInput):
         n_samples = how many samples went into them, cells = H * W.  With world_size > 1 ONE all-reduce moves the sums
         and the sample count (shards may differ in size): the only collective of a sharded evaluation."""
         if world_size > 1:
-            import torch.distributed as dist
-
-            host = dist.get_backend(self.group) != "nccl"
-            dev = s.device
-            buf = torch.empty(s.numel() + 1, dtype=torch.float64, device=dev)
-            buf[:-1].copy_(s.flatten())
-            buf[-1:].fill_(n_samples)   # the count travels with the sums
-            if host:
-                buf = buf.cpu()
-            dist.all_reduce(buf, group=self.group)
-            buf = buf.to(dev)
-            s, n_samples = buf[:-1].view_as(s), buf[-1:]
+            s, n_samples = self._reduce_sums(s, n_samples)
         count = n_samples * cells
         rmse = torch.sqrt(s[0] / count)
         acc = s[1] / torch.sqrt(s[2] * s[3]) if self.clim is not None else None
@@ -237,7 +283,7 @@ def soundness_scores(zonal: torch.Tensor, window: Optional[torch.Tensor], steps:
             "rmse": rmse, "rmse_window": rmse_window}
 
 
-class SoundnessMetrics(_HealpixInput):
+class SoundnessMetrics(_Scorer):
     """The physical-soundness evaluation of reference scripts/evaluate.py:832-872 for rollouts of any length, streamed: feed the
     rollout and its truth chunk by chunk (`update`), in step order, and `finalize` gives the RMSE of the time-and-longitude mean
     per latitude band (global, trade winds, south westerlies by default) and the RMSE of the field averaged over the lead-time
@@ -249,20 +295,18 @@ class SoundnessMetrics(_HealpixInput):
     `step_days`: the model's time step in days (rollout step k has lead time (k + 1) step_days, evaluate.py:346-347).  `std`:
     the per-variable de-normalisation scale [C] of evaluate.py:281-296, as in RolloutMetrics (the means cancel).  `bands`:
     {name: None or [(lat_lo, lat_hi), ...]}, closed intervals.  With `lons_deg` HEALPix chunks [B, K, C, 12, n, n] are taken too
-    and remapped to (lats_deg, lons_deg) on the device like in the other two classes; without it they are refused.  Samples are
-    sharded over ranks: `finalize(world_size)` moves the squares and the sample count in ONE all-reduce."""
+    and remapped to (lats_deg, lons_deg) on the device (see `_Scorer`); without it they are refused.  Samples are sharded over
+    ranks: `finalize(world_size)` moves the squares and the sample count in ONE all-reduce."""
 
     def __init__(self, lats_deg, step_days: float, std: Optional[torch.Tensor] = None, bands=None, window_days=(334.0, 365.0),
                  group=None, lons_deg=None, max_workspace_bytes: int = DEFAULT_WORKSPACE_BYTES):
-        self._init_remap(lats_deg, lons_deg, max_workspace_bytes)
+        super().__init__(lats_deg, lons_deg, max_workspace_bytes, group)
         self.height = len(self._lats)
         self.step_days = float(step_days)
         self.window_days = (float(window_days[0]), float(window_days[1]))
         self.window = window_steps(self.step_days, self.window_days)      # rollout steps [first, last + 1)
         self.bands = dict(DEFAULT_BANDS if bands is None else bands)
         self.std = std.detach().double() if std is not None else None
-        self.group = group
-        self._scratch = {}
         self.reset()
 
     def reset(self):
@@ -300,23 +344,10 @@ class SoundnessMetrics(_HealpixInput):
     def update(self, out: torch.Tensor, target: torch.Tensor, step_begin: int):
         """Adds a chunk [B, K, C, H, W] (or HEALPix [B, K, C, 12, n, n], see `lons_deg`) of K consecutive rollout steps, the first
         of which is rollout step `step_begin`.  Chunks arrive in step order, each with the same B, C, H, W on one device."""
-        if not isinstance(out, torch.Tensor) or not isinstance(target, torch.Tensor):
-            raise _lib.DlwpError("out and target must be tensors")
-        if target.shape != out.shape:
-            raise _lib.DlwpError(f"target shape {tuple(target.shape)} != output shape {tuple(out.shape)}")
+        b, k, c, h, w = self._pair_shape(out, target)
         if int(step_begin) != self.steps:
             raise _lib.DlwpError(f"chunks must arrive in order: this one starts at rollout step {step_begin}, "
                                  f"{self.steps} steps have been seen")
-        hpx = out.dim() == 6
-        if hpx:
-            self._require_remap(out, target)
-            b, k, c = out.shape[:3]
-            h, w = self.height, len(self._lons)
-        elif out.dim() == 5:
-            b, k, c, h, w = out.shape
-        else:
-            raise _lib.DlwpError(f"expected a chunk [B, K, C, H, W], got {out.dim()}-D shape {tuple(out.shape)} (a HEALPix "
-                                 "chunk [B, K, C, 12, n, n] is remapped to lat-lon only when the metric is built with `lons_deg`)")
         if h != self.height:
             raise _lib.DlwpError(f"{h} latitudes in the chunk, {self.height} given to the metric")
         if self.std is not None and self.std.numel() != c:
@@ -325,12 +356,9 @@ class SoundnessMetrics(_HealpixInput):
             raise _lib.DlwpError(f"empty chunk {tuple(out.shape)}")
         if self._geom is not None and (b, c, h, w) != self._geom[:4]:
             raise _lib.DlwpError(f"chunk with (B, C, H, W) = {(b, c, h, w)} after chunks with {self._geom[:4]}")
-        _lib.require_cuda_tensor(out, "out")
-        _lib.require_cuda_tensor(target, "target")
-        dev = out.device
-        if target.device != dev or (self._geom is not None and dev != self._geom[4]):
-            raise _lib.DlwpError(f"out is on {dev}, target on {target.device}"
-                                 + (f", the sums on {self._geom[4]}" if self._geom is not None else "") + ": one device is needed")
+        dev = self._pair_device(out, target)
+        if self._geom is not None and dev != self._geom[4]:
+            raise _lib.DlwpError(f"the chunk is on {dev}, the sums on {self._geom[4]}: one device is needed")
         wb, we = self.chunk_window(self.steps, k)
         if self._geom is None:
             self._geom = (b, c, h, w, dev)
@@ -338,7 +366,7 @@ class SoundnessMetrics(_HealpixInput):
         if we > wb and self._window is None:                 # on first need: most chunks of a year never reach the window
             self._window = torch.zeros(2, b, c, h, w, dtype=torch.float64, device=dev)
         win = self._window if we > wb else None
-        if not hpx:
+        if out.dim() == 5:
             _lib.launch("dlwp_climate_sums_acc_f32", dev, out.contiguous(), target.contiguous(), self._zonal, win,
                         b, k, c, h, w, wb, we)
         else:
@@ -363,23 +391,11 @@ class SoundnessMetrics(_HealpixInput):
         """{"zonal_mean_pred", "zonal_mean_true": [B, C, H], "window_mean_pred", "window_mean_true": [B, C, H, W] or None (this
         rank's samples), "rmse": {band: [C]}, "rmse_window": [C] or None (ALL ranks' samples)}, float64 on the sums' device.  A
         rollout that never reached the window gives None for the window's entries.  With world_size > 1 ONE all-reduce moves
-        [the sum of squares of every score, the sample count] (shards may differ in size): host tensors unless the group's
-        backend is nccl, as in RolloutMetrics.finalize."""
+        [the sum of squares of every score, the sample count] (shards may differ in size)."""
         if self._zonal is None or self.steps == 0:
             raise _lib.DlwpError("finalize() before any chunk: call update() first")
-        reduce = None
-        if world_size > 1:
-            import torch.distributed as dist
-
-            def reduce(buf):
-                host = dist.get_backend(self.group) != "nccl"
-                dev = buf.device
-                if host:
-                    buf = buf.cpu()
-                dist.all_reduce(buf, group=self.group)
-                return buf.to(dev)
         return soundness_scores(self._zonal, self._window, self.steps, self.n_window_steps, self._geom[3], self._lats, self.bands,
-                                self.std, all_reduce=reduce)
+                                self.std, all_reduce=self._reduce if world_size > 1 else None)
 
 
 EARTH_RADIUS_M = 1000 * (6357 + 6378) / 2   # reference scripts/losses.py:13
@@ -391,7 +407,7 @@ def circumference_weights(lats_deg: torch.Tensor) -> torch.Tensor:
     return torch.cos(lats_deg.double() * (math.pi / 180)) * (2 * math.pi * EARTH_RADIUS_M)
 
 
-class ZonalSpectrumMetrics(_HealpixInput):
+class ZonalSpectrumMetrics(_Scorer):
     """Zonal energy spectra of a rollout [B, K, C, H, W] and its targets, and their mean energy log ratio (reference
     scripts/losses.py:16-152, `ZonalSpectrum` + `MELRCalculator`), reduced on the device (dlwp_zonal_power_sums_f32).
 
@@ -405,64 +421,27 @@ class ZonalSpectrumMetrics(_HealpixInput):
     copies stay within `max_workspace_bytes`; without it they are refused."""
 
     def __init__(self, lats_deg: torch.Tensor, group=None, lons_deg=None, max_workspace_bytes: int = DEFAULT_WORKSPACE_BYTES):
-        self._init_remap(lats_deg, lons_deg, max_workspace_bytes)
         self.circ = circumference_weights(torch.as_tensor(lats_deg))
         self.height = int(self.circ.numel())
-        self.group = group
-        self._dev = {}   # device -> circumference weights on it
-        self._ws = {}    # device -> workspaces, the last one the largest and the one in use
-
-    def _on(self, dev):
-        key = str(dev)
-        if key not in self._dev:
-            self._dev[key] = self.circ.to(dev).contiguous()
-        return self._dev[key]
-
-    def _workspace(self, dev, shape):
-        """One workspace per device, shared by every shape: a shape that needs more replaces it by one at least twice as large.
-        The replaced ones stay allocated because a recorded step (sharding.CapturedStep) keeps the address it was recorded
-        with; with the doubling they add up to less than the one in use."""
-        n = max(int(_lib.load().dlwp_zonal_power_workspace_bytes(*shape)), 8)
-        bufs = self._ws.setdefault(str(dev), [])
-        if not bufs or bufs[-1].numel() < n:
-            bufs.append(torch.empty(max(n, 2 * bufs[-1].numel()) if bufs else n, dtype=torch.uint8, device=dev))
-        return bufs[-1]
+        super().__init__(lats_deg, lons_deg, max_workspace_bytes, group, (self.circ,))
 
     def sums(self, out: torch.Tensor, target: torch.Tensor, into: Optional[torch.Tensor] = None) -> torch.Tensor:
         """double [2, K, C, W//2 + 1]: 0 = sum over this rank's samples and latitudes of circ_h P(out), 1 = of P(target)
         (dlwp_zonal_power_sums_f32).  `into`: a [2, K, C, W//2 + 1] double tensor of running sums the new ones are ADDED to
         (dlwp_zonal_power_sums_acc_f32); it is returned.  A HEALPix rollout [B, K, C, 12, n, n] (see `lons_deg`) is remapped chunk
         by chunk and summed into zero-initialised (or `into`) sums."""
-        _lib.require_cuda_tensor(out, "out")
-        _lib.require_cuda_tensor(target, "target")
-        if out.dim() == 6 and self._lons is not None:
-            self._require_remap(out, target)
-            sums = into if into is not None else torch.zeros(2, out.shape[1], out.shape[2], len(self._lons) // 2 + 1,
-                                                             dtype=torch.float64, device=out.device)
-            for o, t in self._remapped_chunks(out, target):
-                self.sums(o, t, into=sums)
-            return sums
-        if out.dim() != 5:
-            raise _lib.DlwpError(f"zonal spectrum: expected a lat-lon rollout [B, K, C, H, W], got {out.dim()}-D shape "
-                                 f"{tuple(out.shape)} (a HEALPix rollout [B, K, C, 12, n, n] is remapped to lat-lon only when the "
-                                 "metric is built with `lons_deg`)")
-        if target.shape != out.shape:
-            raise _lib.DlwpError(f"target shape {tuple(target.shape)} != output shape {tuple(out.shape)}")
-        if target.device != out.device:
-            raise _lib.DlwpError(f"target is on {target.device}, output on {out.device}: both must be on one device")
-        b, k, c, h, w = out.shape
+        b, k, c, h, w = self._check_pair(out, target)
+        nb = w // 2 + 1
+        if out.dim() == 6:
+            return self._healpix_sums(out, target, into, (2, k, c, nb))
         if h != self.height:
             raise _lib.DlwpError(f"zonal spectrum: {h} latitudes in the rollout, {self.height} given to the metric")
         out, target = out.contiguous(), target.contiguous()
         dev = out.device
-        nb = w // 2 + 1
         if into is not None:
-            if not isinstance(into, torch.Tensor) or not into.is_cuda:
-                raise _lib.DlwpError("running sums must be a tensor on an MI355X device")
-            if tuple(into.shape) != (2, k, c, nb) or into.dtype != torch.float64 or not into.is_contiguous() or into.device != dev:
-                raise _lib.DlwpError(f"running sums must be a contiguous double [2, {k}, {c}, {nb}] tensor on {dev}")
-        circ = self._on(dev)
-        ws = self._workspace(dev, (b, k, c, h, w))
+            _lib.require_running_sums(into, (2, k, c, nb), dev)
+        circ, = self._on(dev)
+        ws = self._workspace(dev, _lib.load().dlwp_zonal_power_workspace_bytes(b, k, c, h, w))
         sums = into if into is not None else torch.empty(2, k, c, nb, dtype=torch.float64, device=dev)
         _lib.launch("dlwp_zonal_power_sums_acc_f32" if into is not None else "dlwp_zonal_power_sums_f32", dev, out, target, circ,
                     sums, b, k, c, h, w, ws, ws.numel())
@@ -478,24 +457,13 @@ class ZonalSpectrumMetrics(_HealpixInput):
         count (shards may differ in size).  Returns {"energy_pred", "energy_true", "log_ratio": [K, C, W//2 + 1],
         "melr": [K, C]} in float64."""
         if world_size > 1:
-            import torch.distributed as dist
-
-            host = dist.get_backend(self.group) != "nccl"
-            dev = s.device
-            buf = torch.empty(s.numel() + 1, dtype=torch.float64, device=dev)
-            buf[:-1].copy_(s.flatten())
-            buf[-1:].fill_(n_samples)   # the count travels with the sums
-            if host:
-                buf = buf.cpu()
-            dist.all_reduce(buf, group=self.group)
-            buf = buf.to(dev)
-            s, n_samples = buf[:-1].view_as(s), buf[-1:]
+            s, n_samples = self._reduce_sums(s, n_samples)
         energy = s / (n_samples * self.height)
         log_ratio = torch.log((energy[0] + MELR_EPS) / (energy[1] + MELR_EPS))
         return {"energy_pred": energy[0], "energy_true": energy[1], "log_ratio": log_ratio, "melr": log_ratio.mean(dim=-1)}
 
 
-class SphericalSpectrumMetrics(_HealpixInput):
+class SphericalSpectrumMetrics(_Scorer):
     """Power per total wavenumber l of a rollout [B, K, C, nlat, nlon], of its targets and of their difference, and the
     spectral coherence between rollout and target, on `grid` ("legendre-gauss", "equiangular" or "equiangular-centred": the
     cell-centred lat-lon grids of the data, healpix.reference_grid), reduced on the device by one fused transform-and-reduce
@@ -526,21 +494,9 @@ class SphericalSpectrumMetrics(_HealpixInput):
         self.lmax = self.nlat if lmax is None else int(lmax)
         self.mmax = min(self.lmax, self.nlon // 2 + 1) if mmax is None else int(mmax)
         _sph.check_range(self.nlat, self.nlon, self.lmax, self.mmax)
-        self._init_remap(_sph.latitudes_deg(grid, self.nlat), lons_deg, max_workspace_bytes)
+        super().__init__(_sph.latitudes_deg(grid, self.nlat), lons_deg, max_workspace_bytes, group)
         if self._lons is not None and len(self._lons) != self.nlon:
             raise _lib.DlwpError(f"spherical spectrum: {len(self._lons)} longitudes in lons_deg, nlon = {self.nlon}")
-        self.group = group
-        self._ws = {}    # device -> workspaces, the last one the largest and the one in use
-
-    def _workspace(self, dev, shape):
-        """One workspace per device that only grows (ZonalSpectrumMetrics._workspace: a recorded step keeps its address)."""
-        from . import ops as _ops
-
-        n = _ops.sph_power_workspace_bytes(shape, self.lmax, self.mmax)
-        bufs = self._ws.setdefault(str(dev), [])
-        if not bufs or bufs[-1].numel() < n:
-            bufs.append(torch.empty(max(n, 2 * bufs[-1].numel()) if bufs else n, dtype=torch.uint8, device=dev))
-        return bufs[-1]
 
     def sums(self, out: torch.Tensor, target: torch.Tensor, into: Optional[torch.Tensor] = None) -> torch.Tensor:
         """double [4, K, C, lmax] sums over this rank's samples (see the class; dlwp_sph_power_sums_f32).  `into`: a
@@ -549,26 +505,13 @@ class SphericalSpectrumMetrics(_HealpixInput):
         `into`) sums: the chain of every sum runs over the samples in order, so the chunk size does not change a bit."""
         from . import ops as _ops
 
-        _lib.require_cuda_tensor(out, "out")
-        _lib.require_cuda_tensor(target, "target")
-        if out.dim() == 6 and self._lons is not None:
-            self._require_remap(out, target)
-            sums = into if into is not None else torch.zeros(4, out.shape[1], out.shape[2], self.lmax, dtype=torch.float64,
-                                                             device=out.device)
-            for o, t in self._remapped_chunks(out, target):
-                self.sums(o, t, into=sums)
-            return sums
-        if out.dim() != 5:
-            raise _lib.DlwpError(f"spherical spectrum: expected a lat-lon rollout [B, K, C, nlat, nlon], got {out.dim()}-D shape "
-                                 f"{tuple(out.shape)} (a HEALPix rollout [B, K, C, 12, n, n] is remapped to lat-lon only when the "
-                                 "metric is built with `lons_deg`)")
-        if tuple(out.shape[-2:]) != (self.nlat, self.nlon):
-            raise _lib.DlwpError(f"spherical spectrum: a {out.shape[-2]}x{out.shape[-1]} rollout, the metric was built for "
-                                 f"{self.nlat}x{self.nlon}")
-        if target.shape != out.shape:
-            raise _lib.DlwpError(f"target shape {tuple(target.shape)} != output shape {tuple(out.shape)}")
-        return _ops.sph_power_sums(out, target, self.grid, self.lmax, self.mmax, into=into,
-                                   workspace=self._workspace(out.device, out.shape))
+        b, k, c, h, w = self._check_pair(out, target)
+        if out.dim() == 6:
+            return self._healpix_sums(out, target, into, (4, k, c, self.lmax))
+        if (h, w) != (self.nlat, self.nlon):
+            raise _lib.DlwpError(f"spherical spectrum: a {h}x{w} rollout, the metric was built for {self.nlat}x{self.nlon}")
+        ws = self._workspace(out.device, _ops.sph_power_workspace_bytes(out.shape, self.lmax, self.mmax))
+        return _ops.sph_power_sums(out, target, self.grid, self.lmax, self.mmax, into=into, workspace=ws)
 
     def __call__(self, out: torch.Tensor, target: torch.Tensor, world_size: int = 1):
         """Spectra, coherence and log ratio over ALL ranks' samples (see finalize)."""
@@ -583,18 +526,7 @@ class SphericalSpectrumMetrics(_HealpixInput):
           "log_ratio"  [K, C, lmax]   ln((power_pred + 1e-10) / (power_true + 1e-10))   (MELR_EPS)
           "selr"       [K, C]         the mean of log_ratio over l."""
         if world_size > 1:
-            import torch.distributed as dist
-
-            host = dist.get_backend(self.group) != "nccl"
-            dev = s.device
-            buf = torch.empty(s.numel() + 1, dtype=torch.float64, device=dev)
-            buf[:-1].copy_(s.flatten())
-            buf[-1:].fill_(n_samples)   # the count travels with the sums
-            if host:
-                buf = buf.cpu()
-            dist.all_reduce(buf, group=self.group)
-            buf = buf.to(dev)
-            s, n_samples = buf[:-1].view_as(s), buf[-1:]
+            s, n_samples = self._reduce_sums(s, n_samples)
         power = s[:3] / (n_samples * (4.0 * math.pi))
         prod = s[0] * s[1]
         coherence = torch.where(prod > 0, s[3] / torch.sqrt(torch.where(prod > 0, prod, torch.ones_like(prod))),
@@ -623,7 +555,7 @@ def ensemble_scores(sums: torch.Tensor, ranks: torch.Tensor, count: torch.Tensor
             "rank_histogram": ranks}
 
 
-class EnsembleMetrics(_HealpixInput):
+class EnsembleMetrics(_Scorer):
     """Scores of an ensemble forecast [M, B, k, C, H, W] against its truth [B, k, C, H, W], streamed: feed chunks of lead steps
     and / or of samples (`update`), `finalize` gives the latitude-weighted RMSE of the ensemble mean, the spread, their
     ratio, the CRPS (fair and plain) and the rank histogram per lead step and variable.  Only the running sums -- double
@@ -643,7 +575,6 @@ class EnsembleMetrics(_HealpixInput):
 
     def __init__(self, lats_deg, members: int, steps: int, channels: int, std: Optional[torch.Tensor] = None, group=None,
                  lons_deg=None, max_workspace_bytes: int = DEFAULT_WORKSPACE_BYTES):
-        self._init_remap(lats_deg, lons_deg, max_workspace_bytes)
         self.members, self.steps, self.channels = int(members), int(steps), int(channels)
         if not 2 <= self.members <= 64:
             raise _lib.DlwpError(f"EnsembleMetrics: {self.members} members (2 to 64 are supported)", status=_lib.ERR_UNSUPPORTED)
@@ -654,9 +585,7 @@ class EnsembleMetrics(_HealpixInput):
         self.std = std.detach().float().reshape(-1) if std is not None else None
         if self.std is not None and self.std.numel() != self.channels:
             raise _lib.DlwpError(f"EnsembleMetrics: {self.std.numel()} scales given for {self.channels} variables")
-        self.group = group
-        self._dev = {}   # device -> (latw, std) copies made once
-        self._ws = {}    # device -> partials workspace, grown when a chunk needs more
+        super().__init__(lats_deg, lons_deg, max_workspace_bytes, group, (self.latw, self.std))
         self.reset()
 
     def reset(self):
@@ -687,23 +616,10 @@ class EnsembleMetrics(_HealpixInput):
         self._sums, self._ranks, self._count, self._width = state["sums"], state["ranks"], state["count"], width
         return self
 
-    def _on(self, dev):
-        key = str(dev)
-        if key not in self._dev:
-            self._dev[key] = (self.latw.to(dev).contiguous(), self.std.to(dev).contiguous() if self.std is not None else None)
-        return self._dev[key]
-
-    def _workspace(self, dev, shape):
-        n = max(int(_lib.load().dlwp_ensemble_sums_workspace_bytes(*shape)), 8)
-        buf = self._ws.get(str(dev))
-        if buf is None or buf.numel() < n:
-            buf = self._ws[str(dev)] = torch.empty(n, dtype=torch.uint8, device=dev)
-        return buf
-
     def _launch(self, ens, member_stride, target, b, k, h, w, step_begin):
         dev = target.device
         latw, std = self._on(dev)
-        ws = self._workspace(dev, (b, k, self.channels, h, w))
+        ws = self._workspace(dev, _lib.load().dlwp_ensemble_sums_workspace_bytes(b, k, self.channels, h, w))
         _lib.launch("dlwp_ensemble_sums_acc_f32", dev, ens, target, latw, std, self._sums, self._ranks, self.members, member_stride,
                     b, k, self.channels, h, w, self.steps, step_begin, ws, ws.numel())
 
@@ -711,23 +627,11 @@ class EnsembleMetrics(_HealpixInput):
         """Adds a chunk: ens [M, B, k, C, H, W] (each member contiguous; the members may be any stride apart, e.g. a group view
         of a wider buffer) or HEALPix [M, B, k, C, 12, n, n] (see `lons_deg`) with target [B, k, C, ...], the k consecutive lead
         steps from `step_begin`.  Chunks may arrive in any order; every one counts B samples for its steps."""
-        if not isinstance(ens, torch.Tensor) or not isinstance(target, torch.Tensor):
-            raise _lib.DlwpError("ens and target must be tensors")
-        _lib.require_cuda_tensor(ens, "ens")
-        _lib.require_cuda_tensor(target, "target")
-        if ens.dim() not in (6, 7) or ens.shape[0] != self.members:
-            raise _lib.DlwpError(f"expected an ensemble [{self.members}, B, k, C, H, W], got shape {tuple(ens.shape)}")
-        if tuple(target.shape) != tuple(ens.shape[1:]):
-            raise _lib.DlwpError(f"target shape {tuple(target.shape)} != the members' shape {tuple(ens.shape[1:])}")
-        if target.device != ens.device:
-            raise _lib.DlwpError(f"target is on {target.device}, the ensemble on {ens.device}: both must be on one device")
-        hpx = ens.dim() == 7
-        if hpx and self._lons is None:
-            raise _lib.DlwpError(f"got a 7-D ensemble {tuple(ens.shape)}: a HEALPix ensemble [M, B, k, C, 12, n, n] is remapped to "
-                                 "lat-lon only when the metric is built with `lons_deg` (the longitudes of the lat-lon grid)")
-        m, b, k, c = (int(v) for v in ens.shape[:4])
-        h, w = (self.height, len(self._lons)) if hpx else (int(ens.shape[4]), int(ens.shape[5]))
-        step_begin = int(step_begin)
+        if not isinstance(ens, torch.Tensor) or ens.dim() not in (6, 7) or ens.shape[0] != self.members:
+            raise _lib.DlwpError(f"expected an ensemble [{self.members}, B, k, C, H, W], got "
+                                 f"{tuple(ens.shape) if isinstance(ens, torch.Tensor) else type(ens)}")
+        b, k, c, h, w = self._check_pair(ens[0], target, "ens", "M, ")      # a member and the target are a pair
+        m, step_begin = self.members, int(step_begin)
         if h != self.height:
             raise _lib.DlwpError(f"{h} latitudes in the chunk, {self.height} given to the metric")
         if c != self.channels:
@@ -746,51 +650,27 @@ class EnsembleMetrics(_HealpixInput):
         elif self._sums.device != dev:
             raise _lib.DlwpError(f"the chunk is on {dev}, the sums on {self._sums.device}: one device is needed")
         self._width = w
-        if not hpx:
+        if target.dim() == 5:
             if not ens[0].is_contiguous() or (m > 1 and ens.stride(0) < ens[0].numel()):
                 ens = ens.contiguous()
             self._launch(ens, int(ens.stride(0)), target.contiguous(), b, k, h, w, step_begin)
         else:
-            per = k * c * h * w                                    # floats of one sample of one member on the grid
-            chunk = min(b, self.max_workspace_bytes // (4 * (m + 1) * per))
-            if chunk < 1:
-                raise _lib.DlwpError(f"max_workspace_bytes = {self.max_workspace_bytes} does not hold one sample of the {m} members "
-                                     f"and of the target on the {h}x{w} grid ({4 * (m + 1) * per} bytes)")
-            from . import ops as _ops
-
-            buf = self._remap_ws.get(str(dev))
-            if buf is None or buf.numel() < (m + 1) * chunk * per:
-                buf = self._remap_ws[str(dev)] = torch.empty((m + 1) * chunk * per, dtype=torch.float32, device=dev)
-            for b0 in range(0, b, chunk):                          # all members of a sample in one chunk, a chunk in one call
-                n = min(chunk, b - b0)
-                e = buf[:m * n * per].view(m, n, k, c, h, w)
-                t = buf[m * chunk * per:m * chunk * per + n * per].view(n, k, c, h, w)
-                for j in range(m):
-                    _ops.healpix_to_latlon(ens[j, b0:b0 + n], self._lats, self._lons, out=e[j])
-                _ops.healpix_to_latlon(target[b0:b0 + n], self._lats, self._lons, out=t)
-                self._launch(e, n * per, t, n, k, h, w, step_begin)
+            for *e, t in self._remapped_chunks(*ens, target):   # all members of a sample in one chunk, a chunk in one call
+                stride = e[1].storage_offset() - e[0].storage_offset()      # the members' block: see _remapped_chunks
+                self._launch(e[0], stride, t, t.shape[0], k, h, w, step_begin)
         self._count[step_begin:step_begin + k] += float(b)
         return self
 
     def finalize(self, world_size: int = 1):
         """{"rmse_mean", "spread", "spread_skill", "crps", "crps_ens": [steps, C] double, "rank_histogram": [steps, C, M + 1]
         int64} over ALL ranks' samples (see `ensemble_scores`), on the sums' device.  With world_size > 1 ONE all-reduce moves
-        sums, ranks and counts (the rank counts travel as doubles: exact below 2^53); host tensors unless the group's backend is
-        nccl, as in RolloutMetrics.finalize."""
+        sums, ranks and counts (the rank counts travel as doubles: exact below 2^53)."""
         if self._sums is None:
             raise _lib.DlwpError("finalize() before any chunk: call update() or load_state() first")
         self._check_state(self._sums, self._ranks, self._count)
         s, r, n = self._sums, self._ranks, self._count
         if world_size > 1:
-            import torch.distributed as dist
-
-            host = dist.get_backend(self.group) != "nccl"
-            dev = s.device
-            buf = torch.cat([s.flatten(), r.flatten().double(), n])
-            if host:
-                buf = buf.cpu()
-            dist.all_reduce(buf, group=self.group)
-            buf = buf.to(dev)
+            buf = self._reduce(torch.cat([s.flatten(), r.flatten().double(), n]))
             s = buf[:s.numel()].view_as(s)
             r = buf[s.numel():s.numel() + r.numel()].round().long().view_as(r)
             n = buf[s.numel() + r.numel():]

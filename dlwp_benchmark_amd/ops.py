@@ -2667,10 +2667,7 @@ def sph_power_sums(out: torch.Tensor, target: torch.Tensor, grid: str = "legendr
     dev = out.device
     tab = _sph.device_tables(grid, nlat, nlon, lmax, mmax, dev)
     if into is not None:
-        if not isinstance(into, torch.Tensor) or not into.is_cuda:
-            raise _lib.DlwpError("running sums must be a tensor on an MI355X device")
-        if tuple(into.shape) != (4, k, c, lmax) or into.dtype != torch.float64 or not into.is_contiguous() or into.device != dev:
-            raise _lib.DlwpError(f"running sums must be a contiguous double [4, {k}, {c}, {lmax}] tensor on {dev}")
+        _lib.require_running_sums(into, (4, k, c, lmax), dev)
     need = sph_power_workspace_bytes(out.shape, lmax, mmax)
     if workspace is None:
         workspace = _lib.workspace(need, dev)

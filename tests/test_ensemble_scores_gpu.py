@@ -128,6 +128,34 @@ def test_two_halves_of_the_batch(m):
     assert torch.allclose(fa["crps"], fb["crps"], rtol=1e-5)
 
 
+def test_a_larger_chunk_keeps_the_first_workspace():
+    """a recorded step replays against the workspace address it was recorded with, so a chunk that needs a larger workspace
+    must leave the first one allocated (and the scores what a fresh scorer gives for the same two chunks)"""
+    from dlwp_benchmark_amd import lib as L
+
+    m, c, h, w = 2, 1, 4, 8
+    (b1, k1), (b2, k2) = (1, 1), (2, 2)
+    need = [int(L.load().dlwp_ensemble_sums_workspace_bytes(b, k, c, h, w)) for b, k in ((b1, k1), (b2, k2))]
+    assert 8 <= need[0] < need[1], need
+    x1, y1 = (t.to(DEV) for t in _inputs(m, (b1, k1, c, h, w), "unit", seed=5))
+    x2, y2 = (t.to(DEV) for t in _inputs(m, (b2, k2, c, h, w), "unit", seed=6))
+    em = _metric(h, m, k1 + k2, c)
+    em.update(x1, y1, step_begin=0)
+    first = em._ws[DEV][-1]
+    ptr = first.data_ptr()
+    assert first.numel() == need[0]
+    em.update(x2, y2, step_begin=k1)
+    bufs = em._ws[DEV]
+    assert len(bufs) == 2 and bufs[0] is first and first.data_ptr() == ptr
+    assert bufs[-1].numel() >= need[1] and bufs[-1].data_ptr() != ptr
+    fresh = _metric(h, m, k1 + k2, c)
+    fresh.update(x1, y1, step_begin=0).update(x2, y2, step_begin=k1)
+    got, want = em.finalize(), fresh.finalize()
+    for name, v in want.items():
+        assert torch.equal(got[name], v), name
+    assert bool(torch.isfinite(got["crps"]).all()) and em.state()["count"].tolist() == [1.0, 2.0, 2.0]
+
+
 def test_refusals():
     from dlwp_benchmark_amd import lib as L
     from dlwp_benchmark_amd.metrics import EnsembleMetrics

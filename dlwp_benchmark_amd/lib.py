@@ -433,6 +433,22 @@ def workspace(nbytes: int, device):
     return torch.empty(int(nbytes), dtype=torch.uint8, device=device) if nbytes else None
 
 
+def kept_workspace(bufs: dict, nbytes: int, device, floor: int = 8):
+    """The kernel workspace an owner keeps per device, shared by every shape it runs: `bufs` is the owner's dictionary
+    str(device) -> uint8 tensors, the last one the largest and the one in use.  Returns that one if it holds max(nbytes, floor)
+    bytes; otherwise appends one of that size, or twice the last one's if that is more, and returns it.  The replaced ones
+    stay allocated because a recorded step (sharding.CapturedStep) replays against the address it was recorded with: freed,
+    the caching allocator may hand the block to another tensor under a recording that still writes to it.  With the doubling
+    the replaced ones add up to less than the one in use, and an owner that sees one size allocates exactly that size."""
+    import torch
+
+    nbytes = max(int(nbytes), int(floor))
+    kept = bufs.setdefault(str(device), [])
+    if not kept or kept[-1].numel() < nbytes:
+        kept.append(torch.empty(max(nbytes, 2 * kept[-1].numel()) if kept else nbytes, dtype=torch.uint8, device=device))
+    return kept[-1]
+
+
 def launch(name: str, device, *args, accept=()):
     """The one way Python reaches an entry point whose last parameter is the stream: calls `name` with marshal(args) and
     the current stream of `device`, with `device` current (the guard is entered only when it is not).  Returns the status;

@@ -70,14 +70,8 @@ class _Scorer:
         return self._dev[key]
 
     def _workspace(self, dev, nbytes):
-        """One kernel workspace per device, shared by every shape: a shape that needs more replaces it by one at least twice as
-        large.  The replaced ones stay allocated because a recorded step (sharding.CapturedStep) keeps the address it was
-        recorded with; with the doubling they add up to less than the one in use."""
-        n = max(int(nbytes), 8)
-        bufs = self._ws.setdefault(str(dev), [])
-        if not bufs or bufs[-1].numel() < n:
-            bufs.append(torch.empty(max(n, 2 * bufs[-1].numel()) if bufs else n, dtype=torch.uint8, device=dev))
-        return bufs[-1]
+        """One kernel workspace per device, shared by every shape and kept when it grows (lib.kept_workspace)."""
+        return _lib.kept_workspace(self._ws, nbytes, dev)
 
     def _pair_shape(self, out, target, name="out", lead=""):
         """(B, K, C, H, W) of two tensors of one shape: lat-lon [B, K, C, H, W], or HEALPix [B, K, C, 12, n, n] when the metric

@@ -9,10 +9,13 @@ Every reference backbone has the same boundary:
   * `.eval()` / `.train()` return the module (the reference Swin returns None,
     swin_transformer.py:739-742 -- fixed here).
 """
+from typing import Optional
+
 import torch
 
 from .. import derived
 from .. import lib as _lib
+from ..rollout import rollout_into
 
 
 class HipBackbone(torch.nn.Module):
@@ -20,7 +23,7 @@ class HipBackbone(torch.nn.Module):
 
     def __init__(self):
         super().__init__()
-        self._ws = None
+        self._ws = {}                # device -> kernel workspaces, kept when they grow (lib.kept_workspace)
         self.step_graphs = False     # replay one_step as a HIP graph (launch-bound backbones), see graphs.py
         self._graphed = None
 
@@ -176,9 +179,50 @@ class HipBackbone(torch.nn.Module):
         return rollout_train(self.one_step, self.context_size, constants, prescribed, prognostic)
 
     def _workspace(self, nbytes: int, device) -> torch.Tensor:
-        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != device:
-            self._ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
-        return self._ws
+        return _lib.kept_workspace(self._ws, nbytes, device, floor=256)
 
     def _param_key(self):
         return derived.source_key(*self.parameters(), *self.buffers())
+
+
+class StepBackbone(HipBackbone):
+    """A backbone whose rollout is the shared loop over its `one_step` ([B, in, H, W] -> the increment [B, Cg, H, W]).  Having
+    `rollout_into` is what rollout.rollout_chunks and sharding.ShardedRollout ask a model for, so the backbones that run a loop
+    of their own (ConvLSTM, the diffusion family) derive from HipBackbone, not from this class."""
+
+    def rollout_into(self, out, constants, prescribed, prognostic, step_begin=0, step_end=-1):
+        return rollout_into(self._step_fn(), self.context_size, out, constants, prescribed, prognostic, step_begin, step_end)
+
+    def forward(self, constants: Optional[torch.Tensor] = None, prescribed: Optional[torch.Tensor] = None,
+                prognostic: torch.Tensor = None) -> torch.Tensor:
+        constants, prescribed, prognostic = self._check_inputs(constants, prescribed, prognostic)
+        if self._grad_mode():
+            return self._forward_train(constants, prescribed, prognostic)
+        with torch.no_grad():
+            b, t, cg, h, w = prognostic.shape
+            if t <= self.context_size:
+                raise _lib.DlwpError(f"need more than context_size={self.context_size} frames, got {t}")
+            out = torch.empty(b, t - self.context_size, cg, h, w, device=prognostic.device, dtype=torch.float32)
+            self.rollout_into(out, constants, prescribed, prognostic)
+        return out
+
+
+# ---- the HEALPix face axis: [B, T, C, 12, H, W] tensors whose faces fold into the batch for a backbone that runs per face ----
+def check_faces(t, name: str):
+    """`t` (None passes) is a float32 tensor [B, T, C, 12, H, W] on the device"""
+    if t is not None:
+        _lib.require_cuda_tensor(t, name)
+        if t.dim() != 6 or t.shape[3] != 12:
+            raise _lib.DlwpError(f"{name}: expected [B, T, C, 12, H, W], got {tuple(t.shape)}")
+
+
+def fold_faces(t: torch.Tensor) -> torch.Tensor:
+    """[B, T, C, F, H, W] -> [(B F), T, C, H, W]; dtype and contiguity are the caller's business"""
+    b, tt, c, f, h, w = t.shape
+    return t.permute(0, 3, 1, 2, 4, 5).reshape(b * f, tt, c, h, w)
+
+
+def unfold_faces(out: torch.Tensor, faces: int = 12) -> torch.Tensor:
+    """[(B F), K, C, H, W] -> [B, K, C, F, H, W], a view"""
+    n, k, c, h, w = out.shape
+    return out.reshape(n // faces, faces, k, c, h, w).permute(0, 2, 3, 1, 4, 5)

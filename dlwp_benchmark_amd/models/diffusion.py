@@ -33,7 +33,7 @@ from torch import nn
 from .. import lib as _lib
 from .. import ops
 from .. import training as _T
-from ._base import HipBackbone
+from ._base import HipBackbone, fold_faces
 from .unet import CylinderPad, HEALPixPadding, _resolve_activation
 
 
@@ -311,19 +311,15 @@ class DiffModernUNet(HipBackbone):
             tensors.append(prognostic.flatten(1, 2))
         return torch.cat(tensors, dim=1)
 
-    def _fold_faces(self, t):      # [B, T, C, F, H, W] -> [(B F), T, C, H, W]
-        b, tt, c, f, h, w = t.shape
-        return t.permute(0, 3, 1, 2, 4, 5).reshape(b * f, tt, c, h, w)
-
     # ---- modern_unet.py:141-176
     def single_forward(self, constants, prescribed, prognostic, y_noised, time):
         time = time * (1000 / self.num_refinement_step)
         if prognostic.ndim == 6:
-            prognostic = self._fold_faces(prognostic)
+            prognostic = fold_faces(prognostic)
         if y_noised.ndim == 5:
             y_noised = y_noised.expand(-1, prognostic.shape[1], -1, -1, -1)
         elif y_noised.ndim == 6:
-            y_noised = self._fold_faces(y_noised.expand(-1, prognostic.shape[1], -1, -1, -1, -1))
+            y_noised = fold_faces(y_noised.expand(-1, prognostic.shape[1], -1, -1, -1, -1))
         prognostic_t = torch.cat([prognostic, y_noised], dim=2)
         x_t = self._prepare_inputs(constants=constants, prescribed=prescribed, prognostic=prognostic_t).contiguous()
         emb = self.time_embed(fourier_embedding(time, self.hidden_channels[0]))
@@ -334,7 +330,7 @@ class DiffModernUNet(HipBackbone):
     # ---- modern_unet.py:178-211
     def diffusion_forward(self, constants, prescribed, prognostic, noise_scheduler, target_shape):
         if prognostic.ndim == 6:
-            prognostic = self._fold_faces(prognostic)
+            prognostic = fold_faces(prognostic)
         if len(target_shape) == 6:
             b, t, c, f, h, w = target_shape
             target_shape = (b * f, t, c, h, w)
@@ -392,9 +388,7 @@ class DiffMUNetHPX(DiffModernUNet):
 
     def _prepare_inputs(self, constants=None, prescribed=None, prognostic=None) -> torch.Tensor:
         """:314-327: [(B F), (T C), H, W]."""
-        def fold(t):      # [B, T, C, F, H, W] -> [(B F), (T C), H, W]
-            b, tt, c, f, h, w = t.shape
-            return t.permute(0, 3, 1, 2, 4, 5).reshape(b * f, tt * c, h, w)
+        fold = lambda t: fold_faces(t).flatten(1, 2)
 
         tensors = []
         if constants is not None:

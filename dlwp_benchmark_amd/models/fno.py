@@ -18,7 +18,7 @@ import torch
 from torch import nn
 
 from .. import lib as _lib
-from ._base import HipBackbone
+from ._base import StepBackbone
 
 
 class _DenseComplexTensor(nn.Module):
@@ -138,7 +138,7 @@ def kept_rows(h: int, n_modes_h: int):
     return [(p - sh) % h for p in pos], [(p + sh) % h for p in pos]
 
 
-class FNO2DModule(HipBackbone):
+class FNO2DModule(StepBackbone):
     # the rollout is ONE persistent launch that needs every compute unit resident at once: nothing else (an RCCL
     # kernel of an overlapped collective) may occupy the chip beside it -- sharding.ShardedRollout honours this
     exclusive_launch = True
@@ -393,22 +393,6 @@ class FNO2DModule(HipBackbone):
             parts.append(prog_t.flatten(1, 2))
             outs.append(prog_t[:, -1] + self._train_step(torch.cat(parts, dim=1).contiguous()))
         return torch.stack(outs, dim=1)
-
-    def forward(self, constants: Optional[torch.Tensor] = None, prescribed: Optional[torch.Tensor] = None,
-                prognostic: torch.Tensor = None) -> torch.Tensor:
-        if self.training and torch.is_grad_enabled():
-            for name, t in (("constants", constants), ("prescribed", prescribed), ("prognostic", prognostic)):
-                _lib.require_cuda_tensor(t, name)
-            return self._forward_train(constants, prescribed, prognostic)
-        constants, prescribed, prognostic = self._check_inputs(constants, prescribed, prognostic)
-        with torch.no_grad():
-            b, t, cg, h, w = prognostic.shape
-            ctx = self.context_size
-            if t <= ctx:
-                raise _lib.DlwpError(f"need more than context_size={ctx} frames, got {t}")
-            out = torch.empty(b, t - ctx, cg, h, w, device=prognostic.device, dtype=torch.float32)
-            self.rollout_into(out, constants, prescribed, prognostic)
-        return out
 
 
 class TFNO2DModule(FNO2DModule):

@@ -11,16 +11,13 @@ the head + rearrange at the other end (dlwp_patch_recover_1x1_f32; other patch s
 The rollout is device resident and does NOT reproduce the reference's crash on the second step
 (`.to()` on a list, :336-340) nor its per-step `.cpu()` (:359).
 """
-from typing import Optional
-
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from .. import lib as _lib
 from .. import ops
-from ..rollout import rollout_into
-from ._base import HipBackbone
+from ._base import StepBackbone
 from .swin import _Mlp
 
 
@@ -122,7 +119,7 @@ class _PatchEmbed(nn.Module):
         return self.proj(x).flatten(2).transpose(1, 2)
 
 
-class FourCastNet(HipBackbone):
+class FourCastNet(StepBackbone):
     def __init__(self, img_height=720, img_width=1440, patch_size=(16, 16), constant_channels: int = 4,
                  prescribed_channels: int = 0, prognostic_channels: int = 1, filter="AFNO2D", embed_dim=768, depth=12,
                  mlp_ratio=4., drop_rate=0., drop_path_rate=0., num_blocks=16, sparsity_threshold=0.01,
@@ -171,22 +168,6 @@ class FourCastNet(HipBackbone):
         x = self.head(x)
         return x.view(b, self.h, self.w, p1, p2, self.out_chans).permute(0, 5, 1, 3, 2, 4).reshape(
             b, self.out_chans, self.h * p1, self.w * p2)
-
-    def rollout_into(self, out, constants, prescribed, prognostic, step_begin=0, step_end=-1):
-        return rollout_into(self._step_fn(), self.context_size, out, constants, prescribed, prognostic, step_begin, step_end)
-
-    def forward(self, constants: Optional[torch.Tensor] = None, prescribed: Optional[torch.Tensor] = None,
-                prognostic: torch.Tensor = None) -> torch.Tensor:
-        constants, prescribed, prognostic = self._check_inputs(constants, prescribed, prognostic)
-        if self._grad_mode():
-            return self._forward_train(constants, prescribed, prognostic)
-        with torch.no_grad():
-            b, t, cg, h, w = prognostic.shape
-            if t <= self.context_size:
-                raise _lib.DlwpError(f"need more than context_size={self.context_size} frames, got {t}")
-            out = torch.empty(b, t - self.context_size, cg, h, w, device=prognostic.device, dtype=torch.float32)
-            self.rollout_into(out, constants, prescribed, prognostic)
-        return out
 
 
 AFNONet = FourCastNet

@@ -36,8 +36,7 @@ from .. import icosphere
 from .. import lib as _lib
 from .. import ops
 from .. import training
-from ..rollout import rollout_into
-from ._base import HipBackbone
+from ._base import StepBackbone
 
 _ACTIVATIONS = {"relu": nn.ReLU, "leaky_relu": (nn.LeakyReLU, {"negative_slope": 0.1}), "relu6": nn.ReLU6, "elu": nn.ELU,
                 "selu": nn.SELU, "silu": nn.SiLU, "gelu": nn.GELU, "sigmoid": nn.Sigmoid, "logsigmoid": nn.LogSigmoid,
@@ -140,7 +139,7 @@ def _csc(src, dst, n_dst):
     return order, np.concatenate([[0], np.cumsum(deg)]).astype(np.int32), deg
 
 
-class GraphCastNet(HipBackbone):
+class GraphCastNet(StepBackbone):
     def __init__(self, meshgraph_path: str, input_height: int = 721, input_width: int = 1440, constant_channels: int = 4,
                  prescribed_channels: int = 1, prognostic_channels: int = 8, input_dim_mesh_nodes: int = 3,
                  input_dim_edges: int = 4, processor_layers: int = 16, hidden_layers: int = 1, hidden_dim: int = 512,
@@ -383,20 +382,6 @@ class GraphCastNet(HipBackbone):
             return self._step_torch(x_t)
         return self._step_hip(x_t)
 
-    def rollout_into(self, out, constants, prescribed, prognostic, step_begin=0, step_end=-1):
-        return rollout_into(self._step_fn(), self.context_size, out, constants, prescribed, prognostic, step_begin, step_end)
-
-    def forward(self, constants: Optional[torch.Tensor] = None, prescribed: Optional[torch.Tensor] = None,
-                prognostic: torch.Tensor = None) -> torch.Tensor:
-        constants, prescribed, prognostic = self._check_inputs(constants, prescribed, prognostic)
-        if self.constant_channels == 0:
-            constants = None
-        if self._grad_mode():
-            return self._forward_train(constants, prescribed, prognostic)
-        with torch.no_grad():
-            b, t, cg, h, w = prognostic.shape
-            if t <= self.context_size:
-                raise _lib.DlwpError(f"need more than context_size={self.context_size} frames, got {t}")
-            out = torch.empty(b, t - self.context_size, cg, h, w, device=prognostic.device, dtype=torch.float32)
-            self.rollout_into(out, constants, prescribed, prognostic)
-        return out
+    def _check_inputs(self, constants, prescribed, prognostic):
+        constants, prescribed, prognostic = super()._check_inputs(constants, prescribed, prognostic)
+        return (None if self.constant_channels == 0 else constants), prescribed, prognostic

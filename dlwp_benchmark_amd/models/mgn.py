@@ -25,7 +25,6 @@ does for processors wider than FUSED_MAX_WIDTH.
 DLWP_TRAIN_TORCH_BACKWARD=1 keeps the HIP forward and differentiates the torch composition instead (a cross-check).
 """
 import functools
-from typing import Optional
 
 import numpy as np
 import torch
@@ -34,8 +33,7 @@ from torch import nn
 from .. import lib as _lib
 from .. import ops
 from .. import training
-from ..rollout import rollout_into
-from ._base import HipBackbone
+from ._base import StepBackbone
 
 GRAPH_TYPES = ("grid_2d", "grid_2d_8stencil", "delaunay")
 # Widest processor the step runs on the fused kernels by default.  Measured at B = 32 on 32x64:
@@ -213,7 +211,7 @@ def _graph_attr(graph, name):
     return getattr(graph, name) if hasattr(graph, name) else graph[name]     # attribute object (DictConfig) or mapping
 
 
-class MeshGraphNet(HipBackbone):
+class MeshGraphNet(StepBackbone):
     def __init__(self, constant_channels: int = 4, prescribed_channels: int = 0, prognostic_channels: int = 1,
                  input_dim_edges: int = 2, context_size: int = 5, processor_size: int = 15, message_passing_steps: int = 1,
                  num_layers_node_processor: int = 2, num_layers_edge_processor: int = 2, hidden_dim_processor: int = 128,
@@ -404,19 +402,3 @@ class MeshGraphNet(HipBackbone):
                 x, e = ops.mgn_layer_torch(em, nm, self.aggregation, self.graph_src, self.graph_dst, self.graph_deg, b, x, e)
         y = ops.mgn_mlp_torch(self.node_decoder.model, x)
         return y.view(b, h, w, -1).permute(0, 3, 1, 2)
-
-    def rollout_into(self, out, constants, prescribed, prognostic, step_begin=0, step_end=-1):
-        return rollout_into(self._step_fn(), self.context_size, out, constants, prescribed, prognostic, step_begin, step_end)
-
-    def forward(self, constants: Optional[torch.Tensor] = None, prescribed: Optional[torch.Tensor] = None,
-                prognostic: torch.Tensor = None) -> torch.Tensor:
-        constants, prescribed, prognostic = self._check_inputs(constants, prescribed, prognostic)
-        if self._grad_mode():
-            return self._forward_train(constants, prescribed, prognostic)
-        with torch.no_grad():
-            b, t, cg, h, w = prognostic.shape
-            if t <= self.context_size:
-                raise _lib.DlwpError(f"need more than context_size={self.context_size} frames, got {t}")
-            out = torch.empty(b, t - self.context_size, cg, h, w, device=prognostic.device, dtype=torch.float32)
-            self.rollout_into(out, constants, prescribed, prognostic)
-        return out

@@ -12,16 +12,12 @@ and the padded tokens take part in the softmax (utils/pad.py:21-24); the forward
 by shift_lat while the reverse roll uses shift_lon (:291 vs :310).
 Linear / LayerNorm / (transposed) convolutions run through torch on the GPU (rocBLAS / MIOpen).
 """
-from typing import Optional
-
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .. import lib as _lib
 from .. import ops
-from ..rollout import rollout_into
-from ._base import HipBackbone
+from ._base import StepBackbone
 from .swin import _Mlp
 
 
@@ -240,7 +236,7 @@ class _PatchRecovery2D(nn.Module):
         return out[:, :, hp // 2: hh - (hp - hp // 2), wp // 2: ww - (wp - wp // 2)]
 
 
-class PanguWeather(HipBackbone):
+class PanguWeather(StepBackbone):
     def __init__(self, constant_channels: int = 4, prescribed_channels: int = 0, prognostic_channels: int = 1,
                  embed_dim: int = 192, num_heads: tuple = (6, 12, 12, 6), window_size: tuple = (2, 6, 12),
                  patch_size: tuple = (4, 4), n_lat: int = 721, n_lon: int = 1440, context_size: int = 1, **kwargs):
@@ -326,19 +322,3 @@ class PanguWeather(HipBackbone):
         y = ops.linear(x.reshape(-1, x.shape[-1]), a, precision=precision)
         y = ops.linear(skip.reshape(-1, skip.shape[-1]), b2, resid=y, out=y, precision=precision)
         return y[:, :cg]
-
-    def rollout_into(self, out, constants, prescribed, prognostic, step_begin=0, step_end=-1):
-        return rollout_into(self._step_fn(), self.context_size, out, constants, prescribed, prognostic, step_begin, step_end)
-
-    def forward(self, constants: Optional[torch.Tensor] = None, prescribed: Optional[torch.Tensor] = None,
-                prognostic: torch.Tensor = None) -> torch.Tensor:
-        constants, prescribed, prognostic = self._check_inputs(constants, prescribed, prognostic)
-        if self._grad_mode():
-            return self._forward_train(constants, prescribed, prognostic)
-        with torch.no_grad():
-            b, t, cg, h, w = prognostic.shape
-            if t <= self.context_size:
-                raise _lib.DlwpError(f"need more than context_size={self.context_size} frames, got {t}")
-            out = torch.empty(b, t - self.context_size, cg, h, w, device=prognostic.device, dtype=torch.float32)
-            self.rollout_into(out, constants, prescribed, prognostic)
-        return out

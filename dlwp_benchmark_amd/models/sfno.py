@@ -18,15 +18,12 @@ reference's crash on the second step (`.to()` on a list, fno.py:244-247).
 Left out (NotImplementedError names the key): operator_type other than "driscoll-healy", factorization, spectral_transform
 other than "sht", normalization layers, grid "lobatto", a scale_factor that leaves an odd inner width.
 """
-from typing import Optional
-
 import torch
 from torch import nn
 
 from .. import lib as _lib
 from .. import ops
-from ..rollout import rollout_into
-from ._base import HipBackbone
+from ._base import StepBackbone
 
 _ACTIVATIONS = ("gelu", "relu")
 
@@ -139,7 +136,7 @@ class _SFNO(nn.Module):
         return self._conv(self.decoder["2"], self._conv(self.decoder["0"], y, act=self.act))
 
 
-class SFNO2DModule(HipBackbone):
+class SFNO2DModule(StepBackbone):
     def __init__(self, constant_channels: int = 4, prescribed_channels: int = 1, prognostic_channels: int = 8,
                  spectral_transform='sht', grid="legendre-gauss", num_layers=4, scale_factor=3, embed_dim=256,
                  operator_type='driscoll-healy', context_size: int = 1, height: int = 32, width: int = 64,
@@ -178,19 +175,3 @@ class SFNO2DModule(HipBackbone):
         if x_t.dim() != 4 or x_t.shape[1] != self.in_channels:
             raise _lib.DlwpError(f"x_t {tuple(x_t.shape)}: the model expects [B, {self.in_channels}, H, W]")
         return self.sfno(x_t)
-
-    def rollout_into(self, out, constants, prescribed, prognostic, step_begin=0, step_end=-1):
-        return rollout_into(self._step_fn(), self.context_size, out, constants, prescribed, prognostic, step_begin, step_end)
-
-    def forward(self, constants: Optional[torch.Tensor] = None, prescribed: Optional[torch.Tensor] = None,
-                prognostic: torch.Tensor = None) -> torch.Tensor:
-        constants, prescribed, prognostic = self._check_inputs(constants, prescribed, prognostic)
-        if self._grad_mode():
-            return self._forward_train(constants, prescribed, prognostic)
-        with torch.no_grad():
-            b, t, cg, h, w = prognostic.shape
-            if t <= self.context_size:
-                raise _lib.DlwpError(f"need more than context_size={self.context_size} frames, got {t}")
-            out = torch.empty(b, t - self.context_size, cg, h, w, device=prognostic.device, dtype=torch.float32)
-            self.rollout_into(out, constants, prescribed, prognostic)
-        return out

@@ -25,7 +25,7 @@ class SpectralConv2d(nn.Module):
         self.weights2 = nn.Parameter(self.scale * torch.rand(in_channels, out_channels, modes1, modes2, 2))
         self._plan = None
         self._plan_key = None
-        self._ws = None
+        self._ws = {}         # device -> kernel workspaces, kept when they grow (lib.kept_workspace)
 
     def _destroy_plan(self):
         if self._plan is not None:
@@ -81,8 +81,7 @@ class SpectralConv2d(nn.Module):
             raise _lib.DlwpError(f"x has {c} channels, layer expects {self.in_channels}")
         plan = self._get_plan(h, w, x.device)
         nbytes = _lib.load().dlwp_spectral_conv2d_workspace_bytes(plan, b)
-        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != x.device:
-            self._ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=x.device)
+        ws = _lib.kept_workspace(self._ws, nbytes, x.device, floor=256)
         y = torch.empty(b, self.out_channels, h, w, device=x.device, dtype=torch.float32)
-        _lib.launch("dlwp_spectral_conv2d_f32", x.device, plan, x, y, b, self._ws, nbytes)
+        _lib.launch("dlwp_spectral_conv2d_f32", x.device, plan, x, y, b, ws, nbytes)
         return y

@@ -21,8 +21,7 @@ from torch import nn
 
 from .. import lib as _lib
 from .. import ops
-from ..rollout import rollout_into
-from ._base import HipBackbone
+from ._base import StepBackbone, check_faces
 
 
 class _Mlp(nn.Module):
@@ -176,7 +175,7 @@ class _PatchEmbed(nn.Module):
         return x, wh, ww
 
 
-class SwinTransformer(HipBackbone):
+class SwinTransformer(StepBackbone):
     def __init__(self, constant_channels: int = 4, prescribed_channels: int = 0, prognostic_channels: int = 1,
                  context_size: int = 10, img_height=224, img_width=196, patch_size=4, embed_dim=96,
                  depths=[2, 2, 6, 2], num_heads=[3, 6, 12, 24], mlp_ratio=4., qkv_bias=True, qk_scale=None,
@@ -281,22 +280,6 @@ class SwinTransformer(HipBackbone):
         y = dec[1](xo, h, w, precision="fp32")                         # [B, h*w, Cg]; the output head stays fp32-accurate
         return y.view(b, h, w, -1).permute(0, 3, 1, 2).contiguous()
 
-    def rollout_into(self, out, constants, prescribed, prognostic, step_begin=0, step_end=-1):
-        return rollout_into(self._step_fn(), self.context_size, out, constants, prescribed, prognostic, step_begin, step_end)
-
-    def forward(self, constants: Optional[torch.Tensor] = None, prescribed: Optional[torch.Tensor] = None,
-                prognostic: torch.Tensor = None) -> torch.Tensor:
-        constants, prescribed, prognostic = self._check_inputs(constants, prescribed, prognostic)
-        if self._grad_mode():
-            return self._forward_train(constants, prescribed, prognostic)
-        with torch.no_grad():
-            b, t, cg, h, w = prognostic.shape
-            if t <= self.context_size:
-                raise _lib.DlwpError(f"need more than context_size={self.context_size} frames, got {t}")
-            out = torch.empty(b, t - self.context_size, cg, h, w, device=prognostic.device, dtype=torch.float32)
-            self.rollout_into(out, constants, prescribed, prognostic)
-        return out
-
 
 class SwinTransformerHPX(SwinTransformer):
     """reference swin_transformer.py:745-878: Swin on the HEALPix mesh.  The 12 faces [.., 12, h, w] are laid out as
@@ -324,8 +307,7 @@ class SwinTransformerHPX(SwinTransformer):
     def forward(self, constants: Optional[torch.Tensor] = None, prescribed: Optional[torch.Tensor] = None,
                 prognostic: torch.Tensor = None) -> torch.Tensor:
         for name, t in (("constants", constants), ("prescribed", prescribed), ("prognostic", prognostic)):
-            if t is not None and (t.dim() != 6 or t.shape[3] != 12):
-                raise _lib.DlwpError(f"{name}: expected [B, T, C, 12, H, W], got {tuple(t.shape)}")
+            check_faces(t, name)
         if prognostic is None:
             raise _lib.DlwpError("prognostic is required")
         rect = lambda t: self.faces_to_rect(t).contiguous() if t is not None else None

@@ -26,7 +26,7 @@ from torch import nn
 from .. import lib as _lib
 from .. import ops
 from ..rollout import rollout_into
-from ._base import HipBackbone
+from ._base import HipBackbone, StepBackbone, check_faces, fold_faces, unfold_faces
 
 
 class CylinderPad(nn.Module):
@@ -256,7 +256,7 @@ class _UNetDecoder(nn.Module):
         return ops.small_module(self.output_layer, x, form=self.aux_conv_form)
 
 
-class UNet(HipBackbone):
+class UNet(StepBackbone):
     def __init__(self, constant_channels: int = 4, prescribed_channels: int = 0, prognostic_channels: int = 1,
                  hidden_channels: list = [8, 16, 32], n_convolutions: int = 2, activation=nn.GELU(),
                  context_size: int = 1, mesh: str = "equirectangular", **kwargs):
@@ -275,22 +275,6 @@ class UNet(HipBackbone):
         enc = self.encoder(x)
         return self.decoder(x=enc[-1], skips=enc[::-1])
 
-    def rollout_into(self, out, constants, prescribed, prognostic, step_begin=0, step_end=-1):
-        return rollout_into(self._step_fn(), self.context_size, out, constants, prescribed, prognostic, step_begin, step_end)
-
-    def forward(self, constants: Optional[torch.Tensor] = None, prescribed: Optional[torch.Tensor] = None,
-                prognostic: torch.Tensor = None) -> torch.Tensor:
-        constants, prescribed, prognostic = self._check_inputs(constants, prescribed, prognostic)
-        if self._grad_mode():
-            return self._forward_train(constants, prescribed, prognostic)
-        with torch.no_grad():
-            b, t, cg, h, w = prognostic.shape
-            if t <= self.context_size:
-                raise _lib.DlwpError(f"need more than context_size={self.context_size} frames, got {t}")
-            out = torch.empty(b, t - self.context_size, cg, h, w, device=prognostic.device, dtype=torch.float32)
-            self.rollout_into(out, constants, prescribed, prognostic)
-        return out
-
 
 class UNetHPX(UNet):
     """reference models/unet/unet.py:386-426: the classic U-Net on the HEALPix mesh.  Tensors carry a face
@@ -304,12 +288,6 @@ class UNetHPX(UNet):
                          prognostic_channels=prognostic_channels, hidden_channels=hidden_channels,
                          n_convolutions=n_convolutions, activation=activation, context_size=context_size, mesh="healpix",
                          **kwargs)
-
-    @staticmethod
-    def _fold(t):
-        """[B, T, C, F, H, W] -> [(B F), (T C), H, W]"""
-        b, tt, c, f, h, w = t.shape
-        return t.permute(0, 3, 1, 2, 4, 5).reshape(b * f, tt * c, h, w)
 
     def forward(self, constants: Optional[torch.Tensor] = None, prescribed: Optional[torch.Tensor] = None,
                 prognostic: torch.Tensor = None) -> torch.Tensor:
@@ -677,30 +655,19 @@ class ConvLSTMHPX(ConvLSTM):
 
     def forward(self, constants: Optional[torch.Tensor] = None, prescribed: Optional[torch.Tensor] = None,
                 prognostic: torch.Tensor = None) -> torch.Tensor:
-        for name, t in (("constants", constants), ("prescribed", prescribed), ("prognostic", prognostic)):
-            self._check_faces(t, name)
         if prognostic is None:
             raise _lib.DlwpError("prognostic is required")
-        with torch.set_grad_enabled(self._grad_mode()):
+        with torch.set_grad_enabled(self._grad_mode()):       # (_fold checks each tensor)
             out = self._rollout(self._fold(constants, "constants"), self._fold(prescribed, "prescribed"),
                                 self._fold(prognostic, "prognostic"))
             return self._unfold(out)
-
-    @staticmethod
-    def _check_faces(t, name: str):
-        if t is not None:
-            _lib.require_cuda_tensor(t, name)
-            if t.dim() != 6 or t.shape[3] != 12:
-                raise _lib.DlwpError(f"{name}: expected [B, T, C, 12, H, W], got {tuple(t.shape)}")
 
     def _fold(self, t: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
         """[B, T, C, 12, H, W] -> [B * 12, T, C, H, W]: the faces fold into the batch (`_prepare_inputs` :293-305)"""
         if t is None:
             return None
-        self._check_faces(t, name)
-        b, tt, c, f, h, w = t.shape
-        return t.permute(0, 3, 1, 2, 4, 5).reshape(b * f, tt, c, h, w).float().contiguous()
+        check_faces(t, name)
+        return fold_faces(t).float().contiguous()
 
     def _unfold(self, out: torch.Tensor) -> torch.Tensor:
-        n, k, cg, h, w = out.shape
-        return out.reshape(n // 12, 12, k, cg, h, w).permute(0, 2, 3, 1, 4, 5).contiguous()
+        return unfold_faces(out).contiguous()

@@ -92,7 +92,7 @@ class SpectralOperator:
                     self.n_cols, ri, ro, self.fwd_scale, self.inv_scale)
         _lib.launch("dlwp_spectral_conv2d_plan_create_ex", self.device, ctypes.byref(self._adj), co, ci, height, width, n,
                     self.n_cols, ro, ri, self.fwd_scale, self.inv_scale)
-        self._ws = None
+        self._ws = {}         # device -> kernel workspaces, kept when they grow (lib.kept_workspace)
 
     def __del__(self):
         try:
@@ -104,10 +104,7 @@ class SpectralOperator:
             pass
 
     def _workspace(self, nbytes: int, device) -> torch.Tensor:
-        """grown, never shrunk"""
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
-        return self._ws
+        return _lib.kept_workspace(self._ws, nbytes, device, floor=256)
 
     def _run(self, plan, x: torch.Tensor, weight_real: torch.Tensor, adjoint: bool) -> torch.Tensor:
         _lib.require_cuda_tensor(x, "x")

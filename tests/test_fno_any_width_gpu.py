@@ -176,6 +176,89 @@ def test_captured_step_replay_equals_eager():
     model.verify()
 
 
+def test_captured_step_replays_across_workspace_growth():
+    """a recording made at batch 1 replays the same bits after an eager run at batch 4 has grown the model's workspace: the
+    workspace it was recorded with stays allocated (lib.kept_workspace)"""
+    from dlwp_benchmark_amd.sharding import CapturedStep, ShardedRollout
+    from dlwp_benchmark_amd.synthetic import navier_stokes
+
+    _, model = _pair(_kw(16))
+    runner = ShardedRollout(model, gather=False)
+    small = navier_stokes(1, 4, 32, 64, seed=7)[2].to(DEV)
+    large = navier_stokes(4, 4, 32, 64, seed=8)[2].to(DEV)
+    cap = CapturedStep(lambda c, p, g: runner(constants=c, prescribed=p, prognostic=g), model=model)
+    cap(None, None, small)                      # eager
+    got = cap(None, None, small)                # records and replays
+    torch.cuda.synchronize()
+    want = got.clone()
+    cap(None, None, large)                      # eager at a larger batch: the workspace grows
+    assert len(model._ws[str(DEV)]) == 2
+    got = cap(None, None, small)
+    torch.cuda.synchronize()
+    assert torch.equal(got, want)
+    assert cap.replays >= 2
+    model.verify()
+
+
+def test_a_larger_batch_keeps_the_first_workspace():
+    """a recorded step replays against the workspace address it was recorded with, so a batch that needs a larger workspace
+    must leave the first one allocated"""
+    from dlwp_benchmark_amd import lib as L
+
+    _, model = _pair(_kw(16))
+    plan = model._get_plan(32, 64, DEV)
+    need = {b: int(L.load().dlwp_fno2d_workspace_bytes(plan, b)) for b in (1, 4)}
+    assert 256 <= need[1] < need[4], need
+    model.one_step(torch.randn(1, 1, 32, 64, device=DEV))
+    first = model._ws[str(DEV)][-1]
+    ptr = first.data_ptr()
+    assert first.numel() == need[1]
+    model.one_step(torch.randn(4, 1, 32, 64, device=DEV))
+    torch.cuda.synchronize()
+    bufs = model._ws[str(DEV)]
+    assert len(bufs) == 2 and bufs[0] is first and first.data_ptr() == ptr
+    assert bufs[-1].numel() >= need[4] and bufs[-1].data_ptr() != ptr
+
+
+def test_spectral_layers_keep_their_first_workspace():
+    """the same for SpectralConv2d's inference workspace and for its training operator's (forward, backward-data and weight
+    gradient share one)"""
+    from dlwp_benchmark_amd import lib as L
+    from dlwp_benchmark_amd.models import SpectralConv2d
+
+    lib = L.load()
+    layer = SpectralConv2d(4, 4, 4, 4).to(DEV).eval()
+    x = {b: torch.randn(b, 4, 16, 16, device=DEV) for b in (1, 4)}
+    plan = layer._get_plan(16, 16, DEV)
+    need = {b: max(int(lib.dlwp_spectral_conv2d_workspace_bytes(plan, b)), 256) for b in (1, 4)}
+    assert need[1] < need[4], need
+    with torch.no_grad():
+        layer(x[1])
+        first = layer._ws[str(DEV)][-1]
+        ptr = first.data_ptr()
+        assert first.numel() == need[1]
+        layer(x[4])
+    bufs = layer._ws[str(DEV)]
+    assert len(bufs) == 2 and bufs[0] is first and first.data_ptr() == ptr and bufs[-1].numel() >= need[4]
+
+    layer.train()
+    layer(x[1].clone().requires_grad_()).square().sum().backward()
+    op = layer._train_op
+    need = {b: max(int(lib.dlwp_spectral_conv2d_workspace_bytes(op._fwd, b)), int(lib.dlwp_spectral_conv2d_workspace_bytes(op._adj, b)),
+                   int(lib.dlwp_spectral_conv2d_wgrad_workspace_bytes(op._fwd, b)), 256) for b in (1, 4)}
+    assert need[1] < need[4], need
+    kept = list(op._ws[str(DEV)])              # (the backward may have grown what the forward allocated)
+    ptrs = [t.data_ptr() for t in kept]
+    assert need[1] <= kept[-1].numel() < need[4]
+    layer(x[4].clone().requires_grad_()).square().sum().backward()
+    torch.cuda.synchronize()
+    assert layer._train_op is op
+    bufs = op._ws[str(DEV)]
+    assert len(bufs) > len(kept) and bufs[-1].numel() >= need[4]
+    assert all(a is b for a, b in zip(bufs, kept)) and [t.data_ptr() for t in kept] == ptrs
+    assert all(bool(torch.isfinite(p.grad).all()) for p in layer.parameters())
+
+
 def test_training_step_matches_oracle_autograd_at_hidden_16():
     from dlwp_benchmark_amd.models import FNO2DModule
     from dlwp_benchmark_amd.synthetic import navier_stokes

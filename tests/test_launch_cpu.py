@@ -32,3 +32,22 @@ def test_workspace():
     assert L.workspace(0, "cpu") is None
     ws = L.workspace(12, "cpu")
     assert ws.dtype == torch.uint8 and ws.numel() == 12 and ws.element_size() == 1
+
+
+def test_kept_workspace():
+    """the first buffer is exactly what was asked for, a smaller request reuses it, a larger one at least doubles it and leaves
+    the replaced buffer referenced where it was (a recorded step keeps its address)"""
+    bufs = {}
+    first = L.kept_workspace(bufs, 100, "cpu", floor=8)
+    assert first.dtype == torch.uint8 and first.numel() == 100 and list(bufs) == ["cpu"]
+    ptr = first.data_ptr()
+    assert L.kept_workspace(bufs, 50, "cpu", floor=8) is first and len(bufs["cpu"]) == 1
+    second = L.kept_workspace(bufs, 150, "cpu", floor=8)
+    assert second is bufs["cpu"][-1] and second.numel() >= 200 and len(bufs["cpu"]) == 2
+    assert bufs["cpu"][0] is first and first.data_ptr() == ptr and second.data_ptr() != ptr
+    third = L.kept_workspace(bufs, 10000, "cpu", floor=8)
+    assert third.numel() == 10000 and len(bufs["cpu"]) == 3 and bufs["cpu"][0] is first
+    other = L.kept_workspace(bufs, 16, "meta", floor=8)
+    assert other.numel() == 16 and len(bufs["meta"]) == 1 and bufs["meta"][0] is other and len(bufs["cpu"]) == 3
+    assert L.kept_workspace({}, 1, "cpu", floor=256).numel() == 256
+    assert L.kept_workspace({}, 0, "cpu").numel() == 8

@@ -327,6 +327,9 @@ SIGNATURES = {
                                           c_int32, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
     "dlwp_sph_power_sums_acc_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                               c_int32, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
+    # 2-D Navier-Stokes trajectories from one LDS-resident workgroup each (csrc/navier_stokes.hip)
+    "dlwp_ns2d_rollout_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                        ctypes.c_double, ctypes.c_double, c_void_p]),
 }
 
 _lib = None

@@ -2728,3 +2728,94 @@ def sph_mix_backward(c_in: torch.Tensor, weight: torch.Tensor, g: torch.Tensor, 
             _lib.launch("dlwp_sph_mix_wgrad_f32", dev, cp, gp, gw, b, ci, co, lmax, mmax)
         gw = torch.view_as_complex(gw)
     return gc, gw
+
+
+# ---- 2-D Navier-Stokes trajectories on the unit torus (csrc/navier_stokes.hip) --------------------------
+NS2D_SIZES = (32, 64)         # the grids the resident kernel runs (the work planes of 128 x 128 exceed the LDS)
+NS2D_MAX_STEPS = 100000       # frames * substeps of one launch (kMaxSteps of csrc/navier_stokes.hip, which refuses more)
+_NS2D_TABLES = {}             # (kind, n, ..., device) -> a device table made on the host in float64
+
+
+def _ns2d_table(key, make):
+    if key not in _NS2D_TABLES:
+        _NS2D_TABLES[key] = make()
+    return _NS2D_TABLES[key]
+
+
+def ns2d_li2020_forcing(n: int, device) -> torch.Tensor:
+    """0.1 (sin 2 pi (a + b) + cos 2 pi (a + b)) on the n x n grid of the unit torus (the forcing of Li et al. 2020), made in
+    float64 on the host, kept per (n, device)"""
+    def make():
+        t = torch.arange(n, dtype=torch.float64) / n
+        s = 2.0 * math.pi * (t[:, None] + t[None, :])
+        return (0.1 * (torch.sin(s) + torch.cos(s))).to(torch.float32).to(device).contiguous()
+    return _ns2d_table(("li2020", int(n), str(device)), make)
+
+
+def grf_amplitude(n: int, tau: float, alpha: float, device) -> torch.Tensor:
+    """float32 [n, n / 2 + 1] on `device`: A(k) = n sqrt(2) tau^(alpha - 1) (4 pi^2 |k|^2 + tau^2)^(-alpha / 2) with A(0) = 0 and
+    zeros at |ka| = n / 2 and kb = n / 2 (modes the solver removes), made in float64 on the host, kept per (n, tau, alpha, device)"""
+    n, tau, alpha = int(n), float(tau), float(alpha)
+
+    def make():
+        ka = torch.fft.fftfreq(n, d=1.0 / n).to(torch.float64)[:, None]
+        kb = torch.fft.rfftfreq(n, d=1.0 / n).to(torch.float64)[None, :]
+        lap = 4.0 * math.pi ** 2 * (ka * ka + kb * kb)
+        amp = n * math.sqrt(2.0) * tau ** (alpha - 1.0) * (lap + tau * tau) ** (-alpha / 2.0)
+        amp[0, 0] = 0.0
+        amp[(ka.abs() == n // 2) | (kb == n // 2)] = 0.0
+        return amp.to(torch.float32).to(device).contiguous()
+    return _ns2d_table(("grf", n, tau, alpha, str(device)), make)
+
+
+def navier_stokes_2d(w0: torch.Tensor, frames: int, substeps: int, dt: float, nu: float, forcing="li2020", filter=None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[B, frames, N, N]: the vorticity of B trajectories of the 2-D incompressible Navier-Stokes equations on the unit torus,
+    frame t after t * substeps sub-steps of length dt from w0 [B, N, N] (dlwp_ns2d_rollout_f32: pseudo-spectral, advective form,
+    Crank-Nicolson on the viscous term, 2/3 rule; one workgroup per trajectory, the spectrum resident in LDS for the whole
+    launch).  Frame 0 is w0 times `filter` in spectral space ([N, N / 2 + 1], real) without its modes |ka| = N / 2, kb = N / 2.
+    forcing: "li2020", None, or a tensor [N, N].  A trajectory's bits depend on neither the batch nor on how frames * substeps is
+    divided.  N in NS2D_SIZES and frames * substeps <= NS2D_MAX_STEPS, else the library refuses."""
+    what = "navier_stokes_2d"
+    _lib.require_cuda_tensor(w0, "w0")
+    if w0.dim() != 3 or w0.shape[-1] != w0.shape[-2] or w0.shape[0] < 1:
+        raise _lib.DlwpError(f"{what}: w0 must be [B, N, N] with B >= 1 (got {tuple(w0.shape)})")
+    b, n = int(w0.shape[0]), int(w0.shape[-1])
+    frames, substeps = int(frames), int(substeps)
+    dev = w0.device
+    if isinstance(forcing, str):
+        if forcing != "li2020":
+            raise _lib.DlwpError(f"{what}: forcing {forcing!r}; 'li2020', None or a tensor [N, N]")
+        forcing = ns2d_li2020_forcing(n, dev) if n in NS2D_SIZES else None      # any other N: the library names the limit
+    for name, t, shape in (("forcing", forcing, (n, n)), ("filter", filter, (n, n // 2 + 1))):
+        if t is not None:
+            _lib.require_cuda_tensor(t, name)
+            if tuple(t.shape) != shape or t.device != dev:
+                raise _lib.DlwpError(f"{what}: {name} must be {list(shape)} on {dev} (got {tuple(t.shape)} on {t.device})")
+    if frames < 1 or substeps < 1:
+        raise _lib.DlwpError(f"{what}: frames = {frames} and substeps = {substeps} must be at least 1")
+    if out is None:
+        out = torch.empty(b, frames, n, n, dtype=torch.float32, device=dev)
+    else:
+        _lib.require_cuda_tensor(out, "out")
+        if tuple(out.shape) != (b, frames, n, n) or not out.is_contiguous() or out.device != dev:
+            raise _lib.DlwpError(f"{what}: out must be a contiguous [{b}, {frames}, {n}, {n}] tensor on {dev}")
+    _lib.launch("dlwp_ns2d_rollout_f32", dev, w0.contiguous(), filter.contiguous() if filter is not None else None,
+                forcing.contiguous() if forcing is not None else None, out, b, n, frames, substeps, float(dt), float(nu))
+    return out
+
+
+def gaussian_random_field(shape_or_out, seed: int, offset: int = 0, tau: float = 7.0, alpha: float = 2.5, device=None) -> torch.Tensor:
+    """Periodic Gaussian random fields [..., N, N] with the covariance of the FNO paper's GaussianRF: irfft2(rfft2(z) A) with
+    z = philox_normal(seed, offset) of the same shape and A = grf_amplitude(N, tau, alpha) -- the device stream, then
+    dlwp_ns2d_rollout_f32 with one frame and A as its filter, in place.  The field's standard deviation is near 0.29 at N = 64.
+    `shape_or_out` as in philox_normal."""
+    shape = tuple(int(v) for v in (shape_or_out.shape if isinstance(shape_or_out, torch.Tensor) else shape_or_out))
+    if len(shape) < 2 or shape[-1] != shape[-2] or 0 in shape:
+        raise _lib.DlwpError(f"gaussian_random_field: fields [..., N, N] are needed (got {shape})")
+    z = philox_normal(shape_or_out, seed, offset, device=device)
+    n = int(z.shape[-1])
+    flat = z.view(-1, n, n)
+    amp = grf_amplitude(n, tau, alpha, z.device) if n in NS2D_SIZES else torch.zeros(n, n // 2 + 1, device=z.device)
+    navier_stokes_2d(flat, 1, 1, 1.0, 0.0, forcing=None, filter=amp, out=flat.view(-1, 1, n, n))
+    return z

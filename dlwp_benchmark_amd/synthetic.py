@@ -61,3 +61,52 @@ def weatherbench(batch: int, steps: int, h: int, w: int, prognostic_channels: in
     tt = torch.from_numpy
     return (tt(constants.astype(np.float32)) if constants is not None else None,
             tt(prescribed) if prescribed is not None else None, tt(prog))
+
+
+class NavierStokes2D:
+    """Fields with dynamics in them: trajectories of the 2-D incompressible Navier-Stokes equations in vorticity form on the
+    unit torus -- the data law of Li et al. 2020 ("Fourier Neural Operator for Parametric PDEs": Gaussian random initial
+    vorticity, fixed low-mode forcing, pseudo-spectral Crank-Nicolson steps) -- generated on the device: the initial condition by
+    ops.gaussian_random_field, the integration by ops.navier_stokes_2d, one LDS-resident workgroup per trajectory
+    (csrc/navier_stokes.hip).  A frame is `substeps` sub-steps of length `dt` after the one before it.
+    Unlike navier_stokes() above, frame t + 1 follows from frame t.  Draws are counter-based: `draw` d of a batch of B uses the
+    stream elements [d B n^2, (d + 1) B n^2) of `seed`, so equal (seed, batch, draw) give equal bits."""
+
+    def __init__(self, n: int = 64, viscosity: float = 1e-3, dt: float = 1e-3, substeps: int = 250, forcing="li2020",
+                 tau: float = 7.0, alpha: float = 2.5, seed: int = 0, device="cuda"):
+        self.n, self.viscosity, self.dt, self.substeps = int(n), float(viscosity), float(dt), int(substeps)
+        self.forcing, self.tau, self.alpha, self.seed = forcing, float(tau), float(alpha), int(seed)
+        self.device = torch.device(device)
+
+    def initial(self, batch: int, draw: int = 0) -> torch.Tensor:
+        """[batch, n, n]: Gaussian random initial vorticity, draw `draw` of this batch size"""
+        from . import ops
+        per_draw = -(-int(batch) * self.n * self.n // 4) * 4
+        return ops.gaussian_random_field((int(batch), self.n, self.n), self.seed, offset=int(draw) * per_draw, tau=self.tau,
+                                         alpha=self.alpha, device=self.device)
+
+    def solve(self, w0: torch.Tensor, frames: int) -> torch.Tensor:
+        """[B, frames, n, n]: frame 0 is w0 (band-limited), frame t the vorticity t * substeps * dt later"""
+        from . import ops
+        return ops.navier_stokes_2d(w0, frames, self.substeps, self.dt, self.viscosity, forcing=self.forcing)
+
+    def trajectories(self, batch: int, frames: int, draw: int = 0, scale=None):
+        """(constants=None, prescribed=None, prognostic [B, frames, 1, n, n]) -- the tuple layout of navier_stokes(); with `scale`
+        the field is divided by it"""
+        prog = self.solve(self.initial(batch, draw), frames).unsqueeze(2)
+        if scale is not None:
+            prog = prog / scale
+        return None, None, prog
+
+    @staticmethod
+    def windows(prognostic: torch.Tensor, sequence_length: int, context_size: int):
+        """Every window of `sequence_length` consecutive frames of every trajectory of prognostic [B, F, C, n, n], as the
+        training loop hands them on: (prognostic_in [B (F - L + 1), L, C, n, n] for model(prognostic=...), target = its frames
+        from `context_size` on, what the loss compares the model's output with)"""
+        b, f, c, h, w = prognostic.shape
+        length, ctx = int(sequence_length), int(context_size)
+        if not 1 <= ctx < length <= f:
+            raise ValueError(f"windows: 1 <= context_size {ctx} < sequence_length {length} <= frames {f} is needed")
+        win = prognostic.unfold(1, length, 1)                 # [B, F - L + 1, C, n, n, L]
+        win = win.permute(0, 1, 5, 2, 3, 4).reshape(b * (f - length + 1), length, c, h, w).contiguous()
+        return win, win[:, ctx:].contiguous()

@@ -1389,6 +1389,31 @@ int32_t dlwp_sph_mix_wgrad_packed_f32(const float* c_in_dev, const float* g_dev,
                                       int32_t cout, int32_t lmax, int32_t mmax, void* stream);
 int32_t dlwp_sph_mix_unpack_f32(const float* packed_dev, float* weight_dev, int32_t cin, int32_t cout, int32_t lmax, void* stream);
 
+/* Trajectories of the incompressible 2-D Navier-Stokes equations in vorticity form on the unit torus, solved pseudo-spectrally
+ * (csrc/navier_stokes.hip).  The reference tree holds no solver -- PARITY UNPINNED: the scheme is the one
+ * stated in DESIGN.md section 38.1 (the data law of Li et al. 2020, "Fourier Neural Operator for Parametric PDEs"), pinned by the
+ * float64 restatement tests/ns_ref.py and by the closed-form decay of a Taylor-Green vortex.
+ *   w0_dev [batch, n, n] fp32: the initial vorticity, axis 0 the coordinate a = i / n, axis 1 b = j / n
+ *   filter_dev [n, n / 2 + 1] fp32 or NULL: a real factor on rfft2(w0) (the amplitude table of a Gaussian random field)
+ *   forcing_dev [n, n] fp32 or NULL: the forcing f(a, b), NULL for none
+ *   out_dev [batch, frames, n, n] fp32: frame t is the vorticity after t * substeps sub-steps of length dt; frame 0 is w0
+ *   filtered, with every mode |ka| = n / 2 or kb = n / 2 removed.  With frames == 1 out_dev may be w0_dev itself.
+ * With wh = rfft2(w) (unnormalised), lap = 4 pi^2 (ka^2 + kb^2), lapi = lap except lapi[0, 0] = 1, mask = |ka|, kb <= n / 3, one
+ * sub-step is
+ *   psi = wh / lapi,  (u, v) = irfft2(2 pi i kb psi, -2 pi i ka psi),  (wa, wb) = irfft2(2 pi i ka wh, 2 pi i kb wh),
+ *   F = mask * rfft2(u wa + v wb),  wh <- (-dt F + dt fh + (1 - dt nu lap / 2) wh) / (1 + dt nu lap / 2)
+ * (advective form, Crank-Nicolson on the viscous term).  The modes |ka| = n / 2 and kb = n / 2 of the forcing are dropped as
+ * those of w0 are, so they stay zero; column kb = 0 is kept exactly Hermitian (its ka < 0 half is the conjugate of the other).
+ * One workgroup integrates one trajectory with wh resident in LDS for the whole launch; the 2-D transforms are the radix
+ * passes of csrc/fft_radix.hpp over LDS, the twiddles a float64 host table, the per-mode factors made in float64 at the head of
+ * the kernel: no transcendental runs on the device.  Fixed summation order, no atomics, no inter-workgroup traffic: a
+ * trajectory's bits depend on neither the batch beside it nor on how its sub-steps are divided into frames.
+ * n is 32 or 64 (128 x 128 does not fit the 160 KiB of LDS: DLWP_ERR_UNSUPPORTED, as every other n); batch, frames >= 1,
+ * substeps >= 1, frames * substeps at most the cap stated in csrc/navier_stokes.hip (DLWP_ERR_UNSUPPORTED above it: one
+ * launch stays within seconds), dt > 0, nu >= 0, all finite. */
+int32_t dlwp_ns2d_rollout_f32(const float* w0_dev, const float* filter_dev, const float* forcing_dev, float* out_dev, int32_t batch,
+                              int32_t n, int32_t frames, int32_t substeps, double dt, double nu, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
